@@ -24,7 +24,9 @@ re-derived by anybody.  For N>1:
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 bench.py --gpus 8 ...
     python bench.py --gpus 8 ...        # no launcher: starts the eight ranks itself (below)
 
-Rank 0 prints ONE JSON line.
+Rank 0 prints ONE JSON line.  ``--dump-outputs DIR`` additionally writes what the last timed step returned
+(``best_index.npy``, ``best_u.npy``; multi-rank runs also ``rank_records.npy``) and the sweep's per-candidate
+``u``, ``mu``, ``var`` (``rows.npy``: which rows) for output-for-output comparisons.
 
 ``--gpus N`` (N > 1) without a launcher environment: this process -- before it has made a single GPU
 call, and it never makes one -- starts ``python -m torch.distributed.run --nproc-per-node N bench.py ...``
@@ -413,6 +415,36 @@ def cpu_baseline_worker(args):
     return 0
 
 
+DUMP_MAX_ROWS = 1 << 20      # per-candidate arrays: 4 x 8 B x 2**20 = 32 MB, inside the 64 MB the dump may take
+
+
+def dump_outputs(out_dir, best, records=None, full=None, lo_row=0):
+    """``--dump-outputs DIR``: what the timed path computed, as float64 ``.npy`` files --
+    ``best_index.npy`` (1,) and ``best_u.npy`` (1,): the last timed step's (index, u), what ``GP.acquire`` /
+    ``sharded_acquire`` hand their caller; with more than one rank also ``rank_records.npy`` (world, 2): the gathered
+    per-rank (u, index) winners in rank order.  ``full`` = (u, mu, var) of this rank's shard from ONE
+    ``acquire(..., return_all=True)`` over the same candidates after the timed loop (the same fused sweep with its
+    per-candidate outputs stored): ``u.npy``, ``mu.npy``, ``var.npy`` and ``rows.npy``, the global candidate rows
+    they belong to -- every row up to ``DUMP_MAX_ROWS``, above that a fixed RandomState(2024) sample of that many
+    rows, sorted.  The inputs are seeded (training set RandomState(0), candidates RandomState(1)), so two builds run
+    with the same arguments can be compared file for file.  (Indices stay exact in float64 below 2**53.)"""
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"best_index": np.array([best[0]], dtype=np.float64),
+              "best_u": np.array([best[1]], dtype=np.float64)}
+    if records is not None:
+        arrays["rank_records"] = np.array([[u, i] for u, i in records], dtype=np.float64).reshape(-1, 2)
+    if full is not None:
+        u, mu, var = full
+        m = len(u)
+        keep = np.arange(m) if m <= DUMP_MAX_ROWS else \
+            np.sort(np.random.RandomState(2024).choice(m, size=DUMP_MAX_ROWS, replace=False))
+        arrays["rows"] = (keep + lo_row).astype(np.float64)
+        for name, a in (("u", u), ("mu", mu), ("var", var)):
+            arrays[name] = np.asarray(a, dtype=np.float64)[keep]
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def self_launch(args, argv):
     """``--gpus N`` (N > 1) without a launcher: start the N ranks as a child ``torch.distributed.run`` and pass
     rank 0's line through.  Nothing here touches the GPU (``torch.cuda.device_count()`` only counts), and the
@@ -466,12 +498,20 @@ def main():
                     help="collectives of a multi-rank run: RCCL over xGMI (nccl) or host collectives (gloo)")
     ap.add_argument("--share-device", action="store_true",
                     help="all ranks on cuda:0 (needs --backend gloo): rehearses the multi-rank path on ONE GPU")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step returned (best_index.npy, best_u.npy; "
+                         "multi-rank: rank_records.npy) and the sweep's per-candidate u, mu, var with their rows "
+                         "(rank 0's shard, at most 2**20 rows: a fixed sample above that) as float64 .npy files into DIR")
     ap.add_argument("--cpu-baseline-worker", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
     if args.cpu_baseline_worker:
         return cpu_baseline_worker(args)
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.warmup < 0:
+        ap.error("--warmup must be >= 0")
     if args.share_device and args.backend != "gloo":
         ap.error("--share-device needs --backend gloo (RCCL refuses two ranks on one device)")
 
@@ -586,6 +626,11 @@ def main():
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
     kms = [a.elapsed_time(b) for a, b in kernel_ms]
+    if rank == 0 and args.dump_outputs:
+        gp.kernel_events = None         # the extra sweep below is not a timed one
+        _, _, u_all, mu_all, var_all = gp.acquire(y, T, args.utility, bounds=bounds, idx_offset=lo_row, return_all=True)
+        dump_outputs(args.dump_outputs, best, records if world > 1 else None, (u_all, mu_all, var_all), lo_row)
+        del u_all, mu_all, var_all
 
     if rank == 0:
         total = float(M_total) * args.steps

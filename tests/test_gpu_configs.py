@@ -329,10 +329,11 @@ def test_optimizegp_hip_reproduces_reference_constant(golden_dir):
         assert np.isclose(gp.log_likelihood(y), replay["ll"], rtol=1e-6)
 
 
-def test_findnextpoint_hip_reproduces_reference_constant(golden_dir):
+def test_findnextpoint_hip_reproduces_reference_constant(golden_dir, tmp_path, monkeypatch):
     """test_findNewPoint.py:86-108 on the HIP-backed GP: seed 57, m0 = 50 + two corner points,
     defaultGP(fitAmp=False), BAPE, findNextPoint(computeLnLike=False, seed=57) ->
     [0.79813416, 0.85542199] (rtol 1e-3, the reference's tolerance)."""
+    monkeypatch.chdir(tmp_path)     # findNextPoint's default cache=True writes apRunAPFModelCache.npz into the working directory
     from approxposterior_amd import approx, gpUtils, likelihood as lh
     pins = json.load(open(os.path.join(golden_dir, "pins.json")))
     np.random.seed(57)

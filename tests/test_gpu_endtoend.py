@@ -108,10 +108,11 @@ def test_find_map_sphere(tmp_path, monkeypatch):
     assert np.allclose(0.0, testVal, atol=1.0e-3)
 
 
-def test_sweep_point_search_vs_nelder_mead():
+def test_sweep_point_search_vs_nelder_mead(tmp_path, monkeypatch):
     """The fused sweep over 2e5 prior draws finds a utility at least as good as
     the reference-style 5-restart Nelder-Mead search (up to the grid resolution),
     and gpllBatch equals the scalar guard-by-guard path."""
+    monkeypatch.chdir(tmp_path)     # findNextPoint's default cache=True writes apRunAPFModelCache.npz into the working directory
     from approxposterior_amd import utility as ut
     np.random.seed(57)
     ap = _rosen_ap(60)
@@ -188,10 +189,11 @@ def test_device_ensemble_sampler_matches_host_sampler():
     assert not np.allclose(c4[:, 0], c4[:, 1])
 
 
-def test_default_gp_with_linear_order_end_to_end():
+def test_default_gp_with_linear_order_end_to_end(tmp_path, monkeypatch):
     """defaultGP(order=1) (gpUtils.py:167-173): the reference's optional linear-regression
     term through defaultGP -> optGP -> findNextPoint on the device path; the initial GP is
     the oracle's for the same random draw."""
+    monkeypatch.chdir(tmp_path)     # findNextPoint's default cache=True writes apRunAPFModelCache.npz into the working directory
     import sys, os
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle"))
     import george_oracle as go

@@ -551,13 +551,14 @@ def test_more_than_sixteen_dimensions(n, D):
 from philox_ref import philox_box_numpy as _philox_box_numpy  # noqa: E402
 
 
-def test_device_candidates_are_a_function_of_seed_and_row():
+def test_device_candidates_are_a_function_of_seed_and_row(tmp_path, monkeypatch):
     """``deviceCandidates`` (round 5): the candidate matrix of the sweep drawn on the device by counter-based Philox -- the
     batched counterpart of the ``sampleFn`` draws utility.minimizeObjective starts from (utility.py:334-338) when the prior is
     the box.  (1) the matrix equals a NumPy restatement of the generator (to 1 ulp: the kernel fuses lo + span * u),
     (2) rows generated with an offset are exactly the rows of the whole matrix -- what lets every rank of a sharded sweep
     generate its own shard, (3) uniform in the box, (4) ``findNextPoint(nCandidates=..., deviceCandidates=True)`` picks the
     arg-min of the oracle's utility over that matrix."""
+    monkeypatch.chdir(tmp_path)     # findNextPoint's default cache=True writes apRunAPFModelCache.npz into the working directory
     from approxposterior_amd import approx, gpUtils, likelihood as lh, utility as ut
     go, agp = _mods()
     D = 5
