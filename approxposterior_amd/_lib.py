@@ -14,6 +14,8 @@ ABI_VERSION = 8
 MAX_DIM = 32
 
 UTIL_AGP, UTIL_BAPE, UTIL_JONES, UTIL_NONE = 0, 1, 2, 3
+GMM_EM, GMM_SCORE, GMM_KMEANS = 0, 1, 2
+GMM_MAX_COMP = 16
 
 
 class ApgpError(RuntimeError):
@@ -90,6 +92,9 @@ SIGNATURES = {
     "apgp_kinv_solve_work_len": (_I64, [_I64]),
     "apgp_kinv_solve": (ctypes.c_int, [_P, _I64, _I64, _P, _P, _P]),
     "apgp_grad_loglik": (ctypes.c_int, [_P, _P, _P, _I64, _I64, _KP, _P, _P, _P]),
+    "apgp_gmm_params_len": (_I64, [_I32, _I32]),
+    "apgp_gmm_stats_len": (_I64, [_I32, _I32]),
+    "apgp_gmm_pass": (ctypes.c_int, [_P, _I64, _I32, _I32, _P, _I32, _P, _P, _P, _P]),
 }
 
 _lib = None

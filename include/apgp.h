@@ -407,6 +407,30 @@ int apgp_ensemble_sample(const double* xs, int64_t n, const apgp_kernel_t* kern 
 int apgp_box_candidates(double* T, int64_t m, int32_t ndim, const double* lo /*host*/,
                         const double* hi /*host*/, uint64_t seed, int64_t idx_offset, void* stream);
 
+/* ---- Gaussian-mixture passes (gmmUtils.fitGMM) --------------------------------
+ * One pass over X (n x ndim, row-major, device) and a fixed-order reduction into
+ * stats_out (device, apgp_gmm_stats_len doubles); no atomics, same bits run to run.
+ * params (device, apgp_gmm_params_len doubles): per component k, 2 + D + D(D+1)/2 doubles
+ *   [log w_k, log det U_k, c_k (D), U_k packed upper triangle column by column: U[i][j] at j(j+1)/2 + i]
+ * with U_k the precision Cholesky factor (precision = U U^T) and c_k the centre.
+ * stats_out: [G, then per component (s0, s1 (D), S (D(D+1)/2, packed as U))]
+ *   APGP_GMM_EM:     G = sum_rows log_prob_norm, s0 = sum r, s1 = sum r (x - c_k),
+ *                    S = sum r (x - c_k)(x - c_k)^T, r the responsibilities of the E-step
+ *   APGP_GMM_SCORE:  G only (the rest of stats_out is not written)
+ *   APGP_GMM_KMEANS: r = 1 for the nearest centre c_k (lowest k on ties), else 0; G = the
+ *                    sum of the squared distances to it (log w, log det and U are not read)
+ * row_lp / row_label (device, n each, may be NULL): per row log_prob_norm (k-means: the
+ * squared distance) and the most likely (k-means: nearest) component.
+ * Limits: 1 <= n < 2^31, 1 <= ndim <= APGP_MAX_DIM, 1 <= ncomp <= 16; the *_len functions
+ * return -1 outside them.  Uses per-stream scratch (apgp_release_scratch): not during capture. */
+#define APGP_GMM_EM 0
+#define APGP_GMM_SCORE 1
+#define APGP_GMM_KMEANS 2
+int64_t apgp_gmm_params_len(int32_t ndim, int32_t ncomp);
+int64_t apgp_gmm_stats_len(int32_t ndim, int32_t ncomp);
+int apgp_gmm_pass(const double* X, int64_t n, int32_t ndim, int32_t ncomp, const double* params, int32_t mode,
+                  double* stats_out, double* row_lp, int32_t* row_label, void* stream);
+
 /* ---- K4: gradient of the log-likelihood wrt kernel hyper-parameters -------
  * Replaces george GP.grad_log_likelihood (gpUtils._grad_nll, gpUtils.py:110):
  *   g_k = 0.5 * sum_ij (alpha alpha^T - K^-1)_ij dK_ij/dtheta_k.
