@@ -455,6 +455,12 @@ class ApproxPosterior(object):
                                                                  mcmcKwargs, verbose)
         if onDevice:
             self._requireBoxPrior()
+            # the host sampler's shape check (EnsembleSampler.sample): the device would quietly take the row count
+            p0 = np.asarray(mcmcKwargs["initial_state"], dtype=float)
+            if p0.ndim == 1:
+                p0 = p0.reshape(samplerKwargs["nwalkers"], self.ndim)
+            if p0.shape != (samplerKwargs["nwalkers"], self.ndim):
+                raise ValueError("incompatible input dimensions")
         if onDevice or ranks is not None:
             # one ensemble per rank, seeded base + rank, gathered once along the walker axis
             # (no ranks -- no process group, or distributed=False inside somebody else's: the local chain, seed
@@ -468,7 +474,8 @@ class ApproxPosterior(object):
             chain, logp, naccept = merged[0], merged[1], merged[2]
             self.sampler = emcee.DeviceChain({"chain": chain, "log_prob": logp, "naccept": naccept,
                                               "coords": chain[-1], "final_log_prob": logp[-1],
-                                              "blobs": merged[3] if len(merged) > 3 else None})
+                                              "blobs": merged[3] if len(merged) > 3 else None},
+                                             a=samplerKwargs.get("a", 2.0))
         else:
             self.sampler = self._hostSampler(samplerKwargs, args, kwargs, batched)
             for _ in self.sampler.sample(**mcmcKwargs):
@@ -495,7 +502,7 @@ class ApproxPosterior(object):
         """This rank's ensemble: ``(chain, log_prob, naccept[, blobs])`` for :func:`dist.replicated_ensembles`."""
         if onDevice:
             res = self.gp.sample_ensemble(self.y, mcmcKwargs["initial_state"], mcmcKwargs["iterations"],
-                                          self.bounds, seed=seed)
+                                          self.bounds, a=samplerKwargs.get("a", 2.0), seed=seed)
             return res["chain"], res["log_prob"], res["naccept"]
         sampler = self._hostSampler(samplerKwargs, args, kwargs, batched, seed=seed)
         for _ in sampler.sample(**mcmcKwargs):

@@ -266,14 +266,14 @@ class DeviceChain(EnsembleSampler):
     ``get_autocorr_time``, ``acceptance_fraction``), so burn-in estimation and the
     reference-style post-processing work unchanged."""
 
-    def __init__(self, result):
+    def __init__(self, result, a=2.0):
         chain = result["chain"]
         self.nwalkers = chain.shape[1]
         self.ndim = chain.shape[2]
         self.log_prob_fn = None
         self.args, self.kwargs = (), {}
         self.vectorize = True
-        self.a = 2.0
+        self.a = float(a)                 # the stretch scale the chain was run with
         self.blobs_dtype = None
         self.backend = None
         self._random = None
