@@ -88,6 +88,8 @@ SIGNATURES = {
     "apgp_ensemble_mode": (ctypes.c_int, [ctypes.c_int]),
     "apgp_box_candidates": (ctypes.c_int, [_P, _I64, _I32, ctypes.POINTER(_F64), ctypes.POINTER(_F64), ctypes.c_uint64,
                                            _I64, _P]),
+    "apgp_prior_candidates": (ctypes.c_int, [_P, _I64, _I32, _P, _P, _P, ctypes.c_uint64, _I64, _P]),
+    "apgp_prior_lnprior": (ctypes.c_int, [_P, _I64, _I32, _P, _P, _P, _P, _P]),
     "apgp_release_scratch": (ctypes.c_int, [_P]),
     "apgp_kinv_solve_work_len": (_I64, [_I64]),
     "apgp_kinv_solve": (ctypes.c_int, [_P, _I64, _I64, _P, _P, _P]),

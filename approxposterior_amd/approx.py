@@ -33,7 +33,9 @@ Additions the reference does not have (all off by default):
 * ``_gpllBatch``: the surrogate log-probability of a whole walker ensemble in one
   launch (what the ensemble sampler calls with ``vectorize=True``);
 * ``runMCMC(onDevice=True)`` / ``run(onDevice=True)``: the whole chain as one
-  persistent kernel (box prior only);
+  persistent kernel (a box prior, or a :class:`~approxposterior_amd.priors.JointPrior`
+  of Uniform and Gaussian factors as ``lnprior``: then the chain runs under its
+  support and the lnprior blobs come from the device);
 * several GPUs: launched as ``python -m torch.distributed.run --nproc-per-node N script.py`` with a
   process group initialised before the object is used (``tools/run_c5_dist.py``), every rank runs the
   same outer loop on an identical training set -- the ``nCandidates`` sweep is sharded by rank with one
@@ -55,6 +57,7 @@ from . import gp as george
 from . import gpUtils
 from . import mcmc as emcee   # drop-in for the ``emcee`` names used below
 from . import mcmcUtils
+from . import priors as appriors
 from . import utility as ut
 
 __all__ = ["ApproxPosterior"]
@@ -122,7 +125,7 @@ class ApproxPosterior(object):
     def __init__(self, theta, y, lnprior, lnlike, priorSample, bounds, gp=None,
                  algorithm="bape", distributed=None, group=None):
         self.distributed, self.group = distributed, group
-        self.deviceCandidates = False      # nCandidates drawn on the device, uniform in ``bounds`` (see findNextPoint)
+        self.deviceCandidates = False      # nCandidates drawn on the device (see findNextPoint)
         if theta is None or y is None:
             raise ValueError("Must supply both theta and y for initial GP training set.")
         self.theta = np.array(theta).squeeze()
@@ -245,6 +248,11 @@ class ApproxPosterior(object):
                                      nGPRestarts=nGPRestarts, gpHyperPrior=gpHyperPrior,
                                      distributed=self.distributed, group=self.group)
 
+    def _jointPrior(self):
+        """``lnprior`` when it is a :class:`~approxposterior_amd.priors.JointPrior` (the prior the device paths
+        can evaluate), else None."""
+        return self._lnprior if isinstance(self._lnprior, appriors.JointPrior) else None
+
     # ------------------------------------------------------- design-point selection
     def _selectPoint(self, utility, theta0, nRestarts, method, options, nCandidates, polish):
         """One design point: the minimiser of ``utility`` over the prior.  Under a process group the
@@ -262,7 +270,17 @@ class ApproxPosterior(object):
         total = int(nCandidates)
         kind = ut.utilityKind(utility) if (ranks is not None or self.deviceCandidates) else None
         lo, hi = apdist.shard_bounds(total, ranks[1], ranks[0]) if ranks is not None else (0, total)
-        if self.deviceCandidates:
+        joint = self._jointPrior()
+        # the sweep's gate: the reference's utilities return +inf exactly where lnprior is not finite, which for a
+        # JointPrior is outside its support (infinite edges on Gaussian dimensions)
+        gate = self.bounds if joint is None else [tuple(r) for r in joint.support()]
+        if self.deviceCandidates and joint is not None:
+            # drawn from the prior itself on the device (same stream as box_candidates); the winning row alone is
+            # regenerated below
+            seed = int(np.random.randint(0, 2 ** 31 - 1))
+            mine = self.gp.prior_candidates(hi - lo, joint, seed, idx_offset=lo)
+            row = lambda g: self.gp.prior_candidates(1, joint, seed, idx_offset=g).cpu().numpy()[0]       # noqa: E731
+        elif self.deviceCandidates:
             # the global matrix is a function of (seed, row) alone: this rank generates its rows in HBM, no host draw,
             # no H2D copy; the box ``bounds`` IS the prior here (priorSample is not consulted)
             seed = int(np.random.randint(0, 2 ** 31 - 1))
@@ -273,10 +291,10 @@ class ApproxPosterior(object):
             mine = draws if ranks is None else np.ascontiguousarray(draws[lo:hi])
             row = lambda g: np.array(draws[g])                                                              # noqa: E731
         if ranks is None and not self.deviceCandidates:
-            point, value = ut.sweepObjective(utility, self.y, self.gp, mine, bounds=self.bounds)
+            point, value = ut.sweepObjective(utility, self.y, self.gp, mine, bounds=gate)
         else:
             best, value = apdist.sharded_acquire(
-                lambda offset: self.gp.acquire(self.y, mine, kind, bounds=self.bounds, idx_offset=offset,
+                lambda offset: self.gp.acquire(self.y, mine, kind, bounds=gate, idx_offset=offset,
                                                device_record=True),
                 lo, group=self.group if ranks is not None else None,
                 enabled=self.distributed if ranks is not None else False)     # (no ranks: this process's own record, no gather)
@@ -328,7 +346,9 @@ class ApproxPosterior(object):
         ``polish`` refines the sweep winner with one Nelder-Mead run;
         ``deviceCandidates=True`` draws the candidates on the device, uniformly in ``bounds``
         (counter-based Philox keyed by one integer from NumPy's global stream) instead of calling
-        ``priorSample`` -- valid when the prior IS that box.
+        ``priorSample`` -- valid when the prior IS that box; when ``lnprior`` is a
+        :class:`~approxposterior_amd.priors.JointPrior` they are drawn from that prior instead
+        (``GP.prior_candidates``), and every ``nCandidates`` sweep is gated by ``lnprior.support()``.
         """
         if deviceCandidates is not None:
             self.deviceCandidates = bool(deviceCandidates)
@@ -402,10 +422,13 @@ class ApproxPosterior(object):
                  blobs=np.array([]) if blobs is None else blobs)
 
     def _requireBoxPrior(self):
-        """The on-device sampler (``GP.sample_ensemble``) knows ONE prior: constant inside ``self.bounds``,
-        -inf outside.  ``_gpll`` returns ``mu(theta) + lnprior(theta)`` (approx.py:167-188), so any other
-        ``lnprior`` -- a Gaussian, a tilted box -- would make the device chain sample a different posterior
-        without a word.  ``lnprior`` is probed (own RandomState: the caller's NumPy stream is untouched) at
+        """For an ``lnprior`` that is not a :class:`~approxposterior_amd.priors.JointPrior`, the on-device
+        sampler (``GP.sample_ensemble``) knows ONE prior: constant inside ``self.bounds``, -inf outside.
+        ``_gpll`` returns the pair ``(mu(theta), lnprior(theta))`` (approx.py:167-188): the sampler takes
+        ``mu`` as the log-probability and ``lnprior`` as a blob, so the prior only gates the chain (a walker is
+        rejected where it is not finite).  The device cannot evaluate an arbitrary Python ``lnprior``, neither
+        for that gate nor for the blobs, so it insists on the one prior it reproduces exactly -- the box -- and
+        records no blobs.  ``lnprior`` is probed (own RandomState: the caller's NumPy stream is untouched) at
         the centre, at seeded points inside, just inside every corner and just outside every face: it must be
         one finite constant inside and non-finite outside, else ``ValueError``."""
         lo = np.array([b[0] for b in self.bounds], dtype=np.float64)
@@ -443,7 +466,8 @@ class ApproxPosterior(object):
         emcee does for the reference; ``onDevice=True`` runs the entire chain as one
         persistent kernel (``GP.sample_ensemble``) -- valid when ``lnprior`` is the box
         prior ``self.bounds`` (constant inside, -inf outside): checked (:meth:`_requireBoxPrior`,
-        ``ValueError`` otherwise).
+        ``ValueError`` otherwise) -- or a :class:`~approxposterior_amd.priors.JointPrior`: then the chain
+        runs under ``lnprior.support()`` and carries the lnprior blobs, as the host chain does.
         With ``cache`` the chain goes to ``<runName>.npz`` (keys chain, log_prob, blobs)
         where the reference writes ``<runName>.h5``.
         """
@@ -454,7 +478,8 @@ class ApproxPosterior(object):
         samplerKwargs, mcmcKwargs = mcmcUtils.validateMCMCKwargs(self, samplerKwargs,
                                                                  mcmcKwargs, verbose)
         if onDevice:
-            self._requireBoxPrior()
+            if self._jointPrior() is None:
+                self._requireBoxPrior()
             # the host sampler's shape check (EnsembleSampler.sample): the device would quietly take the row count
             p0 = np.asarray(mcmcKwargs["initial_state"], dtype=float)
             if p0.ndim == 1:
@@ -501,9 +526,12 @@ class ApproxPosterior(object):
     def _sampleReplica(self, seed, samplerKwargs, mcmcKwargs, args, kwargs, batched, onDevice):
         """This rank's ensemble: ``(chain, log_prob, naccept[, blobs])`` for :func:`dist.replicated_ensembles`."""
         if onDevice:
+            joint = self._jointPrior()
+            extra = {} if joint is None else {"prior": joint}
             res = self.gp.sample_ensemble(self.y, mcmcKwargs["initial_state"], mcmcKwargs["iterations"],
-                                          self.bounds, a=samplerKwargs.get("a", 2.0), seed=seed)
-            return res["chain"], res["log_prob"], res["naccept"]
+                                          self.bounds, a=samplerKwargs.get("a", 2.0), seed=seed, **extra)
+            out = (res["chain"], res["log_prob"], res["naccept"])
+            return out if joint is None else out + (res["blobs"],)
         sampler = self._hostSampler(samplerKwargs, args, kwargs, batched, seed=seed)
         for _ in sampler.sample(**mcmcKwargs):
             pass

@@ -11,8 +11,13 @@
 // One workgroup = one independent ensemble (grid.x ensembles = replicas, the
 // only way this path shards); a wavefront evaluates one
 // walker's GP mean with its lanes striding the training points.
-// Only a box prior can be evaluated on the device (arbitrary Python priors
-// cannot): the caller asserts lnprior == const inside [lo, hi], -inf outside.
+// _gpll's lnprior only GATES the chain (a walker is rejected where it is not
+// finite; its value rides along as a blob), so the kernels need the prior's
+// support alone: an axis-aligned box [lo, hi] whose edges may be infinite.
+// Arbitrary Python priors cannot be evaluated here: the caller either asserts
+// lnprior == const inside [lo, hi], -inf outside, or passes a product of
+// Uniform and Gaussian factors (priors.JointPrior), whose support is the box and
+// whose log-density prior_lnprior_kernel below computes over the stored chain.
 #include "apgp_common.h"
 #include "scratch.h"
 #include <atomic>
@@ -656,6 +661,138 @@ extern "C" int apgp_box_candidates(double* T, int64_t m, int32_t ndim, const dou
         APGP_CHECK_ARG(d >= ndim || (a.span[d] >= 0.0 && a.span[d] < INFINITY), "bounds must be finite with lo <= hi");
     }
     hipLaunchKernelGGL(box_candidates_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
+    APGP_CHECK_LAUNCH();
+    return 0;
+}
+
+// ---------------------------------------------------------------------------
+// Candidates drawn from a product prior of Uniform and Gaussian factors (priors.JointPrior), and its log-density.
+// The stream is box_candidates_kernel's: the same counter (row low, row high, d / 2, "CAND"), key and pairing of
+// dimensions, so a Uniform dimension is bit-identical to the box draw of the same row and sharding by idx_offset is
+// unchanged.  A Gaussian dimension turns the same u into the reference's inverse-CDF expression (priors.py
+// GaussianPrior.transform_uniform), evaluated with explicit roundings in the order NumPy evaluates it:
+//   x = mu + (sigma * sqrt(2)) * erfcinv(2 * (1 - u)).
+// prior_lnprior_kernel is JointPrior.batch on the device: per row, sum over d of lc[d] (= -log(high - low), or
+// -log(sigma) - log(2 pi) / 2) minus z^2 / 2 for Gaussian dimensions, z = (x - mu) / sigma; -inf for a non-finite
+// coordinate or one outside a Uniform factor's [low, high].
+// ---------------------------------------------------------------------------
+#define APGP_PRIOR_UNIFORM 0
+#define APGP_PRIOR_GAUSSIAN 1
+
+struct PriorArgs {
+    double* T;                 // candidates out (m x ndim) | rows in for the log-density
+    double* out;               // log-density out (m), NULL for candidates
+    long long m, idx_offset;
+    int ndim;
+    unsigned long long seed;
+    int kind[APGP_MAX_DIM];
+    double p0[APGP_MAX_DIM];   // low | mu
+    double p1[APGP_MAX_DIM];   // candidates: span | sigma;  log-density: high | sigma
+    double lc[APGP_MAX_DIM];   // log-density constant of the factor
+};
+
+// (not inlined: inside the row loop the compiler hoists erfcinv's coefficients into some 400 registers)
+__device__ __attribute__((noinline)) double prior_gauss(double mu, double sigma, double u) {
+    const double w = __dmul_rn(2.0, __dsub_rn(1.0, u));
+    return __dadd_rn(mu, __dmul_rn(__dmul_rn(sigma, 1.4142135623730951), erfcinv(w)));
+}
+
+__device__ __forceinline__ double prior_draw(const PriorArgs& a, int d, double u) {
+    if (a.kind[d] == APGP_PRIOR_UNIFORM) return fma(a.p1[d], u, a.p0[d]);
+    return prior_gauss(a.p0[d], a.p1[d], u);
+}
+
+__global__ __launch_bounds__(256) void prior_candidates_kernel(PriorArgs a) {
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < a.m; i += (long long)gridDim.x * 256) {
+        const unsigned long long g = (unsigned long long)(a.idx_offset + i);
+        double* row = a.T + i * a.ndim;
+        for (int d = 0; d < a.ndim; d += 2) {
+            unsigned int c[4] = {(unsigned int)g, (unsigned int)(g >> 32), (unsigned int)(d >> 1), 0x43414e44u};
+            philox4x32(c, (unsigned int)a.seed, (unsigned int)(a.seed >> 32));
+            row[d] = prior_draw(a, d, u01(c[0], c[1]));
+            if (d + 1 < a.ndim) row[d + 1] = prior_draw(a, d + 1, u01(c[2], c[3]));
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void prior_lnprior_kernel(PriorArgs a) {
+    for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < a.m; i += (long long)gridDim.x * 256) {
+        const double* row = a.T + i * a.ndim;
+        double s = 0.0;
+        bool in = true;
+        for (int d = 0; d < a.ndim; ++d) {
+            const double x = row[d];
+            if (!isfinite(x)) in = false;
+            if (a.kind[d] == APGP_PRIOR_UNIFORM) {
+                if (!(x >= a.p0[d] && x <= a.p1[d])) in = false;
+                s += a.lc[d];
+            } else {
+                const double z = (x - a.p0[d]) / a.p1[d];
+                s += a.lc[d] - 0.5 * z * z;
+            }
+        }
+        a.out[i] = in ? s : -INFINITY;
+    }
+}
+
+// the checks both entries share; fills a (kinds and parameters) or returns the failed check's message
+static const char* prior_args(PriorArgs& a, int32_t ndim, const int32_t* kind, const double* p0, const double* p1,
+                              bool span) {
+    if (!(ndim >= 1 && ndim <= APGP_MAX_DIM)) return "1 <= ndim <= APGP_MAX_DIM required";
+    a.ndim = ndim;
+    for (int d = 0; d < APGP_MAX_DIM; ++d) {
+        a.kind[d] = APGP_PRIOR_UNIFORM;
+        a.p0[d] = a.p1[d] = a.lc[d] = 0.0;
+        if (d >= ndim) continue;
+        const double u = p0[d], v = p1[d];
+        if (kind[d] == APGP_PRIOR_UNIFORM) {
+            if (!(std::isfinite(u) && std::isfinite(v) && u < v && std::isfinite(v - u)))
+                return "a Uniform factor needs finite low < high";
+            a.p0[d] = u;
+            a.p1[d] = span ? v - u : v;
+            a.lc[d] = -std::log(v - u);
+        } else if (kind[d] == APGP_PRIOR_GAUSSIAN) {
+            if (!(std::isfinite(u) && std::isfinite(v) && v > 0.0)) return "a Gaussian factor needs finite mu and sigma > 0";
+            a.kind[d] = APGP_PRIOR_GAUSSIAN;
+            a.p0[d] = u;
+            a.p1[d] = v;
+            a.lc[d] = -std::log(v) - 0.5 * std::log(2.0 * M_PI);
+        } else {
+            return "kind must be 0 (Uniform) or 1 (Gaussian)";
+        }
+    }
+    return nullptr;
+}
+
+static inline unsigned prior_grid(long long m) {
+    const long long b = (m + 255) / 256;
+    return (unsigned)(b < 65536 ? b : 65536);
+}
+
+extern "C" int apgp_prior_candidates(double* T, int64_t m, int32_t ndim, const int32_t* kind, const double* p0,
+                                     const double* p1, uint64_t seed, int64_t idx_offset, void* stream) {
+    APGP_CHECK_ARG(T && kind && p0 && p1, "null pointer");
+    APGP_CHECK_ARG(m >= 0 && idx_offset >= 0, "m >= 0 and idx_offset >= 0 required");
+    PriorArgs a;
+    const char* bad = prior_args(a, ndim, kind, p0, p1, true);
+    APGP_CHECK_ARG(bad == nullptr, bad);
+    if (m == 0) return 0;
+    a.T = T; a.out = nullptr; a.m = m; a.idx_offset = idx_offset; a.seed = seed;
+    hipLaunchKernelGGL(prior_candidates_kernel, dim3(prior_grid(m)), dim3(256), 0, (hipStream_t)stream, a);
+    APGP_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int apgp_prior_lnprior(const double* X, int64_t m, int32_t ndim, const int32_t* kind, const double* p0,
+                                  const double* p1, double* out, void* stream) {
+    APGP_CHECK_ARG(X && kind && p0 && p1 && out, "null pointer");
+    APGP_CHECK_ARG(m >= 0, "m >= 0 required");
+    PriorArgs a;
+    const char* bad = prior_args(a, ndim, kind, p0, p1, false);
+    APGP_CHECK_ARG(bad == nullptr, bad);
+    if (m == 0) return 0;
+    a.T = (double*)X; a.out = out; a.m = m; a.idx_offset = 0; a.seed = 0;
+    hipLaunchKernelGGL(prior_lnprior_kernel, dim3(prior_grid(m)), dim3(256), 0, (hipStream_t)stream, a);
     APGP_CHECK_LAUNCH();
     return 0;
 }

@@ -1328,14 +1328,46 @@ class GP(GeorgeExtras):
                                                int(idx_offset), self._stream(torch)), "apgp_box_candidates")
         return T
 
+    @staticmethod
+    def _prior_records(prior, D):
+        kind, p0, p1 = prior.records()
+        if len(kind) != D:
+            raise ValueError("the prior must have one factor per dimension")
+        kind = np.ascontiguousarray(kind, dtype=np.int32)
+        p0 = np.ascontiguousarray(p0, dtype=np.float64)
+        p1 = np.ascontiguousarray(p1, dtype=np.float64)
+        return kind, p0, p1
+
+    def prior_candidates(self, m, prior, seed, idx_offset=0):
+        """Rows ``idx_offset .. idx_offset + m - 1`` of the global candidate matrix drawn from ``prior`` (a
+        :class:`~approxposterior_amd.priors.JointPrior`) keyed by ``seed``, as a device tensor (m, D) ready for
+        :meth:`acquire`.  Same stream as :meth:`box_candidates`: a Uniform dimension is bit-identical to the box
+        draw of the same row; a Gaussian dimension is the factor's inverse CDF at the same uniform."""
+        torch, dev, lib = self._rt()
+        D = self.kernel.ndim
+        kind, p0, p1 = self._prior_records(prior, D)
+        with self._on(torch, dev):
+            T = torch.empty((int(m), D), dtype=torch.float64, device=dev)
+            if int(m) == 0:
+                return T
+            _lib.check(lib.apgp_prior_candidates(T.data_ptr(), int(m), D, kind.ctypes.data, p0.ctypes.data,
+                                                 p1.ctypes.data, int(seed) & 0xFFFFFFFFFFFFFFFF, int(idx_offset),
+                                                 self._stream(torch)), "apgp_prior_candidates")
+        return T
+
     # -- on-device ensemble MCMC over the GP mean ------------------------------------
-    def sample_ensemble(self, y, initial_state, iterations, bounds, a=2.0, seed=0, store=True):
+    def sample_ensemble(self, y, initial_state, iterations, bounds, a=2.0, seed=0, store=True, prior=None):
         """Run the stretch-move ensemble sampler entirely on the device with
         log-probability = GP mean (what ApproxPosterior._gpll returns) and the box
         prior ``bounds``.  ``initial_state`` is (W, D) for one ensemble or (E, W, D)
         for E independent ensembles (one workgroup each).  Returns a dict with
         ``chain`` (iterations, E*W, D), ``log_prob`` (iterations, E*W), ``coords``,
-        ``final_log_prob`` and ``naccept``."""
+        ``final_log_prob`` and ``naccept``.
+
+        ``prior``: a :class:`~approxposterior_amd.priors.JointPrior`.  The walkers are then gated by
+        ``prior.support()`` (``bounds`` is not used) and, with ``store``, the result also has ``blobs``
+        (iterations, E*W): the prior's log-density at every stored state, NaN where it is -inf, as
+        ``ApproxPosterior._gpllBatch`` returns for a rejected walker."""
         self.recompute()
         torch, dev, lib = self._rt()
         y = self._check_dimensions(y)
@@ -1350,6 +1382,9 @@ class GP(GeorgeExtras):
         if not np.all(np.isfinite(p0)):
             raise ValueError("At least one parameter value was NaN or infinite")
         E, W, _ = p0.shape
+        if prior is not None:
+            records = self._prior_records(prior, D)
+            bounds = prior.support()
         b = np.asarray(bounds, dtype=np.float64).reshape(-1, 2)
         if len(b) != D:
             raise ValueError("bounds must have one (lo, hi) pair per dimension")
@@ -1390,6 +1425,16 @@ class GP(GeorgeExtras):
                    "naccept": nacc.cpu().numpy().reshape(E * W),
                    "chain": chain.cpu().numpy().reshape(iterations, E * W, D) if store else None,
                    "log_prob": lchain.cpu().numpy().reshape(iterations, E * W) if store else None}
+            if prior is not None and store:
+                # the lnprior blobs: one pass of the prior's log-density over the stored chain
+                lp = torch.empty(iterations * E * W, dtype=torch.float64, device=dev)
+                if iterations:
+                    kind, q0, q1 = records
+                    _lib.check(lib.apgp_prior_lnprior(chain.data_ptr(), iterations * E * W, D, kind.ctypes.data,
+                                                      q0.ctypes.data, q1.ctypes.data, lp.data_ptr(), st),
+                               "apgp_prior_lnprior")
+                blobs = lp.cpu().numpy().reshape(iterations, E * W)
+                out["blobs"] = np.where(np.isneginf(blobs), np.nan, blobs)
         return out
 
     # -- K4: gradient of the log-likelihood ------------------------------------------

@@ -5,7 +5,7 @@
 
 Mirror of the reference's ``approxposterior/utility.py`` (``logsubexp`` :69-89,
 ``AGPUtility`` :99-142, ``BAPEUtility`` :145-189, ``JonesUtility`` :192-250,
-``minimizeObjective`` :253-372) with identical names, argument order and
+``minimizeObjective`` :253-372, ``klNumerical`` :26-65) with identical names, argument order and
 sentinel values, plus the batched counterpart the reference lacks:
 :func:`sweepObjective` evaluates a utility over a whole candidate matrix in one
 fused HIP sweep (predict + variance + utility + arg-min) instead of one
@@ -22,7 +22,18 @@ from scipy.optimize import minimize
 from scipy.stats import norm
 
 __all__ = ["logsubexp", "AGPUtility", "BAPEUtility", "JonesUtility",
-           "minimizeObjective", "sweepObjective", "utilityKind"]
+           "minimizeObjective", "sweepObjective", "utilityKind", "klNumerical"]
+
+
+def klNumerical(x, p, q):
+    """Monte Carlo estimate of KL(p || q) from samples ``x`` drawn from p: the mean of
+    log(p(x) / q(x)) over the samples (Hershey & Olsen 2007); ``p`` and ``q`` are density
+    callables.  The estimate may come out negative for few samples."""
+    try:
+        res = np.sum(np.log(p(x) / q(x))) / len(x)
+    except ValueError:
+        raise ValueError("ERROR: inf/NaN encountered.  q(x) = 0 likely occured.")
+    return res
 
 
 def logsubexp(x1, x2):

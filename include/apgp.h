@@ -407,6 +407,22 @@ int apgp_ensemble_sample(const double* xs, int64_t n, const apgp_kernel_t* kern 
 int apgp_box_candidates(double* T, int64_t m, int32_t ndim, const double* lo /*host*/,
                         const double* hi /*host*/, uint64_t seed, int64_t idx_offset, void* stream);
 
+/* ---- product prior of Uniform and Gaussian factors (priors.JointPrior) ---------
+ * One record per dimension (host arrays of ndim entries, 1 <= ndim <= APGP_MAX_DIM):
+ *   kind 0 (Uniform):  p0 = low, p1 = high, finite, low < high
+ *   kind 1 (Gaussian): p0 = mu,  p1 = sigma, finite, sigma > 0
+ * apgp_prior_candidates: T (m x ndim, device) from the stream of apgp_box_candidates -- same
+ *   counter, key and pairing of dimensions, so a Uniform dimension is bit-identical to the box
+ *   draw of the same row; a Gaussian dimension is mu + (sigma sqrt 2) erfcinv(2 (1 - u)).
+ * apgp_prior_lnprior: out[i] (device) = sum_d log-density of row i of X (m x ndim, device);
+ *   -inf for a non-finite coordinate or one outside a Uniform factor's [low, high].
+ * Bad arguments are refused (-1) before anything reaches the device.                      */
+int apgp_prior_candidates(double* T, int64_t m, int32_t ndim, const int32_t* kind /*host*/,
+                          const double* p0 /*host*/, const double* p1 /*host*/, uint64_t seed,
+                          int64_t idx_offset, void* stream);
+int apgp_prior_lnprior(const double* X, int64_t m, int32_t ndim, const int32_t* kind /*host*/,
+                       const double* p0 /*host*/, const double* p1 /*host*/, double* out, void* stream);
+
 /* ---- Gaussian-mixture passes (gmmUtils.fitGMM) --------------------------------
  * One pass over X (n x ndim, row-major, device) and a fixed-order reduction into
  * stats_out (device, apgp_gmm_stats_len doubles); no atomics, same bits run to run.
