@@ -24,6 +24,14 @@ re-derived by anybody.  For N>1:
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 bench.py --gpus 8 ...
     python bench.py --gpus 8 ...        # no launcher: starts the eight ranks itself (below)
 
+A plain run sets up (fit + candidates in HBM), warms up, times the steps, dumps (``--dump-outputs``) and prints;
+the line's ``roofline`` comes from HIP events recorded during the timed steps themselves.  ``--full`` adds what
+takes runs of its own: the oracle check of the winner (``best_checked``, ``best_check``; ``--no-check`` drops it)
+and, at N=1, the host-core ``cpu_baseline`` (``--no-cpu-baseline``) and the ``fit`` / ``mid_n`` legs
+(``--no-fit-leg``).
+
+    python bench.py --gpus 1 --steps 5 --warmup 1 --full
+
 Rank 0 prints ONE JSON line.  ``--dump-outputs DIR`` additionally writes what the last timed step returned
 (``best_index.npy``, ``best_u.npy``; multi-rank runs also ``rank_records.npy``) and the sweep's per-candidate
 ``u``, ``mu``, ``var`` (``rows.npy``: which rows) for output-for-output comparisons.
@@ -34,7 +42,7 @@ as a CHILD process (never ``exec``), passes rank 0's JSON line through and exits
 Fewer than N visible devices is an error (exit 3), never a silent one-rank run; a launcher whose
 ``WORLD_SIZE`` differs from ``--gpus`` likewise (exit 4).  ``--backend gloo --share-device`` puts all N
 ranks on ``cuda:0`` with host collectives: the whole multi-rank bench (shard bounds, the sweep's device
-record, the all-gather, ``ranks_seen``, ``best_check.vs_ranks``) on a single GPU -- a rehearsal of the
+record, the all-gather, ``ranks_seen``, with ``--full`` ``best_check.vs_ranks``) on a single GPU -- a rehearsal of the
 code path, not a scaling measurement (``config.rehearsal`` says so in the line).
 """
 
@@ -485,15 +493,18 @@ def main():
                     help="total candidates per step, split over the ranks (strong scaling; 10000000 = C4)")
     ap.add_argument("--metric", type=float, default=8.0)
     ap.add_argument("--utility", default="agp")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-check", action="store_true", help="skip the oracle check of the winner")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the oracle check of the winner and (one rank) the CPU baseline "
+                         "and the fit / mid-N legs; a plain run does only what the headline needs")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-check", action="store_true", help="with --full: skip the oracle check of the winner")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
     ap.add_argument("--cpu-scalar-calls", type=int, default=2000)
     ap.add_argument("--variance", default="auto", choices=["auto", "inverse", "solve"],
                     help="predictive-variance formulation: the explicit L^-1 contraction (what 'auto' picks for this "
                          "well-conditioned workload; the headline) or the blocked substitution against L "
                          "(secondary measurement; what ill-conditioned factors get)")
-    ap.add_argument("--no-fit-leg", action="store_true", help="skip the _nll timings (GPU and oracle)")
+    ap.add_argument("--no-fit-leg", action="store_true", help="with --full: skip the _nll timings (GPU and oracle)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="collectives of a multi-rank run: RCCL over xGMI (nccl) or host collectives (gloo)")
     ap.add_argument("--share-device", action="store_true",
@@ -590,7 +601,8 @@ def main():
 
     # candidates: ONE global NumPy seed-1 draw; this rank's rows; resident in HBM before the
     # timed region (the H2D copy is reported separately)
-    mine, cands_all = candidate_rows(M_total, D, lo_row, hi_row, keep_all=(rank == 0 and not args.no_check))
+    check = args.full and not args.no_check
+    mine, cands_all = candidate_rows(M_total, D, lo_row, hi_row, keep_all=(rank == 0 and check))
     torch.cuda.synchronize()
     t0 = time.time()
     T = torch.from_numpy(mine).to(dev)
@@ -676,12 +688,13 @@ def main():
             out["roofline"]["kernel"] = out["roofline"]["kernel"].replace(", 0>", ", 2>" if N <= 2048 else ", 1>")
             out["roofline"]["traffic"] = None
             out["roofline"]["traffic_source"] = None
-        if not args.no_check:
+        # --full only: checks and measurements that take runs of their own, after the headline
+        if check:
             gpo, fit_s = oracle_gp(X, y, args.metric, D)
             chk = check_best(gpo, y, cands_all, best, records=records)
             out["best_checked"] = bool(chk["in_chunk"] and chk["vs_sample"] and chk["vs_ranks"] is not False)
             out["best_check"] = chk
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(N, D, args.metric, args.cpu_seconds, args.cpu_scalar_calls)
             # the same reference-faithful scalar path on the GPU (one candidate per predict call:
             # apgp_predict1_host), beside the oracle's scalar_path_value
@@ -693,7 +706,7 @@ def main():
             for i in range(20, 300):
                 gp.predict(y, t1[i:i + 1], return_var=True)
             out["cpu_baseline"]["scalar_path_gpu_value"] = 280.0 / (time.time() - t0)
-        if world == 1 and not args.no_fit_leg:
+        if args.full and world == 1 and not args.no_fit_leg:
             out["fit"] = fit_leg(agp, dev)
             out["mid_n"] = mid_n_leg(agp, dev)
         print(json.dumps(out))

@@ -1,6 +1,6 @@
 """MI355X: ``bench.py --gpus N`` starts its own ranks (missing 1 / weak 4).
 
-``python bench.py --gpus 2 --backend gloo --share-device ...`` -- the shape of the one command the driver runs,
+``python bench.py --gpus 2 --backend gloo --share-device --full ...`` -- the shape of the one command the driver runs,
 without a launcher -- must start two fresh rank processes (both on ``cuda:0``, host collectives), run the whole
 multi-rank bench (shard bounds, the sweep's device record, the all-gather, ``ranks_seen``, ``best_check.vs_ranks``) and
 report ``n_gpus == 2``; its winner is the winner of the single-process sweep over the same global candidate matrix.
@@ -32,7 +32,7 @@ def _run(argv, env=None):
 
 @pytest.mark.gpu
 def test_bench_gpus2_starts_two_ranks_on_one_gpu():
-    proc, lines = _run(["--gpus", "2", "--backend", "gloo", "--share-device"] + SMALL)
+    proc, lines = _run(["--gpus", "2", "--backend", "gloo", "--share-device", "--full"] + SMALL)
     assert proc.returncode == 0, proc.stderr[-3000:]
     assert len(lines) == 1, proc.stdout            # ONE JSON line, from rank 0
     two = json.loads(lines[0])
