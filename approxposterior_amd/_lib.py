@@ -12,6 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libapgp.so")
 ABI_VERSION = 8
 MAX_DIM = 32
+MAX_FANTASY = 32      # APGP_MAX_FANTASY: points per batch of GP.acquire_batch
 
 UTIL_AGP, UTIL_BAPE, UTIL_JONES, UTIL_NONE = 0, 1, 2, 3
 GMM_EM, GMM_SCORE, GMM_KMEANS = 0, 1, 2
@@ -77,6 +78,10 @@ SIGNATURES = {
     "apgp_acquire_solve": (ctypes.c_int, [_P, _I64, _I64, _P, _P, _I64, _KP, _F64, _I32,
                                           ctypes.POINTER(_F64), ctypes.POINTER(_F64), _P,
                                           _F64, _F64, _P, _P, _P, _P, _P, _P]),
+    "apgp_acquire_fantasy_work_len": (_I64, [_I64]),
+    "apgp_acquire_fantasy": (ctypes.c_int, [_P, _I64, _I64, _P, _I64, _KP, _P, _I64, _I32, _P, _I64,
+                                            _P, _P, _P, _I32, ctypes.POINTER(_F64), ctypes.POINTER(_F64), _P,
+                                            _F64, _F64, _P, _P, _P, _P]),
     "apgp_predict1_work_len": (_I64, [_I64]),
     "apgp_predict1_host": (ctypes.c_int, [_P, _P, _I64, _KP, _F64, _P, _I64, _P, _I64, _P, _P, _P]),
     "apgp_predict_mean": (ctypes.c_int, [_P, _I64, _P, _I64, _KP, _F64, _P, _P]),

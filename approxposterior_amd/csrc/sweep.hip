@@ -1250,6 +1250,206 @@ extern "C" int apgp_acquire_solve(const double* T, int64_t m, int64_t idx_offset
                         mu, var, u, part, best, stream);
 }
 
+// ---------------------------------------------------------------------------
+// Fantasy pass of a batch (apgp_acquire_fantasy; DESIGN.md "Batch design points").  Conditioning on
+// x_j at y = mu(x_j) lowers every candidate's variance by C_j(t)^2 with
+//   C_j(t) = (k(t, x_j) - k(t, X).beta_j - sum_{i<j} C_i(t) C_i(x_j)) / sqrt(s_j),
+// which costs what a mean-only prediction costs (beta_j in place of alpha): O(N D) per candidate
+// against the sweep's O(N^2).
+// One thread per candidate, FT_THREADS candidates per workgroup: the candidate's scaled coordinates
+// and its running k(t, X).beta stay in registers; the training rows and beta are staged through LDS
+// in tiles of FT_ROWS rows shared by the workgroup (all lanes of a wavefront read the same LDS words:
+// broadcasts, no bank conflicts).  Four rows per step feed apgp_exp4 (four independent fp64 chains)
+// into four partial sums.  The epilogue holds k(t, x_j), the downdate by the earlier columns, the
+// column store, v_j, the sweep's utility and gate, and the workgroup's arg-min partial.
+// ---------------------------------------------------------------------------
+#define FT_THREADS 256
+#define FT_ROWS 128        // training rows per LDS tile (divides the packed stream's 512-row padding)
+
+struct FantasyArgs {
+    const double* T;
+    const double* xs;
+    const double* beta;
+    double* C;
+    const double* mu;
+    const double* var_in;
+    double* var_out;
+    double* u;
+    const unsigned char* mask;
+    double* part_u;
+    long long* part_i;
+    long long m, idx_offset, ldc, pick_row, n;
+    int ndim, j, kind, has_box, lin_order;
+    double amp, diag_add, lin_coef, zeta, ybest;
+    double sc[APGP_MAX_DIM], lw[APGP_MAX_DIM], lo[APGP_MAX_DIM], hi[APGP_MAX_DIM];
+};
+
+template <int DPAD>
+__global__ __launch_bounds__(FT_THREADS) void fantasy_kernel(FantasyArgs a) {
+    constexpr int XS = DPAD + 2;                 // packed stream row: scaled x | alpha | 0
+    constexpr int PIECES = FT_ROWS * XS / 2;     // 16-byte pieces per tile
+    __shared__ double etab[APGP_EXP_TAB_N];
+    __shared__ __attribute__((aligned(16))) double tile[FT_ROWS * XS];   // scaled x | beta | 0
+    __shared__ double cx[APGP_MAX_FANTASY];      // C_i(x_j), i < j
+    __shared__ double su[FT_THREADS / 64];
+    __shared__ long long si[FT_THREADS / 64];
+    apgp_exp_tab_load(etab);
+    const int tid = threadIdx.x;
+    if (tid < a.j - 1) cx[tid] = a.C[(long long)tid * a.ldc + a.pick_row];
+    const long long row = (long long)blockIdx.x * FT_THREADS + tid;
+    const bool live = row < a.m;
+    double tt[DPAD];
+#pragma unroll
+    for (int d = 0; d < DPAD; ++d) tt[d] = (live && d < a.ndim) ? a.T[row * a.ndim + d] * a.sc[d] : 0.0;
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};
+    const long long ntile = (a.n + FT_ROWS - 1) / FT_ROWS;
+    for (long long ti = 0; ti < ntile; ++ti) {
+        __syncthreads();                         // the previous tile has been consumed
+        const long long r0 = ti * FT_ROWS;       // (rows < ntile * FT_ROWS <= npad: inside the packed stream)
+        for (int e = tid; e < PIECES; e += FT_THREADS) {
+            const int r = e / (XS / 2), p = e - r * (XS / 2);
+            f64x2 v;
+            if (p == DPAD / 2) {                 // the alpha slot carries beta; 0 on the padding rows
+                v.x = (r0 + r < a.n) ? a.beta[r0 + r] : 0.0;
+                v.y = 0.0;
+            } else {
+                v = *(const f64x2*)(a.xs + (r0 + r) * XS + 2 * p);
+            }
+            *(f64x2*)(tile + r * XS + 2 * p) = v;
+        }
+        __syncthreads();
+        for (int r = 0; r < FT_ROWS; r += 4) {
+            double ex[4], kv[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const double* xr = tile + (r + q) * XS;
+                double s = 0.0, s3 = 0.0;
+#pragma unroll
+                for (int d = 0; d < DPAD; d += 2) {
+                    const double df0 = tt[d] - xr[d];
+                    const double df1 = tt[d + 1] - xr[d + 1];
+                    s = fma(df0, df0, s);
+                    s3 = fma(df1, df1, s3);
+                }
+                ex[q] = -(s + s3);
+            }
+            apgp_exp4(ex, kv, etab);
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const double* xr = tile + (r + q) * XS;
+                double k = a.amp * kv[q];
+                if (a.lin_coef != 0.0) {
+                    double ls;
+                    APGP_LIN_SUM(ls, DPAD, a.ndim, a.lin_order, tt[d_] * xr[d_] * a.lw[d_]);
+                    k = fma(a.lin_coef, ls, k);
+                }
+                acc[q] = fma(k, xr[DPAD], acc[q]);
+            }
+        }
+    }
+    double bu = INFINITY;
+    long long bi = -1;
+    if (live) {
+        double xj[DPAD];
+#pragma unroll
+        for (int d = 0; d < DPAD; ++d) xj[d] = d < a.ndim ? a.T[a.pick_row * a.ndim + d] * a.sc[d] : 0.0;
+        double s = 0.0, s3 = 0.0;
+#pragma unroll
+        for (int d = 0; d < DPAD; d += 2) {
+            const double df0 = tt[d] - xj[d];
+            const double df1 = tt[d + 1] - xj[d + 1];
+            s = fma(df0, df0, s);
+            s3 = fma(df1, df1, s3);
+        }
+        double kx = a.amp * apgp_exp(-(s + s3), etab);
+        if (a.lin_coef != 0.0) {
+            double ls;
+            APGP_LIN_SUM(ls, DPAD, a.ndim, a.lin_order, tt[d_] * xj[d_] * a.lw[d_]);
+            kx = fma(a.lin_coef, ls, kx);
+        }
+        double c = kx - ((acc[0] + acc[1]) + (acc[2] + acc[3]));
+        for (int i = 0; i < a.j - 1; ++i) c = fma(-a.C[(long long)i * a.ldc + row], cx[i], c);
+        const double ch = c / sqrt(a.var_in[a.pick_row] + a.diag_add);
+        a.C[(long long)(a.j - 1) * a.ldc + row] = ch;
+        const double v = fma(-ch, ch, a.var_in[row]);
+        a.var_out[row] = v;
+        bool adm = !(a.mask && a.mask[row] == 0);
+        if (a.has_box)
+            for (int d = 0; d < a.ndim; ++d) {
+                const double x = a.T[row * a.ndim + d];
+                if (!(x >= a.lo[d] && x <= a.hi[d])) adm = false;
+            }
+        const double uu = adm ? util_value(a.kind, a.mu[row], v, a.zeta, a.ybest) : INFINITY;
+        if (a.u) a.u[row] = uu;
+        best_merge(bu, bi, uu, a.idx_offset + row);
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+        double ou = __shfl_xor(bu, o);
+        long long oi = __shfl_xor(bi, o);
+        best_merge(bu, bi, ou, oi);
+    }
+    if ((tid & 63) == 0) { su[tid >> 6] = bu; si[tid >> 6] = bi; }
+    __syncthreads();
+    if (tid == 0) {
+        for (int w = 1; w < FT_THREADS / 64; ++w) best_merge(bu, bi, su[w], si[w]);
+        a.part_u[blockIdx.x] = bu;
+        a.part_i[blockIdx.x] = bi;
+    }
+}
+
+// Scratch: the arg-min partials of the fantasy pass's workgroups (value, index) -- 2 doubles each.
+extern "C" int64_t apgp_acquire_fantasy_work_len(int64_t m) {
+    if (m < 1) return 0;
+    if (m > APGP_MAX_M) return -1;
+    return 2 * ((m + FT_THREADS - 1) / FT_THREADS);
+}
+
+extern "C" int apgp_acquire_fantasy(const double* T, int64_t m, int64_t idx_offset, const double* xs, int64_t n,
+                                    const apgp_kernel_t* kern, const double* beta, int64_t pick_row, int32_t j,
+                                    double* C, int64_t ldc, const double* mu, const double* var_in, double* var_out,
+                                    int32_t kind, const double* lo, const double* hi, const uint8_t* mask,
+                                    double zeta, double ybest, double* u, void* part, apgp_best_t* best,
+                                    void* stream) {
+    APGP_CHECK_ARG(T && xs && kern && beta && C && mu && var_in && var_out && part && best, "null pointer");
+    APGP_CHECK_ARG(m >= 1 && m <= APGP_MAX_M && n >= 1 && n <= APGP_MAX_N, "m >= 1 and n >= 1 required");
+    APGP_CHECK_ARG((m + FT_THREADS - 1) / FT_THREADS < (1ll << 31), "m too large for one grid");
+    APGP_CHECK_ARG(j >= 1 && j < APGP_MAX_FANTASY, "1 <= j < APGP_MAX_FANTASY required");
+    APGP_CHECK_ARG(pick_row >= 0 && pick_row < m, "0 <= pick_row < m required");
+    APGP_CHECK_ARG(ldc >= m, "ldc >= m required");
+    APGP_CHECK_ARG(var_in + m <= var_out || var_out + m <= var_in, "var_in and var_out must not overlap");
+    APGP_CHECK_ARG(kind >= APGP_UTIL_AGP && kind <= APGP_UTIL_JONES, "kind must be AGP, BAPE or JONES");
+    APGP_CHECK_ARG((lo == NULL) == (hi == NULL), "lo and hi must be given together");
+    KernConst kc;
+    APGP_CHECK_ARG(apgp_make_kernconst(kern, &kc) == 0, "kernel parameters");
+    FantasyArgs a;
+    a.T = T; a.xs = xs; a.beta = beta; a.C = C; a.mu = mu; a.var_in = var_in; a.var_out = var_out; a.u = u;
+    a.mask = mask;
+    const long long nblk = (m + FT_THREADS - 1) / FT_THREADS;
+    a.part_u = (double*)part;
+    a.part_i = (long long*)((double*)part + nblk);
+    a.m = m; a.idx_offset = idx_offset; a.ldc = ldc; a.pick_row = pick_row; a.n = n;
+    a.ndim = kc.ndim; a.j = j; a.kind = kind; a.has_box = lo != NULL; a.lin_order = kc.lin_order;
+    a.amp = kc.amp; a.diag_add = kc.diag_add; a.lin_coef = kc.lin_coef; a.zeta = zeta; a.ybest = ybest;
+    for (int d = 0; d < APGP_MAX_DIM; ++d) {
+        a.sc[d] = kc.sc[d];
+        a.lw[d] = kc.lw[d];
+        a.lo[d] = (lo && d < kc.ndim) ? lo[d] : 0.0;
+        a.hi[d] = (hi && d < kc.ndim) ? hi[d] : 0.0;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 grid((unsigned)nblk), block(FT_THREADS);
+    switch (kc.dpad) {
+        case 2: hipLaunchKernelGGL(fantasy_kernel<2>, grid, block, 0, s, a); break;
+        case 4: hipLaunchKernelGGL(fantasy_kernel<4>, grid, block, 0, s, a); break;
+        case 8: hipLaunchKernelGGL(fantasy_kernel<8>, grid, block, 0, s, a); break;
+        case 16: hipLaunchKernelGGL(fantasy_kernel<16>, grid, block, 0, s, a); break;
+        default: hipLaunchKernelGGL(fantasy_kernel<32>, grid, block, 0, s, a); break;
+    }
+    hipLaunchKernelGGL(argmin_final_kernel, dim3(1), dim3(1024), 0, s, a.part_u, a.part_i, nblk, best);
+    APGP_CHECK_LAUNCH();
+    return 0;
+}
+
 // Packed tiles of the substitution form, same geometry as apgp_trtri_pack's (512 x 16 tiles, MFMA
 // A-fragment order, row block ib holds chunks 0 .. 32 (ib + 1) - 1):
 //   * below the diagonal 16 x 16 block of a chunk: -L;

@@ -1182,6 +1182,123 @@ class GP(GeorgeExtras):
                               zeta=zeta, idx_offset=idx_offset)
         return res[0] if device_record else res
 
+    def acquire_batch(self, y, t, kind, q, bounds=None, mask=None, zeta=0.01, idx_offset=0, return_all=False):
+        """``q`` design points chosen jointly from the candidate matrix ``t`` (M, D; host array or device
+        tensor, as in :meth:`acquire`) by the kriging believer: pick the arg-min, pretend it was observed at
+        its predictive mean, condition on that fantasy with the hyper-parameters unchanged, pick again.
+
+        One full sweep gives mu and sigma^2 of every candidate; each later pick costs one fantasy pass
+        (``apgp_acquire_fantasy``): the mean does not move and every variance drops by a rank-one term,
+        O(N D) per candidate instead of the sweep's O(N^2).  The GP itself is not modified.
+
+        ``kind``: one utility name, or a sequence of ``q`` names (pick j uses ``kind[j]``).  Returns
+        ``(indices (q,), u (q,))`` with ``u[j]`` pick j's utility under j fantasies; index -1 and +inf for a
+        step without an admissible candidate and every step after it.  ``return_all`` adds the last step's
+        ``(u, mu, var)`` arrays.  ``q = 1`` is :meth:`acquire`: same index, same bits."""
+        if not self.computed:
+            raise RuntimeError("ERROR: Need to compute GP before using it!")
+        q = int(q)
+        if not 1 <= q <= _lib.MAX_FANTASY:
+            raise ValueError("q must be between 1 and %d (APGP_MAX_FANTASY)" % _lib.MAX_FANTASY)
+        kinds = [kind] * q if isinstance(kind, str) else list(kind)
+        if len(kinds) != q:
+            raise ValueError("kind must be one utility name or a sequence of q names")
+        kind_ids = [UTILITY_KINDS[str(k).lower()] for k in kinds]
+        torch, dev, lib = self._rt()
+        y = self._check_dimensions(y)
+        n = len(self._x)
+        ks = self._kernel_struct()
+        D = ks.ndim
+        use_solve = not self._trust_inverse()
+        idx = np.full(q, -1, dtype=np.int64)
+        ub = np.full(q, np.inf)
+        with self._on(torch, dev):
+            st = self._stream(torch)
+            if hasattr(t, "data_ptr"):
+                if t.dim() != 2 or t.shape[1] != D or not t.is_contiguous() \
+                        or str(t.dtype) != "torch.float64" or not t.is_cuda:
+                    raise ValueError("device candidates must be a contiguous (M, D) float64 CUDA tensor")
+                T = t
+            else:
+                T = torch.from_numpy(self.parse_samples(t)).to(dev)
+            m = T.shape[0]
+            if m == 0:
+                return (idx, ub, np.empty(0), np.empty(0), np.empty(0)) if return_all else (idx, ub)
+            if use_solve:
+                self._ensure_lsolve()
+            else:
+                self._ensure_linv()
+            self._ensure_xs(y)
+            f64 = dict(dtype=torch.float64, device=dev)
+            mu = torch.empty(m, **f64)
+            var = [torch.empty(m, **f64), torch.empty(m, **f64) if q > 1 else None]
+            u = torch.empty(m, **f64) if return_all else None
+            part = torch.empty(max(int(lib.apgp_acquire_work_len(m, n)), 2), **f64)
+            best = torch.empty(2, **f64)
+            lo = hi = None
+            if bounds is not None:
+                b = np.asarray(bounds, dtype=np.float64).reshape(-1, 2)
+                if len(b) != D:
+                    raise ValueError("bounds must have one (lo, hi) pair per dimension")
+                lo = (ctypes.c_double * _lib.MAX_DIM)(*b[:, 0])
+                hi = (ctypes.c_double * _lib.MAX_DIM)(*b[:, 1])
+            mask_p = None
+            if mask is not None:
+                mk = np.ascontiguousarray(np.asarray(mask).astype(np.uint8))
+                if mk.shape != (m,):
+                    raise ValueError("mask must have one entry per candidate")
+                mask_d = torch.from_numpy(mk).to(dev)
+                mask_p = mask_d.data_ptr()
+            ybest = float(np.max(y))
+            args = (ctypes.byref(ks), float(self.mean.value), kind_ids[0], lo, hi, mask_p, float(zeta), ybest,
+                    mu.data_ptr(), var[0].data_ptr(), u.data_ptr() if u is not None else None,
+                    part.data_ptr(), best.data_ptr(), st)
+            if use_solve:
+                _lib.check(lib.apgp_acquire_solve(T.data_ptr(), m, int(idx_offset), self._packed_solve.data_ptr(),
+                                                  self._xs.data_ptr(), n, *args), "apgp_acquire_solve")
+            else:
+                _lib.check(lib.apgp_acquire(T.data_ptr(), m, int(idx_offset), self._packed.data_ptr(),
+                                            self._xs.data_ptr(), n, *args), "apgp_acquire")
+            if q > 1:
+                C = torch.empty((q - 1) * m, **f64)          # column-major, ldc = m: column j - 1 holds C_j
+                fpart = torch.empty(max(int(lib.apgp_acquire_fantasy_work_len(m)), 2), **f64)
+                krow = torch.empty(n, **f64)
+                z = torch.empty(n, **f64)
+                beta = torch.empty(n, **f64)
+                ss = torch.empty(1, **f64)
+            cur = 0
+            for j in range(q):
+                bb = best.cpu().numpy()                      # the 16-byte record of the last sweep / pass
+                bi = int(bb[1:2].view(np.int64)[0])
+                if bi < 0:
+                    break
+                idx[j], ub[j] = bi, float(bb[0])
+                if j == q - 1:
+                    break
+                r = bi - int(idx_offset)
+                ybest = max(ybest, float(mu[r].item()))      # (Jones: the fantasy joins the observed values)
+                # beta_j = K^-1 k(X, x_j): the cross row from the candidate row in HBM, two solves against the factor
+                _lib.check(lib.apgp_kernel_cross(T.data_ptr() + 8 * r * D, 1, self._x_d.data_ptr(), n,
+                                                 ctypes.byref(ks), krow.data_ptr(), n, st), "apgp_kernel_cross")
+                for trans, src, dst in ((0, krow, z), (1, z, beta)):
+                    _lib.check(lib.apgp_trsv(self._L.data_ptr(), n, self._ld, src.data_ptr(), 0.0, trans,
+                                             dst.data_ptr(), ss.data_ptr(), st), "apgp_trsv(fantasy)")
+                    if float(ss.item()) != float(ss.item()):
+                        # NaN: the persistent solve could not get its workgroups resident (see _solve) -- once more,
+                        # a launch per 256 rows for this call only
+                        _lib.check(lib.apgp_trsv_ex(self._L.data_ptr(), n, self._ld, src.data_ptr(), 0.0, trans,
+                                                    dst.data_ptr(), None, 1, st), "apgp_trsv(fantasy, multi-launch)")
+                _lib.check(lib.apgp_acquire_fantasy(T.data_ptr(), m, int(idx_offset), self._xs.data_ptr(), n,
+                                                    ctypes.byref(ks), beta.data_ptr(), r, j + 1, C.data_ptr(), m,
+                                                    mu.data_ptr(), var[cur].data_ptr(), var[1 - cur].data_ptr(),
+                                                    kind_ids[j + 1], lo, hi, mask_p, float(zeta), ybest,
+                                                    u.data_ptr() if u is not None else None, fpart.data_ptr(),
+                                                    best.data_ptr(), st), "apgp_acquire_fantasy")
+                cur = 1 - cur
+            if return_all:
+                return idx, ub, u.cpu().numpy(), mu.cpu().numpy(), var[cur].cpu().numpy()
+        return idx, ub
+
     def _sweep(self, y, cand, kind, want, bounds=None, mask=None, zeta=0.01, idx_offset=0,
                cand_device=None):
         torch, dev, lib = self._rt()

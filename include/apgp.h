@@ -329,6 +329,33 @@ int apgp_acquire_solve(const double* T, int64_t m, int64_t idx_offset,
                        double* mu, double* var, double* u,
                        void* part, apgp_best_t* best, void* stream);
 
+/* ---- fantasy update of a sweep (batch design points, kriging believer) -----------
+ * After a sweep over T (mu, var = v_0 written) and picks x_1 .. x_j, conditioning the GP on
+ * x_j = T[pick_row] observed at y = mu(x_j) (hyper-parameters unchanged) leaves mu as it is
+ * and lowers every candidate's variance by a rank-one term.  One pass, for step j:
+ *   s_j   = var_in[pick_row] + kern->diag_add                           (read on the device)
+ *   c(t)  = k(t, x_j) - k(t, X).beta - sum_{i<j} C_i(t) C_i(x_j)        beta = K^-1 k(X, x_j)
+ *   C_j   = c / sqrt(s_j)            -> column j - 1 of C (C_i lives in column i - 1)
+ *   v_j   = var_in - C_j^2           -> var_out
+ *   u     = utility(kind)(mu, v_j), +inf outside [lo, hi] / where mask == 0, arg-min into best
+ * with the sweep's utility formulas, gate and arg-min contract (ties -> lowest index, NaN never
+ * wins).  T: m x ndim; xs: packed training stream (its alpha column is not read); beta: n
+ * (apgp_kernel_cross + two apgp_trsv); C: column-major, ldc >= m, at least j columns.
+ * var_in and var_out must not alias (the pass reads var_in[pick_row] while it writes var_out:
+ * callers ping-pong two buffers).  ybest (Jones): max(y, mu(x_1), .., mu(x_j)).  u may be NULL.
+ * 1 <= j < APGP_MAX_FANTASY: a batch holds at most APGP_MAX_FANTASY points.  kind: AGP / BAPE /
+ * JONES.  part: apgp_acquire_fantasy_work_len(m) doubles, 16-byte aligned.
+ * Added in ABI 8 without changing anything before it: APGP_ABI_VERSION stays 8.              */
+#define APGP_MAX_FANTASY 32
+int64_t apgp_acquire_fantasy_work_len(int64_t m);
+int apgp_acquire_fantasy(const double* T, int64_t m, int64_t idx_offset,
+                         const double* xs, int64_t n, const apgp_kernel_t* kern /*host*/,
+                         const double* beta, int64_t pick_row, int32_t j, double* C, int64_t ldc,
+                         const double* mu, const double* var_in, double* var_out,
+                         int32_t kind, const double* lo /*host*/, const double* hi /*host*/,
+                         const uint8_t* mask, double zeta, double ybest,
+                         double* u, void* part, apgp_best_t* best, void* stream);
+
 /* ---- ONE candidate: george GP.predict(y, t[1 x D], return_var=True) ----------
  * What the reference's scalar utilities evaluate once per Nelder-Mead step
  * (utility.py:131,178,224 <- minimizeObjective, utility.py:336-372; the default
