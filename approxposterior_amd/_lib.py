@@ -15,6 +15,12 @@ MAX_DIM = 32
 MAX_FANTASY = 32      # APGP_MAX_FANTASY: points per batch of GP.acquire_batch
 
 UTIL_AGP, UTIL_BAPE, UTIL_JONES, UTIL_NONE = 0, 1, 2, 3
+UTIL_NEG_MEAN = 4     # -mu (ApproxPosterior.findMAP's objective): apgp_nm_search only
+NM_MAX_RESTARTS = 4096
+NM_MAX_FEV = 1 << 20
+# APGP_NM_STEP_*: the step of one Nelder-Mead iteration in apgp_nm_search's trace
+NM_STEPS = {1: "reflect", 2: "expand", 3: "reflect_exp", 4: "contract_out", 5: "contract_in",
+            6: "shrink_out", 7: "shrink_in", 8: "maxfev"}
 GMM_EM, GMM_SCORE, GMM_KMEANS = 0, 1, 2
 GMM_MAX_COMP = 16
 
@@ -33,6 +39,14 @@ class KernelStruct(ctypes.Structure):
 class BestStruct(ctypes.Structure):
     """``apgp_best_t``."""
     _fields_ = [("u", ctypes.c_double), ("index", ctypes.c_int64)]
+
+
+class NmOptions(ctypes.Structure):
+    """``apgp_nm_options_t``."""
+    _fields_ = [("kind", ctypes.c_int32), ("maxiter", ctypes.c_int32), ("maxfev", ctypes.c_int32),
+                ("reserved", ctypes.c_int32), ("zeta", ctypes.c_double), ("ybest", ctypes.c_double),
+                ("xatol", ctypes.c_double), ("fatol", ctypes.c_double), ("rho", ctypes.c_double),
+                ("chi", ctypes.c_double), ("psi", ctypes.c_double), ("sigma", ctypes.c_double)]
 
 
 _P = ctypes.c_void_p
@@ -84,6 +98,10 @@ SIGNATURES = {
                                             _F64, _F64, _P, _P, _P, _P]),
     "apgp_predict1_work_len": (_I64, [_I64]),
     "apgp_predict1_host": (ctypes.c_int, [_P, _P, _I64, _KP, _F64, _P, _I64, _P, _I64, _P, _P, _P]),
+    "apgp_nm_search_work_len": (_I64, [_I64, _I64]),
+    "apgp_nm_search": (ctypes.c_int, [_P, _I64, _P, _I64, _KP, _F64, _P, _I64, _P, _I64,
+                                      ctypes.POINTER(_F64), ctypes.POINTER(_F64), ctypes.POINTER(NmOptions),
+                                      _P, _P, _P, _P, _P, _P, _P]),
     "apgp_predict_mean": (ctypes.c_int, [_P, _I64, _P, _I64, _KP, _F64, _P, _P]),
     "apgp_predict_mean_host": (ctypes.c_int, [_P, _I64, _P, _I64, _KP, _F64, _P, _P, _P]),
     "apgp_ensemble_sample": (ctypes.c_int, [_P, _I64, _KP, _F64, ctypes.POINTER(_F64), ctypes.POINTER(_F64),

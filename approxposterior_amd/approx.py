@@ -140,6 +140,7 @@ class ApproxPosterior(object):
                  algorithm="bape", distributed=None, group=None):
         self.distributed, self.group = distributed, group
         self.deviceCandidates = False      # nCandidates drawn on the device (see findNextPoint)
+        self.deviceSearch = False          # the Nelder-Mead point search runs on the device (see findNextPoint)
         if theta is None or y is None:
             raise ValueError("Must supply both theta and y for initial GP training set.")
         self.theta = np.array(theta).squeeze()
@@ -275,19 +276,21 @@ class ApproxPosterior(object):
         replicated and rank 0's answer kept."""
         scalarArgs = (self.y, self.gp, self._lnprior)
         ranks = self._ranks()
+        joint = self._jointPrior()
+        # the device gate (sweep and point search): the reference's utilities return +inf exactly where lnprior is not
+        # finite, which for a JointPrior is outside its support (infinite edges on Gaussian dimensions)
+        gate = self.bounds if joint is None else [tuple(r) for r in joint.support()]
+        # (the device point search is gated by `gate`; the host search forwards `bounds` as the reference does)
+        searchBounds = gate if self.deviceSearch else self.bounds
         if nCandidates is None:
             point, value = ut.minimizeObjective(utility, self.y, self.gp, sampleFn=self.priorSample,
                                                 priorFn=self._lnprior, nRestarts=nRestarts, method=method,
-                                                options=options, bounds=self.bounds, theta0=theta0,
-                                                args=scalarArgs)
+                                                options=options, bounds=searchBounds, theta0=theta0,
+                                                args=scalarArgs, onDevice=self.deviceSearch)
             return self._agree(point, value) if ranks is not None else (point, value)
         total = int(nCandidates)
         kind = ut.utilityKind(utility) if (ranks is not None or self.deviceCandidates) else None
         lo, hi = apdist.shard_bounds(total, ranks[1], ranks[0]) if ranks is not None else (0, total)
-        joint = self._jointPrior()
-        # the sweep's gate: the reference's utilities return +inf exactly where lnprior is not finite, which for a
-        # JointPrior is outside its support (infinite edges on Gaussian dimensions)
-        gate = self.bounds if joint is None else [tuple(r) for r in joint.support()]
         if self.deviceCandidates and joint is not None:
             # drawn from the prior itself on the device (same stream as box_candidates); the winning row alone is
             # regenerated below
@@ -319,7 +322,8 @@ class ApproxPosterior(object):
             point, value = ut.minimizeObjective(utility, self.y, self.gp,
                                                 sampleFn=self.priorSample, priorFn=self._lnprior,
                                                 nRestarts=1, method=method, options=options,
-                                                bounds=self.bounds, theta0=point, args=scalarArgs)
+                                                bounds=searchBounds, theta0=point, args=scalarArgs,
+                                                onDevice=self.deviceSearch)
             if ranks is not None:
                 point, value = self._agree(point, value)
         return point, value
@@ -375,7 +379,7 @@ class ApproxPosterior(object):
                       runName="apRun", numNewPoints=1, optGPEveryN=1,
                       gpHyperPrior=gpUtils.defaultHyperPrior, args=None,
                       nCandidates=None, polish=False, deviceCandidates=None, batchSize=None, pool=None,
-                      **kwargs):
+                      deviceSearch=None, **kwargs):
         """Select ``numNewPoints`` design points by minimising the (negative) utility;
         with ``computeLnLike`` evaluate the forward model at each, absorb it into the
         training set / GP and re-fit the hyper-parameters every ``optGPEveryN`` points
@@ -398,6 +402,14 @@ class ApproxPosterior(object):
         ``concurrent.futures`` executor), else serially in pick order.  They are then absorbed in pick order,
         the GP is re-fitted once per batch when a point of the batch meets the ``optGPEveryN`` rule, and the
         cache is written after each batch.  ``batchSize=1`` is the plain ``nCandidates`` search.
+
+        ``deviceSearch=True`` (opt-in; kept on the object like ``deviceCandidates``) runs the Nelder-Mead point search
+        -- the default without ``nCandidates``, and ``polish`` after a sweep -- on the device: all ``nMinObjRestarts``
+        restarts in one launch (``utility.minimizeObjective(onDevice=True)``, :meth:`GP.nelder_mead_search`), same
+        simplex arithmetic as SciPy.  The device evaluates the utility inside ``bounds`` -- or inside
+        ``lnprior.support()`` when ``lnprior`` is a :class:`~approxposterior_amd.priors.JointPrior` -- and +inf
+        outside: it assumes the prior is that box or support.  The solutions are still checked with ``lnprior`` on
+        the host.  Under a process group the search is replicated and rank 0's answer kept, as on the host.
         """
         if batchSize is not None:
             if nCandidates is None:
@@ -411,6 +423,8 @@ class ApproxPosterior(object):
                                           "row's fantasy columns broadcast from the rank that owns it")
         if deviceCandidates is not None:
             self.deviceCandidates = bool(deviceCandidates)
+        if deviceSearch is not None:
+            self.deviceSearch = bool(deviceSearch)
         assert isinstance(numNewPoints, int) and numNewPoints >= 1
         assert isinstance(optGPEveryN, int) and optGPEveryN >= 1
         if verbose and numNewPoints < optGPEveryN:
@@ -652,7 +666,7 @@ class ApproxPosterior(object):
             gpHyperPrior=gpUtils.defaultHyperPrior, eps=1.0, convergenceCheck=False,
             minObjMethod="nelder-mead", minObjOptions=None, args=None,
             nCandidates=None, onDevice=False, batched=True, deviceCandidates=None, batchSize=None, pool=None,
-            **kwargs):
+            deviceSearch=None, **kwargs):
         """BAPE / AGP outer loop (approx.py:229-524): ``nmax`` times, find ``m`` design
         points (re-fitting the GP every ``optGPEveryN``), sample the surrogate posterior,
         record burn-in / thinning, and -- with ``convergenceCheck`` -- stop once the
@@ -662,7 +676,8 @@ class ApproxPosterior(object):
         ``nCandidates`` switches the point search to the fused device sweep
         (``deviceCandidates``: drawn on the device, see :meth:`findNextPoint`);
         ``onDevice`` / ``batched`` are passed to :meth:`runMCMC`; ``batchSize`` / ``pool`` to
-        :meth:`findNextPoint` (design points chosen and their forward models run in batches)."""
+        :meth:`findNextPoint` (design points chosen and their forward models run in batches), and ``deviceSearch``
+        (the Nelder-Mead point search on the device)."""
         if convergenceCheck and onlyLastMCMC:
             raise RuntimeError("If convergenceCheck is True, must run an MCMC each iteration.\n"
                                "convergenceCheck = %d onlyLastMCMC = %d" % (convergenceCheck, onlyLastMCMC))
@@ -691,7 +706,7 @@ class ApproxPosterior(object):
                                minObjMethod=minObjMethod, minObjOptions=minObjOptions,
                                runName=runName, theta0=None, args=args, verbose=verbose,
                                nCandidates=nCandidates, deviceCandidates=deviceCandidates, batchSize=batchSize,
-                               pool=pool, **fit, **kwargs)
+                               pool=pool, deviceSearch=deviceSearch, **fit, **kwargs)
             if timing:
                 self.trainingTime.append(time.time() - clock)
             if cache:
@@ -725,10 +740,12 @@ class ApproxPosterior(object):
                 break
 
     # ----------------------------------------------------------------------------- MAP
-    def findMAP(self, theta0=None, method="nelder-mead", options=None, nRestarts=15):
+    def findMAP(self, theta0=None, method="nelder-mead", options=None, nRestarts=15, deviceSearch=None):
         """Maximum of the function the GP has learned: minimise minus the GP mean from
         ``nRestarts`` starts around ``theta0`` (default: the best training point)
-        (approx.py:862-926).  Returns ``(MAP, MAPVal)``."""
+        (approx.py:862-926).  Returns ``(MAP, MAPVal)``.
+        ``deviceSearch`` (default: the object's ``deviceSearch``) runs the restarts on the device
+        over -mu, gated by ``bounds`` or the JointPrior's support (see :meth:`findNextPoint`)."""
         if theta0 is None:
             start = self.theta[np.argmax(self.y)]
         else:
@@ -738,13 +755,20 @@ class ApproxPosterior(object):
 
         def minusMean(x):
             return -(self._gpll(x)[0]) if np.isfinite(self._lnprior(x)) else np.inf
+        minusMean.searchKind = "negmean"           # -mu on the device (utility.searchKind)
 
+        onDevice = self.deviceSearch if deviceSearch is None else bool(deviceSearch)
+        joint = self._jointPrior()
+        if onDevice:
+            bounds = self.bounds if joint is None else [tuple(r) for r in joint.support()]
+        else:
+            bounds = self.bounds
         if self._ranks() is not None:
             apdist.sync_random_state(0, self.group, enabled=self.distributed)
         best, value = ut.minimizeObjective(minusMean, self.y, self.gp, self.priorSample,
                                            self._lnprior, nRestarts=nRestarts, args=None,
-                                           method=method, options=options, bounds=self.bounds,
-                                           theta0=start)
+                                           method=method, options=options, bounds=bounds,
+                                           theta0=start, onDevice=onDevice)
         if self._ranks() is not None:
             best, value = self._agree(best, value)
         return best, -value
@@ -755,12 +779,13 @@ class ApproxPosterior(object):
                  gpOptions=None, gpP0=None, optGPEveryN=1, nGPRestarts=1,
                  nMinObjRestarts=5, initGPOpt=True, minObjMethod="nelder-mead",
                  gpHyperPrior=gpUtils.defaultHyperPrior, minObjOptions=None,
-                 findMAP=True, args=None, nCandidates=None, deviceCandidates=None, **kwargs):
+                 findMAP=True, args=None, nCandidates=None, deviceCandidates=None, deviceSearch=None, **kwargs):
         """Bayesian optimisation (approx.py:929-1151): one design point per iteration by
         the object's utility (use algorithm="jones"), optionally the MAP of the GP mean
         after each, stop after ``kmax`` consecutive iterations whose best value changed
         by less than ``tol``.  Returns the reference's solution dictionary (thetaBest,
-        valBest, thetas, vals, nev [, thetasMAP, valsMAP, thetaMAPBest, valMAPBest])."""
+        valBest, thetas, vals, nev [, thetasMAP, valsMAP, thetaMAPBest, valMAPBest]).
+        ``deviceSearch`` runs the point searches and the MAP searches on the device (see :meth:`findNextPoint`)."""
         verbose, cache = verbose and self._chief(), cache and self._chief()
         if cache:
             np.savez(_cacheName(runName, "APFModelCache"), theta=self.theta, y=self.y)
@@ -783,7 +808,7 @@ class ApproxPosterior(object):
                                               minObjMethod=minObjMethod, minObjOptions=minObjOptions,
                                               runName=runName, args=args, verbose=verbose,
                                               nCandidates=nCandidates, deviceCandidates=deviceCandidates,
-                                              **fit, **kwargs)
+                                              deviceSearch=deviceSearch, **fit, **kwargs)
             evaluations = iteration + 1
             if verbose:
                 print("Forward model evaluation at: ", point, ", function value: ", value)

@@ -6,6 +6,7 @@
 #include "apgp_common.h"
 #include "mma16.h"
 #include "scratch.h"
+#include "pred1_body.h"
 #include <atomic>
 #include <chrono>
 #include <mutex>
@@ -987,58 +988,16 @@ __global__ __launch_bounds__(1024) void pred1_final_kernel(Pred1Args a) {
 // (the other twelve wavefront partials are zeros) -- so (mu, sigma^2) carry the same bits.
 template <int DPAD>
 __global__ __launch_bounds__(256) void pred1_small_kernel(Pred1Args a, const double* W, long long ldw) {
-    constexpr int XS = DPAD + 2;
     __shared__ double etab[APGP_EXP_TAB_N];
     __shared__ double red[4], red2[4];
     __shared__ __attribute__((aligned(16))) double ks[256];
     __shared__ double vs[256];
     apgp_exp_tab_load(etab);
     __syncthreads();
-    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-    const long long n = a.n;
-    double contrib = 0.0, kv = 0.0;
-    if (t < n) {
-        const double* xr = a.xs + (long long)t * XS;
-        double s = 0.0, s3 = 0.0;
-#pragma unroll
-        for (int d = 0; d < DPAD; d += 2) {
-            const double df0 = a.tt[d] - xr[d], df1 = a.tt[d + 1] - xr[d + 1];
-            s = fma(df0, df0, s);
-            s3 = fma(df1, df1, s3);
-        }
-        kv = a.amp * apgp_exp(-(s + s3), etab);
-        if (a.lin_coef != 0.0) {
-            double ls;
-            APGP_LIN_SUM(ls, DPAD, a.ndim, a.lin_order, a.tt[d_] * xr[d_] * a.lw[d_]);
-            kv = fma(a.lin_coef, ls, kv);
-        }
-        contrib = kv * xr[DPAD];                       // k* alpha
-    }
-    ks[t] = kv;
-    for (int o = 32; o > 0; o >>= 1) contrib += __shfl_xor(contrib, o);
-    if (lane == 0) red[w] = contrib;
-    __syncthreads();
-    // v = W k*: one wavefront per row, as winv_gemv_kernel (shift 0)
-    for (long long i = w; i < n; i += 4) {
-        const double* wr = W + i * ldw;
-        double s0 = 0.0, s1 = 0.0;
-        for (long long k = 2 * lane; k <= i; k += 128) {
-            const f64x2 w2 = *(const f64x2*)(wr + k);
-            s0 = fma(w2.x, ks[k] - 0.0, s0);
-            if (k + 1 <= i) s1 = fma(w2.y, ks[k + 1] - 0.0, s1);
-        }
-        double s = s0 + s1;
-        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-        if (lane == 0) vs[i] = s;
-    }
-    __syncthreads();
-    // sum v^2: virtual thread t of pred1_final_kernel's 1,024
-    double sq = 0.0;
-    if (t < n) sq = fma(vs[t], vs[t], sq);
-    for (int o = 32; o > 0; o >>= 1) sq += __shfl_xor(sq, o);
-    if (lane == 0) red2[w] = sq;
-    __syncthreads();
-    if (t != 0) return;
+    // (the body is shared with the device point search, nmsearch.hip: pred1_body.h)
+    apgp_pred1_small_body<DPAD>(a.xs, a.n, a.tt, a.lw, a.amp, a.lin_coef, a.ndim, a.lin_order, W, ldw, etab, red, red2,
+                                ks, vs);
+    if (threadIdx.x != 0) return;
     double q = 0.0;
     for (int i = 0; i < 4; ++i) q += red2[i];              // (+ twelve zero partials)
     double mu = 0.0;

@@ -30,6 +30,7 @@
 #include "apgp_common.h"
 #include "mma16.h"
 #include "scratch.h"
+#include "util_value.h"             // util_value: the utilities, shared with nmsearch.hip
 #include <chrono>
 #include <mutex>
 #include <stdlib.h>
@@ -75,30 +76,6 @@ struct SweepArgs {
     double mean, amp, zeta, ybest, lin_coef;
     double sc[APGP_MAX_DIM], lo[APGP_MAX_DIM], hi[APGP_MAX_DIM], lw[APGP_MAX_DIM];
 };
-
-__device__ __forceinline__ double util_value(int kind, double mu, double var, double zeta,
-                                             double ybest) {
-    if (kind == APGP_UTIL_AGP) {
-        // utility.py:136  -(mu + 0.5*log(2*pi*e*var)); var < 0 -> NaN as in NumPy
-        return -(mu + 0.5 * log(2.0 * M_PI * M_E * var));
-    } else if (kind == APGP_UTIL_BAPE) {
-        // utility.py:183 with logsubexp(var, 0) (utility.py:85-88):
-        // var <= 0 -> -inf -> utility +inf; else var + log(1 - exp(-var))
-        double lse = (var <= 0.0) ? -INFINITY : var + log(1.0 - exp(0.0 - var));
-        return -((2.0 * mu + var) + lse);
-    } else {
-        // utility.py:229-244; std <= 0 or NaN -> 0.0
-        double sd = sqrt(var);
-        if (sd > 0.0) {
-            double imp = mu - ybest - zeta;
-            double z = imp / sd;
-            double cdf = 0.5 * erfc(-z * M_SQRT1_2);
-            double pdf = exp(-0.5 * z * z) * 0.3989422804014326779399461;
-            return -(imp * cdf + sd * pdf);
-        }
-        return 0.0;
-    }
-}
 
 __device__ __forceinline__ void best_merge(double& bu, long long& bi, double u, long long i) {
     // NaN and +inf (inadmissible) never win; ties resolve to the lowest global index

@@ -41,6 +41,35 @@ __all__ = ["GP", "ExpSquaredKernel", "ConstantKernel", "Product", "ConstantModel
            "kernels", "UTILITY_KINDS"]
 
 UTILITY_KINDS = {"agp": _lib.UTIL_AGP, "bape": _lib.UTIL_BAPE, "jones": _lib.UTIL_JONES}
+# objectives of the device point search (GP.nelder_mead_search): the utilities and -mu (ApproxPosterior.findMAP)
+SEARCH_KINDS = dict(UTILITY_KINDS, negmean=_lib.UTIL_NEG_MEAN)
+NM_OPTIONS = ("adaptive", "maxiter", "maxfev", "xatol", "fatol")
+
+
+def nm_coefficients(ndim, adaptive):
+    """(rho, chi, psi, sigma) of SciPy's Nelder-Mead, computed as SciPy 1.15 computes them (same bits)."""
+    if adaptive:
+        dim = float(ndim)
+        return 1.0, 1 + 2 / dim, 0.75 - 1 / (2 * dim), 1 - 1 / dim
+    return 1.0, 2.0, 0.5, 0.5
+
+
+def nm_limits(ndim, maxiter=None, maxfev=None):
+    """SciPy's (maxiter, maxfev) defaults (N * 200 when neither is given; the other one unbounded when one is).  An
+    unbounded maxfev becomes the most evaluations ``maxiter`` iterations can make (N + 1, then at most N + 2 per
+    iteration), an unbounded maxiter the most iterations ``maxfev`` evaluations allow: the search stops where SciPy's
+    does."""
+    if maxiter is None and maxfev is None:
+        maxiter = maxfev = ndim * 200
+    elif maxiter is None:
+        maxiter = ndim * 200 if maxfev == np.inf else np.inf
+    elif maxfev is None:
+        maxfev = ndim * 200 if maxiter == np.inf else np.inf
+    if maxfev == np.inf:
+        maxfev = (ndim + 1) + (int(maxiter) - 1) * (ndim + 2)
+    if maxiter == np.inf:
+        maxiter = int(maxfev)
+    return int(maxiter), int(maxfev)
 
 
 class _NullContext(object):
@@ -1181,6 +1210,95 @@ class GP(GeorgeExtras):
             res = self._sweep(y, xs, kind=kind_id, want=want, bounds=bounds, mask=mask,
                               zeta=zeta, idx_offset=idx_offset)
         return res[0] if device_record else res
+
+    def nelder_mead_search(self, y, starts, kind, bounds=None, zeta=0.01, options=None, trace=False):
+        """SciPy's Nelder-Mead (``bounds=None``) from every row of ``starts`` (R, D) at once on the device
+        (``apgp_nm_search``: one workgroup per restart, one launch) over the objective ``kind``: "agp", "bape",
+        "jones" (the utilities of :mod:`utility`; Jones with ``zeta`` and max(y)) or "negmean" (-mu, +inf where mu is
+        not finite).  The objective is +inf where a coordinate is not finite or lies outside ``bounds`` (the box prior;
+        None: no box).  sigma^2 comes from the dense inverse or from the factor by the usual gate (``variance_mode`` /
+        the condition estimate); through the inverse at N <= 256 every (mu, sigma^2) is ``predict``'s, bit for bit.
+
+        ``options``: SciPy's ``adaptive``, ``maxiter``, ``maxfev``, ``xatol``, ``fatol`` (any other key raises
+        ``ValueError``; None = SciPy's defaults).  Returns ``(x (R, D), fun (R,), nfev (R,), nit (R,), status (R,))``;
+        with ``trace`` also a list of one dict per restart: ``x`` (nfev, D), ``mu``, ``var``, ``u`` (nfev,) of every
+        evaluation in order (mu = var = NaN where the box refused the point) and ``steps`` (the step of each
+        iteration, ``_lib.NM_STEPS`` codes)."""
+        try:
+            kid = SEARCH_KINDS[str(kind).lower()]
+        except KeyError:
+            raise ValueError("kind must be one of %s" % sorted(SEARCH_KINDS))
+        opts = dict(options or {})
+        unknown = sorted(set(opts) - set(NM_OPTIONS))
+        if unknown:
+            raise ValueError("the device Nelder-Mead search does not take the option(s) %s (it takes %s)"
+                             % (unknown, ", ".join(NM_OPTIONS)))
+        if not self.computed:
+            raise RuntimeError("ERROR: Need to compute GP before using it!")
+        self.recompute()
+        torch, dev, lib = self._rt()
+        y = self._check_dimensions(y)
+        n = len(self._x)
+        ks = self._kernel_struct()
+        D = ks.ndim
+        X0 = np.ascontiguousarray(np.asarray(starts, dtype=np.float64).reshape(-1, D))
+        R = len(X0)
+        if not 1 <= R <= _lib.NM_MAX_RESTARTS:
+            raise ValueError("between 1 and %d restarts per call" % _lib.NM_MAX_RESTARTS)
+        rho, chi, psi, sigma = nm_coefficients(D, bool(opts.get("adaptive", False)))
+        maxiter, maxfev = nm_limits(D, opts.get("maxiter"), opts.get("maxfev"))
+        if not (1 <= maxiter <= _lib.NM_MAX_FEV and 1 <= maxfev <= _lib.NM_MAX_FEV):
+            raise ValueError("maxiter and maxfev must lie between 1 and %d" % _lib.NM_MAX_FEV)
+        opt = _lib.NmOptions(kind=kid, maxiter=maxiter, maxfev=maxfev, reserved=0, zeta=float(zeta),
+                             ybest=float(np.max(y)), xatol=float(opts.get("xatol", 1e-4)),
+                             fatol=float(opts.get("fatol", 1e-4)), rho=rho, chi=chi, psi=psi, sigma=sigma)
+        lo = hi = None
+        if bounds is not None:
+            b = np.asarray(bounds, dtype=np.float64).reshape(-1, 2)
+            if len(b) != D:
+                raise ValueError("bounds must have one (lo, hi) pair per dimension")
+            lo = (ctypes.c_double * _lib.MAX_DIM)(*b[:, 0])
+            hi = (ctypes.c_double * _lib.MAX_DIM)(*b[:, 1])
+        use_solve = not self._trust_inverse()
+        with self._on(torch, dev):
+            st = self._stream(torch)
+            if not use_solve:
+                self._ensure_linv()
+            self._ensure_xs(y)
+            f64 = dict(dtype=torch.float64, device=dev)
+            i32 = dict(dtype=torch.int32, device=dev)
+            starts_d = torch.from_numpy(X0).to(dev)
+            x_out = torch.empty((R, D), **f64)
+            f_out = torch.empty(R, **f64)
+            stats = torch.zeros((R, 3), **i32)
+            work = torch.empty(int(lib.apgp_nm_search_work_len(R, n)), **f64)
+            tr = torch.empty(R * maxfev * (D + 3), **f64) if trace else None
+            steps = torch.zeros(R * maxiter, **i32) if trace else None
+            if use_solve:
+                inv = (None, 0, self._L.data_ptr(), self._ld)
+            else:
+                inv = (self._work.data_ptr(), (n + 63) // 64 * 64, None, 0)
+            _lib.check(lib.apgp_nm_search(starts_d.data_ptr(), R, self._xs.data_ptr(), n, ctypes.byref(ks),
+                                          float(self.mean.value), *inv, lo, hi, ctypes.byref(opt),
+                                          x_out.data_ptr(), f_out.data_ptr(), stats.data_ptr(),
+                                          tr.data_ptr() if tr is not None else None,
+                                          steps.data_ptr() if steps is not None else None, work.data_ptr(), st),
+                       "apgp_nm_search")
+            x = x_out.cpu().numpy()
+            fun = f_out.cpu().numpy()
+            sts = stats.cpu().numpy()
+            if trace:
+                trh = tr.cpu().numpy().reshape(R, maxfev, D + 3)
+                sth = steps.cpu().numpy().reshape(R, maxiter)
+        nfev, nit, status = sts[:, 0].copy(), sts[:, 1].copy(), sts[:, 2].copy()
+        if not trace:
+            return x, fun, nfev, nit, status
+        recs = []
+        for r in range(R):
+            rec = trh[r, :nfev[r]]
+            recs.append({"x": rec[:, :D].copy(), "mu": rec[:, D].copy(), "var": rec[:, D + 1].copy(),
+                         "u": rec[:, D + 2].copy(), "steps": [int(s) for s in sth[r] if s != 0]})
+        return x, fun, nfev, nit, status, recs
 
     def acquire_batch(self, y, t, kind, q, bounds=None, mask=None, zeta=0.01, idx_offset=0, return_all=False):
         """``q`` design points chosen jointly from the candidate matrix ``t`` (M, D; host array or device

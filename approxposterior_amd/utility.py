@@ -22,7 +22,7 @@ from scipy.optimize import minimize
 from scipy.stats import norm
 
 __all__ = ["logsubexp", "AGPUtility", "BAPEUtility", "JonesUtility",
-           "minimizeObjective", "sweepObjective", "utilityKind", "klNumerical"]
+           "minimizeObjective", "sweepObjective", "utilityKind", "searchKind", "klNumerical"]
 
 
 def klNumerical(x, p, q):
@@ -97,9 +97,19 @@ def utilityKind(fn):
         raise ValueError("the batched sweep supports AGPUtility, BAPEUtility and JonesUtility")
 
 
+def searchKind(fn):
+    """The objective kind of the device point search (:meth:`GP.nelder_mead_search`) for ``fn``: the
+    utility's (:func:`utilityKind`), or the kind a function declares in its ``searchKind`` attribute
+    (``ApproxPosterior.findMAP``'s minus-mean objective declares "negmean")."""
+    declared = getattr(fn, "searchKind", None)
+    if declared is not None:
+        return str(declared).lower()
+    return utilityKind(fn)
+
+
 def minimizeObjective(fn, y, gp, sampleFn, priorFn, nRestarts=5,
                       method="nelder-mead", options=None, bounds=None,
-                      theta0=None, args=None, maxIters=100):
+                      theta0=None, args=None, maxIters=100, onDevice=False):
     """Restarted scalar minimisation of a utility (utility.py:253-372).
 
     Same control flow as the reference: ``nRestarts`` SciPy runs from prior
@@ -108,9 +118,28 @@ def minimizeObjective(fn, y, gp, sampleFn, priorFn, nRestarts=5,
     and the best of them returned as ``(theta, value)``.  Differences forced by
     current SciPy (quirks Q1/Q2): the start point is flattened and the objective
     is cast to float.
+
+    ``onDevice=True`` (Nelder-Mead only) runs the restarts on the device
+    (:meth:`GP.nelder_mead_search`, the same simplex arithmetic as SciPy) over
+    the objective :func:`searchKind` names, gated by ``bounds`` -- the box (or
+    the support) the prior is assumed to be: the device evaluates the utility
+    there and +inf outside, it does not call ``priorFn``.  The solutions are
+    checked on the host with ``priorFn`` as above and ``value`` is ``fn`` at the
+    best one.  All ``nRestarts`` starts are drawn first, in restart order, and
+    searched in one launch; the restarts whose solution is refused are then
+    redrawn in restart order and searched together, again until ``maxIters``
+    redraws of one restart raise the same ``RuntimeError``.  Without a redraw
+    NumPy's random stream is consumed exactly as by the host path; with
+    redraws the draws come in another order than the host path's (which
+    redraws a restart before it starts the next one).
     """
     if str(method).lower() == "nelder-mead" and options is None:
         options = {"adaptive": True}
+    if onDevice:
+        if str(method).lower() != "nelder-mead":
+            raise ValueError("onDevice=True runs Nelder-Mead only, not %r" % (method,))
+        return _minimizeOnDevice(fn, y, gp, sampleFn, priorFn, nRestarts, options, bounds, theta0,
+                                 () if args is None else args, maxIters)
     # bounds are only forwarded for the two methods the reference allows
     # (its l-bfgs-b test carries a leading space, utility.py:311; kept)
     if str(method).lower() not in [" l-bfgs-b", "tnc"]:
@@ -143,6 +172,43 @@ def minimizeObjective(fn, y, gp, sampleFn, priorFn, nRestarts=5,
                 break
             t0 = np.array(sampleFn(1)).reshape(1, -1)
             tries += 1
+    best = int(np.argmin([float(np.asarray(v, dtype=float).ravel()[0]) for v in vals]))
+    return np.array(res)[best], vals[best]
+
+
+def _minimizeOnDevice(fn, y, gp, sampleFn, priorFn, nRestarts, options, gate, theta0, args, maxIters):
+    """The ``onDevice`` branch of :func:`minimizeObjective`."""
+    kind = searchKind(fn)
+    if theta0 is not None:
+        theta0 = np.asarray(theta0).squeeze()
+        ndim = max(theta0.ndim, 1)
+    starts = []
+    for _ in range(nRestarts):
+        if theta0 is None:
+            t0 = np.asarray(sampleFn(1)).reshape(1, -1)
+        else:
+            t0 = theta0 + np.min(theta0) * 1.0e-3 * np.random.randn(ndim)
+        starts.append(np.asarray(t0, dtype=float).ravel())
+    starts = np.array(starts)
+    res = [None] * nRestarts
+    tries = [0] * nRestarts
+    pending = list(range(nRestarts))
+    while pending:
+        sols = gp.nelder_mead_search(y, starts[pending], kind, bounds=gate, options=options)[0]
+        refused = []
+        for i, sol in zip(pending, sols):
+            if np.all(np.isfinite(sol)) and np.isfinite(priorFn(sol)):
+                res[i] = sol
+            else:
+                refused.append(i)
+        for i in refused:
+            starts[i] = np.array(sampleFn(1), dtype=float).ravel()
+            tries[i] += 1
+            if tries[i] >= maxIters:
+                raise RuntimeError("ERROR: Cannot find a valid solution. Current iterations: %d\n"
+                                   "Maximum iterations: %d\n" % (tries[i], maxIters))
+        pending = refused
+    vals = [fn(sol, *args) for sol in res]
     best = int(np.argmin([float(np.asarray(v, dtype=float).ravel()[0]) for v in vals]))
     return np.array(res)[best], vals[best]
 

@@ -41,6 +41,7 @@ extern "C" {
 #define APGP_UTIL_BAPE 1         /* utility.BAPEUtility  utility.py:145-189 */
 #define APGP_UTIL_JONES 2        /* utility.JonesUtility utility.py:192-250 */
 #define APGP_UTIL_NONE 3         /* predict only (george.GP.predict)        */
+#define APGP_UTIL_NEG_MEAN 4     /* -mu: ApproxPosterior.findMAP's objective (apgp_nm_search only) */
 
 /*
  * ExpSquared(+Constant)(+Constant*Linear) kernel hyper-parameters in evaluated
@@ -374,6 +375,53 @@ int apgp_predict1_host(const double* t_host /*host*/, const double* xs, int64_t 
                        const apgp_kernel_t* kern /*host*/, double mean,
                        const double* winv, int64_t ldw, const double* L, int64_t ldl,
                        double* work, double* out2_host /*host*/, void* stream);
+
+/* ---- restarted Nelder-Mead point search, all restarts in one launch ------------
+ * The device form of utility.minimizeObjective's default search (SciPy 1.15 _minimize_neldermead, bounds=None):
+ * restart r (one workgroup, no communication between workgroups) starts from row r of `starts` (R x ndim, device)
+ * and minimises the objective
+ *   u(x) = +inf                              if a coordinate is not finite or lies outside [lo, hi] (host arrays,
+ *                                            NULL = no box), else
+ *          utility(kind)(mu(x), sigma^2(x))  kind AGP / BAPE / JONES (apgp_acquire's formulas; JONES: zeta, ybest)
+ *          -mu(x), +inf where mu is not finite  kind APGP_UTIL_NEG_MEAN
+ * mu, sigma^2 as apgp_predict1_host: through winv / ldw (the dense L^-1 of apgp_trtri_pack; n <= 256: the
+ * arithmetic of apgp_predict1_host, same bits) or, with winv = NULL, through the factor L / ldl (an in-workgroup
+ * triangular solve).  The simplex arithmetic is SciPy's, uncontracted; the vertices are re-sorted after every
+ * iteration by a stable sort on the previous position with NaN last.  opt->rho/chi/psi/sigma are SciPy's
+ * coefficients as the host computed them.  Every loop is bounded by maxiter / maxfev.
+ * Outputs (device): x_out R x ndim (the best vertex), f_out R (np.min of the final values: NaN if one is NaN),
+ * stats R x 3 int32 (nfev, nit, status: 0 converged, 1 maxfev, 2 maxiter).
+ * trace (device, may be NULL): R x maxfev records of ndim + 3 doubles (x, mu, sigma^2, u) in evaluation order
+ * (mu = sigma^2 = NaN where the gate refused the point); steps (device, may be NULL): R x maxiter int32, the step
+ * of each iteration (APGP_NM_STEP_*).  work: apgp_nm_search_work_len(R, n) doubles.
+ * Limits: 1 <= ndim <= APGP_MAX_DIM, 1 <= R <= APGP_NM_MAX_RESTARTS, 1 <= maxiter, maxfev <= APGP_NM_MAX_FEV.
+ * Added in ABI 8 without changing anything before it: APGP_ABI_VERSION stays 8.                               */
+#define APGP_NM_MAX_RESTARTS 4096
+#define APGP_NM_MAX_FEV (1 << 20)
+#define APGP_NM_STEP_REFLECT 1          /* xr accepted (fsim[0] <= f(xr) < fsim[-2])                        */
+#define APGP_NM_STEP_EXPAND 2           /* xe accepted                                                      */
+#define APGP_NM_STEP_REFLECT_EXP 3      /* expansion tried, xr kept                                         */
+#define APGP_NM_STEP_CONTRACT_OUT 4     /* outside contraction accepted                                     */
+#define APGP_NM_STEP_CONTRACT_IN 5      /* inside contraction accepted                                      */
+#define APGP_NM_STEP_SHRINK_OUT 6       /* outside contraction refused -> shrink                            */
+#define APGP_NM_STEP_SHRINK_IN 7        /* inside contraction refused -> shrink                             */
+#define APGP_NM_STEP_MAXFEV 8           /* the iteration stopped at maxfev                                  */
+typedef struct apgp_nm_options {
+    int32_t kind;
+    int32_t maxiter;
+    int32_t maxfev;
+    int32_t reserved;
+    double zeta, ybest;
+    double xatol, fatol;
+    double rho, chi, psi, sigma;
+} apgp_nm_options_t;
+int64_t apgp_nm_search_work_len(int64_t restarts, int64_t n);
+int apgp_nm_search(const double* starts, int64_t restarts, const double* xs, int64_t n,
+                   const apgp_kernel_t* kern /*host*/, double mean,
+                   const double* winv, int64_t ldw, const double* L, int64_t ldl,
+                   const double* lo /*host*/, const double* hi /*host*/, const apgp_nm_options_t* opt /*host*/,
+                   double* x_out, double* f_out, int32_t* stats, double* trace, int32_t* steps,
+                   double* work, void* stream);
 
 /* ---- mean-only prediction (the batched ApproxPosterior._gpll path) --------
  * mu_i = k(t_i,X).alpha + mean for m candidates (approx.py:178-180).         */
