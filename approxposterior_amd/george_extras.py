@@ -84,7 +84,7 @@ class GeorgeExtras(object):
         with self._on(torch, dev):
             st = self._stream(torch)
             ks = self._kernel_struct()
-            if getattr(self, "_x_d", None) is None or self._x_d.shape[0] != n:
+            if self._x_d is None or self._x_d.shape[0] != n:
                 self._x_d = torch.from_numpy(self._x).to(dev)
             t_d = torch.from_numpy(np.ascontiguousarray(xs, dtype=np.float64)).to(dev)
             kxt = torch.empty((m, n), dtype=torch.float64, device=dev)

@@ -29,7 +29,10 @@ lacks: ``acquire`` (fused predict + utility + arg-min over a candidate matrix)
 and array-valued ``predict``.
 """
 
+import collections
 import ctypes
+import math
+from operator import is_
 
 import numpy as np
 from numpy.linalg import LinAlgError
@@ -93,6 +96,8 @@ COND_SOLVE = 1.0e10
 # against 0.08 + 0.09 ms for the two triangular solves, 0.82 + 0.05 ms against 2 x 0.72 ms at N = 4096
 # (profiles/r03n_fit_timing.txt).  A bare log_likelihood on a new y keeps the single forward solve.
 W_FIRST_MIN_N = 512
+_LOG_2PI = np.log(2.0 * np.pi)
+_F64 = np.dtype(np.float64)     # (a dtype compares with a dtype faster than with a type: replay guards)
 
 
 # ---------------------------------------------------------------------------
@@ -341,71 +346,44 @@ def _flatten_kernel(kernel, with_linear=False):
     return amp, log_M
 
 
-class _NllPlan(object):
-    """The arguments of one ``apgp_nll_eval`` call, kept between the evaluations of an optimiser loop
-    (``GP._factor_again``): device buffers (referenced, so their addresses stay valid), the kernel struct that is
-    refilled in place, the host record, and what has to be unchanged for the plan to apply."""
-    __slots__ = ("x", "ybytes", "n", "nlog2pi", "stream", "dev_index", "current_device", "raw_stream", "ks", "fn", "args",
-                 "o", "K", "z", "keep")
+class _Replay(object):
+    """One library call kept for the next call that differs only in the per-call slots of ``args`` (the caller fills
+    them in): what a hot loop saves by skipping the generic path's checks and set-up.  It applies while the device and
+    current stream it was built on are current, ``y`` has the bytes it was built for and every object of ``deps`` --
+    the buffers the arguments point into -- is still the GP's own.  ``data``: what the call site keeps with it (its host
+    arrays, its own limits)."""
+    __slots__ = ("fn", "args", "data", "device", "stream", "ybytes", "n", "deps", "current_device", "raw_stream")
 
-    def __init__(self, gp, torch, dev, stream, ks, yv, x_d, y_d, K, z, scr, o, n):
-        self.x = gp._x
-        self.ybytes = yv.tobytes()
-        self.n = n
-        self.nlog2pi = n * np.log(2.0 * np.pi)
-        self.stream = stream
-        self.dev_index = dev.index
-        self.current_device = torch.cuda.current_device
-        self.raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
-        self.ks = ks
-        self.fn = gp._rt()[2].apgp_nll_eval
-        self.o = o
-        self.K, self.z = K, z
-        self.keep = (x_d, y_d, scr)
-        self.args = [x_d.data_ptr(), n, ctypes.byref(ks), y_d.data_ptr(), 0.0, K.data_ptr(), z.data_ptr(),
-                     scr[0].data_ptr(), scr[1].data_ptr(), o.ctypes.data, ctypes.c_void_p(stream)]
+    def __init__(self, fn, args, device, stream, y, deps, queries, data=None):
+        self.fn, self.args, self.data = fn, args, data
+        self.device, self.stream = device, stream
+        self.ybytes, self.n = y.tobytes(), y.size
+        self.deps = deps
+        self.current_device, self.raw_stream = queries     # () -> device index, (index) -> raw stream handle
 
-
-class _OnePlan(object):
-    """The arguments of one ``apgp_predict1_host`` call (one candidate, mean + variance), kept for the next."""
-    __slots__ = ("xs", "p1", "factor", "solve", "ybytes", "n", "ndim", "mean", "ld", "stream", "dev_index", "current_device",
-                 "raw_stream", "ks", "ks_ref", "fn", "xs_ptr", "p1_ptr", "factor_ptr", "stream_arg")
-
-    def __init__(self, gp, torch, dev, stream, ks, yv, n, solve):
-        self.xs, self.p1 = gp._xs, gp._p1_work
-        self.solve = bool(solve)
-        self.factor = gp._L if solve else gp._work          # substitution against L, or the resident dense L^-1
-        self.ld = int(gp._ld) if solve else (n + 63) // 64 * 64
-        self.ybytes = yv.tobytes()
-        self.n, self.ndim = n, int(ks.ndim)
-        self.mean = float(gp.mean.value)
-        self.stream, self.dev_index = stream, dev.index
-        self.current_device = torch.cuda.current_device
-        self.raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
-        self.ks, self.ks_ref = ks, ctypes.byref(ks)
-        self.fn = gp._rt()[2].apgp_predict1_host
-        self.xs_ptr, self.p1_ptr, self.factor_ptr = gp._xs.data_ptr(), gp._p1_work.data_ptr(), self.factor.data_ptr()
-        self.stream_arg = ctypes.c_void_p(stream)
+    def fits(self, y, deps):
+        if not all(map(is_, deps, self.deps)):
+            return False
+        if type(y) is not np.ndarray or y.dtype != _F64 or y.size != self.n or not y.flags.c_contiguous:
+            return False
+        cur = self.current_device()
+        if cur != self.device or self.raw_stream is None or self.raw_stream(cur) != self.stream:
+            return False
+        return y.tobytes() == self.ybytes
 
 
-class _MeanPlan(object):
-    """The arguments of one small ``apgp_predict_mean_host`` call, kept for the next (``GP._predict_mean_again``)."""
-    __slots__ = ("xs", "work", "ybytes", "n", "ndim", "mean", "max_m", "stream", "dev_index", "current_device", "raw_stream",
-                 "ks", "ks_ref", "fn", "xs_ptr", "work_ptr", "stream_arg")
+# nll_batch's work space, kept between the rounds of a fit on one training set, y and stream: the device copy of y, the
+# (K, z, info, record) buffers of each batch size up to 256 MB, the means of a replayed batch
+_BatchWork = collections.namedtuple("_BatchWork", "x x_d stream ybytes y_d bufs means")
 
-    def __init__(self, gp, torch, dev, stream, ks, yv, n):
-        self.xs, self.work = gp._xs, gp._mean_work
-        self.ybytes = yv.tobytes()
-        self.n, self.ndim = n, int(ks.ndim)
-        self.mean = float(gp.mean.value)
-        self.max_m = min(4096, gp._mean_work.numel() // (self.ndim + 1))
-        self.stream, self.dev_index = stream, dev.index
-        self.current_device = torch.cuda.current_device
-        self.raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
-        self.ks, self.ks_ref = ks, ctypes.byref(ks)
-        self.fn = gp._rt()[2].apgp_predict_mean_host
-        self.xs_ptr, self.work_ptr = gp._xs.data_ptr(), gp._mean_work.data_ptr()
-        self.stream_arg = ctypes.c_void_p(stream)
+
+def _records_nll(o, n):
+    """-log-likelihood of each factorisation record (B x 5: log-determinant, min / max L_ii, z.z, info) by the element
+    operations of ``log_likelihood``, in its order; +inf where the factorisation failed or the value is not finite."""
+    with np.errstate(all="ignore"):
+        ll = (-0.5 * (n * _LOG_2PI + o[:, 0])) - 0.5 * o[:, 3]
+    bad = (o[:, 4] != 0.0) | ~np.isfinite(o[:, 0]) | ~np.isfinite(ll)
+    return np.where(bad, np.inf, -ll)
 
 
 # ---------------------------------------------------------------------------
@@ -434,7 +412,18 @@ class GP(GeorgeExtras):
         self._x = None
         self._yerr2 = 0.0
         self._nllMemo = None          # gpUtils._nll: values already evaluated on this training set
-        self._batch_cache = None      # nll_batch: work buffers and the device copy of y, kept between the rounds of a fit
+        self._rt_cache = None         # (torch, device, lib), see _rt
+        self._queries = None          # (current device, raw current stream) queries of torch, see _rt
+        self._x_d = None              # device copy of the training set
+        self._mean_work = None        # scratch of the small predictions and of the evaluations: survives refits
+        self._p1_work = None
+        self._nll_scratch = None
+        self._nll_stream = None       # the stream the private buffers of the last _nll evaluation were made on
+        self._batch = None            # nll_batch's _BatchWork
+        # The previous call's argument list of the hot loops, ready for the next (_Replay): "nll" (the optimiser's
+        # evaluations), "one" (a candidate with variance), "mean" (a few points, mean only) belong to the factor and
+        # go with it; ("batch", B) belongs to self._batch and goes with that.
+        self._replays = {}
         self._reset_device_state()
 
     # -- device plumbing -------------------------------------------------------
@@ -454,20 +443,15 @@ class GP(GeorgeExtras):
         self._work = None         # trtri work (dense L^-1 in first panel)
         self._xs = None           # packed training stream (depends on alpha)
         self._xs_key = None
-        self._mean_work = getattr(self, "_mean_work", None)   # scratch survives refits
-        self._p1_work = getattr(self, "_p1_work", None)
-        self._nll_scratch = getattr(self, "_nll_scratch", None)
-        self._nll_plan = None     # the arguments of the last _nll evaluation, ready for the next (_factor_again)
-        self._mean_plan = None    # ... of the last small mean-only prediction (_predict_mean_again)
-        self._one_plan = None     # ... of the last single-candidate prediction with variance (_predict_one_again)
+        for key in ("nll", "one", "mean"):
+            self._replays.pop(key, None)
         self.cond_estimate = None
         self.log_determinant = None
 
     def _rt(self):
         """(torch, device, lib) -- fails loudly without GPU / extension."""
-        rt = getattr(self, "_rt_cache", None)
-        if rt is not None:
-            return rt
+        if self._rt_cache is not None:
+            return self._rt_cache
         import torch
         lib = _lib.load()
         if not torch.cuda.is_available():
@@ -477,6 +461,7 @@ class GP(GeorgeExtras):
             dev = torch.device("cuda", torch.cuda.current_device())
         elif not isinstance(dev, torch.device):
             dev = torch.device(dev)
+        self._queries = (torch.cuda.current_device, getattr(torch._C, "_cuda_getCurrentRawStream", None))
         self._rt_cache = (torch, dev, lib)
         return self._rt_cache
 
@@ -626,7 +611,7 @@ class GP(GeorgeExtras):
         prev_L, prev_store = prev._L, getattr(prev, "_L_store", None)
         self._reset_device_state()
         self._computed = False
-        with torch.cuda.device(dev):
+        with self._on(torch, dev):
             st = self._stream(torch)
             self._x_d = torch.from_numpy(self._x).to(dev)
             # The factor lives in a growable store shared along the chain of GP objects findNextPoint
@@ -670,37 +655,66 @@ class GP(GeorgeExtras):
             _lib.check(lib.apgp_fit_summary(L.data_ptr(), n1, ld, None, info.data_ptr(), out5.data_ptr(), st),
                        "apgp_fit_summary")
             o = out5.cpu().numpy()          # the only synchronisation of the extension
-        if int(o[4]) != 0 or not np.isfinite(o[0]):
+        try:
+            self._take_record(o, n1, bytes(ks))
+        except LinAlgError:
             store["used"] = -1            # (the failed rows stay in the store: nobody may append to it again)
             self._reset_device_state()
-            raise LinAlgError("%d-th leading minor of the array is not positive definite" % int(o[4]))
+            raise
         self._L = L
         self._L_store = store
         self._ld = ld
+        return True
+
+    def _take_record(self, o, n, key):
+        """Object state from the 5-double record of a factorisation of n rows (log-determinant, min / max L_ii, z.z,
+        LAPACK info); raises as scipy.linalg.cholesky inside george does when it failed.  ``key``: its _factor_key."""
+        if o[4] != 0.0:
+            raise LinAlgError("%d-th leading minor of the array is not positive definite" % int(o[4]))
+        if not math.isfinite(o[0]):          # (np.isfinite on a scalar costs 0.5 us more: once per evaluation)
+            raise LinAlgError("non-finite log-determinant")
         self.log_determinant = float(o[0])
         self.cond_estimate = float((o[2] / o[1]) ** 2)
-        self._const = -0.5 * (n1 * np.log(2.0 * np.pi) + self.log_determinant)
+        self._const = -0.5 * (n * _LOG_2PI + self.log_determinant)
         self._computed = True
         self.kernel.dirty = False
-        self._factored_key = self._factor_key()
-        return True
+        self._factored_key = key
 
     def _factor(self, y, upload_x=False):
         """Gram + Cholesky (+ z = L^-1 (y - mean) carried through the factorisation)
         + log-determinant / diagonal range / z.z / info, fetched with ONE 40-byte
         device-to-host copy.  This is one gpUtils._nll evaluation."""
-        if y is not None and not upload_x and self._nll_plan is not None and self._factor_again(y):
+        r = self._replays.get("nll")
+        if (r is not None and y is not None and not upload_x
+                and r.fits(y, (self._x, self._x_d, self._y_d, self._L, self._z))):
+            # one more evaluation in the buffers of the last one (same training set, y and stream), minus everything
+            # that cannot have changed -- the optimiser loop's path (SciPy asks for ~6e5 evaluations in BASELINE
+            # config 5; the generic path's 17 us of Python between two device evaluations were 7 % of each)
+            ks, o = r.data
+            self._kernel_struct(ks)
+            # (as _reset_device_state: whatever was derived from the previous factor is stale)
+            self._alpha = self._packed = self._packed_solve = self._work = self._xs = self._xs_key = None
+            self._computed = False
+            r.args[4] = float(self.mean.value)
+            try:
+                _lib.check(r.fn(*r.args), "apgp_nll_eval")
+                self._take_record(o, r.n, bytes(ks))
+            except Exception:
+                self._reset_device_state()
+                raise
+            self._ztz_host = float(o[3])
+            self._alpha_mean = self.mean.value
             return
         torch, dev, lib = self._rt()
         x = self._x
         n = len(x)
         yv = None if y is None else self._check_dimensions(y)
-        keep_x = None if upload_x else getattr(self, "_x_d", None)
+        keep_x = None if upload_x else self._x_d
         keep_y = self._y_d if (yv is not None and self._alpha_y is not None
                                and np.array_equal(self._alpha_y, yv)) else None
         keep_nll = (self._L, self._z) if (self._L is not None and self._z is not None and self._L_store is None
                                           and self._nll_owned) else None
-        keep_stream = getattr(self, "_nll_stream", None)
+        keep_stream = self._nll_stream
         self._reset_device_state()
         self._computed = False
         ks = self._kernel_struct()
@@ -739,28 +753,16 @@ class GP(GeorgeExtras):
                 scr = self._nll_scratch = (torch.empty(1, dtype=torch.int32, device=dev),
                                            torch.empty(5, dtype=torch.float64, device=dev))
             o = np.empty(5, dtype=np.float64)
-            _lib.check(lib.apgp_nll_eval(self._x_d.data_ptr(), n, ctypes.byref(ks),
-                                         y_d.data_ptr() if y_d is not None else None,
-                                         float(self.mean.value), K.data_ptr(),
-                                         z.data_ptr() if yv is not None else None,
-                                         scr[0].data_ptr(), scr[1].data_ptr(), o.ctypes.data, st),
-                       "apgp_nll_eval")
+            args = [self._x_d.data_ptr(), n, ctypes.byref(ks), y_d.data_ptr() if y_d is not None else None,
+                    float(self.mean.value), K.data_ptr(), z.data_ptr() if yv is not None else None,
+                    scr[0].data_ptr(), scr[1].data_ptr(), o.ctypes.data, st]
+            _lib.check(lib.apgp_nll_eval(*args), "apgp_nll_eval")
             if yv is None:
                 z = None
             L = K
-        if int(o[4]) != 0:
-            # same failure mode as scipy.linalg.cholesky inside george
-            raise LinAlgError("%d-th leading minor of the array is not positive definite" % int(o[4]))
-        if not np.isfinite(o[0]):
-            raise LinAlgError("non-finite log-determinant")
+        self._take_record(o, n, bytes(ks))      # (raises as scipy.linalg.cholesky inside george)
         self._L = L
         self._ld = n
-        self.log_determinant = float(o[0])
-        self.cond_estimate = float((o[2] / o[1]) ** 2)
-        self._const = -0.5 * (n * np.log(2.0 * np.pi) + self.log_determinant)
-        self._computed = True
-        self.kernel.dirty = False
-        self._factored_key = bytes(ks)
         if z is not None:
             self._z = z
             self._ztz_host = float(o[3])
@@ -769,49 +771,9 @@ class GP(GeorgeExtras):
             self._alpha_mean = self.mean.value
             self._nll_owned = True    # (K, z) came from an _nll evaluation: the next one may refactorise in place
             self._nll_stream = st.value
-            # everything the NEXT evaluation on this training set, y and stream needs, ready to go (_factor_again)
-            self._nll_plan = _NllPlan(self, torch, dev, st.value or 0, ks, yv, self._x_d, y_d, K, z, scr, o, n)
-
-    def _factor_again(self, y):
-        """One more gpUtils._nll evaluation (gpUtils.py:46-80) in the buffers of the last one: what ``_factor`` does when
-        it finds them reusable, minus everything that cannot have changed -- the optimiser loop's path (SciPy asks for
-        ~6e5 evaluations in BASELINE config 5; the generic path's 17 us of Python between two device evaluations were 7 %
-        of each).  False: something differs (training set, y, stream, device, buffers) -- the caller takes the generic path."""
-        plan = self._nll_plan
-        if (plan.x is not self._x or plan.K is not self._L or plan.z is not self._z or self._L_store is not None
-                or not self._nll_owned or type(y) is not np.ndarray or y.dtype != np.float64):
-            return False
-        cur = plan.current_device()
-        if cur != plan.dev_index or plan.raw_stream is None or plan.raw_stream(cur) != plan.stream:
-            return False
-        if y.size != plan.n or not y.flags.c_contiguous or y.tobytes() != plan.ybytes:
-            return False
-        ks = self._kernel_struct(plan.ks)
-        # (as _reset_device_state: whatever was derived from the previous factor is stale)
-        self._alpha = self._packed = self._packed_solve = self._work = self._xs = self._xs_key = None
-        self._computed = False
-        args = plan.args
-        args[4] = float(self.mean.value)
-        rc = plan.fn(*args)
-        if rc != 0:
-            self._reset_device_state()
-            _lib.check(rc, "apgp_nll_eval")
-        o = plan.o
-        if o[4] != 0.0 or not np.isfinite(o[0]):
-            self._reset_device_state()
-            if o[4] != 0.0:
-                raise LinAlgError("%d-th leading minor of the array is not positive definite" % int(o[4]))
-            raise LinAlgError("non-finite log-determinant")
-        logdet = float(o[0])
-        self.log_determinant = logdet
-        self.cond_estimate = float((o[2] / o[1]) ** 2)
-        self._const = -0.5 * (plan.nlog2pi + logdet)
-        self._ztz_host = float(o[3])
-        self._alpha_mean = self.mean.value
-        self._computed = True
-        self.kernel.dirty = False
-        self._factored_key = bytes(ks)
-        return True
+            # everything the NEXT evaluation on this training set, y and stream needs, ready to go
+            self._replays["nll"] = _Replay(lib.apgp_nll_eval, args, dev.index, st.value or 0, yv,
+                                           (x, self._x_d, y_d, K, z), self._queries, data=(ks, o))
 
     def recompute(self, quiet=False, **kwargs):
         if self.kernel.dirty or not self._computed:
@@ -846,7 +808,7 @@ class GP(GeorgeExtras):
             self._ensure_linv()
         via_w = self._work is not None and trust_w
         np64 = (n + 63) // 64 * 64
-        with torch.cuda.device(dev):
+        with self._on(torch, dev):
             st = self._stream(torch)
             if not same or self._z is None:
                 self._y_d = torch.from_numpy(y).to(dev)
@@ -977,27 +939,18 @@ class GP(GeorgeExtras):
         B, n = len(P), len(self._x)
         if P.shape[1] != len(self):
             raise ValueError("dimension mismatch")
-        cache = self._batch_cache
-        fast = None
-        if (B <= 8 and cache is not None and cache["x"] is self._x and type(y) is np.ndarray and y.dtype == np.float64
-                and y.size == n and y.flags.c_contiguous and cache["ybytes"] == y.tobytes()
-                and torch.cuda.current_device() == dev.index and cache["stream"] == (self._stream(torch).value or 0)):
+        r = self._replays.get(("batch", B))
+        if r is not None and r.fits(y, (self._x, self._batch)):
             # a small batch on the training set, y and stream of the previous one (the look-ahead of a Powell line search,
             # the rounds of a lock-step fit): buffers, argument list and struct array are ready
-            fast = cache["plans"].get(B)
-        if fast is not None:
-            karr, o, args, fn = fast
+            karr, o = r.data
             means = self._fast_structs(P, karr)
             if means is not None:
-                marr = fast_means = cache["means"][:B]
-                marr[:] = means
+                self._batch.means[:B] = means
                 self.kernel.dirty = True          # (the buffers the object's own factor may share are not touched; as below)
                 self._computed = False
-                _lib.check(fn(*args), "apgp_nll_eval_batch")
-                with np.errstate(all="ignore"):
-                    ll = (-0.5 * (n * np.log(2.0 * np.pi) + o[:, 0])) - 0.5 * o[:, 3]
-                bad = (o[:, 4] != 0.0) | ~np.isfinite(o[:, 0]) | ~np.isfinite(ll)
-                return np.where(bad, np.inf, -ll)
+                _lib.check(r.fn(*r.args), "apgp_nll_eval_batch")
+                return _records_nll(o, n)
         yv = self._check_dimensions(y)
         out = np.full(B, np.inf)
         saved = self.get_parameter_vector()
@@ -1020,52 +973,46 @@ class GP(GeorgeExtras):
         per = max(1, int((2 << 30) // (8 * n * n)))
         with self._on(torch, dev):
             st = self._stream(torch)
-            if getattr(self, "_x_d", None) is None:
+            if self._x_d is None:
                 self._x_d = torch.from_numpy(self._x).to(dev)
             # the rounds of a lock-step fit (gpUtils._minimizeLockStep) come back with the same y, batch size and stream a few
             # hundred times: the device copy of y and the work buffers are kept (the call is synchronous: nothing of the
             # previous round is in flight)
             ybytes = yv.tobytes()
-            if (cache is None or cache["x_d"] is not self._x_d or cache["stream"] != (st.value or 0)
-                    or cache["ybytes"] != ybytes or cache["x"] is not self._x):
-                cache = self._batch_cache = {"x_d": self._x_d, "x": self._x, "stream": st.value or 0, "ybytes": ybytes,
-                                             "y_d": torch.from_numpy(yv).to(dev), "bufs": {}, "plans": {},
-                                             "means": np.empty(8, dtype=np.float64)}
-            y_d = cache["y_d"]
+            work = self._batch
+            if (work is None or work.x_d is not self._x_d or work.stream != (st.value or 0) or work.ybytes != ybytes
+                    or work.x is not self._x):
+                work = self._batch = _BatchWork(self._x, self._x_d, st.value or 0, ybytes, torch.from_numpy(yv).to(dev),
+                                                {}, np.empty(8, dtype=np.float64))
+                self._replays = {k: v for k, v in self._replays.items() if type(k) is not tuple}   # (the old space's)
             for c0 in range(0, len(live), per):
                 idx = live[c0:c0 + per]
                 nb = len(idx)
                 karr = (_lib.KernelStruct * nb)(*structs[c0:c0 + nb])
                 marr = np.array(means[c0:c0 + nb], dtype=np.float64)
-                bufs = cache["bufs"].get(nb)
+                bufs = work.bufs.get(nb)
                 if bufs is None:
                     bufs = (torch.empty((nb, n, n), dtype=torch.float64, device=dev),
                             torch.empty((nb, n), dtype=torch.float64, device=dev),
                             torch.empty(nb, dtype=torch.int32, device=dev),
                             torch.empty((nb, 5), dtype=torch.float64, device=dev))
                     if 8 * nb * n * n <= (256 << 20):     # (larger work spaces are not hoarded; 6 matrices of N = 2300 fit)
-                        cache["bufs"][nb] = bufs
+                        work.bufs[nb] = bufs
                 K, z, info, o_d = bufs
                 o = np.empty((nb, 5), dtype=np.float64)
                 _lib.check(lib.apgp_nll_eval_batch(self._x_d.data_ptr(), n, nb, ctypes.addressof(karr),
-                                                   y_d.data_ptr(), marr.ctypes.data, K.data_ptr(), z.data_ptr(),
+                                                   work.y_d.data_ptr(), marr.ctypes.data, K.data_ptr(), z.data_ptr(),
                                                    info.data_ptr(), o_d.data_ptr(), o.ctypes.data, st),
                            "apgp_nll_eval_batch")
-                if nb == B and B <= 8 and nb in cache["bufs"] and ctypes.sizeof(_lib.KernelStruct) == 36 * 8:
+                if nb == B and B <= 8 and nb in work.bufs and ctypes.sizeof(_lib.KernelStruct) == 36 * 8:
                     # the next batch of this size on this training set, y and stream: everything but the hyper-vectors ready
                     ka = np.zeros((B, 36), dtype=np.float64)
                     oo = np.empty((B, 5), dtype=np.float64)
-                    cache["plans"][B] = (ka, oo, [self._x_d.data_ptr(), n, B, ka.ctypes.data, y_d.data_ptr(),
-                                                  cache["means"].ctypes.data, K.data_ptr(), z.data_ptr(), info.data_ptr(),
-                                                  o_d.data_ptr(), oo.ctypes.data, ctypes.c_void_p(st.value)],
-                                         lib.apgp_nll_eval_batch)
-                for j, b in enumerate(idx):
-                    if int(o[j, 4]) != 0 or not np.isfinite(o[j, 0]):
-                        continue
-                    const = -0.5 * (n * np.log(2.0 * np.pi) + float(o[j, 0]))
-                    ll = const - 0.5 * float(o[j, 3])
-                    if np.isfinite(ll):
-                        out[b] = -ll
+                    args = [self._x_d.data_ptr(), n, B, ka.ctypes.data, work.y_d.data_ptr(), work.means.ctypes.data,
+                            K.data_ptr(), z.data_ptr(), info.data_ptr(), o_d.data_ptr(), oo.ctypes.data, st]
+                    self._replays[("batch", B)] = _Replay(lib.apgp_nll_eval_batch, args, dev.index, st.value or 0, yv,
+                                                          (self._x, work), self._queries, data=(ka, oo))
+                out[idx] = _records_nll(o, n)
         return out
 
     # -- packed factor / training stream for the sweep -------------------------------
@@ -1074,7 +1021,7 @@ class GP(GeorgeExtras):
         if self._packed is not None:
             return
         n = len(self._x)
-        with torch.cuda.device(dev):
+        with self._on(torch, dev):
             st = self._stream(torch)
             self._work = torch.empty(lib.apgp_trtri_work_len(n), dtype=torch.float64, device=dev)
             self._packed = torch.empty(lib.apgp_packed_linv_len(n), dtype=torch.float64, device=dev)
@@ -1087,7 +1034,7 @@ class GP(GeorgeExtras):
         if self._packed_solve is not None:
             return
         n = len(self._x)
-        with torch.cuda.device(dev):
+        with self._on(torch, dev):
             st = self._stream(torch)
             self._packed_solve = torch.empty(lib.apgp_packed_lsolve_len(n), dtype=torch.float64, device=dev)
             _lib.check(lib.apgp_pack_lsolve(self._L.data_ptr(), n, self._ld, self._packed_solve.data_ptr(), st),
@@ -1100,7 +1047,7 @@ class GP(GeorgeExtras):
             return
         n = len(self._x)
         ks = self._kernel_struct()
-        with torch.cuda.device(dev):
+        with self._on(torch, dev):
             st = self._stream(torch)
             self._xs = torch.empty(lib.apgp_packed_train_len(n, ks.ndim), dtype=torch.float64,
                                    device=dev)
@@ -1110,14 +1057,27 @@ class GP(GeorgeExtras):
 
     # -- predict (george GP.predict) ----------------------------
     def predict(self, y, t, return_cov=True, return_var=False, cache=True, **kwargs):
-        if not return_var and not return_cov and self._mean_plan is not None:
-            mu = self._predict_mean_again(y, t)
-            if mu is not None:
-                return mu
-        if return_var and self._one_plan is not None:
-            res = self._predict_one_again(y, t)
-            if res is not None:
-                return res
+        if (self._computed and not self.kernel.dirty and type(t) is np.ndarray and t.dtype == _F64
+                and t.ndim == 2 and t.flags.c_contiguous):
+            # the replays of _sweep's small calls: the previous call's arguments with new points
+            if return_var:
+                r = self._replays.get("one")
+                # (the factor of the variance form in use: a switch of form is a different object)
+                if (r is not None and t.shape == r.data[1] and r.args[4] == self.mean.value
+                        and r.fits(y, (self._xs, self._p1_work, self._work if self._trust_inverse() else self._L))):
+                    r.args[0] = t.ctypes.data
+                    _lib.check(r.fn(*r.args), "apgp_predict1_host")
+                    o2 = r.data[0]
+                    return np.array([o2[0]]), np.array([o2[1]])
+            elif not return_cov:
+                r = self._replays.get("mean")
+                m, d = t.shape
+                if (r is not None and d == r.data[0] and 0 < m <= r.data[1] and r.args[5] == self.mean.value
+                        and r.fits(y, (self._xs, self._mean_work))):
+                    mu_h = np.empty(m)
+                    r.args[0], r.args[1], r.args[6] = t.ctypes.data, m, mu_h.ctypes.data
+                    _lib.check(r.fn(*r.args), "apgp_predict_mean_host")
+                    return mu_h
         self.recompute()
         xs = self.parse_samples(t)
         if return_cov and not return_var:
@@ -1127,53 +1087,6 @@ class GP(GeorgeExtras):
             return mu
         mu, var = self._sweep(y, xs, kind=None, want=("mu", "var"))
         return mu, var
-
-    def _predict_one_again(self, y, t):
-        """Mean and variance at ONE more point for the model, y and stream of the previous such call (the reference's scalar
-        utilities under Nelder-Mead, utility.py:131,178,224) -- the previous ``apgp_predict1_host`` call's arguments with a new
-        point.  None: something differs, the caller takes the generic path."""
-        plan = self._one_plan
-        if (not self._computed or self.kernel.dirty or plan.xs is not self._xs or plan.p1 is not self._p1_work
-                or plan.factor is not (self._L if plan.solve else self._work) or plan.mean != self.mean.value
-                or plan.solve == self._trust_inverse()          # (variance_mode / the conditioning gate picked the other form)
-                or type(y) is not np.ndarray or y.dtype != np.float64 or type(t) is not np.ndarray or t.dtype != np.float64
-                or t.shape != (1, plan.ndim) or not t.flags.c_contiguous
-                or y.size != plan.n or not y.flags.c_contiguous or y.tobytes() != plan.ybytes):
-            return None
-        cur = plan.current_device()
-        if cur != plan.dev_index or plan.raw_stream is None or plan.raw_stream(cur) != plan.stream:
-            return None
-        o2 = np.empty(2, dtype=np.float64)
-        if plan.solve:
-            rc = plan.fn(t.ctypes.data, plan.xs_ptr, plan.n, plan.ks_ref, plan.mean, None, 0, plan.factor_ptr, plan.ld,
-                         plan.p1_ptr, o2.ctypes.data, plan.stream_arg)
-        else:
-            rc = plan.fn(t.ctypes.data, plan.xs_ptr, plan.n, plan.ks_ref, plan.mean, plan.factor_ptr, plan.ld, None, 0,
-                         plan.p1_ptr, o2.ctypes.data, plan.stream_arg)
-        _lib.check(rc, "apgp_predict1_host")
-        return np.array([o2[0]]), np.array([o2[1]])
-
-    def _predict_mean_again(self, y, t):
-        """The mean at a few more points for the model, y and stream of the previous such call (the walker ensembles of
-        ``ApproxPosterior._gpllBatch``, approx.py:148-189 batched: 4e4 calls per chain in the README example) -- the previous
-        call's arguments with new points, none of the generic path's checks that cannot have changed.  None: something
-        differs, the caller takes the generic path."""
-        plan = self._mean_plan
-        if (not self._computed or self.kernel.dirty or plan.xs is not self._xs or plan.work is not self._mean_work
-                or plan.mean != self.mean.value or type(y) is not np.ndarray or y.dtype != np.float64
-                or type(t) is not np.ndarray or t.dtype != np.float64 or t.ndim != 2 or t.shape[1] != plan.ndim
-                or not t.flags.c_contiguous):
-            return None
-        m = t.shape[0]
-        if not 0 < m <= plan.max_m or y.size != plan.n or not y.flags.c_contiguous or y.tobytes() != plan.ybytes:
-            return None
-        cur = plan.current_device()
-        if cur != plan.dev_index or plan.raw_stream is None or plan.raw_stream(cur) != plan.stream:
-            return None
-        mu_h = np.empty(m, dtype=np.float64)
-        _lib.check(plan.fn(t.ctypes.data, m, plan.xs_ptr, plan.n, plan.ks_ref, plan.mean, mu_h.ctypes.data, plan.work_ptr,
-                           plan.stream_arg), "apgp_predict_mean_host")
-        return mu_h
 
     def acquire(self, y, t, kind, bounds=None, mask=None, zeta=0.01, return_all=False,
                 idx_offset=0, device_record=False):
@@ -1441,12 +1354,14 @@ class GP(GeorgeExtras):
                 if self._mean_work is None or self._mean_work.numel() < need:
                     self._mean_work = torch.empty(max(need, 1024), dtype=torch.float64, device=dev)
                 mu_h = np.empty(m, dtype=np.float64)
-                _lib.check(lib.apgp_predict_mean_host(cand.ctypes.data, m, self._xs.data_ptr(), n,
-                                                      ctypes.byref(ks), float(self.mean.value),
-                                                      mu_h.ctypes.data, self._mean_work.data_ptr(), st),
-                           "apgp_predict_mean_host")
-                # the sampler asks again, for another few points of the same model and y, 4e4 times per chain
-                self._mean_plan = _MeanPlan(self, torch, dev, st.value or 0, ks, y, n)
+                args = [cand.ctypes.data, m, self._xs.data_ptr(), n, ctypes.byref(ks), float(self.mean.value),
+                        mu_h.ctypes.data, self._mean_work.data_ptr(), st]
+                _lib.check(lib.apgp_predict_mean_host(*args), "apgp_predict_mean_host")
+                # the sampler asks again, for another few points of the same model and y, 4e4 times per chain (the walker
+                # ensembles of ApproxPosterior._gpllBatch, approx.py:148-189)
+                max_m = min(4096, self._mean_work.numel() // (ks.ndim + 1))
+                self._replays["mean"] = _Replay(lib.apgp_predict_mean_host, args, dev.index, st.value or 0, y,
+                                                (self._xs, self._mean_work), self._queries, data=(ks.ndim, max_m))
                 return (mu_h,)
             if need_var and kind is None and cand_device is None and len(cand) == 1:
                 # ONE candidate with variance: the reference's scalar utilities (utility.py:131,178,224), once per
@@ -1454,18 +1369,17 @@ class GP(GeorgeExtras):
                 if self._p1_work is None or self._p1_work.numel() < int(lib.apgp_predict1_work_len(n)):
                     self._p1_work = torch.empty(int(lib.apgp_predict1_work_len(n)), dtype=torch.float64, device=dev)
                 o2 = np.empty(2, dtype=np.float64)
-                if use_solve:
-                    _lib.check(lib.apgp_predict1_host(cand.ctypes.data, self._xs.data_ptr(), n, ctypes.byref(ks),
-                                                      float(self.mean.value), None, 0, self._L.data_ptr(), self._ld,
-                                                      self._p1_work.data_ptr(), o2.ctypes.data, st), "apgp_predict1_host")
+                if use_solve:       # substitution against L, or the resident dense L^-1
+                    factor, inv = self._L, (None, 0, self._L.data_ptr(), self._ld)
                 else:
-                    _lib.check(lib.apgp_predict1_host(cand.ctypes.data, self._xs.data_ptr(), n, ctypes.byref(ks),
-                                                      float(self.mean.value), self._work.data_ptr(), (n + 63) // 64 * 64,
-                                                      None, 0, self._p1_work.data_ptr(), o2.ctypes.data, st),
-                               "apgp_predict1_host")
+                    factor, inv = self._work, (self._work.data_ptr(), (n + 63) // 64 * 64, None, 0)
+                args = [cand.ctypes.data, self._xs.data_ptr(), n, ctypes.byref(ks), float(self.mean.value), *inv,
+                        self._p1_work.data_ptr(), o2.ctypes.data, st]
+                _lib.check(lib.apgp_predict1_host(*args), "apgp_predict1_host")
                 if want == ("mu", "var"):
                     # the reference's scalar utilities ask again at the next simplex point, ~460 times per search
-                    self._one_plan = _OnePlan(self, torch, dev, st.value or 0, ks, y, n, use_solve)
+                    self._replays["one"] = _Replay(lib.apgp_predict1_host, args, dev.index, st.value or 0, y,
+                                                   (self._xs, self._p1_work, factor), self._queries, data=(o2, (1, ks.ndim)))
                 res = {"mu": np.array([o2[0]]), "var": np.array([o2[1]])}
                 return tuple(res[w_] for w_ in want)
             T = cand_device if cand_device is not None else torch.from_numpy(cand).to(dev)
@@ -1628,7 +1542,7 @@ class GP(GeorgeExtras):
         n = len(self._x)
         ks = self._kernel_struct()
         iterations = int(iterations)
-        with torch.cuda.device(dev):
+        with self._on(torch, dev):
             st = self._stream(torch)
             self._ensure_xs(y)
             coords = torch.from_numpy(p0).to(dev)
@@ -1682,7 +1596,7 @@ class GP(GeorgeExtras):
             y = self._check_dimensions(y)
             n = len(y)
             ks = self._kernel_struct()
-            with torch.cuda.device(dev):
+            with self._on(torch, dev):
                 st = self._stream(torch)
                 self._solve(y, need_alpha=True)
                 work = torch.empty(lib.apgp_grad_work_len(n), dtype=torch.float64, device=dev)

@@ -272,6 +272,18 @@ def test_nll_batch_is_bit_identical_to_single_evaluations(n, d):
             with np.errstate(all="ignore"):
                 assert np.array_equal(gp.nll_batch(P[:B], y), single[:B])
         assert lib.apgp_nll_side_batches() == before + 4 or lib.apgp_potrf_backoff_skips() > 0
+        # the batch replay: the second call of a size on the same training set, y and stream reuses the first one's
+        # argument list and never enters the generic branch (which sets and restores the parameter vector)
+        Pf = np.delete(P, 3, 0)
+        sf = np.delete(single, 3)
+        def refuse(p):
+            raise AssertionError("the generic branch of nll_batch was entered")
+        for B in (2, 3, 4, 6):
+            first = gp.nll_batch(Pf[:B], y)
+            with pytest.MonkeyPatch.context() as mp:
+                mp.setattr(gp, "set_parameter_vector", refuse)
+                again = gp.nll_batch(Pf[:B], y)
+            assert np.array_equal(first, sf[:B]) and np.array_equal(again, sf[:B]), (B, first, again, sf[:B])
     print("nll_batch N=%d: 7 evaluations %.2f ms batched, %.2f ms one by one" % (n, 1e3 * t_batch, 1e3 * t_single))
 
 

@@ -604,11 +604,11 @@ def test_device_candidates_are_a_function_of_seed_and_row(tmp_path, monkeypatch)
     assert ap.deviceCandidates is True
 
 
-def test_repeated_evaluation_plan_equals_the_generic_path():
-    """``GP._factor_again`` (the optimiser loop's short path: same training set, y, stream -> the previous call's
-    argument list with the kernel struct refilled) against the generic ``_factor``: same values, same factor bits, same
-    object state afterwards; anything that differs (y's contents, the current stream, a failed factorisation, an
-    intervening prediction) falls back or recovers as the generic path does."""
+def test_repeated_evaluation_replay_equals_the_generic_path():
+    """The ``"nll"`` replay of ``GP._factor`` (the optimiser loop's short path: same training set, y, stream -> the
+    previous call's argument list with the kernel struct refilled) against the generic ``_factor``: same values, same
+    factor bits, same object state afterwards; anything that differs (y's contents, the current stream, a failed
+    factorisation, an intervening prediction) falls back or recovers as the generic path does."""
     import torch
     from approxposterior_amd import gpUtils
     go, agp = _mods()
@@ -627,8 +627,8 @@ def test_repeated_evaluation_plan_equals_the_generic_path():
     for it in range(12):
         p = p0 + rs.normal(0, 0.2, size=p0.shape)
         ga._nllMemo = gb._nllMemo = None
-        used += ga._nll_plan is not None
-        gb._nll_plan = None                                   # generic path every time
+        used += "nll" in ga._replays
+        gb._replays.pop("nll", None)                          # generic path every time
         a, b = gpUtils._nll(p, ga, y, None), gpUtils._nll(p, gb, y, None)
         assert a == b and np.isfinite(a)
         assert ga.computed and gb.computed
@@ -644,10 +644,10 @@ def test_repeated_evaluation_plan_equals_the_generic_path():
     # y with other contents (same object, mutated in place): not the plan's y any more
     y2 = y.copy()
     gpUtils._nll(p0, ga, y2, None)
-    assert ga._nll_plan is not None
+    assert "nll" in ga._replays
     y2[3] += 1.0
     ga._nllMemo = gb._nllMemo = None
-    gb._nll_plan = None
+    gb._replays.pop("nll", None)
     assert gpUtils._nll(p0 + 0.01, ga, y2, None) == gpUtils._nll(p0 + 0.01, gb, y2, None)
     # another current stream: fresh buffers, as the generic path
     K_before = ga._L
@@ -655,19 +655,19 @@ def test_repeated_evaluation_plan_equals_the_generic_path():
         v = gpUtils._nll(p0 + 0.02, ga, y2, None)
         torch.cuda.current_stream().synchronize()
     assert ga._L is not K_before
-    gb._nll_plan = None
+    gb._replays.pop("nll", None)
     assert v == gpUtils._nll(p0 + 0.02, gb, y2, None)
     # a Gram matrix that is not positive definite on the short path: +inf, reset state, and the next evaluation is fine
     gpUtils._nll(p0, ga, y, None)
-    assert ga._nll_plan is not None
+    assert "nll" in ga._replays
     bad = p0.copy(); bad[2:] = 19.0; bad[1] = 19.5            # (huge length scales and amplitude: rank-deficient in fp64)
     vb_ = gpUtils._nll(bad, ga, y, None)
-    gb._nll_plan = None
+    gb._replays.pop("nll", None)
     assert vb_ == gpUtils._nll(bad, gb, y, None)
     if not np.isfinite(vb_):
         assert not ga.computed and ga._L is None
     ga._nllMemo = gb._nllMemo = None
-    gb._nll_plan = None
+    gb._replays.pop("nll", None)
     assert gpUtils._nll(p0, ga, y, None) == gpUtils._nll(p0, gb, y, None)
 
 
@@ -752,9 +752,9 @@ def test_two_block_column_fused_evaluation(n, D):
         assert a0[2].tobytes() == a1[2].tobytes()
 
 
-def test_repeated_mean_prediction_plan_equals_the_generic_path():
+def test_repeated_mean_prediction_replay_equals_the_generic_path():
     """``GP.predict(y, t, return_cov=False, return_var=False)`` for a few points at a time (the walker ensembles of the host-loop
-    sampler) re-uses the previous call's arguments (``_predict_mean_again``): same values as the generic path, and anything
+    sampler) re-uses the previous call's arguments (the ``"mean"`` replay): same values as the generic path, and anything
     that changes the model, y, the mean or the stream goes back to it."""
     import torch
     go, agp = _mods()
@@ -771,8 +771,8 @@ def test_repeated_mean_prediction_plan_equals_the_generic_path():
     used = 0
     for it in range(8):
         T = rs.uniform(-5, 5, size=(10 if it % 2 else 7, D))
-        used += ga._mean_plan is not None
-        gb._mean_plan = None
+        used += "mean" in ga._replays
+        gb._replays.pop("mean", None)
         assert np.array_equal(ga.predict(y, T, return_cov=False, return_var=False),
                               gb.predict(y, T, return_cov=False, return_var=False))
     assert used >= 7
@@ -782,20 +782,20 @@ def test_repeated_mean_prediction_plan_equals_the_generic_path():
     T = rs.uniform(-5, 5, size=(10, D))
     mo = gpo.predict(y, T, return_cov=False, return_var=False)
     asum = np.abs(gpo._compute_alpha(y, False)).sum()
-    assert ga._mean_plan is not None and np.abs(ga.predict(y, T, return_cov=False, return_var=False) - mo).max() <= 1e-10 * asum
+    assert "mean" in ga._replays and np.abs(ga.predict(y, T, return_cov=False, return_var=False) - mo).max() <= 1e-10 * asum
     # another y: not the plan's
     y2 = y + 0.5
-    gb._mean_plan = None
+    gb._replays.pop("mean", None)
     assert np.array_equal(ga.predict(y2, T, return_cov=False, return_var=False), gb.predict(y2, T, return_cov=False, return_var=False))
     # new hyper-parameters: the model is dirty, the generic path refactorises
     p = ga.get_parameter_vector() + 0.1
     ga.set_parameter_vector(p); gb.set_parameter_vector(p)
-    gb._mean_plan = None
+    gb._replays.pop("mean", None)
     m1, m2 = ga.predict(y, T, return_cov=False, return_var=False), gb.predict(y, T, return_cov=False, return_var=False)
     assert np.array_equal(m1, m2) and ga.computed
     # a changed mean alone (george: a ConstantModel value), lists and float32 points: generic path, same values
     ga.mean.value += 1.0; gb.mean.value += 1.0
-    gb._mean_plan = None
+    gb._replays.pop("mean", None)
     assert np.array_equal(ga.predict(y, T, return_cov=False, return_var=False), gb.predict(y, T, return_cov=False, return_var=False))
     assert np.array_equal(ga.predict(y, T.tolist(), return_cov=False, return_var=False), ga.predict(y, T, return_cov=False, return_var=False))
     # another current stream
@@ -805,9 +805,9 @@ def test_repeated_mean_prediction_plan_equals_the_generic_path():
     assert np.array_equal(m3, ga.predict(y, T, return_cov=False, return_var=False))
 
 
-def test_repeated_single_candidate_prediction_plan_equals_the_generic_path():
+def test_repeated_single_candidate_prediction_replay_equals_the_generic_path():
     """``GP.predict(y, t, return_var=True)`` for ONE point at a time (the reference's scalar utilities under Nelder-Mead) re-uses
-    the previous call's arguments (``_predict_one_again``), through the dense inverse or -- ``variance_mode = "solve"`` -- the
+    the previous call's arguments (the ``"one"`` replay), through the dense inverse or -- ``variance_mode = "solve"`` -- the
     substitution against L: same (mu, var) as the generic path; a switch of the form, new hyper-parameters or another y go
     back to it."""
     go, agp = _mods()
@@ -826,26 +826,26 @@ def test_repeated_single_candidate_prediction_plan_equals_the_generic_path():
         used = 0
         for it in range(6):
             t = rs.uniform(-5, 5, size=(1, D))
-            used += ga._one_plan is not None
-            gb._one_plan = None
+            used += "one" in ga._replays
+            gb._replays.pop("one", None)
             ma, va = ga.predict(y, t, return_var=True)
             mb, vb = gb.predict(y, t, return_var=True)
             assert np.array_equal(ma, mb) and np.array_equal(va, vb) and ma.shape == va.shape == (1,)
         assert used >= 5
         # the other variance form: not the plan's
         ga.variance_mode = gb.variance_mode = "inverse" if mode == "solve" else "solve"
-        gb._one_plan = None
+        gb._replays.pop("one", None)
         t = rs.uniform(-5, 5, size=(1, D))
         ra, rb = ga.predict(y, t, return_var=True), gb.predict(y, t, return_var=True)
         assert np.array_equal(ra[0], rb[0]) and np.array_equal(ra[1], rb[1])
         # new hyper-parameters, another y, two points at once
         p = ga.get_parameter_vector() + 0.05
         ga.set_parameter_vector(p); gb.set_parameter_vector(p)
-        gb._one_plan = None
+        gb._replays.pop("one", None)
         ra, rb = ga.predict(y, t, return_var=True), gb.predict(y, t, return_var=True)
         assert np.array_equal(ra[0], rb[0]) and np.array_equal(ra[1], rb[1])
         y2 = y - 0.25
-        gb._one_plan = None
+        gb._replays.pop("one", None)
         ra, rb = ga.predict(y2, t, return_var=True), gb.predict(y2, t, return_var=True)
         assert np.array_equal(ra[0], rb[0]) and np.array_equal(ra[1], rb[1])
         T2 = rs.uniform(-5, 5, size=(2, D))
@@ -887,7 +887,7 @@ def test_single_candidate_prediction_in_one_launch(n, D):
         for mode in (0, 1):
             lib.apgp_potrf_mode(mode)
             try:
-                g._one_plan = None
+                g._replays.pop("one", None)
                 out[mode] = g.predict(y, t, return_var=True)
                 again = g.predict(y, t, return_var=True)             # (the repeated-call plan)
                 assert np.array_equal(again[0], out[mode][0], equal_nan=True) and np.array_equal(again[1], out[mode][1], equal_nan=True)

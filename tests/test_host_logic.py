@@ -491,3 +491,30 @@ def test_nelder_mead_lookahead_serves_scipy_the_same_values_in_fewer_device_roun
         got = results[width]
         assert got[0] == base[0] and got[1] == base[1] and got[2] == base[2]
         assert got[4] > 0 and got[3] <= 0.8 * base[3], (got[3], base[3])
+
+
+def test_replay_guard_rejects_each_change_it_covers():
+    """The guard of GP's replayed library calls (``gp._Replay``) with fake device / stream queries: the state it was
+    built on passes; another current stream, another current device, y with other bytes, float32 y, non-contiguous y and
+    a replaced dependency are each rejected on their own."""
+    now = {"device": 1, "stream": {0: 7, 1: 7}}
+    queries = (lambda: now["device"], lambda dev: now["stream"][dev])
+    y = np.linspace(0.0, 1.0, 9)
+    deps = (object(), object())
+    r = agp._Replay(None, [], 1, 7, y, deps, queries)
+    assert r.fits(y, deps) and r.fits(y.copy(), deps)
+    now["stream"][1] = 8
+    assert not r.fits(y, deps)
+    now["stream"][1] = 7
+    now["device"] = 0                       # (the same raw stream handle on the other device)
+    assert not r.fits(y, deps)
+    now["device"] = 1
+    y2 = y.copy()
+    y2[4] += 1e-12
+    assert not r.fits(y2, deps)
+    assert not r.fits(y.astype(np.float32), deps)
+    yn = np.repeat(y, 2)[::2]
+    assert np.array_equal(yn, y) and not yn.flags.c_contiguous
+    assert not r.fits(yn, deps)
+    assert not r.fits(y, (deps[0], object()))
+    assert r.fits(y, deps)
