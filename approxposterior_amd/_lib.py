@@ -120,6 +120,8 @@ SIGNATURES = {
     "apgp_gmm_params_len": (_I64, [_I32, _I32]),
     "apgp_gmm_stats_len": (_I64, [_I32, _I32]),
     "apgp_gmm_pass": (ctypes.c_int, [_P, _I64, _I32, _I32, _P, _I32, _P, _P, _P, _P]),
+    "apgp_autocorr_work_len": (_I64, [_I64, _I64, _I32]),
+    "apgp_autocorr_block": (ctypes.c_int, [_P, _I64, _I64, _I32, _I64, _I64, _I64, _I64, _I32, _P, _P, _P]),
 }
 
 _lib = None

@@ -575,7 +575,7 @@ class ApproxPosterior(object):
 
     def runMCMC(self, samplerKwargs=None, mcmcKwargs=None, runName="apRun",
                 cache=True, estBurnin=True, thinChains=True, verbose=False,
-                args=None, batched=True, onDevice=False, **kwargs):
+                args=None, batched=True, onDevice=False, deviceAutocorr=False, **kwargs):
         """Sample the GP-surrogate posterior with the stretch-move ensemble sampler and
         estimate burn-in / thinning (approx.py:757-859): ``(sampler, iburn, ithin)``.
 
@@ -588,7 +588,12 @@ class ApproxPosterior(object):
         runs under ``lnprior.support()`` and carries the lnprior blobs, as the host chain does.
         With ``cache`` the chain goes to ``<runName>.npz`` (keys chain, log_prob, blobs)
         where the reference writes ``<runName>.h5``.
+        ``deviceAutocorr=True`` (opt-in, needs ``onDevice=True``): the chain also stays on the device and
+        ``estimateBurnin`` gets its autocorrelation time from there (``mcmc.integrated_time(onDevice=True)``); under a
+        process group every rank uploads the gathered chain once and computes the same ``(iburn, ithin)``.
         """
+        if deviceAutocorr and not onDevice:
+            raise ValueError("runMCMC(deviceAutocorr=True) diagnoses the chain of the device sampler: it needs onDevice=True")
         ranks = self._ranks()
         if ranks is not None:
             apdist.sync_random_state(0, self.group, enabled=self.distributed)
@@ -609,16 +614,25 @@ class ApproxPosterior(object):
             # (no ranks -- no process group, or distributed=False inside somebody else's: the local chain, seed
             # ``base``, and no collective whatever group the process has open)
             base = np.random.randint(0, 2 ** 31 - 1)
+            kept = []     # this rank's chain as the device sampler left it (deviceAutocorr)
             merged = apdist.replicated_ensembles(
                 lambda seed: self._sampleReplica(seed, samplerKwargs, mcmcKwargs, args, kwargs,
-                                                 batched, onDevice),
+                                                 batched, onDevice, keep=kept if deviceAutocorr else None),
                 seed=base, group=self.group if ranks is not None else None,
                 enabled=self.distributed if ranks is not None else False)
             chain, logp, naccept = merged[0], merged[1], merged[2]
-            self.sampler = emcee.DeviceChain({"chain": chain, "log_prob": logp, "naccept": naccept,
-                                              "coords": chain[-1], "final_log_prob": logp[-1],
-                                              "blobs": merged[3] if len(merged) > 3 else None},
-                                             a=samplerKwargs.get("a", 2.0))
+            result = {"chain": chain, "log_prob": logp, "naccept": naccept,
+                      "coords": chain[-1], "final_log_prob": logp[-1],
+                      "blobs": merged[3] if len(merged) > 3 else None}
+            if deviceAutocorr:
+                if ranks is None:
+                    result["chain_device"] = kept[0]
+                else:
+                    # the gathered chain of every rank's ensemble, uploaded once: the same input, hence the same
+                    # (iburn, ithin), on every rank without a collective
+                    import torch
+                    result["chain_device"] = torch.from_numpy(chain).to(kept[0].device)
+            self.sampler = emcee.DeviceChain(result, a=samplerKwargs.get("a", 2.0))
         else:
             self.sampler = self._hostSampler(samplerKwargs, args, kwargs, batched)
             for _ in self.sampler.sample(**mcmcKwargs):
@@ -641,13 +655,18 @@ class ApproxPosterior(object):
         return emcee.EnsembleSampler(**setup, backend=None, args=args, kwargs=kwargs,
                                      blobs_dtype=[("lnprior", float)])
 
-    def _sampleReplica(self, seed, samplerKwargs, mcmcKwargs, args, kwargs, batched, onDevice):
-        """This rank's ensemble: ``(chain, log_prob, naccept[, blobs])`` for :func:`dist.replicated_ensembles`."""
+    def _sampleReplica(self, seed, samplerKwargs, mcmcKwargs, args, kwargs, batched, onDevice, keep=None):
+        """This rank's ensemble: ``(chain, log_prob, naccept[, blobs])`` for :func:`dist.replicated_ensembles`.
+        ``keep``: a list that receives the device tensor of the chain (device sampler only)."""
         if onDevice:
             joint = self._jointPrior()
             extra = {} if joint is None else {"prior": joint}
+            if keep is not None:
+                extra["keep_device"] = True
             res = self.gp.sample_ensemble(self.y, mcmcKwargs["initial_state"], mcmcKwargs["iterations"],
                                           self.bounds, a=samplerKwargs.get("a", 2.0), seed=seed, **extra)
+            if keep is not None:
+                keep.append(res["chain_device"])
             out = (res["chain"], res["log_prob"], res["naccept"])
             return out if joint is None else out + (res["blobs"],)
         sampler = self._hostSampler(samplerKwargs, args, kwargs, batched, seed=seed)
@@ -666,7 +685,7 @@ class ApproxPosterior(object):
             gpHyperPrior=gpUtils.defaultHyperPrior, eps=1.0, convergenceCheck=False,
             minObjMethod="nelder-mead", minObjOptions=None, args=None,
             nCandidates=None, onDevice=False, batched=True, deviceCandidates=None, batchSize=None, pool=None,
-            deviceSearch=None, **kwargs):
+            deviceSearch=None, deviceAutocorr=False, **kwargs):
         """BAPE / AGP outer loop (approx.py:229-524): ``nmax`` times, find ``m`` design
         points (re-fitting the GP every ``optGPEveryN``), sample the surrogate posterior,
         record burn-in / thinning, and -- with ``convergenceCheck`` -- stop once the
@@ -677,7 +696,10 @@ class ApproxPosterior(object):
         (``deviceCandidates``: drawn on the device, see :meth:`findNextPoint`);
         ``onDevice`` / ``batched`` are passed to :meth:`runMCMC`; ``batchSize`` / ``pool`` to
         :meth:`findNextPoint` (design points chosen and their forward models run in batches), and ``deviceSearch``
-        (the Nelder-Mead point search on the device)."""
+        (the Nelder-Mead point search on the device).  ``deviceAutocorr`` is passed to :meth:`runMCMC` too (burn-in and
+        thinning from the device's autocorrelation estimate; needs ``onDevice=True``)."""
+        if deviceAutocorr and not onDevice:
+            raise ValueError("run(deviceAutocorr=True) needs onDevice=True")
         if convergenceCheck and onlyLastMCMC:
             raise RuntimeError("If convergenceCheck is True, must run an MCMC each iteration.\n"
                                "convergenceCheck = %d onlyLastMCMC = %d" % (convergenceCheck, onlyLastMCMC))
@@ -720,7 +742,7 @@ class ApproxPosterior(object):
                                            runName="%s%d" % (runName, iteration), cache=cache,
                                            estBurnin=estBurnin, thinChains=thinChains,
                                            verbose=verbose, args=args, onDevice=onDevice,
-                                           batched=batched, **kwargs)
+                                           batched=batched, deviceAutocorr=deviceAutocorr, **kwargs)
             self.iburns.append(iburn)
             self.ithins.append(ithin)
             if timing:

@@ -1505,7 +1505,8 @@ class GP(GeorgeExtras):
         return T
 
     # -- on-device ensemble MCMC over the GP mean ------------------------------------
-    def sample_ensemble(self, y, initial_state, iterations, bounds, a=2.0, seed=0, store=True, prior=None):
+    def sample_ensemble(self, y, initial_state, iterations, bounds, a=2.0, seed=0, store=True, prior=None,
+                        keep_device=False):
         """Run the stretch-move ensemble sampler entirely on the device with
         log-probability = GP mean (what ApproxPosterior._gpll returns) and the box
         prior ``bounds``.  ``initial_state`` is (W, D) for one ensemble or (E, W, D)
@@ -1516,7 +1517,10 @@ class GP(GeorgeExtras):
         ``prior``: a :class:`~approxposterior_amd.priors.JointPrior`.  The walkers are then gated by
         ``prior.support()`` (``bounds`` is not used) and, with ``store``, the result also has ``blobs``
         (iterations, E*W): the prior's log-density at every stored state, NaN where it is -inf, as
-        ``ApproxPosterior._gpllBatch`` returns for a rejected walker."""
+        ``ApproxPosterior._gpllBatch`` returns for a rejected walker.
+
+        ``keep_device``: with ``store``, the result also has ``chain_device``, the device tensor (iterations, E*W, D)
+        that ``chain`` was copied from (``DeviceChain.get_autocorr_time`` then reads it in place)."""
         self.recompute()
         torch, dev, lib = self._rt()
         y = self._check_dimensions(y)
@@ -1574,6 +1578,8 @@ class GP(GeorgeExtras):
                    "naccept": nacc.cpu().numpy().reshape(E * W),
                    "chain": chain.cpu().numpy().reshape(iterations, E * W, D) if store else None,
                    "log_prob": lchain.cpu().numpy().reshape(iterations, E * W) if store else None}
+            if keep_device and store:
+                out["chain_device"] = chain.view(iterations, E * W, D)
             if prior is not None and store:
                 # the lnprior blobs: one pass of the prior's log-density over the stored chain
                 lp = torch.empty(iterations * E * W, dtype=torch.float64, device=dev)

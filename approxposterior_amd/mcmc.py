@@ -64,11 +64,117 @@ def _auto_window(taus, c):
     return len(taus) - 1
 
 
-def integrated_time(x, c=5, tol=50, quiet=False):
+# Device path of integrated_time (csrc/autocorr.hip, DESIGN.md "Chain diagnostics"): the autocorrelation function is
+# asked for in blocks of lags -- AUTOCORR_BLOCK first, then as many again as are there already -- until every dimension
+# has its window.
+AUTOCORR_BLOCK = 256
+# Lags after which the device path stops extending and the call is finished by the host FFT estimator below: the
+# direct sum costs O(n_t * lags) per series, the FFT O(n_t log n_t) whatever the window.
+# Measured (tools/autocorr_timing.py, profiles/autocorr_timing.json, MI355X against 16 host threads): no crossing up to
+# all n_t lags at 2e4 x 64 x 8 -- lags 0..4095 take 5.3 ms, all 20000 lags 18.4 ms, the host call 168 ms -- and a near
+# tie at all lags at 2e4 x 20 x 2 (10.3 ms against 10.9 ms; 2.3 ms at 4096).  The cap sits below both, so a chain that
+# reaches it and is then handed to the host pays at most those 5.3 ms (3 %) on top of the host call.
+AUTOCORR_LAG_CAP = 4096
+autocorr_fallbacks = 0      # calls the device path handed to the host estimator because the window lay past the cap
+
+
+class _DeviceAcf(object):
+    """Blocks of the walker-averaged autocorrelation function of one chain, from ``apgp_autocorr_block``.
+    ``x``: a (n_t, n_w, n_d) NumPy array (uploaded once) or torch tensor; a device tensor whose steps are whole
+    rows of a contiguous chain (``chain[discard::thin]``) is read in place through the row stride."""
+
+    def __init__(self, x):
+        import ctypes
+        import torch
+        from . import _lib
+        self._torch, self._lib, self._check, self._vp = torch, _lib.load(), _lib.check, ctypes.c_void_p
+        if not torch.is_tensor(x):
+            x = torch.from_numpy(np.ascontiguousarray(x, dtype=np.float64)).to(torch.device("cuda", torch.cuda.current_device()))
+        elif x.device.type != "cuda":
+            x = x.to(torch.device("cuda", torch.cuda.current_device()))
+        if x.dtype != torch.float64:
+            x = x.to(torch.float64)
+        self.n_t, self.n_w, self.n_d = (int(v) for v in x.shape)
+        series = self.n_w * self.n_d
+        rows = x.stride(0) if self.n_t > 1 else series
+        if x.stride(2) != 1 or x.stride(1) != self.n_d or rows < series or rows % series != 0:
+            x = x.contiguous()
+            rows = series
+        self._x, self._stride = x, rows // series
+        need = int(self._lib.apgp_autocorr_work_len(self.n_t, self.n_w, self.n_d))
+        if need < 0:
+            raise ValueError("chain of shape %s is outside the limits of apgp_autocorr_block" % (tuple(x.shape),))
+        with torch.cuda.device(x.device):
+            self._work = torch.empty(need, dtype=torch.float64, device=x.device)
+        self._have_stats = False
+
+    def __call__(self, lag0, nlags):
+        torch, x = self._torch, self._x
+        with torch.cuda.device(x.device):
+            f = torch.empty((self.n_d, nlags), dtype=torch.float64, device=x.device)
+            st = self._vp(torch.cuda.current_stream().cuda_stream)
+            self._check(self._lib.apgp_autocorr_block(x.data_ptr(), self.n_t, self.n_w, self.n_d, 0, self._stride,
+                                                      int(lag0), int(nlags), int(self._have_stats),
+                                                      self._work.data_ptr(), f.data_ptr(), st), "apgp_autocorr_block")
+            self._have_stats = True
+            return f.cpu().numpy()
+
+
+def _windows_from_blocks(acf, n_t, n_d, c, block, cap):
+    """Sokal's window and tau per dimension from an autocorrelation function served in blocks of lags:
+    ``acf(lag0, nlags) -> (n_d, nlags)``.  After each block the host lines of :func:`integrated_time` run on the lags
+    that are there; a dimension is done at the first lag M >= c tau(M), all are done when every one of the n_t lags is
+    there.  Returns ``(tau, windows)``, or ``None`` once ``cap`` lags did not settle every dimension."""
+    f = np.empty((n_d, 0))
+    tau_est = np.empty(n_d)
+    windows = np.empty(n_d, dtype=int)
+    limit = min(n_t, max(int(cap), 1))
+    while True:
+        have = f.shape[1]
+        more = min(max(have, int(block)), limit - have)
+        f = np.concatenate([f, np.asarray(acf(have, more), dtype=float)[:, :more]], axis=1)
+        have += more
+        open_dims = 0
+        for d in range(n_d):
+            taus = 2.0 * np.cumsum(f[d]) - 1.0
+            m = np.arange(have) < c * taus
+            if have < n_t and m.all():
+                open_dims += 1                # no lag with M >= c tau(M) yet
+                continue
+            windows[d] = _auto_window(taus, c)
+            tau_est[d] = taus[windows[d]]
+        if open_dims == 0:
+            return tau_est, windows
+        if have >= limit:
+            return None
+
+
+def integrated_time(x, c=5, tol=50, quiet=False, onDevice=False):
     """Integrated autocorrelation time per dimension of a chain ``x`` of shape
     (nsteps, nwalkers, ndim), Sokal's automated windowing with window constant
     ``c`` (the estimator behind emcee's ``get_autocorr_time``; with ``tol=0`` it
-    always returns an estimate, which is how mcmcUtils.py:198 calls it)."""
+    always returns an estimate, which is how mcmcUtils.py:198 calls it).
+
+    ``onDevice=True``, or an ``x`` that is a torch tensor on the GPU: the autocorrelation function comes from the
+    device in blocks of lags, summed directly (``apgp_autocorr_block``), and only as far as the windows need it; the
+    windowing lines are the ones below.  A chain whose window lies past ``AUTOCORR_LAG_CAP`` lags is handed to the host
+    estimator for that call (``autocorr_fallbacks`` counts them).  Same return value either way."""
+    global autocorr_fallbacks
+    if onDevice or _is_device_tensor(x):
+        if _is_tensor(x):
+            xd = x if x.dim() == 3 else (x[:, None, None] if x.dim() == 1 else (x[:, :, None] if x.dim() == 2 else None))
+        else:
+            xd = np.atleast_1d(x)
+            xd = xd[:, np.newaxis, np.newaxis] if xd.ndim == 1 else (xd[:, :, np.newaxis] if xd.ndim == 2 else xd)
+        if xd is None or len(xd.shape) != 3:
+            raise ValueError("invalid dimensions")
+        n_t, n_d = int(xd.shape[0]), int(xd.shape[2])
+        done = _windows_from_blocks(_device_acf(xd), n_t, n_d, c, AUTOCORR_BLOCK, AUTOCORR_LAG_CAP)
+        if done is not None:
+            return _checked_tau(done[0], n_t, tol, quiet)
+        autocorr_fallbacks += 1
+    if _is_tensor(x):
+        x = x.detach().cpu().numpy()
     x = np.atleast_1d(x)
     if x.ndim == 1:
         x = x[:, np.newaxis, np.newaxis]
@@ -101,6 +207,23 @@ def integrated_time(x, c=5, tol=50, quiet=False):
         taus = 2.0 * np.cumsum(f) - 1.0
         windows[d] = _auto_window(taus, c)
         tau_est[d] = taus[windows[d]]
+    return _checked_tau(tau_est, n_t, tol, quiet)
+
+
+def _is_tensor(x):
+    return type(x).__module__.split(".")[0] == "torch" and hasattr(x, "data_ptr")
+
+
+def _is_device_tensor(x):
+    return _is_tensor(x) and x.device.type == "cuda"
+
+
+def _device_acf(x):
+    return _DeviceAcf(x)
+
+
+def _checked_tau(tau_est, n_t, tol, quiet):
+    """``tau_est``, or :class:`AutocorrError` when the chain is shorter than ``tol`` times it (emcee's rule)."""
     flag = tol * tau_est > n_t
     if np.any(flag) and tol > 0:
         msg = ("The chain is shorter than {0} times the integrated autocorrelation time for {1} "
@@ -279,6 +402,7 @@ class DeviceChain(EnsembleSampler):
         self._random = None
         self.iteration = chain.shape[0]
         self._chain = chain
+        self._chain_device = result.get("chain_device")   # the same chain as a device tensor (sample_ensemble(keep_device=True))
         self._log_prob = result["log_prob"]
         blobs = result.get("blobs")
         self._blobs = [] if blobs is None else blobs      # (iterations, walkers) lnprior values of a gathered host chain
@@ -289,3 +413,12 @@ class DeviceChain(EnsembleSampler):
 
     def sample(self, *args, **kwargs):
         raise NotImplementedError("a finished on-device chain cannot be advanced from the host")
+
+    def get_autocorr_time(self, discard=0, thin=1, **kwargs):
+        """As :meth:`EnsembleSampler.get_autocorr_time`; a chain that is still on the device is diagnosed there
+        (``integrated_time(onDevice=True)`` on the strided view, no copy)."""
+        if self._chain_device is None:
+            return super(DeviceChain, self).get_autocorr_time(discard=discard, thin=thin, **kwargs)
+        discard, thin = int(discard), int(thin)
+        kwargs["onDevice"] = True
+        return thin * integrated_time(self._chain_device[discard + thin - 1::thin], **kwargs)

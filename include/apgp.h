@@ -522,6 +522,26 @@ int64_t apgp_gmm_stats_len(int32_t ndim, int32_t ncomp);
 int apgp_gmm_pass(const double* X, int64_t n, int32_t ndim, int32_t ncomp, const double* params, int32_t mode,
                   double* stats_out, double* row_lp, int32_t* row_label, void* stream);
 
+/* ---- Chain diagnostics: a block of the walker-averaged autocorrelation function ------------
+ * (mcmc.integrated_time(onDevice=True).)  x (device, fp64) is an ensemble chain laid out (steps, n_w, n_d) row-major as
+ * GP.sample_ensemble stores it; step t of the series is row row0 + t * row_stride of it (a get_chain(discard=, thin=)
+ * view needs no copy), n_t steps in all.  With m_kd the mean over t of x[t,k,d] and
+ *   A_kd(l) = sum_{t = 0}^{n_t - l - 1} (x[t,k,d] - m_kd) (x[t+l,k,d] - m_kd),
+ * f (device, n_d x nlags row-major) receives
+ *   f[d][l - lag0] = (1 / n_w) * sum_k A_kd(l) / A_kd(0)        for lag0 <= l < lag0 + nlags
+ * by direct summation (no FFT); a lag l >= n_t has an empty sum, f = 0 there.  A series with A(0) = 0 makes its
+ * dimension's f NaN (0/0) and no other.  Partial sums over time chunks are combined in a fixed order that depends on
+ * n_t only: no atomics, the same input gives the same bits whatever blocks of lags are asked for.
+ * work (device): apgp_autocorr_work_len(n_t, n_w, n_d) doubles.  reuse_stats = 0: the means and A(0) are computed and
+ * left in work; reuse_stats != 0: work still holds them from an earlier call on the same x, n_t, row0 and row_stride.
+ * Limits: 1 <= n_t, nlags < 2^31, 0 <= lag0, row0 < 2^31, 1 <= row_stride < 2^31, 1 <= n_w <= 2^24,
+ * 1 <= n_d <= APGP_MAX_DIM, (row0 + (n_t - 1) row_stride + 1) n_w n_d <= 2^60; apgp_autocorr_work_len returns -1
+ * outside them.  Bad arguments are refused (-1) before anything reaches the device.
+ * Added in ABI 8 without changing anything before it: APGP_ABI_VERSION stays 8.                                      */
+int64_t apgp_autocorr_work_len(int64_t n_t, int64_t n_w, int32_t n_d);
+int apgp_autocorr_block(const double* x, int64_t n_t, int64_t n_w, int32_t n_d, int64_t row0, int64_t row_stride,
+                        int64_t lag0, int64_t nlags, int32_t reuse_stats, double* work, double* f, void* stream);
+
 /* ---- K4: gradient of the log-likelihood wrt kernel hyper-parameters -------
  * Replaces george GP.grad_log_likelihood (gpUtils._grad_nll, gpUtils.py:110):
  *   g_k = 0.5 * sum_ij (alpha alpha^T - K^-1)_ij dK_ij/dtheta_k.
