@@ -690,7 +690,9 @@ __global__ __launch_bounds__(S2_THREADS, 1) void sweep2_kernel(SweepArgs a) {
             }
         }
         if (inb && a.mask && a.mask[crow] == 0) adm = false;
-        fl_cur = (adm ? 1 : 0) | (has_nan ? 2 : 0) | (inb ? 4 : 0);
+        // a row with a NaN coordinate is inadmissible with or without a box: Jones would give it 0.0 (sqrt(var) > 0 is false),
+        // which ties with an underflowed tail and, at the lowest index, would win
+        fl_cur = ((adm && !has_nan) ? 1 : 0) | (has_nan ? 2 : 0) | (inb ? 4 : 0);
         ktt_cur = LIN ? fma(a.lin_coef, ktl, a.amp) : a.amp;
     };
     // generate the B operands of tile (jb, kc) of the current block -> LDS buffer bb (and, on
@@ -1024,7 +1026,7 @@ __global__ __launch_bounds__(64) void sweep_finish_kernel(SweepArgs a) {
         if (a.mu) a.mu[crow] = mu;
         if (a.var) a.var[crow] = var;
         if (a.kind != APGP_UTIL_NONE) {
-            const double uu = adm ? util_value(a.kind, mu, var, a.zeta, a.ybest) : INFINITY;
+            const double uu = (adm && !has_nan) ? util_value(a.kind, mu, var, a.zeta, a.ybest) : INFINITY;   // (as the sweep)
             if (a.u) a.u[crow] = uu;
             best_merge(bu, bi, uu, a.idx_offset + crow);
         }
@@ -1356,6 +1358,10 @@ __global__ __launch_bounds__(FT_THREADS) void fantasy_kernel(FantasyArgs a) {
                 const double x = a.T[row * a.ndim + d];
                 if (!(x >= a.lo[d] && x <= a.hi[d])) adm = false;
             }
+        // a row with a NaN coordinate is inadmissible, as in the sweep (a scaled coordinate is NaN where the coordinate is)
+#pragma unroll
+        for (int d = 0; d < DPAD; ++d)
+            if (tt[d] != tt[d]) adm = false;
         const double uu = adm ? util_value(a.kind, a.mu[row], v, a.zeta, a.ybest) : INFINITY;
         if (a.u) a.u[row] = uu;
         best_merge(bu, bi, uu, a.idx_offset + row);

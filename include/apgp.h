@@ -287,6 +287,10 @@ int apgp_pack_train(const double* X, const double* alpha, int64_t n,
  *         mask[i] == 0
  * and the arg-min over candidates (ties -> lowest index, NaN never wins):
  * the batched counterpart of utility.minimizeObjective (utility.py:253-372).
+ * A row of T with a NaN coordinate is inadmissible with or without a box or a mask (the reference
+ * refuses it in its prior): mu = var = NaN, u = +inf, never the arg-min -- in apgp_acquire,
+ * apgp_acquire_solve and apgp_acquire_fantasy alike.  (The reference's JONES formula alone would
+ * give such a row 0.0, its ``std > 0`` being false, which ties with an underflowed tail.)
  * mu / var / u may be NULL (not stored).  lo/hi are host arrays or NULL.
  * part: scratch of apgp_acquire_work_len(m, n) doubles, 16-byte aligned: the
  *       per-block arg-min partials plus, for n > APGP_ROW_BLOCK, the stream in

@@ -18,6 +18,7 @@ from scipy.optimize import minimize
 from scipy.stats import norm
 
 import nm_ref
+import util_ref
 
 pytestmark = pytest.mark.gpu
 
@@ -123,6 +124,16 @@ def _check_evaluations(gp, y, rec, kind, b, exact):
         # log(1 - exp(-var)): a one-ulp difference of exp() is amplified by 1 / var for small var
         tol = tol + 8.0 * np.finfo(float).eps / np.maximum(np.abs(var_d), 1e-300)
     assert np.all(np.abs(u_d[both] - want[both]) <= tol[both]), np.max(np.abs(u_d[both] - want[both]) / tol[both])
+    if kind in util_ref.KINDS:
+        # against the 60-digit truth of the device's own (mu, sigma^2), within the smaller of the tolerance above and the
+        # forward-error bound of the formula (tests/util_ref.py); NaN / +inf / 0.0 by class
+        ybest = float(np.max(y))
+        for i in range(len(u_d)):
+            cls, r = util_ref.judge(kind, u_d[i], mu_d[i], var_d[i], 0.01, ybest)
+            assert r <= 1.0, (kind, i, cls, r, u_d[i], mu_d[i], var_d[i])
+            b = util_ref.bound(kind, mu_d[i], var_d[i], 0.01, ybest)
+            if cls == "value" and b is not None:
+                assert r * b <= tol[i], (kind, i, r * b, tol[i], u_d[i], mu_d[i], var_d[i])
 
 
 CASES = [(n, form) for n in (50, 90, 256, 300, 1152) for form in ("inverse", "solve")]
