@@ -75,6 +75,12 @@ struct SweepArgs {
     int ndim, nrb, kind, has_box, n, ncache, lin_order;
     double mean, amp, zeta, ybest, lin_coef;
     double sc[APGP_MAX_DIM], lo[APGP_MAX_DIM], hi[APGP_MAX_DIM], lw[APGP_MAX_DIM];
+    // pruned sweep (sweep2_kernel<.., LIST = true>, sweep_finish_kernel): "candidate block k of this launch" is
+    // blk_list[k], k < *blk_count -- a count the device computed; the launch is sized for the largest count it may
+    // meet and does nothing unless list_lo < *blk_count <= list_hi
+    const long long* blk_list;
+    const long long* blk_count;
+    long long list_lo, list_hi;
 };
 
 __device__ __forceinline__ void best_merge(double& bu, long long& bi, double u, long long i) {
@@ -174,7 +180,11 @@ static constexpr bool s2_structured_feeder(int dpad, bool solve) { return dpad =
 // unrolled diagonal tiles (N <= 256 S2_STATIC_DIAG_NRB) -- a separate instantiation: the 65 KiB of
 // unrolled code slowed the run-time-indexed path of the SAME kernel by 20 % at N = 4096 (333 vs 276 ms;
 // identical hot loops, only their placement differs), so large N run the kernel that does not contain it.
-template <int DPAD, bool LIN, int MODE>
+// LIST: the candidate blocks of the launch come from a device list (SweepArgs::blk_list) -- an instantiation of its own,
+// so that the full sweep's code is what it was before the list existed (this kernel's speed hangs on how hipcc
+// allocates its scalars: DESIGN.md section 6, the NaN-refusal episode).  The indirection sits where a block's
+// candidates are loaded; the tile loop never sees it.
+template <int DPAD, bool LIN, int MODE, bool LIST = false>
 __global__ __launch_bounds__(S2_THREADS, 1) void sweep2_kernel(SweepArgs a) {
     constexpr bool SOLVE = MODE != 0;
     constexpr bool STATIC_DIAG = MODE == 2;
@@ -197,6 +207,18 @@ __global__ __launch_bounds__(S2_THREADS, 1) void sweep2_kernel(SweepArgs a) {
     double* Cst = red_u + 8;                      // sc | lo | hi | lw (4 x APGP_MAX_DIM), feeder only
     const int t = threadIdx.x, lane = t & 63, w = t >> 6;
     const int cl = lane & 15, kq = lane >> 4;
+    // blocks [S2_BLK_BEGIN, S2_BLK_END) of this launch; LIST: positions 0 .. count - 1 in the list.  (Macros, not
+    // variables: the full sweep's instantiation reads a.blk_begin / a.blk_end where it always did -- loaded once at
+    // the top instead, hipcc allocated the feeders' scalars differently.)
+    long long lst_end = 0;
+    if constexpr (LIST) {
+        lst_end = *a.blk_count;
+        if (lst_end <= a.list_lo || lst_end > a.list_hi) return;    // (the whole grid: another launch has this count)
+        const long long nwg = a.split ? lst_end * ((a.n + S2_ROWS - 1) / S2_ROWS) : lst_end;
+        if ((long long)blockIdx.x >= nwg) return;                   // (before the first barrier, the whole workgroup)
+    }
+#define S2_BLK_BEGIN (LIST ? 0ll : a.blk_begin)
+#define S2_BLK_END (LIST ? lst_end : a.blk_end)
     apgp_exp_tab_load(Etab);
     if (t == 256) {
 #pragma unroll
@@ -223,13 +245,13 @@ __global__ __launch_bounds__(S2_THREADS, 1) void sweep2_kernel(SweepArgs a) {
     // Split mode (short last round / small launches): ONE (candidate block, row block) item,
     // heaviest row blocks first; the shares go to sp_q / sp_mu and sweep_finish_kernel.
     int jb_lo = 0, jb_hi = nrb2;
-    long long blk0 = a.blk_begin + blockIdx.x, blk_step = gridDim.x;
+    long long blk0 = S2_BLK_BEGIN + blockIdx.x, blk_step = gridDim.x;
     if (a.split) {
-        const int nsplit = (int)(a.blk_end - a.blk_begin);
-        blk0 = a.blk_begin + (int)blockIdx.x % nsplit;
+        const int nsplit = (int)(S2_BLK_END - S2_BLK_BEGIN);
+        blk0 = S2_BLK_BEGIN + (int)blockIdx.x % nsplit;
         jb_lo = nrb2 - 1 - (int)blockIdx.x / nsplit;
         jb_hi = jb_lo + 1;
-        blk_step = a.blk_end;
+        blk_step = S2_BLK_END;
     }
     auto successor = [&](int& jb, int& kc, long long& blk) {
         ++kc;
@@ -272,7 +294,7 @@ __global__ __launch_bounds__(S2_THREADS, 1) void sweep2_kernel(SweepArgs a) {
         // layout the feeders of the inverse form write: [half][wavefront][lane] x 16 B)
         const __amdgpu_buffer_rsrc_t rs_kv = __builtin_amdgcn_make_buffer_rsrc(
             (void*)(a.kcache + (long long)blockIdx.x * a.ncache * SW_BCH), 0, (int)a.kslot_bytes, 0x00020000);
-        for (long long blk = blk0; blk < a.blk_end; blk += blk_step) {
+        for (long long blk = blk0; blk < S2_BLK_END; blk += blk_step) {
             double qtot = 0.0;
             for (int jb = jb_lo; jb < jb_hi; ++jb) {
                 const int nkc = nkc_of(jb);
@@ -668,6 +690,10 @@ __global__ __launch_bounds__(S2_THREADS, 1) void sweep2_kernel(SweepArgs a) {
     auto load_candidates = [&](long long blk) {
         // snapshot the finished block, then set up the new one
         mu_fin = mu_tot; ktt_fin = ktt_cur; fl_fin = fl_cur; blk_fin = blk_cur;
+        if constexpr (LIST) {                     // position in the list -> the block's number in the candidate matrix
+            const bool live = blk < S2_BLK_END;
+            blk = live ? a.blk_list[blk] : a.blk_end;
+        }
         blk_cur = blk; mu_cur = 0.0; mu_tot = 0.0;
         const long long crow = blk * SW_CAND + hw * 16 + cl;
         const bool inb = blk < a.blk_end && crow < a.m;
@@ -759,7 +785,8 @@ __global__ __launch_bounds__(S2_THREADS, 1) void sweep2_kernel(SweepArgs a) {
         __syncthreads();                          // E1
         if (a.split) {
             if (kq == 0) {
-                const long long e = ((blk_fin - a.blk_begin) * SW_CAND + hw * 16 + cl) * nrb2 + jb_lo;
+                // (LIST: the shares are indexed by the block's position in the list -- a split workgroup has one block)
+                const long long e = ((LIST ? blk0 : blk_fin - a.blk_begin) * SW_CAND + hw * 16 + cl) * nrb2 + jb_lo;
                 a.sp_q[e] = Shq[hw * 16 + cl];
                 a.sp_mu[e] = mu_fin;
             }
@@ -863,7 +890,7 @@ __global__ __launch_bounds__(S2_THREADS, 1) void sweep2_kernel(SweepArgs a) {
         __syncthreads();                              // P
         int slot = 1, par = 1, gpar = 1;
         bool first_tile = true;
-        for (long long blk = blk0; blk < a.blk_end; blk += blk_step) {
+        for (long long blk = blk0; blk < S2_BLK_END; blk += blk_step) {
             for (int jb = jb_lo; jb < jb_hi; ++jb) {
                 const int nkc = nkc_of(jb), nd0 = nd0_of(jb);
                 // ---- run of parked tiles: image + parked operands by LDS-DMA, nothing else ----
@@ -901,7 +928,7 @@ __global__ __launch_bounds__(S2_THREADS, 1) void sweep2_kernel(SweepArgs a) {
                 }
             }
         }
-        load_candidates(a.blk_end);                   // (no next block: only snapshots the finished one)
+        load_candidates(S2_BLK_END);                  // (no next block: only snapshots the finished one)
         S2_BARRIER(0);                                // barrier of the last tile
         epilogue();
 #undef S2_BARRIER
@@ -948,7 +975,7 @@ __global__ __launch_bounds__(S2_THREADS, 1) void sweep2_kernel(SweepArgs a) {
         long long ntile_blk = 0;
         for (int jb = jb_lo; jb < jb_hi; ++jb) ntile_blk += nkc_of(jb);
         long long nblk_mine = 0;
-        for (long long b = blk0; b < a.blk_end; b += blk_step) ++nblk_mine;
+        for (long long b = blk0; b < S2_BLK_END; b += blk_step) ++nblk_mine;
         const long long ntot = ntile_blk * nblk_mine;
         bool last_m1 = (ntile_blk == 1), last_m2 = false;
         int slot = 1, par = 1;
@@ -990,6 +1017,9 @@ __global__ __launch_bounds__(S2_THREADS, 1) void sweep2_kernel(SweepArgs a) {
     }
 }
 
+#undef S2_BLK_BEGIN
+#undef S2_BLK_END
+
 // The short last round of the persistent grid (and every launch with fewer candidate blocks
 // than CUs) is split by ROW BLOCK: one workgroup per (candidate block, row block) writes its
 // share of sum V^2 and of mu, this kernel adds the shares in row-block order (deterministic)
@@ -998,7 +1028,12 @@ __global__ __launch_bounds__(S2_THREADS, 1) void sweep2_kernel(SweepArgs a) {
 // 256 CUs would keep 247 of them idle for a whole block time.
 __global__ __launch_bounds__(64) void sweep_finish_kernel(SweepArgs a) {
     const int c = threadIdx.x;
-    const long long blk = a.blk_begin + blockIdx.x;
+    long long blk = a.blk_begin + blockIdx.x;
+    if (a.blk_list) {                             // pruned sweep: the split launch's blocks come from the device list
+        const long long cnt = *a.blk_count;
+        if (cnt <= a.list_lo || cnt > a.list_hi || (long long)blockIdx.x >= cnt) return;
+        blk = a.blk_list[blockIdx.x];
+    }
     const long long crow = blk * SW_CAND + c;
     double bu = INFINITY;
     long long bi = -1;
@@ -1071,10 +1106,13 @@ static int s2_prepare_device() {
     if (done[dev]) return 0;
     const int lds = (int)s2_lds_bytes<DPAD>();
     hipError_t e = hipSuccess;
-    const void* kernels[6] = {(const void*)sweep2_kernel<DPAD, false, 0>, (const void*)sweep2_kernel<DPAD, true, 0>,
-                              (const void*)sweep2_kernel<DPAD, false, 1>, (const void*)sweep2_kernel<DPAD, true, 1>,
-                              (const void*)sweep2_kernel<DPAD, false, 2>, (const void*)sweep2_kernel<DPAD, true, 2>};
-    for (int i = 0; i < 6 && e == hipSuccess; ++i)
+    const void* kernels[12] = {(const void*)sweep2_kernel<DPAD, false, 0>, (const void*)sweep2_kernel<DPAD, true, 0>,
+                               (const void*)sweep2_kernel<DPAD, false, 1>, (const void*)sweep2_kernel<DPAD, true, 1>,
+                               (const void*)sweep2_kernel<DPAD, false, 2>, (const void*)sweep2_kernel<DPAD, true, 2>,
+                               (const void*)sweep2_kernel<DPAD, false, 0, true>, (const void*)sweep2_kernel<DPAD, true, 0, true>,
+                               (const void*)sweep2_kernel<DPAD, false, 1, true>, (const void*)sweep2_kernel<DPAD, true, 1, true>,
+                               (const void*)sweep2_kernel<DPAD, false, 2, true>, (const void*)sweep2_kernel<DPAD, true, 2, true>};
+    for (int i = 0; i < 12 && e == hipSuccess; ++i)
         e = hipFuncSetAttribute(kernels[i], hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     if (e != hipSuccess) {
         apgp_set_error("apgp_acquire: hipFuncSetAttribute(%d B of LDS) failed on device %d: %s", lds, dev,
@@ -1085,31 +1123,34 @@ static int s2_prepare_device() {
     return 0;
 }
 
+// one launch of the kernel that fits (form, N, LinearKernel term); LIST: its blocks come from a.blk_list
+template <int DPAD, bool LIST>
+static void s2_launch(const SweepArgs& a, hipStream_t s, bool solve, unsigned grid) {
+    const size_t lds = s2_lds_bytes<DPAD>();
+    if (solve && a.nrb <= S2_STATIC_DIAG_NRB) {
+        if (a.lin_coef != 0.0)
+            hipLaunchKernelGGL((sweep2_kernel<DPAD, true, 2, LIST>), dim3(grid), dim3(S2_THREADS), lds, s, a);
+        else
+            hipLaunchKernelGGL((sweep2_kernel<DPAD, false, 2, LIST>), dim3(grid), dim3(S2_THREADS), lds, s, a);
+    } else if (solve) {
+        if (a.lin_coef != 0.0)
+            hipLaunchKernelGGL((sweep2_kernel<DPAD, true, 1, LIST>), dim3(grid), dim3(S2_THREADS), lds, s, a);
+        else
+            hipLaunchKernelGGL((sweep2_kernel<DPAD, false, 1, LIST>), dim3(grid), dim3(S2_THREADS), lds, s, a);
+    } else if (a.lin_coef != 0.0)
+        hipLaunchKernelGGL((sweep2_kernel<DPAD, true, 0, LIST>), dim3(grid), dim3(S2_THREADS), lds, s, a);
+    else
+        hipLaunchKernelGGL((sweep2_kernel<DPAD, false, 0, LIST>), dim3(grid), dim3(S2_THREADS), lds, s, a);
+}
+
 template <int DPAD>
 static int launch_sweep(const SweepArgs& a0, hipStream_t s, bool solve) {
     const int rc = s2_prepare_device<DPAD>();
     if (rc != 0) return rc;
     SweepArgs a = a0;
-    const size_t lds = s2_lds_bytes<DPAD>();
     const long long ncb = (a.m + SW_CAND - 1) / SW_CAND;
     const int nrb2 = s2_nrb(a.n);
     a.nrb = nrb2;
-    auto launch = [&](unsigned grid) {
-        if (solve && nrb2 <= S2_STATIC_DIAG_NRB) {
-            if (a.lin_coef != 0.0)
-                hipLaunchKernelGGL((sweep2_kernel<DPAD, true, 2>), dim3(grid), dim3(S2_THREADS), lds, s, a);
-            else
-                hipLaunchKernelGGL((sweep2_kernel<DPAD, false, 2>), dim3(grid), dim3(S2_THREADS), lds, s, a);
-        } else if (solve) {
-            if (a.lin_coef != 0.0)
-                hipLaunchKernelGGL((sweep2_kernel<DPAD, true, 1>), dim3(grid), dim3(S2_THREADS), lds, s, a);
-            else
-                hipLaunchKernelGGL((sweep2_kernel<DPAD, false, 1>), dim3(grid), dim3(S2_THREADS), lds, s, a);
-        } else if (a.lin_coef != 0.0)
-            hipLaunchKernelGGL((sweep2_kernel<DPAD, true, 0>), dim3(grid), dim3(S2_THREADS), lds, s, a);
-        else
-            hipLaunchKernelGGL((sweep2_kernel<DPAD, false, 0>), dim3(grid), dim3(S2_THREADS), lds, s, a);
-    };
     // full rounds on the persistent grid, then the remainder split by row block (the substitution
     // form cannot split: its row blocks depend on each other -- the last round just runs short)
     long long rest = ncb % SW_GRID;
@@ -1117,26 +1158,366 @@ static int launch_sweep(const SweepArgs& a0, hipStream_t s, bool solve) {
     const long long full = ncb - rest;
     if (full > 0) {
         a.blk_begin = 0; a.blk_end = full; a.split = 0;
-        launch((unsigned)(full < SW_GRID ? full : SW_GRID));
+        s2_launch<DPAD, false>(a, s, solve, (unsigned)(full < SW_GRID ? full : SW_GRID));
     }
     if (rest > 0) {
         a.blk_begin = full; a.blk_end = ncb; a.split = 1;
         a.ncache = 0;                             // no parking across workgroups
         a.kslot_bytes = SW_BCH * 8;
-        launch((unsigned)(rest * nrb2));
+        s2_launch<DPAD, false>(a, s, solve, (unsigned)(rest * nrb2));
         hipLaunchKernelGGL(sweep_finish_kernel, dim3((unsigned)rest), dim3(64), 0, s, a);
     }
     return 0;
 }
 
+// The blocks blk_list[0 .. *blk_count) (count <= max_count, known to the device only) through the same kernel.  No host
+// round trip: up to `cap` blocks (inverse form, N > 256) go split by row block -- a grid sized for cap blocks whose
+// surplus workgroups leave at once --, more than cap over the persistent grid; both launches are enqueued and the
+// count decides on the device which of them works.
+template <int DPAD>
+static void launch_sweep_list(const SweepArgs& a0, hipStream_t s, bool solve, const long long* list,
+                              const long long* count, long long max_count, long long cap) {
+    SweepArgs a = a0;
+    const int nrb2 = s2_nrb(a.n);
+    a.nrb = nrb2;
+    a.blk_list = list; a.blk_count = count;
+    a.blk_begin = 0; a.blk_end = (a.m + SW_CAND - 1) / SW_CAND;     // (LIST: one past the largest block NUMBER)
+    const bool can_split = !solve && nrb2 >= 2 && a.sp_q != NULL;
+    if (cap > max_count) cap = max_count;
+    if (can_split) {
+        SweepArgs b = a;
+        b.split = 1; b.ncache = 0; b.kslot_bytes = SW_BCH * 8;
+        b.list_lo = 0; b.list_hi = cap;
+        s2_launch<DPAD, true>(b, s, solve, (unsigned)(cap * nrb2));
+        hipLaunchKernelGGL(sweep_finish_kernel, dim3((unsigned)cap), dim3(64), 0, s, b);
+    }
+    if (!can_split || max_count > cap) {
+        a.split = 0;
+        a.list_lo = can_split ? cap : 0; a.list_hi = APGP_MAX_M;
+        s2_launch<DPAD, true>(a, s, solve, (unsigned)(max_count < SW_GRID ? max_count : SW_GRID));
+    }
+}
+
+// ---------------------------------------------------------------------------
+// Pruned arg-min ("Branch and bound on the arg-min").  acquire returns ONE row.  For every
+// candidate var = k(t,t) - |L^-1 k*|^2 <= k(t,t), and the three utilities do not increase with var at fixed mu, so
+//   b_i = util(mu_i, k(t_i,t_i)) <= u_i,
+// at the price of a mean-only prediction (N (3D + 4) flops against N^2).  A candidate whose bound lies above the
+// utility tau of ANY fully evaluated admissible candidate can neither be the arg-min nor tie it.  Whole 64-row blocks
+// are pruned, never rows: a surviving row keeps its block, lane and global index and goes through the sweep's own
+// kernel, so its utility has the bits the full sweep gives it.
+//   1. prune_bound_kernel   bmin[blk] = min_i (b_i - slack_i) (+inf: no admissible row); part_u/part_i = (+inf, -1)
+//   2. prune_seed_kernel    the PR_SEED blocks with the smallest bmin
+//   3. sweep on the seeds   -> their part_u / part_i
+//   4. prune_select_kernel  tau = min part_u of the seeds; the blocks with bmin <= tau that are not seeds, in
+//                           ascending order, and their count
+//   5. sweep on that list; argmin_final_kernel over all partials as ever.
+// slack_i (prune_bound_kernel) covers every rounding between b_i as computed there and u_i as the sweep computes it,
+// so "bmin <= tau" keeps every row that could win or TIE: the lowest global index still wins.
+// tau = +inf (no seed row with a finite utility): every block with an admissible row survives.
+// ---------------------------------------------------------------------------
+#define PR_THREADS 256
+#define PR_CPT 2            // candidates per thread: two blocks per wavefront, half the LDS reads per kernel value
+#define PR_ROWS 128         // training rows per LDS tile (divides the packed stream's 512-row padding)
+#define PR_SEED 16          // seed blocks: one split launch of 16 x nrb workgroups covers the chip from N = 4096 on
+// candidates below which the full sweep is taken (apgp_set_sweep_prune(1)).  The pruned call costs about one block's
+// time whatever m is (the seeds), the full sweep m N^2: measured crossover between m = 4096 and 16384 at N = 4096,
+// between 16384 and 65536 at N = 1152 (docs/experiments.md, round 7)
+static inline int64_t pr_min_m(int64_t n) { return n >= 4096 ? 16384 : 65536; }
+
+struct PruneArgs {
+    const double* T;
+    const double* xs;
+    const unsigned char* mask;
+    double* bmin;
+    double* part_u;
+    long long* part_i;
+    long long m, ncb, n;
+    int ndim, kind, has_box, lin_order;
+    double mean, amp, lin_coef, zeta, ybest;
+    double sc[APGP_MAX_DIM], lw[APGP_MAX_DIM], lo[APGP_MAX_DIM], hi[APGP_MAX_DIM];
+};
+
+template <int DPAD>
+__global__ __launch_bounds__(PR_THREADS) void prune_bound_kernel(PruneArgs a) {
+    constexpr int XS = DPAD + 2;                 // packed stream row: scaled x | alpha | 0
+    constexpr int PIECES = PR_ROWS * XS / 2;     // 16-byte pieces per tile
+    __shared__ double etab[APGP_EXP_TAB_N];
+    __shared__ __attribute__((aligned(16))) double tile[PR_ROWS * XS];
+    apgp_exp_tab_load(etab);
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    // wavefront w: candidate blocks blk0, blk0 + 1 (the sweep's SW_CAND blocks, same numbering), lane = row in block
+    const long long blk0 = ((long long)blockIdx.x * (PR_THREADS / 64) + w) * PR_CPT;
+    double tt[PR_CPT][DPAD], ktt[PR_CPT];
+    bool adm[PR_CPT];
+#pragma unroll
+    for (int c = 0; c < PR_CPT; ++c) {
+        // admissibility and k(t,t) exactly as the sweep's load_candidates
+        const long long row = (blk0 + c) * SW_CAND + lane;
+        const bool live = blk0 + c < a.ncb && row < a.m;
+        bool ok = live, has_nan = false;
+        double ktl = a.lin_order == 0 ? (double)a.ndim : 0.0;
+#pragma unroll
+        for (int d = 0; d < DPAD; ++d) {
+            double v = 0.0;
+            if (live && d < a.ndim) {
+                v = a.T[row * a.ndim + d];
+                if (a.has_box && !(v >= a.lo[d] && v <= a.hi[d])) ok = false;
+                if (v != v) has_nan = true;
+            }
+            tt[c][d] = v * a.sc[d];
+            if (a.lin_coef != 0.0 && a.lin_order > 0) {
+                const double p = v * v;
+                double q = p;
+                for (int e = 1; e < a.lin_order; ++e) q *= p;
+                ktl += q;
+            }
+        }
+        if (live && a.mask && a.mask[row] == 0) ok = false;
+        adm[c] = ok && !has_nan;
+        ktt[c] = a.lin_coef != 0.0 ? fma(a.lin_coef, ktl, a.amp) : a.amp;
+    }
+    // mu - mean = sum_k k(t, x_k) alpha_k in four partial sums, and S = sum_k |k(t, x_k)| |alpha_k| for the slack
+    double acc[PR_CPT][4], sab[PR_CPT][4];
+#pragma unroll
+    for (int c = 0; c < PR_CPT; ++c)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) { acc[c][q] = 0.0; sab[c][q] = 0.0; }
+    const long long ntile = (a.n + PR_ROWS - 1) / PR_ROWS;
+    for (long long ti = 0; ti < ntile; ++ti) {
+        __syncthreads();                         // the previous tile has been consumed
+        const double* src = a.xs + ti * (PR_ROWS * XS);      // (rows < ntile * PR_ROWS <= npad: inside the packed stream)
+        for (int e = tid; e < PIECES; e += PR_THREADS) *((f64x2*)tile + e) = *((const f64x2*)src + e);
+        __syncthreads();
+        for (int r = 0; r < PR_ROWS; r += 4) {
+#pragma unroll
+            for (int c = 0; c < PR_CPT; ++c) {
+                double ex[4], kv[4];
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const double* xr = tile + (r + q) * XS;
+                    double s2 = 0.0, s3 = 0.0;
+#pragma unroll
+                    for (int d = 0; d < DPAD; d += 2) {
+                        const double df0 = tt[c][d] - xr[d];
+                        const double df1 = tt[c][d + 1] - xr[d + 1];
+                        s2 = fma(df0, df0, s2);
+                        s3 = fma(df1, df1, s3);
+                    }
+                    ex[q] = -(s2 + s3);
+                }
+                apgp_exp4(ex, kv, etab);
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const double* xr = tile + (r + q) * XS;
+                    double k = kv[q] * a.amp, kabs = k;
+                    if (a.lin_coef != 0.0) {
+                        // the sweep's LinearKernel sum (produce_b: pairs of dimensions), and the sum of its |terms|
+                        double ls = a.lin_order == 0 ? (double)a.ndim : 0.0, la = ls;
+                        if (a.lin_order > 0)
+#pragma unroll
+                            for (int d = 0; d < DPAD; d += 2) {
+                                const double p0 = tt[c][d] * xr[d] * a.lw[d], p1 = tt[c][d + 1] * xr[d + 1] * a.lw[d + 1];
+                                double q0 = p0, q1 = p1;
+                                for (int e = 1; e < a.lin_order; ++e) { q0 *= p0; q1 *= p1; }
+                                ls += q0 + q1;
+                                la += fabs(q0) + fabs(q1);
+                            }
+                        kabs = fma(a.lin_coef, la, k);
+                        k = fma(a.lin_coef, ls, k);
+                    }
+                    acc[c][q] = fma(k, xr[DPAD], acc[c][q]);
+                    sab[c][q] = fma(kabs, fabs(xr[DPAD]), sab[c][q]);
+                }
+            }
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < PR_CPT; ++c) {
+        const double mu = ((acc[c][0] + acc[c][1]) + (acc[c][2] + acc[c][3])) + a.mean;
+        const double S = (sab[c][0] + sab[c][1]) + (sab[c][2] + sab[c][3]);
+        double b = util_value(a.kind, mu, ktt[c], a.zeta, a.ybest);
+        // slack: what the sweep's u_i, evaluated at var_i <= k(t,t), may lie below this b_i through rounding alone,
+        // with eps = 2^-53.
+        //  * mu.  Both passes add the same N products k alpha (the kernel values come from the same expressions) in
+        //    different orders: each sum is within gamma_N S, gamma_N <~ (N + 2) eps, of the exact one, so the two
+        //    differ by <= 2 (N + 2) eps S; doubled, plus (8 Dpad + 32) eps S should hipcc contract a kernel value's
+        //    expressions differently in the two kernels (Dpad + 4 operations, S counts the LinearKernel terms by
+        //    their absolute values).  |du/dmu| is 1 (AGP), 2 (BAPE), Phi(z) <= 1 (Jones): factor 2.
+        //  * util_value at equal mu.  Its terms are each within a few eps of |mu|, |ybest| + |zeta|, k(t,t), |b| or 1
+        //    (log, erfc, exp to ~1 ulp; z = imp / sd to eps, and z^2 phi(z) <= 0.3), so two evaluations that are
+        //    ordered exactly are ordered to 64 eps (1 + |mu| + |ybest| + |zeta| + k(t,t) + |b|) as computed.  Where
+        //    var_i is so small that ITS evaluation is worse conditioned than that (AGP: log var; BAPE: log(1 - exp(-var)),
+        //    absolute error eps / (1 - exp(-var))), u_i exceeds b_i by more than it loses; BAPE at a tiny k(t,t)
+        //    itself gets the term 16 eps / (1 - exp(-k(t,t))).
+        //    (Jones with var_i <= 0 or NaN is 0.0: b_i = -EI <= 0 up to the same rounding.)
+        // A bound that is NaN bounds nothing: -inf, the block is evaluated.
+        const double eps = 0x1p-53;
+        double slack = 2.0 * (4.0 * (double)(a.n + 16) + 8.0 * DPAD + 32.0) * eps * S +
+                       64.0 * eps * (1.0 + fabs(mu) + fabs(a.ybest) + fabs(a.zeta) + ktt[c] + fabs(b));
+        if (a.kind == APGP_UTIL_BAPE) slack += 16.0 * eps / (1.0 - exp(0.0 - ktt[c]));
+        b -= slack;
+        if (!(b == b)) b = -INFINITY;
+        if (!adm[c]) b = INFINITY;
+        for (int o = 32; o > 0; o >>= 1) b = fmin(b, __shfl_xor(b, o));
+        if (lane == 0 && blk0 + c < a.ncb) {
+            a.bmin[blk0 + c] = b;
+            a.part_u[blk0 + c] = INFINITY;       // a pruned block's partial: never wins
+            a.part_i[blk0 + c] = -1;
+        }
+    }
+}
+
+// (value, block) pairs in ascending order: by value, then by block number
+__device__ __forceinline__ bool pr_less(double v, long long i, double w, long long j) { return v < w || (v == w && i < j); }
+
+// The PR_SEED blocks with the smallest bmin (fewer if fewer have an admissible row), one workgroup: PR_SEED
+// passes, each the smallest pair above the previous pick.
+__global__ __launch_bounds__(1024) void prune_seed_kernel(const double* bmin, long long ncb, long long* seeds,
+                                                          long long* counts) {
+    __shared__ double sv[16];
+    __shared__ long long si[16];
+    __shared__ double pick_v;
+    __shared__ long long pick_i;
+    double pv = -INFINITY;
+    long long pi = -1;
+    int ns = 0;
+    for (; ns < PR_SEED; ++ns) {
+        double bv = INFINITY;
+        long long bi = -1;                        // (-1: nothing left)
+        for (long long p = threadIdx.x; p < ncb; p += 1024) {
+            const double v = bmin[p];
+            if (v < INFINITY && pr_less(pv, pi, v, p) && (bi < 0 || pr_less(v, p, bv, bi))) { bv = v; bi = p; }
+        }
+        for (int o = 32; o > 0; o >>= 1) {
+            const double ov = __shfl_xor(bv, o);
+            const long long oi = __shfl_xor(bi, o);
+            if (oi >= 0 && (bi < 0 || pr_less(ov, oi, bv, bi))) { bv = ov; bi = oi; }
+        }
+        if ((threadIdx.x & 63) == 0) { sv[threadIdx.x >> 6] = bv; si[threadIdx.x >> 6] = bi; }
+        __syncthreads();
+        if (threadIdx.x == 0) {
+            for (int i = 1; i < 16; ++i)
+                if (si[i] >= 0 && (bi < 0 || pr_less(sv[i], si[i], bv, bi))) { bv = sv[i]; bi = si[i]; }
+            pick_v = bv; pick_i = bi;
+            if (bi >= 0) seeds[ns] = bi;
+        }
+        __syncthreads();
+        pv = pick_v; pi = pick_i;
+        if (pi < 0) break;
+    }
+    if (threadIdx.x == 0) { counts[0] = ns; counts[1] = 0; }
+}
+
+// tau = the smallest utility the seed blocks found (part_u of the seeds; tau_in if part_u == NULL: a planted
+// value, apgp_sweep_prune_select); survivors = blocks with an admissible row (bmin < +inf), bmin <= tau, not a seed --
+// written in ascending order (each thread a contiguous range, a scan over the threads' counts), count to counts[1].
+__global__ __launch_bounds__(1024) void prune_select_kernel(const double* bmin, long long ncb, const long long* seeds,
+                                                            long long* counts, const double* part_u, double tau_in,
+                                                            long long* list) {
+    __shared__ long long sd[PR_SEED];
+    __shared__ long long cnt[1024];
+    const int t = threadIdx.x;
+    const int ns = (int)counts[0];
+    if (t < PR_SEED) sd[t] = t < ns ? seeds[t] : -1;
+    __syncthreads();
+    double tau = tau_in;
+    if (part_u) {
+        tau = INFINITY;
+        for (int i = 0; i < ns; ++i) tau = fmin(tau, part_u[sd[i]]);      // (fmin: a NaN partial never lowers tau)
+    }
+    auto keep = [&](long long p) {
+        const double v = bmin[p];
+        if (!(v < INFINITY && v <= tau)) return false;
+        for (int i = 0; i < ns; ++i)
+            if (sd[i] == p) return false;
+        return true;
+    };
+    const long long per = (ncb + 1023) / 1024;
+    const long long p0 = (long long)t * per, p1 = p0 + per < ncb ? p0 + per : ncb;
+    long long c = 0;
+    for (long long p = p0; p < p1; ++p) c += keep(p) ? 1 : 0;
+    cnt[t] = c;
+    __syncthreads();
+    for (int o = 1; o < 1024; o <<= 1) {          // inclusive scan
+        const long long add = t >= o ? cnt[t - o] : 0;
+        __syncthreads();
+        cnt[t] += add;
+        __syncthreads();
+    }
+    long long pos = cnt[t] - c;
+    for (long long p = p0; p < p1; ++p)
+        if (keep(p)) list[pos++] = p;
+    if (t == 1023) {
+        counts[1] = cnt[1023];
+        counts[2] = __double_as_longlong(tau);
+    }
+}
+
+static int g_sweep_prune = 1;
+
+extern "C" int apgp_set_sweep_prune(int v) {
+    const int old = __atomic_exchange_n(&g_sweep_prune, v < 0 ? 0 : v, __ATOMIC_RELAXED);
+    return old;
+}
+
+extern "C" int apgp_get_sweep_prune(void) { return __atomic_load_n(&g_sweep_prune, __ATOMIC_RELAXED); }
+
+static inline long long pr_ncb(int64_t m) { return (m + SW_CAND - 1) / SW_CAND; }
+// doubles of the full sweep's scratch (the layout below up to the row-block shares)
+static inline long long s2_work_len(int64_t m, int64_t n) {
+    const long long ncb = pr_ncb(m);
+    const long long slots = ncb < SW_GRID ? ncb : SW_GRID;
+    return 2 * ncb + slots * s2_ncache(n) * SW_BCH + 2 * (long long)S2_SPLIT_MAX * SW_CAND * s2_nrb(n);
+}
+
+extern "C" int64_t apgp_sweep_prune_counts_offset(int64_t m, int64_t n) {
+    if (m < 1 || n < 1 || m > APGP_MAX_M || n > APGP_MAX_N) return -1;
+    return s2_work_len(m, n) + 2 * pr_ncb(m) + PR_SEED;
+}
+
+extern "C" int apgp_sweep_prune_select(const double* bmin, int64_t ncb, const int64_t* seeds, int64_t* counts,
+                                       double tau, int64_t* list, void* stream) {
+    APGP_CHECK_ARG(bmin && seeds && counts && list, "null pointer");
+    APGP_CHECK_ARG(ncb >= 1 && ncb <= APGP_MAX_M / SW_CAND, "ncb >= 1 required");
+    hipLaunchKernelGGL(prune_select_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, bmin, (long long)ncb,
+                       (const long long*)seeds, (long long*)counts, (const double*)NULL, tau, (long long*)list);
+    APGP_CHECK_LAUNCH();
+    return 0;
+}
+
+template <int DPAD>
+static int launch_pruned(const SweepArgs& a, hipStream_t s, bool solve, void* part) {
+    const int rc = s2_prepare_device<DPAD>();
+    if (rc != 0) return rc;
+    const long long ncb = pr_ncb(a.m);
+    double* bmin = (double*)part + s2_work_len(a.m, a.n);
+    long long* list = (long long*)(bmin + ncb);
+    long long* seeds = list + ncb;
+    long long* counts = seeds + PR_SEED;
+    PruneArgs p;
+    p.T = a.T; p.xs = a.xs; p.mask = a.mask; p.bmin = bmin; p.part_u = a.part_u; p.part_i = a.part_i;
+    p.m = a.m; p.ncb = ncb; p.n = a.n;
+    p.ndim = a.ndim; p.kind = a.kind; p.has_box = a.has_box; p.lin_order = a.lin_order;
+    p.mean = a.mean; p.amp = a.amp; p.lin_coef = a.lin_coef; p.zeta = a.zeta; p.ybest = a.ybest;
+    for (int d = 0; d < APGP_MAX_DIM; ++d) { p.sc[d] = a.sc[d]; p.lw[d] = a.lw[d]; p.lo[d] = a.lo[d]; p.hi[d] = a.hi[d]; }
+    const long long per_wg = (PR_THREADS / 64) * PR_CPT;
+    hipLaunchKernelGGL(prune_bound_kernel<DPAD>, dim3((unsigned)((ncb + per_wg - 1) / per_wg)), dim3(PR_THREADS), 0, s, p);
+    hipLaunchKernelGGL(prune_seed_kernel, dim3(1), dim3(1024), 0, s, bmin, ncb, seeds, counts);
+    launch_sweep_list<DPAD>(a, s, solve, seeds, counts, ncb < PR_SEED ? ncb : PR_SEED, PR_SEED);
+    hipLaunchKernelGGL(prune_select_kernel, dim3(1), dim3(1024), 0, s, bmin, ncb, seeds, counts, a.part_u, 0.0, list);
+    launch_sweep_list<DPAD>(a, s, solve, list, counts + 1, ncb, S2_SPLIT_MAX);
+    return 0;
+}
+
 // Layout of the caller's scratch (doubles): [2 ncb arg-min partials | slots x ncache x SW_BCH
-// parked operands | 2 x S2_SPLIT_MAX x SW_CAND x nrb row-block shares of the split last round]
+// parked operands | 2 x S2_SPLIT_MAX x SW_CAND x nrb row-block shares of the split last round (s2_work_len up to
+// here) | pruned sweep: ncb block bounds bmin | ncb surviving block numbers | PR_SEED seed block numbers | 8 words:
+// seed count, survivor count, bit pattern of tau]
 extern "C" int64_t apgp_acquire_work_len(int64_t m, int64_t n) {
     if (m < 1 || n < 1) return 0;
     if (m > APGP_MAX_M || n > APGP_MAX_N) return -1;
-    const long long ncb = (m + SW_CAND - 1) / SW_CAND;
-    const long long slots = ncb < SW_GRID ? ncb : SW_GRID;
-    return 2 * ncb + slots * s2_ncache(n) * SW_BCH + 2 * (long long)S2_SPLIT_MAX * SW_CAND * s2_nrb(n);
+    return s2_work_len(m, n) + 2 * pr_ncb(m) + PR_SEED + 8;
 }
 
 static int acquire_impl(bool solve, const double* T, int64_t m, int64_t idx_offset, const double* packed_linv,
@@ -1185,14 +1566,30 @@ static int acquire_impl(bool solve, const double* T, int64_t m, int64_t idx_offs
         a.lo[d] = (lo && d < kc.ndim) ? lo[d] : 0.0;
         a.hi[d] = (hi && d < kc.ndim) ? hi[d] : 0.0;
     }
+    a.blk_list = NULL; a.blk_count = NULL; a.list_lo = 0; a.list_hi = 0;
     hipStream_t s = (hipStream_t)stream;
+    // the pruned arg-min: only the winner is asked for (mu / var / u per candidate need the full sweep), the switch
+    // is on and m is large enough to pay for the bound pass (switch value >= 2: that value is the threshold)
+    const int pr_mode = apgp_get_sweep_prune();
+    const bool prune = pr_mode > 0 && kind != APGP_UTIL_NONE && !mu && !var && !u && part &&
+                       m >= (pr_mode == 1 ? pr_min_m(n) : (int64_t)pr_mode);
     int rc;
-    switch (kc.dpad) {
-        case 2: rc = launch_sweep<2>(a, s, solve); break;
-        case 4: rc = launch_sweep<4>(a, s, solve); break;
-        case 8: rc = launch_sweep<8>(a, s, solve); break;
-        case 16: rc = launch_sweep<16>(a, s, solve); break;
-        default: rc = launch_sweep<32>(a, s, solve); break;
+    if (prune) {
+        switch (kc.dpad) {
+            case 2: rc = launch_pruned<2>(a, s, solve, part); break;
+            case 4: rc = launch_pruned<4>(a, s, solve, part); break;
+            case 8: rc = launch_pruned<8>(a, s, solve, part); break;
+            case 16: rc = launch_pruned<16>(a, s, solve, part); break;
+            default: rc = launch_pruned<32>(a, s, solve, part); break;
+        }
+    } else {
+        switch (kc.dpad) {
+            case 2: rc = launch_sweep<2>(a, s, solve); break;
+            case 4: rc = launch_sweep<4>(a, s, solve); break;
+            case 8: rc = launch_sweep<8>(a, s, solve); break;
+            case 16: rc = launch_sweep<16>(a, s, solve); break;
+            default: rc = launch_sweep<32>(a, s, solve); break;
+        }
     }
     if (rc != 0) return rc;
     if (kind != APGP_UTIL_NONE)

@@ -408,6 +408,11 @@ class GP(GeorgeExtras):
         self._device_arg = device
         self.variance_mode = None     # None: by condition estimate; "solve" / "inverse": forced
         self.extend_max_rows = None   # rows compute(x, previous=...) may append before it refactorises (None: by cost)
+        # arg-min-only sweeps skip candidate blocks that cannot win (apgp_set_sweep_prune): None: the library's
+        # process-wide setting (default on); False / 0: the full sweep; True / 1: on; >= 2: on from that many candidates
+        self.sweep_prune = None
+        self.sweep_prune_stats = False    # True: keep (seed blocks, surviving blocks, bits of tau) of the last pruned sweep
+        self.last_prune_counts = None     # ... here, as a device int64[3] tensor (tools/sweep_prune_ab.py, the tests)
         self._computed = False
         self._x = None
         self._yerr2 = 0.0
@@ -1429,12 +1434,20 @@ class GP(GeorgeExtras):
                       var.data_ptr() if var is not None else None,
                       u.data_ptr() if u is not None else None,
                       part.data_ptr(), best.data_ptr(), st)
-            if use_solve:
-                _lib.check(lib.apgp_acquire_solve(T.data_ptr(), m, int(idx_offset), self._packed_solve.data_ptr(),
-                                                  self._xs.data_ptr(), n, *common), "apgp_acquire_solve")
-            else:
-                _lib.check(lib.apgp_acquire(T.data_ptr(), m, int(idx_offset), self._packed.data_ptr(),
-                                            self._xs.data_ptr(), n, *common), "apgp_acquire")
+            prune_was = None if self.sweep_prune is None else lib.apgp_set_sweep_prune(int(self.sweep_prune))
+            try:
+                if use_solve:
+                    _lib.check(lib.apgp_acquire_solve(T.data_ptr(), m, int(idx_offset), self._packed_solve.data_ptr(),
+                                                      self._xs.data_ptr(), n, *common), "apgp_acquire_solve")
+                else:
+                    _lib.check(lib.apgp_acquire(T.data_ptr(), m, int(idx_offset), self._packed.data_ptr(),
+                                                self._xs.data_ptr(), n, *common), "apgp_acquire")
+            finally:
+                if prune_was is not None:
+                    lib.apgp_set_sweep_prune(prune_was)
+            if self.sweep_prune_stats and kid != _lib.UTIL_NONE and mu is None and var is None and u is None:
+                off = int(lib.apgp_sweep_prune_counts_offset(m, n))
+                self.last_prune_counts = part[off:off + 3].view(torch.int64).clone()
             if ev is not None:
                 e1 = torch.cuda.Event(enable_timing=True)
                 e1.record()

@@ -297,7 +297,8 @@ int apgp_pack_train(const double* X, const double* alpha, int64_t n,
  *       which each persistent workgroup parks the k* operands it generated for
  *       one row block so that later row blocks do not regenerate them, and the
  *       per-row-block shares of the candidate blocks of a short last round
- *       (those are split over one workgroup per row block).
+ *       (those are split over one workgroup per row block), and the block
+ *       bounds, block lists and counters of the pruned arg-min (below).
  * best: device apgp_best_t, written by the final reduction kernel.
  * ybest = max(y) and zeta are used by JONES only.                            */
 int64_t apgp_acquire_work_len(int64_t m, int64_t n);
@@ -333,6 +334,30 @@ int apgp_acquire_solve(const double* T, int64_t m, int64_t idx_offset,
                        const uint8_t* mask, double zeta, double ybest,
                        double* mu, double* var, double* u,
                        void* part, apgp_best_t* best, void* stream);
+
+/* ---- pruned arg-min of the sweep (branch and bound) ------------------------------
+ * When only the winner is asked for (kind != APGP_UTIL_NONE, mu = var = u = NULL), apgp_acquire and
+ * apgp_acquire_solve skip the 64-row candidate blocks that cannot hold it: var <= k(t,t) and the
+ * utilities do not increase with var, so b = utility(mu, k(t,t)) -- a mean-only prediction -- bounds
+ * a row's utility from below, and a block whose smallest bound (less a rounding slack) lies above a
+ * utility already found is never contracted.  Surviving blocks run through the sweep's own kernel:
+ * best has the index and the bits of the full sweep, ties included.  No host synchronisation; safe
+ * on a capturing stream.
+ * apgp_set_sweep_prune(v): process-wide switch, returns the previous value.  0: always the full
+ * sweep; 1 (default): pruned from a built-in candidate count on (16384 for n >= 4096, else 65536);
+ * v >= 2: pruned whenever m >= v.
+ * apgp_sweep_prune_counts_offset(m, n): index into `part` (in 8-byte words) of three int64 the last
+ * pruned call left there: seed blocks, surviving blocks beyond the seeds, bit pattern of tau.
+ * apgp_sweep_prune_select: the selection step alone, for tests -- tau planted by the caller.
+ * bmin: ncb block bounds; seeds: 16 int64 block numbers of which the first counts[0] are read;
+ * counts: int64[3], [0] read, [1] and [2] written (survivor count, bit pattern of tau); list: ncb
+ * int64, receives the blocks with bmin < +inf, bmin <= tau that are no seeds, in ascending order.
+ * All pointers device memory.                                                              */
+int apgp_set_sweep_prune(int v);
+int apgp_get_sweep_prune(void);
+int64_t apgp_sweep_prune_counts_offset(int64_t m, int64_t n);
+int apgp_sweep_prune_select(const double* bmin, int64_t ncb, const int64_t* seeds, int64_t* counts,
+                            double tau, int64_t* list, void* stream);
 
 /* ---- fantasy update of a sweep (batch design points, kriging believer) -----------
  * After a sweep over T (mu, var = v_0 written) and picks x_1 .. x_j, conditioning the GP on
