@@ -77,7 +77,7 @@ class GeorgeExtras(object):
         product as plain library calls (rocBLAS trsm / gemm through torch), all on the device.
         Memory: (2 N + M) M doubles."""
         torch, dev, lib = self._rt()
-        mu, = self._sweep(y, xs, kind=None, want=("mu",))
+        mu = self._mean(y, xs)
         n, m = len(self._x), len(xs)
         if m == 0:
             return mu, np.empty((0, 0), dtype=np.float64)

@@ -372,6 +372,35 @@ class _Replay(object):
         return y.tobytes() == self.ybytes
 
 
+def _box(bounds, D, optional=True):
+    """The box ``bounds`` (a low and a high edge for each dimension) as the C ABI's two ``double[MAX_DIM]``; (None, None) for no
+    box where the call can do without one."""
+    if bounds is None and optional:
+        return None, None
+    b = np.asarray(bounds, dtype=np.float64).reshape(-1, 2)
+    if len(b) != D:
+        raise ValueError("bounds must have one (lo, hi) pair per dimension")
+    arr = ctypes.c_double * _lib.MAX_DIM
+    return arr(*b[:, 0]), arr(*b[:, 1])
+
+
+def _seed64(seed):
+    return int(seed) & 0xFFFFFFFFFFFFFFFF
+
+
+def _ptr(tensor):
+    return None if tensor is None else tensor.data_ptr()
+
+
+def _best_record(best):
+    """(index, utility) of the sweep's 16-byte ``apgp_best_t`` record ``best`` (device): one copy to the host."""
+    bb = best.cpu().numpy()
+    return int(bb[1:2].view(np.int64)[0]), float(bb[0])
+
+
+# what one sweep left on the device: the arg-min record and the per-candidate arrays that were asked for (else None)
+_Swept = collections.namedtuple("_Swept", "best mu var u")
+
 # nll_batch's work space, kept between the rounds of a fit on one training set, y and stream: the device copy of y, the
 # (K, z, info, record) buffers of each batch size up to 256 MB, the means of a replayed batch
 _BatchWork = collections.namedtuple("_BatchWork", "x x_d stream ybytes y_d bufs means")
@@ -792,6 +821,51 @@ class GP(GeorgeExtras):
                 raise
         return True
 
+    # -- arguments of the acquisition-side library calls --------------------------------
+    def _candidates(self, t):
+        """The candidate matrix ``t`` as a device tensor (M, D): a torch tensor is checked and taken as it is (candidates
+        already resident in HBM), anything else is parsed and uploaded once."""
+        if hasattr(t, "data_ptr"):
+            if t.dim() != 2 or t.shape[1] != self.kernel.ndim or not t.is_contiguous() \
+                    or str(t.dtype) != "torch.float64" or not t.is_cuda:
+                raise ValueError("device candidates must be a contiguous (M, D) float64 CUDA tensor")
+            return t
+        torch, dev, _ = self._rt()
+        return torch.from_numpy(self.parse_samples(t)).to(dev)
+
+    def _mask(self, mask, m):
+        """The admissibility ``mask`` of ``m`` candidates as a device uint8 tensor (None: no mask)."""
+        if mask is None:
+            return None
+        mk = np.ascontiguousarray(np.asarray(mask).astype(np.uint8))
+        if mk.shape != (m,):
+            raise ValueError("mask must have one entry per candidate")
+        torch, dev, _ = self._rt()
+        return torch.from_numpy(mk).to(dev)
+
+    def _variance_operand(self, use_solve):
+        """The (W, ldw, L, ldl) arguments of the calls that take sigma^2 from the resident dense W = L^-1 or, with
+        ``use_solve``, by substitution against the factor -- and the buffer a replay of such a call depends on."""
+        if use_solve:
+            return (None, 0, self._L.data_ptr(), self._ld), self._L
+        return (self._work.data_ptr(), (len(self._x) + 63) // 64 * 64, None, 0), self._work
+
+    def _trsv(self, st, src, shift, trans, dst, ss, what, retry_ss=None):
+        """dst = L^-1 (src - shift) (``trans`` 1: L^-T) by the persistent solve on stream ``st``, dst . dst into ``ss``;
+        returns that as a float.  NaN there: the solve could not get its workgroups resident (apgp.h: it writes NaN
+        instead of hanging) -- or the factor is not finite, in which case the re-run says so too.  Once more then, a
+        launch per 256 rows, chosen for THIS call only: other threads' and streams' solves keep their path.
+        ``retry_ss``: where the re-run writes dst . dst (None: nowhere); given, its value is the one returned."""
+        lib = self._rt()[2]
+        solve = (self._L.data_ptr(), len(self._x), self._ld, src.data_ptr(), shift, trans, dst.data_ptr())
+        _lib.check(lib.apgp_trsv(*solve, ss.data_ptr(), st), "apgp_trsv(%s)" % what)
+        norm2 = float(ss.item())
+        if norm2 != norm2:
+            _lib.check(lib.apgp_trsv_ex(*solve, _ptr(retry_ss), 1, st), "apgp_trsv(%s, multi-launch)" % what)
+            if retry_ss is not None:
+                norm2 = float(retry_ss.item())
+        return norm2
+
     # -- K3: z = L^-1 (y - mean), alpha = L^-T z -----------------------------------
     def _solve(self, y, need_alpha):
         """Ensures z (and alpha) for this y; returns z.z as a float.  With the dense
@@ -823,19 +897,10 @@ class GP(GeorgeExtras):
                     _lib.check(lib.apgp_winv_apply(self._work.data_ptr(), np64, n, self._y_d.data_ptr(),
                                                    float(self.mean.value), 0, self._z.data_ptr(),
                                                    ztz.data_ptr(), None, st), "apgp_winv_apply(forward)")
-                else:
-                    _lib.check(lib.apgp_trsv(self._L.data_ptr(), n, self._ld, self._y_d.data_ptr(),
-                                             float(self.mean.value), 0, self._z.data_ptr(),
-                                             ztz.data_ptr(), st), "apgp_trsv(forward)")
-                self._ztz_host = float(ztz.item())
-                if not via_w and self._ztz_host != self._ztz_host:
-                    # NaN: the persistent solve could not get its workgroups resident (apgp.h: it writes NaN instead of
-                    # hanging) -- or the factor is not finite, in which case the re-run says so too.  Once more, a launch per
-                    # 256 rows -- chosen for THIS call only (apgp_trsv_ex): other threads' and streams' solves keep their path.
-                    _lib.check(lib.apgp_trsv_ex(self._L.data_ptr(), n, self._ld, self._y_d.data_ptr(),
-                                                float(self.mean.value), 0, self._z.data_ptr(),
-                                                ztz.data_ptr(), 1, st), "apgp_trsv(forward, multi-launch)")
                     self._ztz_host = float(ztz.item())
+                else:
+                    self._ztz_host = self._trsv(st, self._y_d, float(self.mean.value), 0, self._z, ztz, "forward",
+                                                retry_ss=ztz)
                 self._alpha = None
                 self._xs = None
                 self._alpha_y = np.array(y, copy=True)
@@ -848,12 +913,7 @@ class GP(GeorgeExtras):
                                                    self._alpha.data_ptr(), None, wk.data_ptr(), st),
                                "apgp_winv_apply(backward)")
                 else:
-                    asq = torch.empty(1, dtype=torch.float64, device=dev)
-                    _lib.check(lib.apgp_trsv(self._L.data_ptr(), n, self._ld, self._z.data_ptr(), 0.0, 1,
-                                             self._alpha.data_ptr(), asq.data_ptr(), st), "apgp_trsv(backward)")
-                    if float(asq.item()) != float(asq.item()):      # (NaN: see the forward solve)
-                        _lib.check(lib.apgp_trsv_ex(self._L.data_ptr(), n, self._ld, self._z.data_ptr(), 0.0, 1,
-                                                    self._alpha.data_ptr(), None, 1, st), "apgp_trsv(backward, multi-launch)")
+                    self._trsv(st, self._z, 0.0, 1, self._alpha, torch.empty(1, dtype=torch.float64, device=dev), "backward")
                 self._xs = None
         return self._ztz_host
 
@@ -1064,7 +1124,7 @@ class GP(GeorgeExtras):
     def predict(self, y, t, return_cov=True, return_var=False, cache=True, **kwargs):
         if (self._computed and not self.kernel.dirty and type(t) is np.ndarray and t.dtype == _F64
                 and t.ndim == 2 and t.flags.c_contiguous):
-            # the replays of _sweep's small calls: the previous call's arguments with new points
+            # the replays of the small calls (_mean_host, _predict_one): the previous call's arguments with new points
             if return_var:
                 r = self._replays.get("one")
                 # (the factor of the variance form in use: a switch of form is a different object)
@@ -1088,10 +1148,135 @@ class GP(GeorgeExtras):
         if return_cov and not return_var:
             return self._predict_cov(y, xs)
         if not return_var:
-            mu, = self._sweep(y, xs, kind=None, want=("mu",))
-            return mu
-        mu, var = self._sweep(y, xs, kind=None, want=("mu", "var"))
-        return mu, var
+            return self._mean(y, xs)
+        if len(xs) == 1:
+            return self._predict_one(y, xs)
+        y = self._check_dimensions(y)
+        if len(xs) == 0:        # (as every empty candidate set: y is still checked, nothing is prepared on the device)
+            return np.empty(0), np.empty(0)
+        torch, dev, _ = self._rt()
+        s = self._sweep(y, torch.from_numpy(xs).to(dev), _lib.UTIL_NONE, with_mu=True, with_var=True)
+        return s.mu.cpu().numpy(), s.var.cpu().numpy()
+
+    def _mean(self, y, xs):
+        """The predictive mean at the host points ``xs`` (M, D), by the route of their number."""
+        if len(xs) == 0:
+            self._check_dimensions(y)
+            return np.empty(0)
+        if len(xs) <= 4096:
+            return self._mean_host(y, xs)
+        torch, dev, _ = self._rt()
+        return self._mean_device(y, torch.from_numpy(xs).to(dev)).cpu().numpy()
+
+    def _mean_host(self, y, xs):
+        """Latency-bound mean-only call (the sampler's _gpll batches) at 1 .. 4096 host points: host buffers in and out
+        through ONE library call and one synchronisation."""
+        torch, dev, lib = self._rt()
+        y = self._check_dimensions(y)
+        n, m = len(self._x), len(xs)
+        ks = self._kernel_struct()
+        with self._on(torch, dev):
+            st = self._stream(torch)
+            self._ensure_xs(y)
+            need = m * (ks.ndim + 1)
+            if self._mean_work is None or self._mean_work.numel() < need:
+                self._mean_work = torch.empty(max(need, 1024), dtype=torch.float64, device=dev)
+            mu_h = np.empty(m, dtype=np.float64)
+            args = [xs.ctypes.data, m, self._xs.data_ptr(), n, ctypes.byref(ks), float(self.mean.value),
+                    mu_h.ctypes.data, self._mean_work.data_ptr(), st]
+            _lib.check(lib.apgp_predict_mean_host(*args), "apgp_predict_mean_host")
+            # the sampler asks again, for another few points of the same model and y, 4e4 times per chain (the walker
+            # ensembles of ApproxPosterior._gpllBatch, approx.py:148-189)
+            max_m = min(4096, self._mean_work.numel() // (ks.ndim + 1))
+            self._replays["mean"] = _Replay(lib.apgp_predict_mean_host, args, dev.index, st.value or 0, y,
+                                            (self._xs, self._mean_work), self._queries, data=(ks.ndim, max_m))
+        return mu_h
+
+    def _mean_device(self, y, T):
+        """The predictive mean at the rows of the device tensor ``T`` (M >= 1, D), as a device tensor."""
+        torch, dev, lib = self._rt()
+        y = self._check_dimensions(y)
+        ks = self._kernel_struct()
+        with self._on(torch, dev):
+            self._ensure_xs(y)
+            mu = torch.empty(T.shape[0], dtype=torch.float64, device=dev)
+            _lib.check(lib.apgp_predict_mean(T.data_ptr(), T.shape[0], self._xs.data_ptr(), len(self._x),
+                                             ctypes.byref(ks), float(self.mean.value), mu.data_ptr(),
+                                             self._stream(torch)), "apgp_predict_mean")
+        return mu
+
+    def _predict_one(self, y, xs):
+        """(mu, sigma^2) at ONE host point: the reference's scalar utilities (utility.py:131,178,224), once per
+        Nelder-Mead step of minimizeObjective -- three small launches, the result through the mailbox."""
+        torch, dev, lib = self._rt()
+        y = self._check_dimensions(y)
+        n = len(self._x)
+        ks = self._kernel_struct()
+        use_solve = not self._trust_inverse()
+        with self._on(torch, dev):
+            st = self._stream(torch)
+            if not use_solve:
+                self._ensure_linv()     # first: with W resident alpha is two matrix-vector products
+            self._ensure_xs(y)          # (above the conditioning gate a single candidate solves against L itself)
+            if self._p1_work is None or self._p1_work.numel() < int(lib.apgp_predict1_work_len(n)):
+                self._p1_work = torch.empty(int(lib.apgp_predict1_work_len(n)), dtype=torch.float64, device=dev)
+            o2 = np.empty(2, dtype=np.float64)
+            inv, factor = self._variance_operand(use_solve)
+            args = [xs.ctypes.data, self._xs.data_ptr(), n, ctypes.byref(ks), float(self.mean.value), *inv,
+                    self._p1_work.data_ptr(), o2.ctypes.data, st]
+            _lib.check(lib.apgp_predict1_host(*args), "apgp_predict1_host")
+            # the reference's scalar utilities ask again at the next simplex point, ~460 times per search
+            self._replays["one"] = _Replay(lib.apgp_predict1_host, args, dev.index, st.value or 0, y,
+                                           (self._xs, self._p1_work, factor), self._queries, data=(o2, (1, ks.ndim)))
+        return np.array([o2[0]]), np.array([o2[1]])
+
+    def _sweep(self, y, T, kind_id, lo=None, hi=None, mask_d=None, zeta=0.01, idx_offset=0,
+               with_mu=False, with_var=False, with_u=False):
+        """The fused predict + utility + arg-min over the rows of the device tensor ``T`` (M >= 1, D), sigma^2 through
+        the dense inverse or, above the conditioning gate, by substitution against the factor.  ``kind_id``: a utility
+        or ``UTIL_NONE`` (prediction only); ``with_mu`` / ``with_var`` / ``with_u``: keep that per-candidate array.  Everything stays
+        on the device (``_Swept``): the callers decide what to copy to the host."""
+        torch, dev, lib = self._rt()
+        y = self._check_dimensions(y)
+        n, m = len(self._x), T.shape[0]
+        ks = self._kernel_struct()
+        use_solve = not self._trust_inverse()
+        with self._on(torch, dev):
+            st = self._stream(torch)
+            if use_solve:
+                self._ensure_lsolve()
+            else:
+                self._ensure_linv()     # first: with W resident alpha is two matrix-vector products
+            self._ensure_xs(y)
+            f64 = dict(dtype=torch.float64, device=dev)
+            mu, var, u = (torch.empty(m, **f64) if keep else None for keep in (with_mu, with_var, with_u))
+            part = torch.empty(max(int(lib.apgp_acquire_work_len(m, n)), 2), **f64)
+            best = torch.empty(2, **f64)
+            ev = getattr(self, "kernel_events", None)   # bench.py: HIP events around the launch
+            if ev is not None:
+                e0 = torch.cuda.Event(enable_timing=True)
+                e0.record()
+            args = (self._xs.data_ptr(), n, ctypes.byref(ks), float(self.mean.value), kind_id, lo, hi, _ptr(mask_d),
+                    float(zeta), float(np.max(y)), _ptr(mu), _ptr(var), _ptr(u), part.data_ptr(), best.data_ptr(), st)
+            prune_was = None if self.sweep_prune is None else lib.apgp_set_sweep_prune(int(self.sweep_prune))
+            try:
+                if use_solve:
+                    _lib.check(lib.apgp_acquire_solve(T.data_ptr(), m, int(idx_offset), self._packed_solve.data_ptr(),
+                                                      *args), "apgp_acquire_solve")
+                else:
+                    _lib.check(lib.apgp_acquire(T.data_ptr(), m, int(idx_offset), self._packed.data_ptr(), *args),
+                               "apgp_acquire")
+            finally:
+                if prune_was is not None:
+                    lib.apgp_set_sweep_prune(prune_was)
+            if self.sweep_prune_stats and kind_id != _lib.UTIL_NONE and mu is None and var is None and u is None:
+                off = int(lib.apgp_sweep_prune_counts_offset(m, n))
+                self.last_prune_counts = part[off:off + 3].view(torch.int64).clone()
+            if ev is not None:
+                e1 = torch.cuda.Event(enable_timing=True)
+                e1.record()
+                ev.append((e0, e1))
+        return _Swept(best, mu, var, u)
 
     def acquire(self, y, t, kind, bounds=None, mask=None, zeta=0.01, return_all=False,
                 idx_offset=0, device_record=False):
@@ -1112,22 +1297,25 @@ class GP(GeorgeExtras):
         if not self.computed:
             raise RuntimeError("ERROR: Need to compute GP before using it!")
         kind_id = UTILITY_KINDS[str(kind).lower()]
-        want = ("best", "u", "mu", "var") if return_all else ("best",)
+        if device_record and return_all:
+            raise ValueError("device_record returns the arg-min record only")
+        torch, dev, _ = self._rt()
+        lo, hi = _box(bounds, self.kernel.ndim)
+        T = self._candidates(t)
+        mask_d = self._mask(mask, T.shape[0])
+        y = self._check_dimensions(y)
+        if T.shape[0] == 0:
+            # empty candidate set: nothing admissible (index -1, +inf), empty arrays -- and nothing prepared on the device
+            if device_record:
+                return torch.tensor([int(np.float64(np.inf).view(np.int64)), -1], dtype=torch.int64, device=dev)
+            return (-1, float("inf")) + ((np.empty(0),) * 3 if return_all else ())
+        s = self._sweep(y, T, kind_id, lo, hi, mask_d, zeta, idx_offset, with_mu=return_all, with_var=return_all,
+                        with_u=return_all)
         if device_record:
-            if return_all:
-                raise ValueError("device_record returns the arg-min record only")
-            want = ("best_device",)
-        if hasattr(t, "data_ptr"):      # candidates already resident in HBM (torch tensor)
-            if t.dim() != 2 or t.shape[1] != self.kernel.ndim or not t.is_contiguous() \
-                    or str(t.dtype) != "torch.float64" or not t.is_cuda:
-                raise ValueError("device candidates must be a contiguous (M, D) float64 CUDA tensor")
-            res = self._sweep(y, None, kind=kind_id, want=want, bounds=bounds, mask=mask,
-                              zeta=zeta, idx_offset=idx_offset, cand_device=t)
-        else:
-            xs = self.parse_samples(t)
-            res = self._sweep(y, xs, kind=kind_id, want=want, bounds=bounds, mask=mask,
-                              zeta=zeta, idx_offset=idx_offset)
-        return res[0] if device_record else res
+            return s.best.view(torch.int64)
+        if not return_all:
+            return _best_record(s.best)
+        return _best_record(s.best) + (s.u.cpu().numpy(), s.mu.cpu().numpy(), s.var.cpu().numpy())
 
     def nelder_mead_search(self, y, starts, kind, bounds=None, zeta=0.01, options=None, trace=False):
         """SciPy's Nelder-Mead (``bounds=None``) from every row of ``starts`` (R, D) at once on the device
@@ -1153,12 +1341,9 @@ class GP(GeorgeExtras):
                              % (unknown, ", ".join(NM_OPTIONS)))
         if not self.computed:
             raise RuntimeError("ERROR: Need to compute GP before using it!")
-        self.recompute()
-        torch, dev, lib = self._rt()
         y = self._check_dimensions(y)
-        n = len(self._x)
-        ks = self._kernel_struct()
-        D = ks.ndim
+        D = self.kernel.ndim
+        lo, hi = _box(bounds, D)
         X0 = np.ascontiguousarray(np.asarray(starts, dtype=np.float64).reshape(-1, D))
         R = len(X0)
         if not 1 <= R <= _lib.NM_MAX_RESTARTS:
@@ -1170,13 +1355,9 @@ class GP(GeorgeExtras):
         opt = _lib.NmOptions(kind=kid, maxiter=maxiter, maxfev=maxfev, reserved=0, zeta=float(zeta),
                              ybest=float(np.max(y)), xatol=float(opts.get("xatol", 1e-4)),
                              fatol=float(opts.get("fatol", 1e-4)), rho=rho, chi=chi, psi=psi, sigma=sigma)
-        lo = hi = None
-        if bounds is not None:
-            b = np.asarray(bounds, dtype=np.float64).reshape(-1, 2)
-            if len(b) != D:
-                raise ValueError("bounds must have one (lo, hi) pair per dimension")
-            lo = (ctypes.c_double * _lib.MAX_DIM)(*b[:, 0])
-            hi = (ctypes.c_double * _lib.MAX_DIM)(*b[:, 1])
+        torch, dev, lib = self._rt()
+        n = len(self._x)
+        ks = self._kernel_struct()
         use_solve = not self._trust_inverse()
         with self._on(torch, dev):
             st = self._stream(torch)
@@ -1192,15 +1373,11 @@ class GP(GeorgeExtras):
             work = torch.empty(int(lib.apgp_nm_search_work_len(R, n)), **f64)
             tr = torch.empty(R * maxfev * (D + 3), **f64) if trace else None
             steps = torch.zeros(R * maxiter, **i32) if trace else None
-            if use_solve:
-                inv = (None, 0, self._L.data_ptr(), self._ld)
-            else:
-                inv = (self._work.data_ptr(), (n + 63) // 64 * 64, None, 0)
+            inv, _ = self._variance_operand(use_solve)
             _lib.check(lib.apgp_nm_search(starts_d.data_ptr(), R, self._xs.data_ptr(), n, ctypes.byref(ks),
                                           float(self.mean.value), *inv, lo, hi, ctypes.byref(opt),
                                           x_out.data_ptr(), f_out.data_ptr(), stats.data_ptr(),
-                                          tr.data_ptr() if tr is not None else None,
-                                          steps.data_ptr() if steps is not None else None, work.data_ptr(), st),
+                                          _ptr(tr), _ptr(steps), work.data_ptr(), st),
                        "apgp_nm_search")
             x = x_out.cpu().numpy()
             fun = f_out.cpu().numpy()
@@ -1242,59 +1419,26 @@ class GP(GeorgeExtras):
         kind_ids = [UTILITY_KINDS[str(k).lower()] for k in kinds]
         torch, dev, lib = self._rt()
         y = self._check_dimensions(y)
-        n = len(self._x)
-        ks = self._kernel_struct()
-        D = ks.ndim
-        use_solve = not self._trust_inverse()
+        n, D = len(self._x), self.kernel.ndim
+        lo, hi = _box(bounds, D)
+        T = self._candidates(t)
+        m = T.shape[0]
+        mask_d = self._mask(mask, m)
         idx = np.full(q, -1, dtype=np.int64)
         ub = np.full(q, np.inf)
+        if m == 0:
+            return (idx, ub, np.empty(0), np.empty(0), np.empty(0)) if return_all else (idx, ub)
+        # the first pick is acquire's sweep, with its prune override and event hook: neither changes this call, whose mu
+        # and var arrays are always asked for -- the library prunes only when none of mu, var, u is (acquire_impl)
+        s = self._sweep(y, T, kind_ids[0], lo, hi, mask_d, zeta, idx_offset, with_mu=True, with_var=True,
+                        with_u=return_all)
+        best, mu, u = s.best, s.mu, s.u
+        ks = self._kernel_struct()
+        ybest = float(np.max(y))
         with self._on(torch, dev):
             st = self._stream(torch)
-            if hasattr(t, "data_ptr"):
-                if t.dim() != 2 or t.shape[1] != D or not t.is_contiguous() \
-                        or str(t.dtype) != "torch.float64" or not t.is_cuda:
-                    raise ValueError("device candidates must be a contiguous (M, D) float64 CUDA tensor")
-                T = t
-            else:
-                T = torch.from_numpy(self.parse_samples(t)).to(dev)
-            m = T.shape[0]
-            if m == 0:
-                return (idx, ub, np.empty(0), np.empty(0), np.empty(0)) if return_all else (idx, ub)
-            if use_solve:
-                self._ensure_lsolve()
-            else:
-                self._ensure_linv()
-            self._ensure_xs(y)
             f64 = dict(dtype=torch.float64, device=dev)
-            mu = torch.empty(m, **f64)
-            var = [torch.empty(m, **f64), torch.empty(m, **f64) if q > 1 else None]
-            u = torch.empty(m, **f64) if return_all else None
-            part = torch.empty(max(int(lib.apgp_acquire_work_len(m, n)), 2), **f64)
-            best = torch.empty(2, **f64)
-            lo = hi = None
-            if bounds is not None:
-                b = np.asarray(bounds, dtype=np.float64).reshape(-1, 2)
-                if len(b) != D:
-                    raise ValueError("bounds must have one (lo, hi) pair per dimension")
-                lo = (ctypes.c_double * _lib.MAX_DIM)(*b[:, 0])
-                hi = (ctypes.c_double * _lib.MAX_DIM)(*b[:, 1])
-            mask_p = None
-            if mask is not None:
-                mk = np.ascontiguousarray(np.asarray(mask).astype(np.uint8))
-                if mk.shape != (m,):
-                    raise ValueError("mask must have one entry per candidate")
-                mask_d = torch.from_numpy(mk).to(dev)
-                mask_p = mask_d.data_ptr()
-            ybest = float(np.max(y))
-            args = (ctypes.byref(ks), float(self.mean.value), kind_ids[0], lo, hi, mask_p, float(zeta), ybest,
-                    mu.data_ptr(), var[0].data_ptr(), u.data_ptr() if u is not None else None,
-                    part.data_ptr(), best.data_ptr(), st)
-            if use_solve:
-                _lib.check(lib.apgp_acquire_solve(T.data_ptr(), m, int(idx_offset), self._packed_solve.data_ptr(),
-                                                  self._xs.data_ptr(), n, *args), "apgp_acquire_solve")
-            else:
-                _lib.check(lib.apgp_acquire(T.data_ptr(), m, int(idx_offset), self._packed.data_ptr(),
-                                            self._xs.data_ptr(), n, *args), "apgp_acquire")
+            var = [s.var, torch.empty(m, **f64) if q > 1 else None]
             if q > 1:
                 C = torch.empty((q - 1) * m, **f64)          # column-major, ldc = m: column j - 1 holds C_j
                 fpart = torch.empty(max(int(lib.apgp_acquire_fantasy_work_len(m)), 2), **f64)
@@ -1304,11 +1448,10 @@ class GP(GeorgeExtras):
                 ss = torch.empty(1, **f64)
             cur = 0
             for j in range(q):
-                bb = best.cpu().numpy()                      # the 16-byte record of the last sweep / pass
-                bi = int(bb[1:2].view(np.int64)[0])
+                bi, bu = _best_record(best)                  # the 16-byte record of the last sweep / pass
                 if bi < 0:
                     break
-                idx[j], ub[j] = bi, float(bb[0])
+                idx[j], ub[j] = bi, bu
                 if j == q - 1:
                     break
                 r = bi - int(idx_offset)
@@ -1316,158 +1459,18 @@ class GP(GeorgeExtras):
                 # beta_j = K^-1 k(X, x_j): the cross row from the candidate row in HBM, two solves against the factor
                 _lib.check(lib.apgp_kernel_cross(T.data_ptr() + 8 * r * D, 1, self._x_d.data_ptr(), n,
                                                  ctypes.byref(ks), krow.data_ptr(), n, st), "apgp_kernel_cross")
-                for trans, src, dst in ((0, krow, z), (1, z, beta)):
-                    _lib.check(lib.apgp_trsv(self._L.data_ptr(), n, self._ld, src.data_ptr(), 0.0, trans,
-                                             dst.data_ptr(), ss.data_ptr(), st), "apgp_trsv(fantasy)")
-                    if float(ss.item()) != float(ss.item()):
-                        # NaN: the persistent solve could not get its workgroups resident (see _solve) -- once more,
-                        # a launch per 256 rows for this call only
-                        _lib.check(lib.apgp_trsv_ex(self._L.data_ptr(), n, self._ld, src.data_ptr(), 0.0, trans,
-                                                    dst.data_ptr(), None, 1, st), "apgp_trsv(fantasy, multi-launch)")
+                self._trsv(st, krow, 0.0, 0, z, ss, "fantasy")
+                self._trsv(st, z, 0.0, 1, beta, ss, "fantasy")
                 _lib.check(lib.apgp_acquire_fantasy(T.data_ptr(), m, int(idx_offset), self._xs.data_ptr(), n,
                                                     ctypes.byref(ks), beta.data_ptr(), r, j + 1, C.data_ptr(), m,
                                                     mu.data_ptr(), var[cur].data_ptr(), var[1 - cur].data_ptr(),
-                                                    kind_ids[j + 1], lo, hi, mask_p, float(zeta), ybest,
-                                                    u.data_ptr() if u is not None else None, fpart.data_ptr(),
-                                                    best.data_ptr(), st), "apgp_acquire_fantasy")
+                                                    kind_ids[j + 1], lo, hi, _ptr(mask_d), float(zeta), ybest,
+                                                    _ptr(u), fpart.data_ptr(), best.data_ptr(), st),
+                           "apgp_acquire_fantasy")
                 cur = 1 - cur
             if return_all:
                 return idx, ub, u.cpu().numpy(), mu.cpu().numpy(), var[cur].cpu().numpy()
         return idx, ub
-
-    def _sweep(self, y, cand, kind, want, bounds=None, mask=None, zeta=0.01, idx_offset=0,
-               cand_device=None):
-        torch, dev, lib = self._rt()
-        y = self._check_dimensions(y)
-        n = len(self._x)
-        need_var = kind is not None or "var" in want
-        ks = self._kernel_struct()
-        use_solve = need_var and not self._trust_inverse()
-        with self._on(torch, dev):
-            st = self._stream(torch)
-            one = need_var and kind is None and cand_device is None and cand is not None and len(cand) == 1
-            if need_var and not use_solve:
-                self._ensure_linv()     # first: with W resident alpha is two matrix-vector products
-            elif need_var and not one:
-                self._ensure_lsolve()   # (a single candidate solves against L itself)
-            self._ensure_xs(y)
-            if not need_var and cand_device is None and 0 < len(cand) <= 4096:
-                # latency-bound mean-only call (the sampler's _gpll batches): host buffers
-                # in and out through ONE library call and one synchronisation
-                m = len(cand)
-                need = m * (ks.ndim + 1)
-                if self._mean_work is None or self._mean_work.numel() < need:
-                    self._mean_work = torch.empty(max(need, 1024), dtype=torch.float64, device=dev)
-                mu_h = np.empty(m, dtype=np.float64)
-                args = [cand.ctypes.data, m, self._xs.data_ptr(), n, ctypes.byref(ks), float(self.mean.value),
-                        mu_h.ctypes.data, self._mean_work.data_ptr(), st]
-                _lib.check(lib.apgp_predict_mean_host(*args), "apgp_predict_mean_host")
-                # the sampler asks again, for another few points of the same model and y, 4e4 times per chain (the walker
-                # ensembles of ApproxPosterior._gpllBatch, approx.py:148-189)
-                max_m = min(4096, self._mean_work.numel() // (ks.ndim + 1))
-                self._replays["mean"] = _Replay(lib.apgp_predict_mean_host, args, dev.index, st.value or 0, y,
-                                                (self._xs, self._mean_work), self._queries, data=(ks.ndim, max_m))
-                return (mu_h,)
-            if need_var and kind is None and cand_device is None and len(cand) == 1:
-                # ONE candidate with variance: the reference's scalar utilities (utility.py:131,178,224), once per
-                # Nelder-Mead step of minimizeObjective -- three small launches, the result through the mailbox
-                if self._p1_work is None or self._p1_work.numel() < int(lib.apgp_predict1_work_len(n)):
-                    self._p1_work = torch.empty(int(lib.apgp_predict1_work_len(n)), dtype=torch.float64, device=dev)
-                o2 = np.empty(2, dtype=np.float64)
-                if use_solve:       # substitution against L, or the resident dense L^-1
-                    factor, inv = self._L, (None, 0, self._L.data_ptr(), self._ld)
-                else:
-                    factor, inv = self._work, (self._work.data_ptr(), (n + 63) // 64 * 64, None, 0)
-                args = [cand.ctypes.data, self._xs.data_ptr(), n, ctypes.byref(ks), float(self.mean.value), *inv,
-                        self._p1_work.data_ptr(), o2.ctypes.data, st]
-                _lib.check(lib.apgp_predict1_host(*args), "apgp_predict1_host")
-                if want == ("mu", "var"):
-                    # the reference's scalar utilities ask again at the next simplex point, ~460 times per search
-                    self._replays["one"] = _Replay(lib.apgp_predict1_host, args, dev.index, st.value or 0, y,
-                                                   (self._xs, self._p1_work, factor), self._queries, data=(o2, (1, ks.ndim)))
-                res = {"mu": np.array([o2[0]]), "var": np.array([o2[1]])}
-                return tuple(res[w_] for w_ in want)
-            T = cand_device if cand_device is not None else torch.from_numpy(cand).to(dev)
-            m = T.shape[0]
-            if m == 0:
-                # empty candidate set: nothing admissible (index -1, +inf), empty arrays
-                empty = {"best": (-1, float("inf")), "mu": (np.empty(0),), "var": (np.empty(0),),
-                         "u": (np.empty(0),)}
-                if "best_device" in want:
-                    empty["best_device"] = (torch.tensor([int(np.float64(np.inf).view(np.int64)), -1],
-                                                         dtype=torch.int64, device=dev),)
-                return tuple(v for w_ in want for v in empty[w_])
-            if not need_var:
-                mu = torch.empty(m, dtype=torch.float64, device=dev)
-                _lib.check(lib.apgp_predict_mean(T.data_ptr(), m, self._xs.data_ptr(), n,
-                                                 ctypes.byref(ks), float(self.mean.value),
-                                                 mu.data_ptr(), st), "apgp_predict_mean")
-                return (mu.cpu().numpy(),)
-            mu = torch.empty(m, dtype=torch.float64, device=dev) if "mu" in want else None
-            var = torch.empty(m, dtype=torch.float64, device=dev) if "var" in want else None
-            u = torch.empty(m, dtype=torch.float64, device=dev) if "u" in want else None
-            nwork = int(lib.apgp_acquire_work_len(m, n))
-            part = torch.empty(max(nwork, 2), dtype=torch.float64, device=dev)
-            best = torch.empty(2, dtype=torch.float64, device=dev)
-            lo = hi = None
-            if bounds is not None:
-                b = np.asarray(bounds, dtype=np.float64).reshape(-1, 2)
-                if len(b) != ks.ndim:
-                    raise ValueError("bounds must have one (lo, hi) pair per dimension")
-                lo = (ctypes.c_double * _lib.MAX_DIM)(*b[:, 0])
-                hi = (ctypes.c_double * _lib.MAX_DIM)(*b[:, 1])
-            mask_d = None
-            if mask is not None:
-                mk = np.ascontiguousarray(np.asarray(mask).astype(np.uint8))
-                if mk.shape != (m,):
-                    raise ValueError("mask must have one entry per candidate")
-                mask_d = torch.from_numpy(mk).to(dev)
-            kid = _lib.UTIL_NONE if kind is None else kind
-            ybest = float(np.max(y))
-            ev = getattr(self, "kernel_events", None)   # bench.py: HIP events around the launch
-            if ev is not None:
-                e0 = torch.cuda.Event(enable_timing=True)
-                e0.record()
-            common = (ctypes.byref(ks), float(self.mean.value), kid, lo, hi,
-                      mask_d.data_ptr() if mask_d is not None else None, float(zeta), ybest,
-                      mu.data_ptr() if mu is not None else None,
-                      var.data_ptr() if var is not None else None,
-                      u.data_ptr() if u is not None else None,
-                      part.data_ptr(), best.data_ptr(), st)
-            prune_was = None if self.sweep_prune is None else lib.apgp_set_sweep_prune(int(self.sweep_prune))
-            try:
-                if use_solve:
-                    _lib.check(lib.apgp_acquire_solve(T.data_ptr(), m, int(idx_offset), self._packed_solve.data_ptr(),
-                                                      self._xs.data_ptr(), n, *common), "apgp_acquire_solve")
-                else:
-                    _lib.check(lib.apgp_acquire(T.data_ptr(), m, int(idx_offset), self._packed.data_ptr(),
-                                                self._xs.data_ptr(), n, *common), "apgp_acquire")
-            finally:
-                if prune_was is not None:
-                    lib.apgp_set_sweep_prune(prune_was)
-            if self.sweep_prune_stats and kid != _lib.UTIL_NONE and mu is None and var is None and u is None:
-                off = int(lib.apgp_sweep_prune_counts_offset(m, n))
-                self.last_prune_counts = part[off:off + 3].view(torch.int64).clone()
-            if ev is not None:
-                e1 = torch.cuda.Event(enable_timing=True)
-                e1.record()
-                ev.append((e0, e1))
-            out = []
-            for w in want:
-                if w == "best_device":
-                    import torch as _t
-                    out.append(best.view(_t.int64))
-                elif w == "best":
-                    bb = best.cpu().numpy()
-                    out.append(int(bb[1:2].view(np.int64)[0]))
-                    out.append(float(bb[0]))
-                elif w == "mu":
-                    out.append(mu.cpu().numpy())
-                elif w == "var":
-                    out.append(var.cpu().numpy())
-                elif w == "u":
-                    out.append(u.cpu().numpy())
-        return tuple(out)
 
     # -- candidate matrix of the sweep drawn on the device -----------------------------
     def box_candidates(self, m, bounds, seed, idx_offset=0):
@@ -1477,16 +1480,12 @@ class GP(GeorgeExtras):
         (utility.py:334-338) without the host draw and the H2D copy (26 ms per 1e6 x 8 against an 18 ms sweep)."""
         torch, dev, lib = self._rt()
         D = self.kernel.ndim
-        b = np.asarray(bounds, dtype=np.float64).reshape(-1, 2)
-        if len(b) != D:
-            raise ValueError("bounds must have one (lo, hi) pair per dimension")
-        lo = (ctypes.c_double * _lib.MAX_DIM)(*b[:, 0])
-        hi = (ctypes.c_double * _lib.MAX_DIM)(*b[:, 1])
+        lo, hi = _box(bounds, D, optional=False)
         with self._on(torch, dev):
             T = torch.empty((int(m), D), dtype=torch.float64, device=dev)
             if int(m) == 0:
                 return T
-            _lib.check(lib.apgp_box_candidates(T.data_ptr(), int(m), D, lo, hi, int(seed) & 0xFFFFFFFFFFFFFFFF,
+            _lib.check(lib.apgp_box_candidates(T.data_ptr(), int(m), D, lo, hi, _seed64(seed),
                                                int(idx_offset), self._stream(torch)), "apgp_box_candidates")
         return T
 
@@ -1513,7 +1512,7 @@ class GP(GeorgeExtras):
             if int(m) == 0:
                 return T
             _lib.check(lib.apgp_prior_candidates(T.data_ptr(), int(m), D, kind.ctypes.data, p0.ctypes.data,
-                                                 p1.ctypes.data, int(seed) & 0xFFFFFFFFFFFFFFFF, int(idx_offset),
+                                                 p1.ctypes.data, _seed64(seed), int(idx_offset),
                                                  self._stream(torch)), "apgp_prior_candidates")
         return T
 
@@ -1551,11 +1550,7 @@ class GP(GeorgeExtras):
         if prior is not None:
             records = self._prior_records(prior, D)
             bounds = prior.support()
-        b = np.asarray(bounds, dtype=np.float64).reshape(-1, 2)
-        if len(b) != D:
-            raise ValueError("bounds must have one (lo, hi) pair per dimension")
-        lo = (ctypes.c_double * _lib.MAX_DIM)(*b[:, 0])
-        hi = (ctypes.c_double * _lib.MAX_DIM)(*b[:, 1])
+        lo, hi = _box(bounds, D, optional=False)
         n = len(self._x)
         ks = self._kernel_struct()
         iterations = int(iterations)
@@ -1571,7 +1566,7 @@ class GP(GeorgeExtras):
                 coords.copy_(torch.from_numpy(p0))
                 _lib.check(lib.apgp_ensemble_sample_ex(
                     self._xs.data_ptr(), n, ctypes.byref(ks), float(self.mean.value), lo, hi, W, E,
-                    iterations, float(a), int(seed) & 0xFFFFFFFFFFFFFFFF, coords.data_ptr(), logp.data_ptr(),
+                    iterations, float(a), _seed64(seed), coords.data_ptr(), logp.data_ptr(),
                     chain.data_ptr() if store else None, lchain.data_ptr() if store else None,
                     nacc.data_ptr(), mode, st), "apgp_ensemble_sample")
                 return logp.cpu().numpy().reshape(E * W)
