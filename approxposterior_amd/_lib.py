@@ -96,6 +96,9 @@ SIGNATURES = {
     "apgp_get_sweep_prune": (ctypes.c_int, []),
     "apgp_sweep_prune_counts_offset": (_I64, [_I64, _I64]),
     "apgp_sweep_prune_select": (ctypes.c_int, [_P, _I64, _P, _P, _F64, _P, _P]),
+    "apgp_prune_bounds": (ctypes.c_int, [_P, _I64, _P, _I64, _KP, _F64, _I32, ctypes.POINTER(_F64), ctypes.POINTER(_F64),
+                                         _P, _F64, _F64, ctypes.c_int, _P, _P]),
+    "apgp_sweep_prune_seeds": (ctypes.c_int, [_P, _I64, _P, _P, _P]),
     "apgp_acquire_fantasy_work_len": (_I64, [_I64]),
     "apgp_acquire_fantasy": (ctypes.c_int, [_P, _I64, _I64, _P, _I64, _KP, _P, _I64, _I32, _P, _I64,
                                             _P, _P, _P, _I32, ctypes.POINTER(_F64), ctypes.POINTER(_F64), _P,

@@ -1221,8 +1221,9 @@ static void launch_sweep_list(const SweepArgs& a0, hipStream_t s, bool solve, co
 #define PR_ROWS 128         // training rows per LDS tile (divides the packed stream's 512-row padding)
 #define PR_SEED 16          // seed blocks: one split launch of 16 x nrb workgroups covers the chip from N = 4096 on
 // candidates below which the full sweep is taken (apgp_set_sweep_prune(1)).  The pruned call costs about one block's
-// time whatever m is (the seeds), the full sweep m N^2: measured crossover between m = 4096 and 16384 at N = 4096,
-// between 16384 and 65536 at N = 1152 (docs/experiments.md, round 7)
+// time whatever m is (the seeds), the full sweep m N^2.  Re-measured with the fp32 bound pass (docs/experiments.md,
+// round 9): pruned / full = 0.95 at m = 4096 and 0.29 at 16384 for N = 4096; 0.94 at 16384 and 0.27 at 65536 for
+// N = 1152 -- level at the lower neighbours, against 1.27x when nothing prunes: the thresholds stay
 static inline int64_t pr_min_m(int64_t n) { return n >= 4096 ? 16384 : 65536; }
 
 struct PruneArgs {
@@ -1236,25 +1237,42 @@ struct PruneArgs {
     int ndim, kind, has_box, lin_order;
     double mean, amp, lin_coef, zeta, ybest;
     double sc[APGP_MAX_DIM], lw[APGP_MAX_DIM], lo[APGP_MAX_DIM], hi[APGP_MAX_DIM];
+    // refine stage (prune_bound_kernel<.., LIST = true>): the blocks blk_list[0 .. *blk_count), a count the device computed
+    const long long* blk_list;
+    const long long* blk_count;
+    // coarse stage: per block the smallest b WITHOUT the slack (NULL: not wanted) -- where the minimum probably lies,
+    // which is what the seeds are chosen by; a seed need not come from a valid bound
+    double* est;
 };
 
-template <int DPAD>
+// LIST: the refine stage of a call that bounded coarsely first (prune_bound32_kernel): only the blocks of a device list,
+// bmin[blk] = max(coarse, this bound) -- both are valid, the larger prunes more --, and no pre-fill of the partials.  The
+// launch is sized for the longest list; a workgroup beyond the count leaves before its first barrier.
+template <int DPAD, bool LIST = false>
 __global__ __launch_bounds__(PR_THREADS) void prune_bound_kernel(PruneArgs a) {
     constexpr int XS = DPAD + 2;                 // packed stream row: scaled x | alpha | 0
     constexpr int PIECES = PR_ROWS * XS / 2;     // 16-byte pieces per tile
     __shared__ double etab[APGP_EXP_TAB_N];
     __shared__ __attribute__((aligned(16))) double tile[PR_ROWS * XS];
+    long long lst_count = 0;
+    if (LIST) {
+        lst_count = *a.blk_count;
+        if ((long long)blockIdx.x * (PR_THREADS / 64) * PR_CPT >= lst_count) return;
+    }
     apgp_exp_tab_load(etab);
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
     // wavefront w: candidate blocks blk0, blk0 + 1 (the sweep's SW_CAND blocks, same numbering), lane = row in block
     const long long blk0 = ((long long)blockIdx.x * (PR_THREADS / 64) + w) * PR_CPT;
+    long long blk[PR_CPT];
+#pragma unroll
+    for (int c = 0; c < PR_CPT; ++c) blk[c] = !LIST ? blk0 + c : (blk0 + c < lst_count ? a.blk_list[blk0 + c] : a.ncb);
     double tt[PR_CPT][DPAD], ktt[PR_CPT];
     bool adm[PR_CPT];
 #pragma unroll
     for (int c = 0; c < PR_CPT; ++c) {
         // admissibility and k(t,t) exactly as the sweep's load_candidates
-        const long long row = (blk0 + c) * SW_CAND + lane;
-        const bool live = blk0 + c < a.ncb && row < a.m;
+        const long long row = blk[c] * SW_CAND + lane;
+        const bool live = blk[c] < a.ncb && row < a.m;
         bool ok = live, has_nan = false;
         double ktl = a.lin_order == 0 ? (double)a.ndim : 0.0;
 #pragma unroll
@@ -1360,10 +1378,205 @@ __global__ __launch_bounds__(PR_THREADS) void prune_bound_kernel(PruneArgs a) {
         if (!(b == b)) b = -INFINITY;
         if (!adm[c]) b = INFINITY;
         for (int o = 32; o > 0; o >>= 1) b = fmin(b, __shfl_xor(b, o));
+        if (lane == 0 && blk[c] < a.ncb) {
+            if (LIST) {
+                a.bmin[blk[c]] = fmax(a.bmin[blk[c]], b);
+            } else {
+                a.bmin[blk[c]] = b;
+                if (a.part_u) {
+                    a.part_u[blk[c]] = INFINITY;     // a pruned block's partial: never wins
+                    a.part_i[blk[c]] = -1;
+                }
+            }
+        }
+    }
+}
+
+// ---------------------------------------------------------------------------
+// Coarse bound in single precision (pure squared-exponential kernels: lin_coef == 0).  A bound has to lie below the
+// row's utility, not to be tight: the N kernel values per candidate are computed in fp32 with the hardware exponential
+// (about 11 issue slots per value with packed fp32 arithmetic, against ~38 fp64 operations), everything the slack rests
+// on stays in fp64.  Same outputs as prune_bound_kernel.
+//   * exact part: admissibility (box, mask, NaN) and k(t,t) as in load_candidates; util_value in fp64 on (mu32, k(t,t)).
+//   * coordinates: a = (t sc - c) kappa and b = (x - c) kappa are formed in fp64 and then converted, c = the first
+//     training row, kappa^2 = log2(e): a data set far from the origin keeps its differences, and
+//     k = amp 2^-|a - b|^2 needs no multiply in front of v_exp_f32.
+//   * PR32_CPT candidate blocks per wavefront share every LDS read of a training row (16-byte reads of fp32 rows; the
+//     alphas of PR32_FLUSH rows in 16-byte reads): 2.25 reads per row against 11 PR32_CPT issue slots of arithmetic.
+//   * sums: fp32 over PR32_FLUSH rows, then added into fp64 -- the accumulation error does not grow with N.
+//   * the next tile's 16-byte pieces of the packed fp64 stream are loaded into registers before the current tile is
+//     consumed, converted and stored after it.
+// Error of mu32 against the exact sum over the fp64 inputs (t sc, x, alpha), u = 2^-24, r = |t sc - x|,
+// A = |t sc - c|, per training row, in units of amp |alpha|:
+//   * distance.  a_d, b_d convert with relative error u each and their fp32 difference rounds once more:
+//     |d^_d - d_d| <= 2 u (1 + u) (|a_d| + |b_d|); over the dimensions (Cauchy-Schwarz, |b| <= A + r) the sum of squares
+//     is off by <= u (8 A r + 4 r^2) + 32 u^2 A^2 + ..., the two fma chains and their sum add (Dpad / 2 + 1) u r^2:
+//     eta(r) <= u (8 A r + C r^2) + 32 u^2 A^2 with C = Dpad / 2 + 5 in the exponent.  Behind the gate
+//     u (8 A + Dpad + 8) <= 2^-8 (else the slack is +inf), eta <= (r + r^2) / 256 and
+//     |k^ - k| <= e^-r^2 (e^eta - 1) <= u (8 A max_r(r e^(-r^2 + eta)) + C max_r(r^2 e^(-r^2 + eta))) + 32 u^2 A^2
+//              <= u (3.52 A + 0.38 C) + u A / 64          (the maxima are 0.431 and 0.371)
+//              <= u (4 A + Dpad / 2 + 4)                  (with room for the fp64 roundings of a, b, kappa: 2^-29 u each)
+//   * centring.  x - c rounds once (relative, above), but t sc - c may be contracted to one fma, which differs from the
+//     sweep's rounded t sc less c by eps |t sc| <= eps (|c| + A) per coordinate, eps = 2^-53: an ABSOLUTE shift delta
+//     of a, |delta| <= 1.21 eps (|c| + A) with kappa, that no relative term covers once |c| >~ 2^29.  It moves the
+//     exponent by <= 2 r |delta| + |delta|^2 and k by <= max_r(2 r e^-r^2) |delta| (1 + ...) <= 2 eps (|c| + A); the
+//     gate takes eps (|c| + A) into its sum, so the linearisation holds as for eta.
+//   * exponential: v_exp_f32 is good to 1 ulp, allowed 4 u;  alpha -> fp32: u;  PR32_FLUSH = 8 fma into one fp32 sum:
+//     8 u (k^ <= 1);  one u to spare: 18 u together with the constant above.
+//   * flushes: a kernel value, an alpha or a product below 2^-126 may become 0: 2^-120 (sum |alpha| + N).
+//   * sum |alpha| itself is summed the same way (fp32 over 8 rows, then fp64): below the true one by <= 2^-20 of it;
+//     it is taken times 1 + 2^-16.
+// |mu32 - mu| <= e32 = amp ((u (4 A + Dpad / 2 + 18) + 2 eps (|c| + A)) sum|alpha| + 2^-120 (sum|alpha| + N)); the slack is
+// prune_bound_kernel's with S <= amp sum|alpha| plus 2 e32 (|du/dmu| <= 2).  Not finite: -inf, the block goes on to
+// the fp64 bound.
+// Variants measured: docs/experiments.md, round 9.
+// ---------------------------------------------------------------------------
+#define PR32_CPT 4          // candidate blocks per wavefront (2 and 8 measured: docs/experiments.md, round 9)
+#define PR32_ROWS 128       // training rows per LDS tile
+#define PR32_FLUSH 8        // rows per fp32 partial sum
+typedef float f32x2 __attribute__((ext_vector_type(2)));
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+// (the candidates' coordinates stay in registers: Dpad / 2 x blocks packed pairs)
+static constexpr int pr32_cpt(int dpad) { return dpad <= 8 ? PR32_CPT : dpad == 16 ? 2 : 1; }
+
+template <int DPAD>
+__global__ __launch_bounds__(PR_THREADS) void prune_bound32_kernel(PruneArgs a) {
+    constexpr int XS = DPAD + 2;                         // packed stream row: scaled x | alpha | 0
+    constexpr int PIECES = PR32_ROWS * XS / 2;           // 16-byte pieces per tile
+    constexpr int NP = (PIECES + PR_THREADS - 1) / PR_THREADS;
+    constexpr int HD = DPAD / 2;
+    constexpr int CPT = pr32_cpt(DPAD);
+    const double kappa = 0x1.3379f6df3f4ccp+0;           // sqrt(log2(e))
+    __shared__ __attribute__((aligned(16))) float xt[PR32_ROWS * DPAD];
+    __shared__ __attribute__((aligned(16))) float at[PR32_ROWS];
+    __shared__ double cen[DPAD];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    if (tid < DPAD) cen[tid] = a.xs[tid];
+    const long long blk0 = ((long long)blockIdx.x * (PR_THREADS / 64) + w) * CPT;
+    f32x2 tt[CPT][HD];
+    double ktt[CPT], an[CPT];
+    bool adm[CPT];
+#pragma unroll
+    for (int c = 0; c < CPT; ++c) {
+        // admissibility and k(t,t) exactly as the sweep's load_candidates (lin_coef == 0: k(t,t) = amp)
+        const long long row = (blk0 + c) * SW_CAND + lane;
+        const bool live = blk0 + c < a.ncb && row < a.m;
+        bool ok = live, has_nan = false;
+        double a2 = 0.0;
+#pragma unroll
+        for (int d = 0; d < DPAD; ++d) {
+            double v = 0.0;
+            if (live && d < a.ndim) {
+                v = a.T[row * a.ndim + d];
+                if (a.has_box && !(v >= a.lo[d] && v <= a.hi[d])) ok = false;
+                if (v != v) has_nan = true;
+            }
+            const double ce = v * a.sc[d] - a.xs[d];
+            a2 = fma(ce, ce, a2);
+            tt[c][d >> 1][d & 1] = (float)(ce * kappa);
+        }
+        if (live && a.mask && a.mask[row] == 0) ok = false;
+        adm[c] = ok && !has_nan;
+        ktt[c] = a.amp;
+        an[c] = sqrt(a2);
+    }
+    double acc[CPT], sal = 0.0, c2 = 0.0;
+#pragma unroll
+    for (int c = 0; c < CPT; ++c) acc[c] = 0.0;
+#pragma unroll
+    for (int d = 0; d < DPAD; ++d) c2 = fma(a.xs[d], a.xs[d], c2);
+    const double cn = sqrt(c2);                          // |c|
+    const long long ntile = (a.n + PR32_ROWS - 1) / PR32_ROWS;
+    f64x2 pre[NP];
+    auto fetch = [&](long long ti) {                     // (rows < ntile * PR32_ROWS <= npad: inside the packed stream)
+        const f64x2* src = (const f64x2*)(a.xs + ti * (PR32_ROWS * XS));
+#pragma unroll
+        for (int i = 0; i < NP; ++i) {
+            const int e = tid + i * PR_THREADS;
+            pre[i] = e < PIECES ? src[e] : f64x2{0.0, 0.0};
+        }
+    };
+    fetch(0);
+    __syncthreads();                                     // cen
+    for (long long ti = 0; ti < ntile; ++ti) {
+#pragma unroll
+        for (int i = 0; i < NP; ++i) {
+            const int e = tid + i * PR_THREADS;
+            if (e < PIECES) {
+                const int r = (2 * e) / XS, col = (2 * e) % XS;      // (XS is even: a piece never straddles two rows)
+                if (col < DPAD)
+                    *(f32x2*)(xt + r * DPAD + col) = f32x2{(float)((pre[i].x - cen[col]) * kappa),
+                                                           (float)((pre[i].y - cen[col + 1]) * kappa)};
+                else
+                    at[r] = (float)pre[i].x;
+            }
+        }
+        __syncthreads();
+        if (ti + 1 < ntile) fetch(ti + 1);
+        for (int r0 = 0; r0 < PR32_ROWS; r0 += PR32_FLUSH) {
+            float al[PR32_FLUSH], ps[CPT], pa = 0.0f;
+#pragma unroll
+            for (int q = 0; q < PR32_FLUSH; q += 4) *(f32x4*)(al + q) = *(const f32x4*)(at + r0 + q);
+#pragma unroll
+            for (int c = 0; c < CPT; ++c) ps[c] = 0.0f;
+#pragma unroll
+            for (int q = 0; q < PR32_FLUSH; ++q) {
+                f32x2 xr[HD];
+                if constexpr (DPAD >= 4) {
+#pragma unroll
+                    for (int h = 0; h < HD; h += 2) {
+                        const f32x4 v = *(const f32x4*)(xt + (r0 + q) * DPAD + 2 * h);
+                        xr[h] = f32x2{v.x, v.y};
+                        xr[h + 1] = f32x2{v.z, v.w};
+                    }
+                } else {
+                    xr[0] = *(const f32x2*)(xt + (r0 + q) * DPAD);
+                }
+                pa += fabsf(al[q]);
+#pragma unroll
+                for (int c = 0; c < CPT; ++c) {
+                    f32x2 s2 = f32x2{0.0f, 0.0f};
+#pragma unroll
+                    for (int h = 0; h < HD; ++h) {
+                        const f32x2 df = tt[c][h] - xr[h];
+                        s2 = __builtin_elementwise_fma(df, df, s2);
+                    }
+                    const float k = __builtin_amdgcn_exp2f(-(s2.x + s2.y));
+                    ps[c] = fmaf(k, al[q], ps[c]);
+                }
+            }
+#pragma unroll
+            for (int c = 0; c < CPT; ++c) acc[c] += (double)ps[c];
+            sal += (double)pa;
+        }
+        __syncthreads();                                 // the tile has been consumed
+    }
+    const double u32 = 0x1p-24, eps = 0x1p-53;
+    const double sa = sal * (1.0 + 0x1p-16);
+#pragma unroll
+    for (int c = 0; c < CPT; ++c) {
+        const double mu = fma(a.amp, acc[c], a.mean);
+        double b = util_value(a.kind, mu, ktt[c], a.zeta, a.ybest);
+        double e32 = a.amp * ((u32 * (4.0 * an[c] + 0.5 * DPAD + 18.0) + 2.0 * eps * (cn + an[c])) * sa +
+                              0x1p-120 * (sa + (double)a.n));
+        if (!(u32 * (8.0 * an[c] + DPAD + 8.0) + eps * (cn + an[c]) <= 0x1p-8)) e32 = INFINITY;
+        // prune_bound_kernel's slack with S <= amp sum|alpha|, and the fp32 part on top
+        double slack = 2.0 * e32 + 2.0 * (4.0 * (double)(a.n + 16) + 8.0 * DPAD + 32.0) * eps * (a.amp * sa) +
+                       64.0 * eps * (1.0 + fabs(mu) + fabs(a.ybest) + fabs(a.zeta) + ktt[c] + fabs(b));
+        if (a.kind == APGP_UTIL_BAPE) slack += 16.0 * eps / (1.0 - exp(0.0 - ktt[c]));
+        double be = b;
+        b -= slack;
+        if (!(b == b)) b = -INFINITY;
+        if (!(be == be)) be = -INFINITY;
+        if (!adm[c]) b = be = INFINITY;
+        for (int o = 32; o > 0; o >>= 1) { b = fmin(b, __shfl_xor(b, o)); be = fmin(be, __shfl_xor(be, o)); }
         if (lane == 0 && blk0 + c < a.ncb) {
             a.bmin[blk0 + c] = b;
-            a.part_u[blk0 + c] = INFINITY;       // a pruned block's partial: never wins
-            a.part_i[blk0 + c] = -1;
+            if (a.est) a.est[blk0 + c] = be;
+            if (a.part_u) {
+                a.part_u[blk0 + c] = INFINITY;           // a pruned block's partial: never wins
+                a.part_i[blk0 + c] = -1;
+            }
         }
     }
 }
@@ -1371,50 +1584,81 @@ __global__ __launch_bounds__(PR_THREADS) void prune_bound_kernel(PruneArgs a) {
 // (value, block) pairs in ascending order: by value, then by block number
 __device__ __forceinline__ bool pr_less(double v, long long i, double w, long long j) { return v < w || (v == w && i < j); }
 
-// The PR_SEED blocks with the smallest bmin (fewer if fewer have an admissible row), one workgroup: PR_SEED
-// passes, each the smallest pair above the previous pick.
-__global__ __launch_bounds__(1024) void prune_seed_kernel(const double* bmin, long long ncb, long long* seeds,
-                                                          long long* counts) {
-    __shared__ double sv[16];
-    __shared__ long long si[16];
-    __shared__ double pick_v;
-    __shared__ long long pick_i;
-    double pv = -INFINITY;
-    long long pi = -1;
-    int ns = 0;
-    for (; ns < PR_SEED; ++ns) {
-        double bv = INFINITY;
-        long long bi = -1;                        // (-1: nothing left)
-        for (long long p = threadIdx.x; p < ncb; p += 1024) {
-            const double v = bmin[p];
-            if (v < INFINITY && pr_less(pv, pi, v, p) && (bi < 0 || pr_less(v, p, bv, bi))) { bv = v; bi = p; }
-        }
+#define PR_NONE 0x7fffffffffffffffll                     // block number of an empty shortlist entry, value +inf
+
+// a sorted shortlist of the PR_SEED smallest pairs seen, in registers (every index is a compile-time constant)
+__device__ __forceinline__ void pr_short_insert(double (&lv)[PR_SEED], long long (&li)[PR_SEED], double v, long long p) {
+    if (!pr_less(v, p, lv[PR_SEED - 1], li[PR_SEED - 1])) return;
+    lv[PR_SEED - 1] = v; li[PR_SEED - 1] = p;
+#pragma unroll
+    for (int s = PR_SEED - 1; s > 0; --s) {
+        const bool up = pr_less(lv[s], li[s], lv[s - 1], li[s - 1]);
+        const double tv = lv[s]; const long long tp = li[s];
+        lv[s] = up ? lv[s - 1] : tv; li[s] = up ? li[s - 1] : tp;
+        lv[s - 1] = up ? tv : lv[s - 1]; li[s - 1] = up ? tp : li[s - 1];
+    }
+}
+
+// The PR_SEED smallest pairs of a wavefront's 64 shortlists, in order: lane r < PR_SEED returns the r-th (PR_NONE if
+// there are fewer).  PR_SEED rounds: the smallest head wins, its lane drops it.
+__device__ __forceinline__ void pr_wave_merge(double (&lv)[PR_SEED], long long (&li)[PR_SEED], double& mv, long long& mi) {
+    const int lane = threadIdx.x & 63;
+    mv = INFINITY; mi = PR_NONE;
+    for (int r = 0; r < PR_SEED; ++r) {
+        double bv = lv[0];
+        long long bi = li[0];
         for (int o = 32; o > 0; o >>= 1) {
             const double ov = __shfl_xor(bv, o);
             const long long oi = __shfl_xor(bi, o);
-            if (oi >= 0 && (bi < 0 || pr_less(ov, oi, bv, bi))) { bv = ov; bi = oi; }
+            if (pr_less(ov, oi, bv, bi)) { bv = ov; bi = oi; }
         }
-        if ((threadIdx.x & 63) == 0) { sv[threadIdx.x >> 6] = bv; si[threadIdx.x >> 6] = bi; }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            for (int i = 1; i < 16; ++i)
-                if (si[i] >= 0 && (bi < 0 || pr_less(sv[i], si[i], bv, bi))) { bv = sv[i]; bi = si[i]; }
-            pick_v = bv; pick_i = bi;
-            if (bi >= 0) seeds[ns] = bi;
+        if (lane == r) { mv = bv; mi = bi; }
+        if (bi != PR_NONE && li[0] == bi) {
+#pragma unroll
+            for (int s = 0; s + 1 < PR_SEED; ++s) { lv[s] = lv[s + 1]; li[s] = li[s + 1]; }
+            lv[PR_SEED - 1] = INFINITY; li[PR_SEED - 1] = PR_NONE;
         }
-        __syncthreads();
-        pv = pick_v; pi = pick_i;
-        if (pi < 0) break;
     }
-    if (threadIdx.x == 0) { counts[0] = ns; counts[1] = 0; }
+}
+
+// The PR_SEED blocks with the smallest bmin below +inf (fewer if fewer have an admissible row), ascending by (value,
+// block number), one workgroup, ONE pass over bmin: every thread keeps a sorted shortlist of its strided share, each
+// wavefront merges its 64 shortlists, the first wavefront merges the 16 results.
+__global__ __launch_bounds__(1024) void prune_seed_kernel(const double* bmin, long long ncb, long long* seeds,
+                                                          long long* counts) {
+    __shared__ double sv[16 * PR_SEED];
+    __shared__ long long si[16 * PR_SEED];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    double lv[PR_SEED], mv;
+    long long li[PR_SEED], mi;
+#pragma unroll
+    for (int s = 0; s < PR_SEED; ++s) { lv[s] = INFINITY; li[s] = PR_NONE; }
+    for (long long p = threadIdx.x; p < ncb; p += 1024) {
+        const double v = bmin[p];
+        if (v < INFINITY) pr_short_insert(lv, li, v, p);
+    }
+    pr_wave_merge(lv, li, mv, mi);
+    if (lane < PR_SEED) { sv[w * PR_SEED + lane] = mv; si[w * PR_SEED + lane] = mi; }
+    __syncthreads();
+    if (w != 0) return;
+#pragma unroll
+    for (int s = 0; s < PR_SEED; ++s) { lv[s] = INFINITY; li[s] = PR_NONE; }
+    for (int e = lane; e < 16 * PR_SEED; e += 64)
+        if (si[e] != PR_NONE) pr_short_insert(lv, li, sv[e], si[e]);
+    pr_wave_merge(lv, li, mv, mi);
+    const bool have = lane < PR_SEED && mi != PR_NONE;
+    if (have) seeds[lane] = mi;
+    const int ns = __popcll(__ballot(have));
+    if (lane == 0) { counts[0] = ns; counts[1] = 0; counts[3] = 0; }
 }
 
 // tau = the smallest utility the seed blocks found (part_u of the seeds; tau_in if part_u == NULL: a planted
 // value, apgp_sweep_prune_select); survivors = blocks with an admissible row (bmin < +inf), bmin <= tau, not a seed --
-// written in ascending order (each thread a contiguous range, a scan over the threads' counts), count to counts[1].
+// written in ascending order (each thread a contiguous range, a scan over the threads' counts), count to counts[1] and,
+// if given, to *count2.
 __global__ __launch_bounds__(1024) void prune_select_kernel(const double* bmin, long long ncb, const long long* seeds,
                                                             long long* counts, const double* part_u, double tau_in,
-                                                            long long* list) {
+                                                            long long* list, long long* count2) {
     __shared__ long long sd[PR_SEED];
     __shared__ long long cnt[1024];
     const int t = threadIdx.x;
@@ -1451,6 +1695,7 @@ __global__ __launch_bounds__(1024) void prune_select_kernel(const double* bmin, 
     if (t == 1023) {
         counts[1] = cnt[1023];
         counts[2] = __double_as_longlong(tau);
+        if (count2) *count2 = cnt[1023];
     }
 }
 
@@ -1481,11 +1726,38 @@ extern "C" int apgp_sweep_prune_select(const double* bmin, int64_t ncb, const in
     APGP_CHECK_ARG(bmin && seeds && counts && list, "null pointer");
     APGP_CHECK_ARG(ncb >= 1 && ncb <= APGP_MAX_M / SW_CAND, "ncb >= 1 required");
     hipLaunchKernelGGL(prune_select_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, bmin, (long long)ncb,
-                       (const long long*)seeds, (long long*)counts, (const double*)NULL, tau, (long long*)list);
+                       (const long long*)seeds, (long long*)counts, (const double*)NULL, tau, (long long*)list,
+                       (long long*)NULL);
     APGP_CHECK_LAUNCH();
     return 0;
 }
 
+static void pr_fill_args(PruneArgs& p, const SweepArgs& a, double* bmin, double* part_u, long long* part_i) {
+    p.T = a.T; p.xs = a.xs; p.mask = a.mask; p.bmin = bmin; p.part_u = part_u; p.part_i = part_i;
+    p.m = a.m; p.ncb = pr_ncb(a.m); p.n = a.n;
+    p.ndim = a.ndim; p.kind = a.kind; p.has_box = a.has_box; p.lin_order = a.lin_order;
+    p.mean = a.mean; p.amp = a.amp; p.lin_coef = a.lin_coef; p.zeta = a.zeta; p.ybest = a.ybest;
+    for (int d = 0; d < APGP_MAX_DIM; ++d) { p.sc[d] = a.sc[d]; p.lw[d] = a.lw[d]; p.lo[d] = a.lo[d]; p.hi[d] = a.hi[d]; }
+    p.blk_list = NULL; p.blk_count = NULL; p.est = NULL;
+}
+
+// the bound pass over all blocks: coarse (fp32 kernel values; pure squared-exponential kernels only) or fp64
+template <int DPAD>
+static void launch_bound(const PruneArgs& p, hipStream_t s, bool coarse) {
+    const long long per_wg = (PR_THREADS / 64) * (coarse ? pr32_cpt(DPAD) : PR_CPT);
+    const dim3 grid((unsigned)((p.ncb + per_wg - 1) / per_wg));
+    if (coarse)
+        hipLaunchKernelGGL(prune_bound32_kernel<DPAD>, grid, dim3(PR_THREADS), 0, s, p);
+    else
+        hipLaunchKernelGGL((prune_bound_kernel<DPAD, false>), grid, dim3(PR_THREADS), 0, s, p);
+}
+
+// 1. bound over all blocks (coarse if the kernel allows)  2. seeds  3. sweep on the seeds -> tau  4. select: list A
+// (counts[3])  5. fp64 bound on list A, bmin = max of the two  6. select again: list B (counts[1]), written over list A
+// 7. sweep on list B.  With a LinearKernel term steps 5 and 6 fall away: list A is list B.
+// After a coarse stage the seeds are the blocks with the smallest b WITHOUT slack (PruneArgs::est): where the fp32 slack
+// exceeds the spread of the bounds (an ill-conditioned fit: sum |alpha| is huge against the spread of mu) the bounds
+// themselves order the blocks by little more than |t - c|, the seeds would be arbitrary and tau prune nothing.
 template <int DPAD>
 static int launch_pruned(const SweepArgs& a, hipStream_t s, bool solve, void* part) {
     const int rc = s2_prepare_device<DPAD>();
@@ -1495,17 +1767,24 @@ static int launch_pruned(const SweepArgs& a, hipStream_t s, bool solve, void* pa
     long long* list = (long long*)(bmin + ncb);
     long long* seeds = list + ncb;
     long long* counts = seeds + PR_SEED;
+    const bool coarse = a.lin_coef == 0.0;
     PruneArgs p;
-    p.T = a.T; p.xs = a.xs; p.mask = a.mask; p.bmin = bmin; p.part_u = a.part_u; p.part_i = a.part_i;
-    p.m = a.m; p.ncb = ncb; p.n = a.n;
-    p.ndim = a.ndim; p.kind = a.kind; p.has_box = a.has_box; p.lin_order = a.lin_order;
-    p.mean = a.mean; p.amp = a.amp; p.lin_coef = a.lin_coef; p.zeta = a.zeta; p.ybest = a.ybest;
-    for (int d = 0; d < APGP_MAX_DIM; ++d) { p.sc[d] = a.sc[d]; p.lw[d] = a.lw[d]; p.lo[d] = a.lo[d]; p.hi[d] = a.hi[d]; }
-    const long long per_wg = (PR_THREADS / 64) * PR_CPT;
-    hipLaunchKernelGGL(prune_bound_kernel<DPAD>, dim3((unsigned)((ncb + per_wg - 1) / per_wg)), dim3(PR_THREADS), 0, s, p);
-    hipLaunchKernelGGL(prune_seed_kernel, dim3(1), dim3(1024), 0, s, bmin, ncb, seeds, counts);
+    pr_fill_args(p, a, bmin, a.part_u, a.part_i);
+    if (coarse) p.est = (double*)(counts + 8);
+    launch_bound<DPAD>(p, s, coarse);
+    hipLaunchKernelGGL(prune_seed_kernel, dim3(1), dim3(1024), 0, s, coarse ? (const double*)p.est : (const double*)bmin, ncb,
+                       seeds, counts);
     launch_sweep_list<DPAD>(a, s, solve, seeds, counts, ncb < PR_SEED ? ncb : PR_SEED, PR_SEED);
-    hipLaunchKernelGGL(prune_select_kernel, dim3(1), dim3(1024), 0, s, bmin, ncb, seeds, counts, a.part_u, 0.0, list);
+    hipLaunchKernelGGL(prune_select_kernel, dim3(1), dim3(1024), 0, s, bmin, ncb, seeds, counts, a.part_u, 0.0, list,
+                       counts + 3);
+    if (coarse) {
+        p.blk_list = list; p.blk_count = counts + 3;
+        const long long per_wg = (PR_THREADS / 64) * PR_CPT;
+        hipLaunchKernelGGL((prune_bound_kernel<DPAD, true>), dim3((unsigned)((ncb + per_wg - 1) / per_wg)), dim3(PR_THREADS),
+                           0, s, p);
+        hipLaunchKernelGGL(prune_select_kernel, dim3(1), dim3(1024), 0, s, bmin, ncb, seeds, counts, a.part_u, 0.0, list,
+                           (long long*)NULL);
+    }
     launch_sweep_list<DPAD>(a, s, solve, list, counts + 1, ncb, S2_SPLIT_MAX);
     return 0;
 }
@@ -1513,11 +1792,12 @@ static int launch_pruned(const SweepArgs& a, hipStream_t s, bool solve, void* pa
 // Layout of the caller's scratch (doubles): [2 ncb arg-min partials | slots x ncache x SW_BCH
 // parked operands | 2 x S2_SPLIT_MAX x SW_CAND x nrb row-block shares of the split last round (s2_work_len up to
 // here) | pruned sweep: ncb block bounds bmin | ncb surviving block numbers | PR_SEED seed block numbers | 8 words:
-// seed count, survivor count, bit pattern of tau]
+// seed count, survivor count, bit pattern of tau, blocks the coarse bound kept (list A; list B is written over it) |
+// ncb block minima of the coarse stage's b without slack]
 extern "C" int64_t apgp_acquire_work_len(int64_t m, int64_t n) {
     if (m < 1 || n < 1) return 0;
     if (m > APGP_MAX_M || n > APGP_MAX_N) return -1;
-    return s2_work_len(m, n) + 2 * pr_ncb(m) + PR_SEED + 8;
+    return s2_work_len(m, n) + 3 * pr_ncb(m) + PR_SEED + 8;
 }
 
 static int acquire_impl(bool solve, const double* T, int64_t m, int64_t idx_offset, const double* packed_linv,
@@ -1605,6 +1885,51 @@ extern "C" int apgp_acquire(const double* T, int64_t m, int64_t idx_offset, cons
                             apgp_best_t* best, void* stream) {
     return acquire_impl(false, T, m, idx_offset, packed_linv, xs, n, kern, mean, kind, lo, hi, mask, zeta, ybest,
                         mu, var, u, part, best, stream);
+}
+
+// Test hooks of the pruned arg-min (include/apgp.h): one bound pass over all blocks into the caller's buffer, and the
+// seed step alone.
+extern "C" int apgp_prune_bounds(const double* T, int64_t m, const double* xs, int64_t n, const apgp_kernel_t* kern,
+                                 double mean, int32_t kind, const double* lo, const double* hi, const uint8_t* mask,
+                                 double zeta, double ybest, int coarse, double* bmin_out, void* stream) {
+    APGP_CHECK_ARG(T && xs && kern && bmin_out, "null pointer");
+    APGP_CHECK_ARG(m >= 1 && m <= APGP_MAX_M && n >= 1 && n <= APGP_MAX_N, "m >= 1 and n >= 1 required");
+    APGP_CHECK_ARG(kind >= APGP_UTIL_AGP && kind < APGP_UTIL_NONE, "unknown utility kind");
+    APGP_CHECK_ARG((lo == NULL) == (hi == NULL), "lo and hi must be given together");
+    KernConst kc;
+    APGP_CHECK_ARG(apgp_make_kernconst(kern, &kc) == 0, "kernel parameters");
+    APGP_CHECK_ARG(!coarse || kc.lin_coef == 0.0, "the coarse bound takes pure squared-exponential kernels only");
+    PruneArgs p;
+    p.T = T; p.xs = xs; p.mask = mask; p.bmin = bmin_out; p.part_u = NULL; p.part_i = NULL;
+    p.m = m; p.ncb = pr_ncb(m); p.n = n;
+    p.ndim = kc.ndim; p.kind = kind; p.has_box = lo != NULL; p.lin_order = kc.lin_order;
+    p.mean = mean; p.amp = kc.amp; p.lin_coef = kc.lin_coef; p.zeta = zeta; p.ybest = ybest;
+    for (int d = 0; d < APGP_MAX_DIM; ++d) {
+        p.sc[d] = kc.sc[d];
+        p.lw[d] = kc.lw[d];
+        p.lo[d] = (lo && d < kc.ndim) ? lo[d] : 0.0;
+        p.hi[d] = (hi && d < kc.ndim) ? hi[d] : 0.0;
+    }
+    p.blk_list = NULL; p.blk_count = NULL; p.est = NULL;
+    hipStream_t s = (hipStream_t)stream;
+    switch (kc.dpad) {
+        case 2: launch_bound<2>(p, s, coarse != 0); break;
+        case 4: launch_bound<4>(p, s, coarse != 0); break;
+        case 8: launch_bound<8>(p, s, coarse != 0); break;
+        case 16: launch_bound<16>(p, s, coarse != 0); break;
+        default: launch_bound<32>(p, s, coarse != 0); break;
+    }
+    APGP_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int apgp_sweep_prune_seeds(const double* bmin, int64_t ncb, int64_t* seeds, int64_t* counts, void* stream) {
+    APGP_CHECK_ARG(bmin && seeds && counts, "null pointer");
+    APGP_CHECK_ARG(ncb >= 1 && ncb <= APGP_MAX_M / SW_CAND, "ncb >= 1 required");
+    hipLaunchKernelGGL(prune_seed_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, bmin, (long long)ncb,
+                       (long long*)seeds, (long long*)counts);
+    APGP_CHECK_LAUNCH();
+    return 0;
 }
 
 // ---------------------------------------------------------------------------

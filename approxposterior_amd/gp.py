@@ -440,8 +440,8 @@ class GP(GeorgeExtras):
         # arg-min-only sweeps skip candidate blocks that cannot win (apgp_set_sweep_prune): None: the library's
         # process-wide setting (default on); False / 0: the full sweep; True / 1: on; >= 2: on from that many candidates
         self.sweep_prune = None
-        self.sweep_prune_stats = False    # True: keep (seed blocks, surviving blocks, bits of tau) of the last pruned sweep
-        self.last_prune_counts = None     # ... here, as a device int64[3] tensor (tools/sweep_prune_ab.py, the tests)
+        self.sweep_prune_stats = False    # True: keep (seed blocks, surviving blocks, bits of tau, blocks the coarse
+        self.last_prune_counts = None     # bound left) of the last pruned sweep here, as a device int64[4] tensor
         self._computed = False
         self._x = None
         self._yerr2 = 0.0
@@ -1271,7 +1271,7 @@ class GP(GeorgeExtras):
                     lib.apgp_set_sweep_prune(prune_was)
             if self.sweep_prune_stats and kind_id != _lib.UTIL_NONE and mu is None and var is None and u is None:
                 off = int(lib.apgp_sweep_prune_counts_offset(m, n))
-                self.last_prune_counts = part[off:off + 3].view(torch.int64).clone()
+                self.last_prune_counts = part[off:off + 4].view(torch.int64).clone()
             if ev is not None:
                 e1 = torch.cuda.Event(enable_timing=True)
                 e1.record()
@@ -1316,6 +1316,29 @@ class GP(GeorgeExtras):
         if not return_all:
             return _best_record(s.best)
         return _best_record(s.best) + (s.u.cpu().numpy(), s.mu.cpu().numpy(), s.var.cpu().numpy())
+
+    def prune_bounds(self, y, t, kind, coarse=True, bounds=None, mask=None, zeta=0.01):
+        """The bound pass of the pruned arg-min alone (``apgp_prune_bounds``; the tests): for every 64-row block of the
+        candidates ``t`` the smallest lower bound of a row's utility, +inf for a block without an admissible row --
+        ``coarse``: the single-precision stage, else the double-precision one.  Arguments as :meth:`acquire`'s."""
+        if not self.computed:
+            raise RuntimeError("ERROR: Need to compute GP before using it!")
+        kind_id = UTILITY_KINDS[str(kind).lower()]
+        torch, dev, lib = self._rt()
+        lo, hi = _box(bounds, self.kernel.ndim)
+        T = self._candidates(t)
+        m = T.shape[0]
+        mask_d = self._mask(mask, m)
+        y = self._check_dimensions(y)
+        ks = self._kernel_struct()
+        with self._on(torch, dev):
+            self._ensure_xs(y)
+            bmin = torch.empty((m + 63) // 64, dtype=torch.float64, device=dev)
+            _lib.check(lib.apgp_prune_bounds(T.data_ptr(), m, self._xs.data_ptr(), len(self._x), ctypes.byref(ks),
+                                             float(self.mean.value), kind_id, lo, hi, _ptr(mask_d), float(zeta),
+                                             float(np.max(y)), int(bool(coarse)), bmin.data_ptr(), self._stream(torch)),
+                       "apgp_prune_bounds")
+        return bmin.cpu().numpy()
 
     def nelder_mead_search(self, y, starts, kind, bounds=None, zeta=0.01, options=None, trace=False):
         """SciPy's Nelder-Mead (``bounds=None``) from every row of ``starts`` (R, D) at once on the device

@@ -346,8 +346,13 @@ int apgp_acquire_solve(const double* T, int64_t m, int64_t idx_offset,
  * apgp_set_sweep_prune(v): process-wide switch, returns the previous value.  0: always the full
  * sweep; 1 (default): pruned from a built-in candidate count on (16384 for n >= 4096, else 65536);
  * v >= 2: pruned whenever m >= v.
- * apgp_sweep_prune_counts_offset(m, n): index into `part` (in 8-byte words) of three int64 the last
- * pruned call left there: seed blocks, surviving blocks beyond the seeds, bit pattern of tau.
+ * For a pure squared-exponential kernel (lin_coef == 0) the bound is taken in two stages: a coarse one
+ * over all blocks whose kernel values are single precision (its slack covers their error), then the
+ * double-precision bound on the blocks the coarse one left at or below tau; with a LinearKernel term
+ * the double-precision bound alone.
+ * apgp_sweep_prune_counts_offset(m, n): index into `part` (in 8-byte words) of four int64 the last
+ * pruned call left there: seed blocks, surviving blocks beyond the seeds, bit pattern of tau, blocks
+ * beyond the seeds the coarse bound left (equal to the second without a coarse stage).
  * apgp_sweep_prune_select: the selection step alone, for tests -- tau planted by the caller.
  * bmin: ncb block bounds; seeds: 16 int64 block numbers of which the first counts[0] are read;
  * counts: int64[3], [0] read, [1] and [2] written (survivor count, bit pattern of tau); list: ncb
@@ -358,6 +363,17 @@ int apgp_get_sweep_prune(void);
 int64_t apgp_sweep_prune_counts_offset(int64_t m, int64_t n);
 int apgp_sweep_prune_select(const double* bmin, int64_t ncb, const int64_t* seeds, int64_t* counts,
                             double tau, int64_t* list, void* stream);
+/* Two more steps alone, for tests.  apgp_prune_bounds: one bound pass over all ceil(m / 64) blocks into
+ * bmin_out (device), arguments as apgp_acquire's; coarse != 0: the single-precision stage (refused
+ * with a LinearKernel term), 0: the double-precision bound.  apgp_sweep_prune_seeds: the seed step --
+ * seeds: 16 int64, receives the blocks with the smallest bmin below +inf, ascending by (value, block
+ * number); counts: int64[4], [0] = their number, [1] = [3] = 0.
+ * Added in ABI 8 without changing anything before it: APGP_ABI_VERSION stays 8.             */
+int apgp_prune_bounds(const double* T, int64_t m, const double* xs, int64_t n,
+                      const apgp_kernel_t* kern /*host*/, double mean, int32_t kind,
+                      const double* lo /*host*/, const double* hi /*host*/, const uint8_t* mask,
+                      double zeta, double ybest, int coarse, double* bmin_out, void* stream);
+int apgp_sweep_prune_seeds(const double* bmin, int64_t ncb, int64_t* seeds, int64_t* counts, void* stream);
 
 /* ---- fantasy update of a sweep (batch design points, kriging believer) -----------
  * After a sweep over T (mu, var = v_0 written) and picks x_1 .. x_j, conditioning the GP on

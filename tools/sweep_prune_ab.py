@@ -11,7 +11,7 @@ bound pass + seeds are pure overhead;  the crossover in m at N = 1152 and N = 40
     python tools/sweep_prune_ab.py [--pairs 10] [--out profiles/r07_sweep_prune_ab.json] [--legs c3,c2,c5,flat,cross]
 
 Prints one JSON document (and writes it to --out): per leg the medians, min / max, the ratio, the seed and surviving
-block counts and the winner of both legs (they must be equal, bit for bit -- the tool stops if they are not)."""
+block counts (and the blocks the coarse bound left) and the winner of both legs (they must be equal, bit for bit -- the tool stops if they are not)."""
 import argparse
 import json
 import os
@@ -55,6 +55,7 @@ def ab(gp, y, T, kind, box, pairs, warmup, on_value):
     off, on = stats(t[0]), stats(t[on_value])
     return {"off": off, "on": on, "on_over_off": on["median_ms"] / off["median_ms"],
             "blocks": (T.shape[0] + 63) // 64, "seed_blocks": int(c[0]), "surviving_blocks": int(c[1]),
+            "coarse_blocks": int(c[3]) if len(c) > 3 else None,
             "tau": float(c[2:3].view(np.float64)[0]), "best": [int(res[0][0]), float(res[0][1])]}
 
 
