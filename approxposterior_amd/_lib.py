@@ -109,6 +109,10 @@ SIGNATURES = {
     "apgp_nm_search": (ctypes.c_int, [_P, _I64, _P, _I64, _KP, _F64, _P, _I64, _P, _I64,
                                       ctypes.POINTER(_F64), ctypes.POINTER(_F64), ctypes.POINTER(NmOptions),
                                       _P, _P, _P, _P, _P, _P, _P]),
+    "apgp_predict_grad_work_len": (_I64, [_I64, _I64]),
+    "apgp_predict_grad": (ctypes.c_int, [_P, _I64, _P, _I64, _KP, _F64, _P, _I64, _P, _I64, _I32,
+                                         ctypes.POINTER(_F64), ctypes.POINTER(_F64), _F64, _F64,
+                                         _P, _P, _P, _P, _P, _P, _P, _P]),
     "apgp_predict_mean": (ctypes.c_int, [_P, _I64, _P, _I64, _KP, _F64, _P, _P]),
     "apgp_predict_mean_host": (ctypes.c_int, [_P, _I64, _P, _I64, _KP, _F64, _P, _P, _P]),
     "apgp_ensemble_sample": (ctypes.c_int, [_P, _I64, _KP, _F64, ctypes.POINTER(_F64), ctypes.POINTER(_F64),

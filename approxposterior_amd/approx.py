@@ -269,7 +269,7 @@ class ApproxPosterior(object):
         return self._lnprior if isinstance(self._lnprior, appriors.JointPrior) else None
 
     # ------------------------------------------------------- design-point selection
-    def _selectPoint(self, utility, theta0, nRestarts, method, options, nCandidates, polish):
+    def _selectPoint(self, utility, theta0, nRestarts, method, options, nCandidates, polish, searchJac=False):
         """One design point: the minimiser of ``utility`` over the prior.  Under a process group the
         ``nCandidates`` draw is ONE global matrix (same random state on every rank), each rank sweeps its
         contiguous rows and the winners meet in a 16-byte-per-rank all-gather; the Nelder-Mead search is
@@ -286,7 +286,7 @@ class ApproxPosterior(object):
             point, value = ut.minimizeObjective(utility, self.y, self.gp, sampleFn=self.priorSample,
                                                 priorFn=self._lnprior, nRestarts=nRestarts, method=method,
                                                 options=options, bounds=searchBounds, theta0=theta0,
-                                                args=scalarArgs, onDevice=self.deviceSearch)
+                                                args=scalarArgs, onDevice=self.deviceSearch, jac=searchJac)
             return self._agree(point, value) if ranks is not None else (point, value)
         total = int(nCandidates)
         kind = ut.utilityKind(utility) if (ranks is not None or self.deviceCandidates) else None
@@ -323,7 +323,7 @@ class ApproxPosterior(object):
                                                 sampleFn=self.priorSample, priorFn=self._lnprior,
                                                 nRestarts=1, method=method, options=options,
                                                 bounds=searchBounds, theta0=point, args=scalarArgs,
-                                                onDevice=self.deviceSearch)
+                                                onDevice=self.deviceSearch, jac=searchJac)
             if ranks is not None:
                 point, value = self._agree(point, value)
         return point, value
@@ -379,7 +379,7 @@ class ApproxPosterior(object):
                       runName="apRun", numNewPoints=1, optGPEveryN=1,
                       gpHyperPrior=gpUtils.defaultHyperPrior, args=None,
                       nCandidates=None, polish=False, deviceCandidates=None, batchSize=None, pool=None,
-                      deviceSearch=None, **kwargs):
+                      deviceSearch=None, searchJac=False, **kwargs):
         """Select ``numNewPoints`` design points by minimising the (negative) utility;
         with ``computeLnLike`` evaluate the forward model at each, absorb it into the
         training set / GP and re-fit the hyper-parameters every ``optGPEveryN`` points
@@ -410,6 +410,10 @@ class ApproxPosterior(object):
         ``lnprior.support()`` when ``lnprior`` is a :class:`~approxposterior_amd.priors.JointPrior` -- and +inf
         outside: it assumes the prior is that box or support.  The solutions are still checked with ``lnprior`` on
         the host.  Under a process group the search is replicated and rank 0's answer kept, as on the host.
+
+        ``searchJac=True`` (opt-in, with a gradient ``minObjMethod`` such as "l-bfgs-b"; not with ``deviceSearch``) gives
+        the host point search -- and ``polish`` -- the utility's exact gradient (``utility.minimizeObjective(jac=True)``,
+        :meth:`GP.predict_grad`) instead of SciPy's finite differences.
         """
         if batchSize is not None:
             if nCandidates is None:
@@ -448,7 +452,7 @@ class ApproxPosterior(object):
             if self.algorithm == "alternate":      # AGP, BAPE, AGP, ... (approx.py:656-661)
                 self.utility = (ut.AGPUtility, ut.BAPEUtility)[count % 2]
             point, _ = self._selectPoint(self.utility, theta0, nMinObjRestarts, minObjMethod,
-                                         minObjOptions, nCandidates, polish)
+                                         minObjOptions, nCandidates, polish, searchJac=searchJac)
             points.append(point)
             if not computeLnLike:
                 continue
@@ -685,7 +689,7 @@ class ApproxPosterior(object):
             gpHyperPrior=gpUtils.defaultHyperPrior, eps=1.0, convergenceCheck=False,
             minObjMethod="nelder-mead", minObjOptions=None, args=None,
             nCandidates=None, onDevice=False, batched=True, deviceCandidates=None, batchSize=None, pool=None,
-            deviceSearch=None, deviceAutocorr=False, **kwargs):
+            deviceSearch=None, deviceAutocorr=False, searchJac=False, **kwargs):
         """BAPE / AGP outer loop (approx.py:229-524): ``nmax`` times, find ``m`` design
         points (re-fitting the GP every ``optGPEveryN``), sample the surrogate posterior,
         record burn-in / thinning, and -- with ``convergenceCheck`` -- stop once the
@@ -696,7 +700,8 @@ class ApproxPosterior(object):
         (``deviceCandidates``: drawn on the device, see :meth:`findNextPoint`);
         ``onDevice`` / ``batched`` are passed to :meth:`runMCMC`; ``batchSize`` / ``pool`` to
         :meth:`findNextPoint` (design points chosen and their forward models run in batches), and ``deviceSearch``
-        (the Nelder-Mead point search on the device).  ``deviceAutocorr`` is passed to :meth:`runMCMC` too (burn-in and
+        (the Nelder-Mead point search on the device) and ``searchJac`` (exact gradients for a gradient
+        ``minObjMethod``).  ``deviceAutocorr`` is passed to :meth:`runMCMC` too (burn-in and
         thinning from the device's autocorrelation estimate; needs ``onDevice=True``)."""
         if deviceAutocorr and not onDevice:
             raise ValueError("run(deviceAutocorr=True) needs onDevice=True")
@@ -728,7 +733,7 @@ class ApproxPosterior(object):
                                minObjMethod=minObjMethod, minObjOptions=minObjOptions,
                                runName=runName, theta0=None, args=args, verbose=verbose,
                                nCandidates=nCandidates, deviceCandidates=deviceCandidates, batchSize=batchSize,
-                               pool=pool, deviceSearch=deviceSearch, **fit, **kwargs)
+                               pool=pool, deviceSearch=deviceSearch, searchJac=searchJac, **fit, **kwargs)
             if timing:
                 self.trainingTime.append(time.time() - clock)
             if cache:
@@ -762,12 +767,14 @@ class ApproxPosterior(object):
                 break
 
     # ----------------------------------------------------------------------------- MAP
-    def findMAP(self, theta0=None, method="nelder-mead", options=None, nRestarts=15, deviceSearch=None):
+    def findMAP(self, theta0=None, method="nelder-mead", options=None, nRestarts=15, deviceSearch=None,
+                searchJac=False):
         """Maximum of the function the GP has learned: minimise minus the GP mean from
         ``nRestarts`` starts around ``theta0`` (default: the best training point)
         (approx.py:862-926).  Returns ``(MAP, MAPVal)``.
         ``deviceSearch`` (default: the object's ``deviceSearch``) runs the restarts on the device
-        over -mu, gated by ``bounds`` or the JointPrior's support (see :meth:`findNextPoint`)."""
+        over -mu, gated by ``bounds`` or the JointPrior's support (see :meth:`findNextPoint`).
+        ``searchJac=True`` (with a gradient ``method``) gives the host search the exact gradient of -mu."""
         if theta0 is None:
             start = self.theta[np.argmax(self.y)]
         else:
@@ -790,7 +797,7 @@ class ApproxPosterior(object):
         best, value = ut.minimizeObjective(minusMean, self.y, self.gp, self.priorSample,
                                            self._lnprior, nRestarts=nRestarts, args=None,
                                            method=method, options=options, bounds=bounds,
-                                           theta0=start, onDevice=onDevice)
+                                           theta0=start, onDevice=onDevice, jac=searchJac)
         if self._ranks() is not None:
             best, value = self._agree(best, value)
         return best, -value
@@ -801,13 +808,15 @@ class ApproxPosterior(object):
                  gpOptions=None, gpP0=None, optGPEveryN=1, nGPRestarts=1,
                  nMinObjRestarts=5, initGPOpt=True, minObjMethod="nelder-mead",
                  gpHyperPrior=gpUtils.defaultHyperPrior, minObjOptions=None,
-                 findMAP=True, args=None, nCandidates=None, deviceCandidates=None, deviceSearch=None, **kwargs):
+                 findMAP=True, args=None, nCandidates=None, deviceCandidates=None, deviceSearch=None,
+                 searchJac=False, **kwargs):
         """Bayesian optimisation (approx.py:929-1151): one design point per iteration by
         the object's utility (use algorithm="jones"), optionally the MAP of the GP mean
         after each, stop after ``kmax`` consecutive iterations whose best value changed
         by less than ``tol``.  Returns the reference's solution dictionary (thetaBest,
         valBest, thetas, vals, nev [, thetasMAP, valsMAP, thetaMAPBest, valMAPBest]).
-        ``deviceSearch`` runs the point searches and the MAP searches on the device (see :meth:`findNextPoint`)."""
+        ``deviceSearch`` runs the point searches and the MAP searches on the device (see :meth:`findNextPoint`);
+        ``searchJac`` gives both host searches exact gradients (with a gradient ``minObjMethod``)."""
         verbose, cache = verbose and self._chief(), cache and self._chief()
         if cache:
             np.savez(_cacheName(runName, "APFModelCache"), theta=self.theta, y=self.y)
@@ -830,7 +839,7 @@ class ApproxPosterior(object):
                                               minObjMethod=minObjMethod, minObjOptions=minObjOptions,
                                               runName=runName, args=args, verbose=verbose,
                                               nCandidates=nCandidates, deviceCandidates=deviceCandidates,
-                                              deviceSearch=deviceSearch, **fit, **kwargs)
+                                              deviceSearch=deviceSearch, searchJac=searchJac, **fit, **kwargs)
             evaluations = iteration + 1
             if verbose:
                 print("Forward model evaluation at: ", point, ", function value: ", value)
@@ -842,7 +851,8 @@ class ApproxPosterior(object):
             history["vals"].append(self.y[top])
             if findMAP:
                 mapPoint, mapValue = self.findMAP(theta0=theta0, method=minObjMethod,
-                                                  options=minObjOptions, nRestarts=nMinObjRestarts)
+                                                  options=minObjOptions, nRestarts=nMinObjRestarts,
+                                                  searchJac=searchJac)
                 if verbose:
                     print("Current MAP solution: ", mapPoint, mapValue)
                 history["thetasMAP"].append(mapPoint)

@@ -451,12 +451,13 @@ class GP(GeorgeExtras):
         self._x_d = None              # device copy of the training set
         self._mean_work = None        # scratch of the small predictions and of the evaluations: survives refits
         self._p1_work = None
+        self._pg_work = None
         self._nll_scratch = None
         self._nll_stream = None       # the stream the private buffers of the last _nll evaluation were made on
         self._batch = None            # nll_batch's _BatchWork
         # The previous call's argument list of the hot loops, ready for the next (_Replay): "nll" (the optimiser's
-        # evaluations), "one" (a candidate with variance), "mean" (a few points, mean only) belong to the factor and
-        # go with it; ("batch", B) belongs to self._batch and goes with that.
+        # evaluations), "one" (a candidate with variance), "mean" (a few points, mean only), "pgrad" (a point with its
+        # gradients) belong to the factor and go with it; ("batch", B) belongs to self._batch and goes with that.
         self._replays = {}
         self._reset_device_state()
 
@@ -477,7 +478,7 @@ class GP(GeorgeExtras):
         self._work = None         # trtri work (dense L^-1 in first panel)
         self._xs = None           # packed training stream (depends on alpha)
         self._xs_key = None
-        for key in ("nll", "one", "mean"):
+        for key in ("nll", "one", "mean", "pgrad"):
             self._replays.pop(key, None)
         self.cond_estimate = None
         self.log_determinant = None
@@ -1229,6 +1230,98 @@ class GP(GeorgeExtras):
             self._replays["one"] = _Replay(lib.apgp_predict1_host, args, dev.index, st.value or 0, y,
                                            (self._xs, self._p1_work, factor), self._queries, data=(o2, (1, ks.ndim)))
         return np.array([o2[0]]), np.array([o2[1]])
+
+    # -- predictive gradients (apgp_predict_grad) -----------------------------------------------
+    def predict_grad(self, y, t, kind=None, bounds=None, zeta=0.01, return_device=False):
+        """mu, sigma^2 and their gradients with respect to the query point, at every row of ``t`` ((M, D) or one point
+        (D,); host array or device tensor as in :meth:`acquire`), by ``apgp_predict_grad``: dmu = J^T alpha,
+        dvar = d k(t,t)/dt - 2 J^T K^-1 k with J_nd = d k(t, x_n)/d t_d, K^-1 k through the dense inverse or, above the
+        conditioning gate, by a forward and a backward substitution against the factor (``variance_mode`` forces one).
+
+        ``kind=None``: returns ``(mu (M,), var (M,), dmu (M, D), dvar (M, D))``.  ``kind`` "agp" / "bape" / "jones"
+        (with ``zeta`` and max(y)) / "negmean": returns ``(u (M,), du (M, D), mu, var)``, du by the chain rule through the
+        utility's derivatives.  ``bounds``: the box prior; a row outside it or with a non-finite coordinate has
+        mu = var = dmu = dvar = NaN, u = +inf, du = 0.  Where a utility leaves its smooth branch (BAPE with var <= 0,
+        Jones with a standard deviation not > 0) du = 0.  NumPy arrays, or with ``return_device`` device tensors
+        (stream-ordered on the current stream)."""
+        if not self.computed:
+            raise RuntimeError("ERROR: Need to compute GP before using it!")
+        if kind is None:
+            kid = _lib.UTIL_NONE
+        else:
+            try:
+                kid = SEARCH_KINDS[str(kind).lower()]
+            except KeyError:
+                raise ValueError("kind must be None or one of %s" % sorted(SEARCH_KINDS))
+        D = self.kernel.ndim
+        bkey = None if bounds is None else np.asarray(bounds, dtype=np.float64).tobytes()
+        host_point = (type(t) is np.ndarray and t.dtype == _F64 and t.size == D and t.ndim in (1, 2)
+                      and t.flags.c_contiguous and not return_device)
+        if host_point:
+            # the optimiser's next evaluation: the previous call's arguments, buffers and checks with a new point
+            r = self._replays.get("pgrad")
+            if (r is not None and r.data[0] == (kid, bkey, float(zeta), self.mean.value)
+                    and r.fits(y, (self._xs, self._pg_work, self._work if self._trust_inverse() else self._L))):
+                _, torch, T_d, out = r.data
+                T_d.copy_(torch.from_numpy(t.reshape(1, D)))
+                _lib.check(r.fn(*r.args), "apgp_predict_grad")
+                return self._pgrad_split(out.cpu().numpy(), 1, D, kid)
+        torch, dev, lib = self._rt()
+        lo, hi = _box(bounds, D)
+        if hasattr(t, "data_ptr"):
+            T = self._candidates(t)
+        else:
+            arr = np.asarray(t, dtype=np.float64)
+            if arr.ndim == 1:
+                if arr.size != D:
+                    raise ValueError("Dimension mismatch")
+                arr = arr.reshape(1, D)
+            if arr.ndim != 2 or arr.shape[1] != D:
+                raise ValueError("Dimension mismatch")
+            T = None
+        y = self._check_dimensions(y)
+        n = len(self._x)
+        m = int(T.shape[0] if T is not None else arr.shape[0])
+        ks = self._kernel_struct()
+        use_solve = not self._trust_inverse()
+        with self._on(torch, dev):
+            st = self._stream(torch)
+            if T is None:
+                T = torch.from_numpy(np.ascontiguousarray(arr)).to(dev)
+            out = torch.empty(m * (3 + 3 * D), dtype=torch.float64, device=dev)
+            if m == 0:
+                res = self._pgrad_split(out, 0, D, kid)
+                return res if return_device else tuple(o.cpu().numpy() for o in res)
+            if not use_solve:
+                self._ensure_linv()     # first: with W resident alpha is two matrix-vector products
+            self._ensure_xs(y)
+            need = int(lib.apgp_predict_grad_work_len(m, n))
+            if self._pg_work is None or self._pg_work.numel() < need:
+                self._pg_work = torch.empty(need, dtype=torch.float64, device=dev)
+            inv, factor = self._variance_operand(use_solve)
+            p0 = out.data_ptr()
+            with_u = kid != _lib.UTIL_NONE
+            args = [T.data_ptr(), m, self._xs.data_ptr(), n, ctypes.byref(ks), float(self.mean.value), *inv, kid,
+                    lo, hi, float(zeta), float(np.max(y)),
+                    p0, p0 + 8 * m, p0 + 16 * m if with_u else None, p0 + 24 * m, p0 + 8 * m * (3 + D),
+                    p0 + 8 * m * (3 + 2 * D) if with_u else None, self._pg_work.data_ptr(), st]
+            _lib.check(lib.apgp_predict_grad(*args), "apgp_predict_grad")
+            if host_point:
+                self._replays["pgrad"] = _Replay(
+                    lib.apgp_predict_grad, args, dev.index, st.value or 0, y, (self._xs, self._pg_work, factor),
+                    self._queries, data=((kid, bkey, float(zeta), self.mean.value), torch, T, out))
+            if return_device:
+                return self._pgrad_split(out, m, D, kid)
+            return self._pgrad_split(out.cpu().numpy(), m, D, kid)
+
+    @staticmethod
+    def _pgrad_split(out, m, D, kid):
+        """The results of :meth:`predict_grad` from its packed output buffer (mu | var | u | dmu | dvar | du)."""
+        mu, var, u = out[:m], out[m:2 * m], out[2 * m:3 * m]
+        dmu, dvar, du = (out[m * (3 + j * D):m * (3 + (j + 1) * D)].reshape(m, D) for j in range(3))
+        if kid == _lib.UTIL_NONE:
+            return mu, var, dmu, dvar
+        return u, du, mu, var
 
     def _sweep(self, y, T, kind_id, lo=None, hi=None, mask_d=None, zeta=0.01, idx_offset=0,
                with_mu=False, with_var=False, with_u=False):

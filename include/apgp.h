@@ -468,6 +468,38 @@ int apgp_nm_search(const double* starts, int64_t restarts, const double* xs, int
                    double* x_out, double* f_out, int32_t* stats, double* trace, int32_t* steps,
                    double* work, void* stream);
 
+/* ---- predictive gradients: mu, sigma^2, a utility and their derivatives in t ---------
+ * For each of the m rows t of T (device, m x ndim), with the kernel of apgp_kernel_t exactly as defined above
+ * (the linear term included):
+ *   k_n = k(t, x_n)                         J_nd   = d k(t, x_n) / d t_d
+ *   mu  = k.alpha + mean                    dmu_d  = sum_n alpha_n J_nd
+ *   v   = L^-1 k,  w = L^-T v (= K^-1 k)
+ *   var = k(t,t) - |v|^2                    dvar_d = d k(t,t) / d t_d - 2 sum_n w_n J_nd
+ *   u   = utility(kind)(mu, var)            du_d   = (du/dmu) dmu_d + (du/dvar) dvar_d
+ * d k(t,t) / d t_d is zero for the pure squared-exponential kernel and lin_coef 2 P t_d^(2P-1) with a linear term.
+ * kind (csrc/util_grad.h): AGP du/dmu = -1, du/dvar = -1 / (2 var); BAPE -2, -(2 + 1 / expm1(var)); JONES -Phi(z),
+ * -phi(z) / (2 sd) (zeta, ybest as apgp_acquire); APGP_UTIL_NEG_MEAN -1, 0; APGP_UTIL_NONE: u and du are not written.
+ * Variance route as apgp_predict1_host / apgp_nm_search: winv / ldw (the dense L^-1 of apgp_trtri_pack, 16-byte
+ * aligned, ldw even) -> v = W k, w = W^T v, two passes over W per block of 8 points; or winv = NULL and L / ldl -> a
+ * forward and a backward substitution against the factor, a workgroup per block of 4 points (use it above the
+ * conditioning gate).  xs: the packed training stream (with alpha).
+ * Outputs (device, each may be NULL): mu, var, u (m); dmu, dvar, du (m x ndim, row-major).
+ * A row with a non-finite coordinate or outside [lo, hi] (host arrays, NULL = no box): mu = var = dmu = dvar = NaN,
+ * u = +inf, du = 0.  BAPE with var <= 0: u = +inf, du = 0.  JONES with sd not > 0: u = 0, du = 0.  NEG_MEAN with a
+ * non-finite mu: u = +inf, du = 0.  AGP with var < 0: u and du NaN, as NumPy would give.
+ * work: apgp_predict_grad_work_len(m, n) doubles (device, 16-byte aligned); the call works through the rows in chunks
+ * of what that holds.  0 <= m <= APGP_MAX_M (2^40), 1 <= n <= 2^24, 1 <= ndim <= APGP_MAX_DIM; the *_len function
+ * returns -1 outside them (and for m = 0).  No atomics and a fixed order in every sum: the same input gives the same
+ * bits, and a row's results do not depend on the other rows of the call.
+ * Added in ABI 8 without changing anything before it: APGP_ABI_VERSION stays 8.                                   */
+int64_t apgp_predict_grad_work_len(int64_t m, int64_t n);
+int apgp_predict_grad(const double* T, int64_t m, const double* xs, int64_t n,
+                      const apgp_kernel_t* kern /*host*/, double mean,
+                      const double* winv, int64_t ldw, const double* L, int64_t ldl,
+                      int32_t kind, const double* lo /*host*/, const double* hi /*host*/, double zeta, double ybest,
+                      double* mu, double* var, double* u, double* dmu, double* dvar, double* du,
+                      double* work, void* stream);
+
 /* ---- mean-only prediction (the batched ApproxPosterior._gpll path) --------
  * mu_i = k(t_i,X).alpha + mean for m candidates (approx.py:178-180).         */
 int apgp_predict_mean(const double* T, int64_t m, const double* xs, int64_t n,
