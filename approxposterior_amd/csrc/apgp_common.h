@@ -47,6 +47,11 @@ static inline int64_t apgp_round_up(int64_t n, int64_t b) { return (n + b - 1) /
 //   k(x,x') = amp * exp(-sum_d (xs_d - xs'_d)^2),  xs = x * sqrt(inv_metric/2)
 // and, when lin_coef != 0, the linear-regression term in the same scaled coordinates:
 //   k_lin(x,x') = lin_coef * sum_d (xs_d xs'_d lw_d)^P,  lw_d = 1 / sc_d^2
+// What holds, and what tests/test_gpu_kvalue.py asserts: the Gram kernel, the cross kernel (both through
+// apgp_gram_value, contraction off) and the k* of predict_mean_kernel give the same bits for the pure
+// squared-exponential kernel; the Gram and cross kernels also with a linear term.  The mean and sweep kernels are
+// compiled with hipcc's default -ffp-contract=fast, which may fuse APGP_LIN_SUM's `q_ *= p_; acc += q_`: with a
+// linear term their k* agrees with the Gram value to the rounding budget of tests/kvalue_ref.py, not to the bit.
 struct KernConst {
     double sc[APGP_MAX_DIM];
     double lw[APGP_MAX_DIM];

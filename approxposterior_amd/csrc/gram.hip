@@ -149,9 +149,12 @@ extern "C" int apgp_gram(const double* X, int64_t n, const apgp_kernel_t* kern, 
 
 
 // ---------------------------------------------------------------------------
-// Cross kernel matrix  C_ij = amp * exp(-|xs1_i - xs2_j|^2)  (no diagonal term):
+// Cross kernel matrix  C_ij = amp * exp(-|xs1_i - xs2_j|^2) [+ linear term]  (no diagonal term):
 // george ``kernel.get_value(x1, x2)``.  Used by the incremental factor update
 // (new training rows against the old ones).  One thread per output element.
+// The value is apgp_gram_value's on coordinates scaled as gram_body scales them (x * sc rounded on its own: written
+// as one expression, x1 * sc - x2 * sc contracts to fma(x1, sc, -(x2 * sc))), so that a row appended to a factor has
+// the bits the Gram kernel would have given it -- tests/test_gpu_kvalue.py holds both to the same restatement.
 // ---------------------------------------------------------------------------
 struct CrossArgs {
     const double* X1;
@@ -161,30 +164,22 @@ struct CrossArgs {
     KernConst kc;
 };
 
+template <int DPAD>
 __global__ __launch_bounds__(256) void kernel_cross_kernel(CrossArgs a) {
+#pragma clang fp contract(off)
     __shared__ double etab[APGP_EXP_TAB_N];
     apgp_exp_tab_load(etab);
     __syncthreads();
     const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
     if (e >= a.m * a.n) return;
     const long long i = e / a.n, j = e % a.n;
-    double s = 0.0, s3 = 0.0;
-    for (int d = 0; d < a.kc.dpad; d += 2) {
-        double df0 = 0.0, df1 = 0.0;
-        if (d < a.kc.ndim) df0 = a.X1[i * a.kc.ndim + d] * a.kc.sc[d] - a.X2[j * a.kc.ndim + d] * a.kc.sc[d];
-        if (d + 1 < a.kc.ndim)
-            df1 = a.X1[i * a.kc.ndim + d + 1] * a.kc.sc[d + 1] - a.X2[j * a.kc.ndim + d + 1] * a.kc.sc[d + 1];
-        s = fma(df0, df0, s);
-        s3 = fma(df1, df1, s3);
+    double xi[DPAD], xc[DPAD];
+#pragma unroll
+    for (int d = 0; d < DPAD; ++d) {
+        xi[d] = d < a.kc.ndim ? a.X1[i * a.kc.ndim + d] * a.kc.sc[d] : 0.0;
+        xc[d] = d < a.kc.ndim ? a.X2[j * a.kc.ndim + d] * a.kc.sc[d] : 0.0;
     }
-    double k = a.kc.amp * apgp_exp(-(s + s3), etab);
-    if (a.kc.lin_coef != 0.0) {
-        double ls;
-        APGP_LIN_SUM(ls, a.kc.ndim, a.kc.ndim, a.kc.lin_order,
-                     a.X1[i * a.kc.ndim + d_] * a.X2[j * a.kc.ndim + d_]);
-        k = fma(a.kc.lin_coef, ls, k);
-    }
-    a.C[i * a.ldc + j] = k;
+    a.C[i * a.ldc + j] = apgp_gram_value<DPAD>(xi, xc, a.kc, false, etab);
 }
 
 extern "C" int apgp_kernel_cross(const double* X1, int64_t m, const double* X2, int64_t n,
@@ -194,8 +189,15 @@ extern "C" int apgp_kernel_cross(const double* X1, int64_t m, const double* X2, 
     CrossArgs a;
     APGP_CHECK_ARG(apgp_make_kernconst(kern, &a.kc) == 0, "kernel parameters");
     a.X1 = X1; a.X2 = X2; a.C = C; a.m = m; a.n = n; a.ldc = ldc;
-    hipLaunchKernelGGL(kernel_cross_kernel, dim3((unsigned)((m * n + 255) / 256)), dim3(256), 0,
-                       (hipStream_t)stream, a);
+    dim3 grid((unsigned)((m * n + 255) / 256)), block(256);
+    hipStream_t s = (hipStream_t)stream;
+    switch (a.kc.dpad) {
+        case 2: hipLaunchKernelGGL(kernel_cross_kernel<2>, grid, block, 0, s, a); break;
+        case 4: hipLaunchKernelGGL(kernel_cross_kernel<4>, grid, block, 0, s, a); break;
+        case 8: hipLaunchKernelGGL(kernel_cross_kernel<8>, grid, block, 0, s, a); break;
+        case 16: hipLaunchKernelGGL(kernel_cross_kernel<16>, grid, block, 0, s, a); break;
+        default: hipLaunchKernelGGL(kernel_cross_kernel<32>, grid, block, 0, s, a); break;
+    }
     APGP_CHECK_LAUNCH();
     return 0;
 }

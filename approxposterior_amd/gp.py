@@ -597,6 +597,10 @@ class GP(GeorgeExtras):
         if x.shape[1] > _lib.MAX_DIM:
             raise ValueError("approxposterior_amd supports at most %d input dimensions (APGP_MAX_DIM in include/apgp.h: the "
                              "kernels keep a point's coordinates in registers); got %d" % (_lib.MAX_DIM, x.shape[1]))
+        if not np.isfinite(x).all():
+            # george: scipy's cholesky refuses the NaN Gram matrix a non-finite coordinate gives (ValueError).  Here the
+            # kernels' exp clamps its argument, NaN included, to -700: K would come out finite and factorise
+            raise ValueError("array must not contain infs or NaNs")
         if x is x_in or (isinstance(x_in, np.ndarray) and np.shares_memory(x, x_in)):
             x = x.copy()              # the object owns its training set: a caller who edits x in place afterwards is not seen
         same_x = self._x is not None and self._x.shape == x.shape and np.array_equal(self._x, x)

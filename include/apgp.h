@@ -92,14 +92,21 @@ int64_t apgp_trtri_work_len(int64_t n);
  * N x N matrix K (leading dimension ldk >= N), diagonal included; nothing above the
  * diagonal is touched (allocate K zeroed if a dense lower-triangular array is wanted):
  * apgp_potrf, the only consumer, reads the lower triangle only, and half the HBM writes
- * is half the kernel's time.                                                          */
+ * is half the kernel's time.
+ * Domain: finite coordinates; a non-finite one is not detected.  The kernels' exp clamps its
+ * argument to [-700, 700] and the clamp maps NaN to -700, so a NaN or infinite coordinate
+ * yields finite entries (~amp * 1e-304) where george yields NaN: the caller checks X
+ * (GP.compute does, and raises as george does).                                        */
 int apgp_gram(const double* X, int64_t n, const apgp_kernel_t* kern /*host*/,
               double* K, int64_t ldk, void* stream);
 
 /* ---- cross kernel matrix ------------------------------------------------------
  * C (m x n, ld ldc) = k(X1_i, X2_j) without the diagonal term: george
  * ``kernel.get_value(x1, x2)``.  Feeds the incremental factor update when
- * ApproxPosterior.findNextPoint appends a design point (approx.py:693-717).     */
+ * ApproxPosterior.findNextPoint appends a design point (approx.py:693-717).
+ * C_ij has the bits apgp_gram gives K_ij for the same two points (off the diagonal),
+ * linear term included.  Domain as apgp_gram: finite coordinates; a non-finite one is
+ * not detected.                                                                   */
 int apgp_kernel_cross(const double* X1, int64_t m, const double* X2, int64_t n,
                       const apgp_kernel_t* kern /*host*/, double* C, int64_t ldc, void* stream);
 
