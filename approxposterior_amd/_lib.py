@@ -49,6 +49,14 @@ class NmOptions(ctypes.Structure):
                 ("chi", ctypes.c_double), ("psi", ctypes.c_double), ("sigma", ctypes.c_double)]
 
 
+class EnsMove(ctypes.Structure):
+    """``apgp_ens_move_t``: one entry of the ensemble sampler's move table."""
+    _fields_ = [("kind", ctypes.c_int32), ("weight", ctypes.c_double), ("p0", ctypes.c_double), ("p1", ctypes.c_double)]
+
+
+ENS_MOVE_STRETCH, ENS_MOVE_DE, ENS_MOVE_SNOOKER = 0, 1, 2
+ENS_MAX_MOVES = 8     # APGP_ENS_MAX_MOVES
+
 _P = ctypes.c_void_p
 _I64 = ctypes.c_int64
 _I32 = ctypes.c_int32
@@ -119,6 +127,9 @@ SIGNATURES = {
                                             _I32, _I32, _I64, _F64, ctypes.c_uint64, _P, _P, _P, _P, _P, _P]),
     "apgp_ensemble_sample_ex": (ctypes.c_int, [_P, _I64, _KP, _F64, ctypes.POINTER(_F64), ctypes.POINTER(_F64),
                                                _I32, _I32, _I64, _F64, ctypes.c_uint64, _P, _P, _P, _P, _P, ctypes.c_int, _P]),
+    "apgp_ensemble_sample_moves": (ctypes.c_int, [_P, _I64, _KP, _F64, ctypes.POINTER(_F64), ctypes.POINTER(_F64),
+                                                  _I32, _I32, _I64, _F64, ctypes.c_uint64, _P, _P, _P, _P, _P, ctypes.c_int,
+                                                  ctypes.POINTER(EnsMove), _I32, _P]),
     "apgp_ensemble_mode": (ctypes.c_int, [ctypes.c_int]),
     "apgp_box_candidates": (ctypes.c_int, [_P, _I64, _I32, ctypes.POINTER(_F64), ctypes.POINTER(_F64), ctypes.c_uint64,
                                            _I64, _P]),

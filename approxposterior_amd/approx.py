@@ -582,6 +582,8 @@ class ApproxPosterior(object):
                 args=None, batched=True, onDevice=False, deviceAutocorr=False, **kwargs):
         """Sample the GP-surrogate posterior with the stretch-move ensemble sampler and
         estimate burn-in / thinning (approx.py:757-859): ``(sampler, iburn, ithin)``.
+        ``samplerKwargs["moves"]`` (``mcmc.moves.DEMove()``, ``DESnookerMove()``, weighted lists, as emcee's ``moves``)
+        replaces the stretch move on the host sampler and on the device sampler alike.
 
         ``batched`` (default) evaluates each half-ensemble with ONE mean-only GP launch
         (:meth:`_gpllBatch`); ``batched=False`` calls :meth:`_gpll` once per walker as
@@ -636,7 +638,7 @@ class ApproxPosterior(object):
                     # (iburn, ithin), on every rank without a collective
                     import torch
                     result["chain_device"] = torch.from_numpy(chain).to(kept[0].device)
-            self.sampler = emcee.DeviceChain(result, a=samplerKwargs.get("a", 2.0))
+            self.sampler = emcee.DeviceChain(result, a=samplerKwargs.get("a", 2.0), moves=samplerKwargs.get("moves"))
         else:
             self.sampler = self._hostSampler(samplerKwargs, args, kwargs, batched)
             for _ in self.sampler.sample(**mcmcKwargs):
@@ -667,6 +669,8 @@ class ApproxPosterior(object):
             extra = {} if joint is None else {"prior": joint}
             if keep is not None:
                 extra["keep_device"] = True
+            if samplerKwargs.get("moves") is not None:
+                extra["moves"] = samplerKwargs["moves"]
             res = self.gp.sample_ensemble(self.y, mcmcKwargs["initial_state"], mcmcKwargs["iterations"],
                                           self.bounds, a=samplerKwargs.get("a", 2.0), seed=seed, **extra)
             if keep is not None:

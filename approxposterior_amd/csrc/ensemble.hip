@@ -20,6 +20,7 @@
 // whose log-density prior_lnprior_kernel below computes over the stored chain.
 #include "apgp_common.h"
 #include "scratch.h"
+#include "ens_moves.h"
 #include <atomic>
 #include <mutex>
 
@@ -33,36 +34,15 @@ struct EnsArgs {
     long long n, iterations;
     int ndim, nwalkers, lin_order;
     unsigned long long seed;
-    double mean, amp, a_stretch, lin_coef;
+    double mean, amp, lin_coef;
+    EnsMoves mv;           // the move table; ens_propose (ens_moves.h) forms the proposals
     double sc[APGP_MAX_DIM], lo[APGP_MAX_DIM], hi[APGP_MAX_DIM], lw[APGP_MAX_DIM];
 };
-
-__device__ __forceinline__ void philox4x32(unsigned int (&c)[4], unsigned int k0, unsigned int k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const unsigned long long p0 = (unsigned long long)0xD2511F53u * c[0];
-        const unsigned long long p1 = (unsigned long long)0xCD9E8D57u * c[2];
-        const unsigned int n0 = (unsigned int)(p1 >> 32) ^ c[1] ^ k0;
-        const unsigned int n1 = (unsigned int)p1;
-        const unsigned int n2 = (unsigned int)(p0 >> 32) ^ c[3] ^ k1;
-        const unsigned int n3 = (unsigned int)p0;
-        c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-}
-
-__device__ __forceinline__ double u01(unsigned int a, unsigned int b) {
-    // 53-bit uniform in (0, 1)
-    return ((double)(a >> 5) * 67108864.0 + (double)(b >> 6) + 0.5) * (1.0 / 9007199254740992.0);
-}
-
-#define ENS_MAXW 256
 
 // XLDS: the packed training stream (Npad x (DPAD+2) doubles) is staged into LDS once
 // (it is re-read by every walker of every half-step); falls back to L2 when it does
 // not fit beside the sampler state.
-template <int DPAD, bool XLDS>
+template <int DPAD, bool XLDS, bool ALLMOVES>
 __global__ __launch_bounds__(1024) void ensemble_kernel(EnsArgs a) {
     constexpr int XS = DPAD + 2;
     extern __shared__ __attribute__((aligned(16))) double xsl[];
@@ -71,7 +51,7 @@ __global__ __launch_bounds__(1024) void ensemble_kernel(EnsArgs a) {
     __shared__ double lp[ENS_MAXW];
     __shared__ double qs[ENS_MAXW / 2][DPAD];  // scaled proposals of the active half
     __shared__ double lpq[ENS_MAXW / 2];
-    __shared__ double fac[ENS_MAXW / 2];       // (D-1) log z
+    __shared__ double fac[ENS_MAXW / 2];       // log proposal factor of the move
     __shared__ double uacc[ENS_MAXW / 2];
     __shared__ int qok[ENS_MAXW / 2];
     __shared__ int nacc[ENS_MAXW];
@@ -168,36 +148,26 @@ __global__ __launch_bounds__(1024) void ensemble_kernel(EnsArgs a) {
     __syncthreads();
 
     const unsigned int k0 = (unsigned int)a.seed, k1 = (unsigned int)(a.seed >> 32) ^ (unsigned int)(ens * 0x9E3779B9u);
+    // the move of a one-entry table (the default) is read once, not per iteration
+    const bool mixed = a.mv.n > 1;
+    int mkind = a.mv.kind[0];
+    double mp0 = a.mv.p0[0], mp1 = a.mv.p1[0];
     for (long long it = 0; it < a.iterations; ++it) {
         // random cyclic offset of the red/blue partition for this iteration
         unsigned int cr[4] = {(unsigned int)it, (unsigned int)(it >> 32), 0xFFFFFFFFu, 0x5u};
         philox4x32(cr, k0, k1);
         const int rot = (int)(cr[0] % (unsigned int)W);
+        if (mixed) {                                            // the iteration's move: uniform over the workgroup(s)
+            const int mi = ens_pick_move(a.mv, cr);
+            mkind = a.mv.kind[mi]; mp0 = a.mv.p0[mi]; mp1 = a.mv.p1[mi];
+        }
         for (int split = 0; split < 2; ++split) {
             // walker index of slot i of the active half S and of the complement C
             auto s_idx = [&](int i) { int v = i + split * H + rot; return v >= W ? v - W : v; };
             auto c_idx = [&](int i) { int v = i + (1 - split) * H + rot; return v >= W ? v - W : v; };
             if (t < H) {
-                unsigned int c1[4] = {(unsigned int)it, (unsigned int)(it >> 32), (unsigned int)(split * ENS_MAXW + t), 0x1u};
-                philox4x32(c1, k0, k1);
-                const double u = u01(c1[0], c1[1]);
-                const double z = ((a.a_stretch - 1.0) * u + 1.0);
-                const double zz = z * z / a.a_stretch;
-                const int j = c_idx((int)(c1[2] % (unsigned int)H));
-                const int s = s_idx(t);
-                bool ok = true;
-#pragma unroll
-                for (int d = 0; d < DPAD; ++d) {
-                    const double q = cs[j][d] - (cs[j][d] - cs[s][d]) * zz;
-                    qs[t][d] = q;
-                    // prior gate in scaled coordinates (lo/hi were scaled on the host)
-                    if (d < D && !(q >= a.lo[d] && q <= a.hi[d])) ok = false;
-                }
-                qok[t] = ok ? 1 : 0;
-                fac[t] = (D - 1.0) * log(zz);
-                unsigned int c2[4] = {(unsigned int)it, (unsigned int)(it >> 32), (unsigned int)(split * ENS_MAXW + t), 0x2u};
-                philox4x32(c2, k0, k1);
-                uacc[t] = u01(c2[0], c2[1]);
+                qok[t] = ens_propose<DPAD, ALLMOVES>(mkind, mp0, mp1, cs, s_idx(t), c_idx, H, D, a.lo, a.hi, it, split, t, k0, k1, qs[t],
+                                           fac[t], uacc[t]) ? 1 : 0;
             }
             __syncthreads();
             if constexpr (DPAD > 8) {
@@ -273,7 +243,7 @@ struct EnsMwArgs {
 };
 typedef unsigned int ens_u32x4 __attribute__((ext_vector_type(4)));
 
-template <int DPAD, bool XLDS>
+template <int DPAD, bool XLDS, bool ALLMOVES>
 __global__ __launch_bounds__(256) void ensemble_mw_kernel(EnsMwArgs q) {
     const EnsArgs& a = q.e;
     constexpr int XS = DPAD + 2;
@@ -364,34 +334,25 @@ __global__ __launch_bounds__(256) void ensemble_mw_kernel(EnsMwArgs q) {
     const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc((void*)(q.xchg + ens * 2 * (ENS_MAXW / 2) * 2), 0,
                                                                           2 * (ENS_MAXW / 2) * 16, 0x00020000);
     const unsigned int k0 = (unsigned int)a.seed, k1 = (unsigned int)(a.seed >> 32) ^ (unsigned int)(ens * 0x9E3779B9u);
+    // the move of a one-entry table (the default) is read once, not per iteration
+    const bool mixed = a.mv.n > 1;
+    int mkind = a.mv.kind[0];
+    double mp0 = a.mv.p0[0], mp1 = a.mv.p1[0];
     bool dead = false;
     for (long long it = 0; it < a.iterations && !dead; ++it) {
         unsigned int cr[4] = {(unsigned int)it, (unsigned int)(it >> 32), 0xFFFFFFFFu, 0x5u};
         philox4x32(cr, k0, k1);
         const int rot = (int)(cr[0] % (unsigned int)W);
+        if (mixed) {                                            // the iteration's move: uniform over the workgroup(s)
+            const int mi = ens_pick_move(a.mv, cr);
+            mkind = a.mv.kind[mi]; mp0 = a.mv.p0[mi]; mp1 = a.mv.p1[mi];
+        }
         for (int split = 0; split < 2; ++split) {
             auto s_idx = [&](int i) { int v = i + split * H + rot; return v >= W ? v - W : v; };
             auto c_idx = [&](int i) { int v = i + (1 - split) * H + rot; return v >= W ? v - W : v; };
             if (t < H) {
-                unsigned int c1[4] = {(unsigned int)it, (unsigned int)(it >> 32), (unsigned int)(split * ENS_MAXW + t), 0x1u};
-                philox4x32(c1, k0, k1);
-                const double u = u01(c1[0], c1[1]);
-                const double z = ((a.a_stretch - 1.0) * u + 1.0);
-                const double zz = z * z / a.a_stretch;
-                const int j = c_idx((int)(c1[2] % (unsigned int)H));
-                const int sw = s_idx(t);
-                bool ok = true;
-#pragma unroll
-                for (int d = 0; d < DPAD; ++d) {
-                    const double qv = cs[j][d] - (cs[j][d] - cs[sw][d]) * zz;
-                    qs[t][d] = qv;
-                    if (d < D && !(qv >= a.lo[d] && qv <= a.hi[d])) ok = false;
-                }
-                qok[t] = ok ? 1 : 0;
-                fac[t] = (D - 1.0) * log(zz);
-                unsigned int c2[4] = {(unsigned int)it, (unsigned int)(it >> 32), (unsigned int)(split * ENS_MAXW + t), 0x2u};
-                philox4x32(c2, k0, k1);
-                uacc[t] = u01(c2[0], c2[1]);
+                qok[t] = ens_propose<DPAD, ALLMOVES>(mkind, mp0, mp1, cs, s_idx(t), c_idx, H, D, a.lo, a.hi, it, split, t, k0, k1, qs[t],
+                                           fac[t], uacc[t]) ? 1 : 0;
             }
             __syncthreads();
             // this workgroup's proposals g, g + G, ... (two per pass over the training stream), published as they are done
@@ -484,30 +445,98 @@ __global__ __launch_bounds__(256) void ens_mark_failed_kernel(const unsigned lon
 // 0 = several workgroups per ensemble where that helps and fits (default) | 1 = the single-workgroup kernel only.
 // A test / profiling switch, not read from the environment.  Returns the previous value.
 static std::atomic<int> g_ens_mode{0};
-static thread_local int tl_ens_mode = -1;       // >= 0: this thread's current call overrides the switch (apgp_ensemble_sample_ex)
 extern "C" int apgp_ensemble_mode(int mode) {
     if (mode < 0) return g_ens_mode.load();
     return g_ens_mode.exchange(mode ? 1 : 0);
 }
 
-extern "C" int apgp_ensemble_sample(const double* xs, int64_t n, const apgp_kernel_t* kern, double mean,
-                                    const double* lo, const double* hi, int32_t nwalkers,
-                                    int32_t nensembles, int64_t iterations, double a_stretch,
-                                    uint64_t seed, double* coords, double* logp, double* chain,
-                                    double* logp_chain, int64_t* naccept, void* stream) {
+// one instantiation per padded dimension (and, AM, per "holds every move" / "stretch only")
+#define APGP_ENS_BY_DPAD(LAUNCH, AM)           \
+    switch (kc.dpad) {                         \
+        case 2: LAUNCH(2, 0, AM); break;       \
+        case 4: LAUNCH(4, 1, AM); break;       \
+        case 8: LAUNCH(8, 2, AM); break;       \
+        case 16: LAUNCH(16, 3, AM); break;     \
+        default: LAUNCH(32, 4, AM); break;     \
+    }
+
+// fills mv from the caller's table (NULL with nmoves == 0: the stretch move at a_stretch alone) or returns the failed check
+static const char* ens_move_table(EnsMoves& mv, const apgp_ens_move_t* moves, int32_t nmoves, double a_stretch,
+                                  int ndim, int nwalkers) {
+    apgp_ens_move_t one = {APGP_ENS_MOVE_STRETCH, 1.0, a_stretch, 0.0};
+    if (moves == nullptr) {
+        if (nmoves != 0) return "moves is NULL but nmoves is not 0";
+        moves = &one;
+        nmoves = 1;
+    }
+    if (!(nmoves >= 1 && nmoves <= APGP_ENS_MAX_MOVES)) return "1 <= nmoves <= APGP_ENS_MAX_MOVES required";
+    double total = 0.0;
+    for (int m = 0; m < nmoves; ++m) {
+        if (!(std::isfinite(moves[m].weight) && moves[m].weight > 0.0)) return "move weights must be finite and > 0";
+        total = total + moves[m].weight;
+    }
+    if (!std::isfinite(total)) return "move weights must have a finite sum";
+    double acc = 0.0;
+    for (int m = 0; m < APGP_ENS_MAX_MOVES; ++m) {
+        mv.kind[m] = APGP_ENS_MOVE_STRETCH;
+        mv.cum[m] = 1.0;
+        mv.p0[m] = 2.0;
+        mv.p1[m] = 0.0;
+        if (m >= nmoves) continue;
+        const double u = moves[m].p0, v = moves[m].p1;
+        acc = acc + moves[m].weight;
+        mv.kind[m] = moves[m].kind;
+        mv.cum[m] = acc / total;
+        mv.p0[m] = u;
+        switch (moves[m].kind) {
+            case APGP_ENS_MOVE_STRETCH:
+                if (!(u > 1.0)) return "stretch scale a must be > 1";
+                break;
+            case APGP_ENS_MOVE_DE:
+                if (!(std::isfinite(u) && u >= 0.0)) return "DE sigma must be finite and >= 0";
+                if (!(std::isfinite(v) && v >= 0.0)) return "DE gamma0 must be finite and > 0 (0: the default)";
+                if (nwalkers < 4) return "the DE move needs at least 4 walkers";
+                mv.p1[m] = v > 0.0 ? v : 2.38 / std::sqrt(2.0 * ndim);
+                break;
+            case APGP_ENS_MOVE_SNOOKER:
+                if (!(std::isfinite(u) && u > 0.0)) return "snooker gammas must be finite and > 0";
+                if (nwalkers < 6) return "the snooker move needs at least 6 walkers";
+                break;
+            default:
+                return "unknown move kind";
+        }
+    }
+    mv.n = nmoves;
+    return nullptr;
+}
+
+extern "C" int apgp_ensemble_sample_moves(const double* xs, int64_t n, const apgp_kernel_t* kern, double mean,
+                                          const double* lo, const double* hi, int32_t nwalkers,
+                                          int32_t nensembles, int64_t iterations, double a_stretch,
+                                          uint64_t seed, double* coords, double* logp, double* chain,
+                                          double* logp_chain, int64_t* naccept, int mode,
+                                          const apgp_ens_move_t* moves, int32_t nmoves, void* stream) {
     APGP_CHECK_ARG(xs && kern && lo && hi && coords && logp && naccept, "null pointer");
     APGP_CHECK_ARG(n >= 1 && n <= APGP_MAX_N && iterations >= 0 && nensembles >= 1, "n, iterations, nensembles");
     KernConst kc;
     APGP_CHECK_ARG(apgp_make_kernconst(kern, &kc) == 0, "kernel parameters");
     APGP_CHECK_ARG(nwalkers >= 2 && nwalkers % 2 == 0 && nwalkers <= ENS_MAXW, "nwalkers must be even and <= 256");
     APGP_CHECK_ARG(nwalkers >= 2 * kc.ndim, "nwalkers must be at least twice the dimension");
-    APGP_CHECK_ARG(a_stretch > 1.0, "stretch scale a must be > 1");
+    EnsMoves mv;
+    const char* bad = ens_move_table(mv, moves, nmoves, a_stretch, kc.ndim, nwalkers);
+    APGP_CHECK_ARG(bad == nullptr, bad);
     for (int d = 0; d < kc.ndim; ++d) APGP_CHECK_ARG(kc.sc[d] > 0.0, "inverse metric must be positive");
+    // the kernel for THIS call (mode 0: several workgroups per ensemble where that helps, 1: the single-workgroup kernel,
+    // < 0: the process-wide switch apgp_ensemble_mode)
+    // a table of stretch entries only runs the kernels that hold no other move
+    bool allmoves = false;
+    for (int m = 0; m < mv.n; ++m) allmoves = allmoves || mv.kind[m] != APGP_ENS_MOVE_STRETCH;
+    const int ens_mode = mode < 0 ? g_ens_mode.load() : (mode ? 1 : 0);
     EnsArgs a;
     a.xs = xs; a.coords = coords; a.logp = logp; a.chain = chain; a.logp_chain = logp_chain;
     a.naccept = (long long*)naccept; a.n = apgp_npad(n); a.iterations = iterations;
     a.ndim = kc.ndim; a.nwalkers = nwalkers; a.seed = seed; a.mean = mean; a.amp = kc.amp;
-    a.a_stretch = a_stretch;
+    a.mv = mv;
     a.lin_coef = kc.lin_coef; a.lin_order = kc.lin_order;
     for (int d = 0; d < APGP_MAX_DIM; ++d) {
         a.lw[d] = kc.lw[d];
@@ -525,7 +554,7 @@ extern "C" int apgp_ensemble_sample(const double* xs, int64_t n, const apgp_kern
         // proposals of a half-step, at most (CUs / ensembles), at least 2; every workgroup must be resident (one per CU
         // with the training stream in LDS)
         int devn = 0, cus = 0;
-        if ((tl_ens_mode >= 0 ? tl_ens_mode : g_ens_mode.load()) == 0 && hipGetDevice(&devn) == hipSuccess &&
+        if (ens_mode == 0 && hipGetDevice(&devn) == hipSuccess &&
             hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, devn) == hipSuccess && devn >= 0 && devn < 64) {
             int G = nwalkers / 2;
             if ((long long)G * nensembles > cus) G = cus / nensembles;
@@ -534,40 +563,35 @@ extern "C" int apgp_ensemble_sample(const double* xs, int64_t n, const apgp_kern
                 const size_t words = (size_t)nensembles * 2 * (ENS_MAXW / 2) * 2 + 8;      // (+ the status word)
                 unsigned long long* xchg = (unsigned long long*)apgp_stream_scratch(4, s, words);
                 if (!xchg || hipMemsetAsync(xchg, 0, words * 8, s) != hipSuccess) {
-                    apgp_set_error("apgp_ensemble_sample: exchange buffer");
+                    apgp_set_error("apgp_ensemble_sample_moves: exchange buffer");
                     return -2;
                 }
                 EnsMwArgs q;
                 q.e = a; q.xchg = xchg; q.status = xchg + (words - 8); q.timeout = 5000000ull; q.G = G;      // 50 ms of the 100 MHz clock
                 dim3 gridm((unsigned)(nensembles * G)), blockm(256);
                 static std::mutex attr_mu_m;
-                static bool attr_done_m[5][64] = {{false}};
-#define APGP_LAUNCH_ENS_MW(DP, SLOT)                                                                   \
+                static bool attr_done_m[2][5][64] = {{{false}}};
+#define APGP_LAUNCH_ENS_MW(DP, SLOT, AM)                                                                  \
     do {                                                                                               \
         if (xlds) {                                                                                    \
             {                                                                                          \
                 std::lock_guard<std::mutex> lk(attr_mu_m);                                             \
-                if (!attr_done_m[SLOT][devn]) {                                                        \
-                    if (hipFuncSetAttribute((const void*)ensemble_mw_kernel<DP, true>,                 \
+                if (!attr_done_m[AM][SLOT][devn]) {                                                        \
+                    if (hipFuncSetAttribute((const void*)ensemble_mw_kernel<DP, true, AM>,                 \
                                             hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024) != hipSuccess) { \
-                        apgp_set_error("apgp_ensemble_sample: hipFuncSetAttribute(96 KiB of LDS) failed"); \
+                        apgp_set_error("apgp_ensemble_sample_moves: hipFuncSetAttribute(96 KiB of LDS) failed"); \
                         return -2;                                                                     \
                     }                                                                                  \
-                    attr_done_m[SLOT][devn] = true;                                                    \
+                    attr_done_m[AM][SLOT][devn] = true;                                                    \
                 }                                                                                      \
             }                                                                                          \
-            hipLaunchKernelGGL((ensemble_mw_kernel<DP, true>), gridm, blockm, xbytes, s, q);           \
+            hipLaunchKernelGGL((ensemble_mw_kernel<DP, true, AM>), gridm, blockm, xbytes, s, q);           \
         } else {                                                                                       \
-            hipLaunchKernelGGL((ensemble_mw_kernel<DP, false>), gridm, blockm, 0, s, q);               \
+            hipLaunchKernelGGL((ensemble_mw_kernel<DP, false, AM>), gridm, blockm, 0, s, q);               \
         }                                                                                              \
     } while (0)
-                switch (kc.dpad) {
-                    case 2: APGP_LAUNCH_ENS_MW(2, 0); break;
-                    case 4: APGP_LAUNCH_ENS_MW(4, 1); break;
-                    case 8: APGP_LAUNCH_ENS_MW(8, 2); break;
-                    case 16: APGP_LAUNCH_ENS_MW(16, 3); break;
-                    default: APGP_LAUNCH_ENS_MW(32, 4); break;
-                }
+                if (allmoves) { APGP_ENS_BY_DPAD(APGP_LAUNCH_ENS_MW, true) }
+                else { APGP_ENS_BY_DPAD(APGP_LAUNCH_ENS_MW, false) }
 #undef APGP_LAUNCH_ENS_MW
                 hipLaunchKernelGGL(ens_mark_failed_kernel, dim3(1), dim3(256), 0, s, q.status, logp, (int)(nensembles * nwalkers));
                 APGP_CHECK_LAUNCH();
@@ -579,39 +603,34 @@ extern "C" int apgp_ensemble_sample(const double* xs, int64_t n, const apgp_kern
     // device and instantiation
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) {
-        apgp_set_error("apgp_ensemble_sample: hipGetDevice failed");
+        apgp_set_error("apgp_ensemble_sample_moves: hipGetDevice failed");
         return -2;
     }
     static std::mutex attr_mu;
-    static bool attr_done[5][64] = {{false}};
-#define APGP_LAUNCH_ENS(DP, SLOT)                                                                      \
+    static bool attr_done[2][5][64] = {{{false}}};
+#define APGP_LAUNCH_ENS(DP, SLOT, AM)                                                                     \
     do {                                                                                               \
         if (xlds) {                                                                                    \
             {                                                                                          \
                 std::lock_guard<std::mutex> lock(attr_mu);                                             \
-                if (!attr_done[SLOT][dev]) {                                                           \
-                    const hipError_t e_ = hipFuncSetAttribute((const void*)ensemble_kernel<DP, true>,  \
+                if (!attr_done[AM][SLOT][dev]) {                                                           \
+                    const hipError_t e_ = hipFuncSetAttribute((const void*)ensemble_kernel<DP, true, AM>,  \
                                                               hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024); \
                     if (e_ != hipSuccess) {                                                            \
-                        apgp_set_error("apgp_ensemble_sample: hipFuncSetAttribute(96 KiB of LDS) failed on device %d: %s", \
+                        apgp_set_error("apgp_ensemble_sample_moves: hipFuncSetAttribute(96 KiB of LDS) failed on device %d: %s", \
                                        dev, hipGetErrorString(e_));                                    \
                         return -2;                                                                     \
                     }                                                                                  \
-                    attr_done[SLOT][dev] = true;                                                       \
+                    attr_done[AM][SLOT][dev] = true;                                                       \
                 }                                                                                      \
             }                                                                                          \
-            hipLaunchKernelGGL((ensemble_kernel<DP, true>), grid, block, xbytes, s, a);                \
+            hipLaunchKernelGGL((ensemble_kernel<DP, true, AM>), grid, block, xbytes, s, a);                \
         } else {                                                                                       \
-            hipLaunchKernelGGL((ensemble_kernel<DP, false>), grid, block, 0, s, a);                    \
+            hipLaunchKernelGGL((ensemble_kernel<DP, false, AM>), grid, block, 0, s, a);                    \
         }                                                                                              \
     } while (0)
-    switch (kc.dpad) {
-        case 2: APGP_LAUNCH_ENS(2, 0); break;
-        case 4: APGP_LAUNCH_ENS(4, 1); break;
-        case 8: APGP_LAUNCH_ENS(8, 2); break;
-        case 16: APGP_LAUNCH_ENS(16, 3); break;
-        default: APGP_LAUNCH_ENS(32, 4); break;
-    }
+    if (allmoves) { APGP_ENS_BY_DPAD(APGP_LAUNCH_ENS, true) }
+    else { APGP_ENS_BY_DPAD(APGP_LAUNCH_ENS, false) }
 #undef APGP_LAUNCH_ENS
     APGP_CHECK_LAUNCH();
     return 0;
@@ -799,16 +818,22 @@ extern "C" int apgp_prior_lnprior(const double* X, int64_t m, int32_t ndim, cons
 
 // apgp_ensemble_sample with the kernel chosen PER CALL (mode 0: several workgroups per ensemble where that helps, 1: the
 // single-workgroup kernel, < 0: the process-wide switch apgp_ensemble_mode): the re-run after a give-up (NaN in logp) does
-// not change what other threads' calls get.
+// not change what other threads' calls get.  Both are apgp_ensemble_sample_moves with the stretch move alone.
 extern "C" int apgp_ensemble_sample_ex(const double* xs, int64_t n, const apgp_kernel_t* kern, double mean,
                                        const double* lo, const double* hi, int32_t nwalkers,
                                        int32_t nensembles, int64_t iterations, double a_stretch,
                                        uint64_t seed, double* coords, double* logp, double* chain,
                                        double* logp_chain, int64_t* naccept, int mode, void* stream) {
-    const int saved = tl_ens_mode;
-    tl_ens_mode = mode < 0 ? -1 : (mode ? 1 : 0);
-    const int rc = apgp_ensemble_sample(xs, n, kern, mean, lo, hi, nwalkers, nensembles, iterations, a_stretch, seed, coords,
-                                        logp, chain, logp_chain, naccept, stream);
-    tl_ens_mode = saved;
-    return rc;
+    const apgp_ens_move_t one = {APGP_ENS_MOVE_STRETCH, 1.0, a_stretch, 0.0};
+    return apgp_ensemble_sample_moves(xs, n, kern, mean, lo, hi, nwalkers, nensembles, iterations, a_stretch, seed, coords,
+                                      logp, chain, logp_chain, naccept, mode, &one, 1, stream);
+}
+
+extern "C" int apgp_ensemble_sample(const double* xs, int64_t n, const apgp_kernel_t* kern, double mean,
+                                    const double* lo, const double* hi, int32_t nwalkers,
+                                    int32_t nensembles, int64_t iterations, double a_stretch,
+                                    uint64_t seed, double* coords, double* logp, double* chain,
+                                    double* logp_chain, int64_t* naccept, void* stream) {
+    return apgp_ensemble_sample_ex(xs, n, kern, mean, lo, hi, nwalkers, nensembles, iterations, a_stretch, seed, coords,
+                                   logp, chain, logp_chain, naccept, -1, stream);
 }

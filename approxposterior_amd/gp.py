@@ -1638,7 +1638,7 @@ class GP(GeorgeExtras):
 
     # -- on-device ensemble MCMC over the GP mean ------------------------------------
     def sample_ensemble(self, y, initial_state, iterations, bounds, a=2.0, seed=0, store=True, prior=None,
-                        keep_device=False):
+                        keep_device=False, moves=None):
         """Run the stretch-move ensemble sampler entirely on the device with
         log-probability = GP mean (what ApproxPosterior._gpll returns) and the box
         prior ``bounds``.  ``initial_state`` is (W, D) for one ensemble or (E, W, D)
@@ -1652,7 +1652,12 @@ class GP(GeorgeExtras):
         ``ApproxPosterior._gpllBatch`` returns for a rejected walker.
 
         ``keep_device``: with ``store``, the result also has ``chain_device``, the device tensor (iterations, E*W, D)
-        that ``chain`` was copied from (``DeviceChain.get_autocorr_time`` then reads it in place)."""
+        that ``chain`` was copied from (``DeviceChain.get_autocorr_time`` then reads it in place).
+
+        ``moves``: what ``mcmc.EnsembleSampler(moves=...)`` accepts -- a ``mcmc.StretchMove``, ``DEMove`` or
+        ``DESnookerMove``, a list of them or of ``(move, weight)`` pairs; one move is drawn per iteration for the whole
+        ensemble (``apgp_ensemble_sample_moves``).  ``None`` is the stretch move at ``a``; ``a`` other than 2.0 beside
+        ``moves`` is a ``ValueError``.  The snooker's norms are taken in the kernel's scaled coordinates."""
         self.recompute()
         torch, dev, lib = self._rt()
         y = self._check_dimensions(y)
@@ -1674,6 +1679,14 @@ class GP(GeorgeExtras):
         n = len(self._x)
         ks = self._kernel_struct()
         iterations = int(iterations)
+        table, ntable = None, 0
+        if moves is not None:
+            from . import mcmc
+            pairs = mcmc.move_table(moves, W, a)
+            table, ntable = (_lib.EnsMove * len(pairs))(), len(pairs)
+            for rec, (mv, w) in zip(table, pairs):
+                rec.kind, rec.p0, rec.p1 = mv.record(D)
+                rec.weight = w
         with self._on(torch, dev):
             st = self._stream(torch)
             self._ensure_xs(y)
@@ -1684,11 +1697,14 @@ class GP(GeorgeExtras):
             lchain = torch.empty((iterations, E, W), dtype=torch.float64, device=dev) if store else None
             def launch(mode):
                 coords.copy_(torch.from_numpy(p0))
-                _lib.check(lib.apgp_ensemble_sample_ex(
-                    self._xs.data_ptr(), n, ctypes.byref(ks), float(self.mean.value), lo, hi, W, E,
-                    iterations, float(a), _seed64(seed), coords.data_ptr(), logp.data_ptr(),
-                    chain.data_ptr() if store else None, lchain.data_ptr() if store else None,
-                    nacc.data_ptr(), mode, st), "apgp_ensemble_sample")
+                args = (self._xs.data_ptr(), n, ctypes.byref(ks), float(self.mean.value), lo, hi, W, E,
+                        iterations, float(a), _seed64(seed), coords.data_ptr(), logp.data_ptr(),
+                        chain.data_ptr() if store else None, lchain.data_ptr() if store else None,
+                        nacc.data_ptr(), mode)
+                if table is None:
+                    _lib.check(lib.apgp_ensemble_sample_ex(*args, st), "apgp_ensemble_sample")
+                else:
+                    _lib.check(lib.apgp_ensemble_sample_moves(*args, table, ntable, st), "apgp_ensemble_sample_moves")
                 return logp.cpu().numpy().reshape(E * W)
             final = launch(-1)
             if np.any(np.isnan(final)):

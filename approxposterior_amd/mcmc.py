@@ -17,6 +17,7 @@ subset of emcee's interface the reference touches:
     sampler.get_log_prob(...), sampler.get_blobs(...)
     sampler.get_autocorr_time(tol=0)                (mcmcUtils.py:198)
     sampler.acceptance_fraction, sampler.iteration
+    EnsembleSampler(..., moves=...) with moves.StretchMove, moves.DEMove, moves.DESnookerMove and weighted mixtures
 
 What is new relative to the reference's usage: with ``vectorize=True`` the
 log-probability function receives the whole half-ensemble (S, D) in ONE call,
@@ -29,7 +30,7 @@ whole replicas.
 
 import numpy as np
 
-__all__ = ["EnsembleSampler", "integrated_time", "AutocorrError"]
+__all__ = ["EnsembleSampler", "integrated_time", "AutocorrError", "StretchMove", "DEMove", "DESnookerMove", "moves"]
 
 
 class AutocorrError(Exception):
@@ -234,8 +235,125 @@ def _checked_tau(tau_est, n_t, tol, quiet):
     return tau_est
 
 
+class StretchMove(object):
+    """The Goodman & Weare (2010) stretch move with scale ``a`` > 1: the sampler's default."""
+    kind = 0          # APGP_ENS_MOVE_STRETCH
+    min_walkers = 2
+
+    def __init__(self, a=2.0):
+        self.a = float(a)
+        if not (np.isfinite(self.a) and self.a > 1.0):
+            raise ValueError("StretchMove: a must be > 1")
+
+    def record(self, ndim):
+        """``(kind, p0, p1)`` of ``apgp_ens_move_t`` (include/apgp.h)."""
+        return self.kind, self.a, 0.0
+
+    def __repr__(self):
+        return "StretchMove(a=%r)" % self.a
+
+
+class DEMove(object):
+    """Differential evolution (ter Braak 2006) with the jitter on gamma of Nelson et al. (2013): for walker s, an ordered
+    pair of distinct walkers c_j, c_k of the other half and n ~ N(0, 1),
+    ``q = s + gamma0 (1 + sigma n) (c_j - c_k)``, log proposal factor 0; ``gamma0`` defaults to 2.38 / sqrt(2 ndim).
+    ``DEMove(gamma0=1.0)`` mixed in with a small weight is the usual mode-jumping idiom.  Needs 4 walkers.
+
+    The textbook move behind emcee's interface: a valid sampler of the same family (pinned by a stationarity test), not
+    draw-for-draw emcee -- emcee is neither installed here nor was its source at hand."""
+    kind = 1          # APGP_ENS_MOVE_DE
+    min_walkers = 4
+
+    def __init__(self, sigma=1.0e-5, gamma0=None):
+        self.sigma = float(sigma)
+        self.gamma0 = None if gamma0 is None else float(gamma0)
+        if not (np.isfinite(self.sigma) and self.sigma >= 0.0):
+            raise ValueError("DEMove: sigma must be >= 0")
+        if self.gamma0 is not None and not (np.isfinite(self.gamma0) and self.gamma0 > 0.0):
+            raise ValueError("DEMove: gamma0 must be > 0 or None")
+
+    def g0(self, ndim):
+        return 2.38 / np.sqrt(2.0 * ndim) if self.gamma0 is None else self.gamma0
+
+    def record(self, ndim):
+        return self.kind, self.sigma, float(self.g0(ndim))
+
+    def __repr__(self):
+        return "DEMove(sigma=%r, gamma0=%r)" % (self.sigma, self.gamma0)
+
+
+class DESnookerMove(object):
+    """The snooker update (ter Braak & Vrugt 2008): for walker s and three distinct walkers z = c_j, z1 = c_k, z2 = c_l of
+    the other half, ``e = (s - z) / |s - z|``, ``q = s + gammas (e . (z1 - z2)) e``, log proposal factor
+    ``(ndim - 1) (log|q - z| - log|s - z|)``.  ``s == z`` gives a NaN proposal, which is rejected like one outside the
+    prior.  Needs 6 walkers.  The host sampler takes the norms in plain coordinates, the device sampler in the GP's
+    scaled coordinates (DESIGN.md "Ensemble moves").
+
+    The textbook move behind emcee's interface: a valid sampler of the same family (pinned by a stationarity test), not
+    draw-for-draw emcee -- emcee is neither installed here nor was its source at hand."""
+    kind = 2          # APGP_ENS_MOVE_SNOOKER
+    min_walkers = 6
+
+    def __init__(self, gammas=1.7):
+        self.gammas = float(gammas)
+        if not (np.isfinite(self.gammas) and self.gammas > 0.0):
+            raise ValueError("DESnookerMove: gammas must be > 0")
+
+    def record(self, ndim):
+        return self.kind, self.gammas, 0.0
+
+    def __repr__(self):
+        return "DESnookerMove(gammas=%r)" % self.gammas
+
+
+class _Moves(object):
+    """``mcmc.moves``: the namespace emcee calls ``emcee.moves``."""
+    StretchMove, DEMove, DESnookerMove = StretchMove, DEMove, DESnookerMove
+
+
+moves = _Moves()
+MAX_MOVES = 8         # APGP_ENS_MAX_MOVES
+
+
+def move_table(moves, nwalkers, a=2.0):
+    """``[(move, weight), ...]`` with the weights normalised, from what ``EnsembleSampler(moves=...)`` accepts: ``None``
+    (the stretch move at ``a``), one move, a list of moves (equal weights) or a list of ``(move, weight)`` pairs, at most
+    ``MAX_MOVES`` entries.  ``ValueError`` for ``a`` other than 2.0 beside ``moves`` (``a`` belongs to the default move
+    alone), a weight that is not positive and finite, or fewer walkers than a listed move needs."""
+    if moves is None:
+        return [(StretchMove(a), 1.0)]
+    if float(a) != 2.0:
+        raise ValueError("a belongs to the default stretch move: with moves, pass StretchMove(a) in the list")
+    known = (StretchMove, DEMove, DESnookerMove)
+    if isinstance(moves, known):
+        moves = [moves]
+    try:
+        entries = list(moves)
+    except TypeError:
+        raise ValueError("moves must be a move, a list of moves or a list of (move, weight) pairs")
+    if not 1 <= len(entries) <= MAX_MOVES:
+        raise ValueError("moves must list between 1 and %d moves" % MAX_MOVES)
+    pairs = []
+    for e in entries:
+        mv, w = (e, 1.0) if isinstance(e, known) else (tuple(e) if np.ndim(e) == 1 and len(e) == 2 else (None, 0.0))
+        if not isinstance(mv, known):
+            raise ValueError("moves: %r is not a StretchMove, DEMove or DESnookerMove (or a (move, weight) pair)" % (e,))
+        w = float(w)
+        if not (np.isfinite(w) and w > 0.0):
+            raise ValueError("moves: weights must be positive and finite")
+        if nwalkers < mv.min_walkers:
+            raise ValueError("%r needs at least %d walkers" % (mv, mv.min_walkers))
+        pairs.append((mv, w))
+    total = 0.0
+    for _, w in pairs:
+        total = total + w
+    return [(mv, w / total) for mv, w in pairs]
+
+
 class EnsembleSampler(object):
-    """Goodman-Weare stretch-move ensemble sampler (emcee-3 semantics)."""
+    """Red/blue ensemble sampler (emcee-3 semantics): the Goodman-Weare stretch move by default, or ``moves`` -- a
+    :class:`StretchMove`, :class:`DEMove` or :class:`DESnookerMove`, a list of them, or a list of ``(move, weight)``
+    pairs; one move is drawn per iteration for the whole ensemble.  ``sampler.moves`` is the normalised table."""
 
     def __init__(self, nwalkers, ndim, log_prob_fn, args=None, kwargs=None, backend=None,
                  blobs_dtype=None, vectorize=False, a=2.0, seed=None, moves=None, pool=None):
@@ -244,8 +362,10 @@ class EnsembleSampler(object):
             if nwalkers % 2 != 0:
                 raise ValueError("The number of walkers must be even.")
             raise ValueError("The number of walkers needs to be at least twice the dimension.")
-        if moves is not None or pool is not None:
-            raise NotImplementedError("only the default stretch move, no pool")
+        if pool is not None:
+            raise NotImplementedError("no pool: the log-probability is evaluated in this process")
+        self._default_move = moves is None
+        self.moves = move_table(moves, int(nwalkers), a)
         self.nwalkers = int(nwalkers)
         self.ndim = int(ndim)
         self.log_prob_fn = log_prob_fn
@@ -322,21 +442,34 @@ class EnsembleSampler(object):
             if np.any(np.isneginf(self._lp)) and np.all(np.isneginf(self._lp)):
                 raise ValueError("Initial state has a zero probability for every walker")
         nw, nd, a = self.nwalkers, self.ndim, self.a
+        weights = np.cumsum([w for _, w in self.moves])
         for _ in range(int(iterations)):
             inds = np.arange(nw) % 2
             self._random.shuffle(inds)
             halves = (np.flatnonzero(inds == 0), np.flatnonzero(inds == 1))
+            # the iteration's move (a table of one draws nothing: the default's stream is the stretch sampler's)
+            move = self.moves[0][0] if len(self.moves) == 1 else \
+                self.moves[min(int(np.searchsorted(weights, self._random.rand(), side="right")), len(self.moves) - 1)][0]
             for split in range(2):
                 S, C = halves[split], halves[1 - split]
                 s, c = self._coords[S], self._coords[C]
-                zz = ((a - 1.0) * self._random.rand(len(S)) + 1.0) ** 2.0 / a
-                factors = (nd - 1.0) * np.log(zz)
-                rint = self._random.randint(len(C), size=(len(S),))
-                q = c[rint] - (c[rint] - s) * zz[:, None]
+                if self._default_move:
+                    zz = ((a - 1.0) * self._random.rand(len(S)) + 1.0) ** 2.0 / a
+                    factors = (nd - 1.0) * np.log(zz)
+                    rint = self._random.randint(len(C), size=(len(S),))
+                    q = c[rint] - (c[rint] - s) * zz[:, None]
+                    valid = None
+                else:
+                    q, factors = self._propose(move, s, c)
+                    valid = np.all(np.isfinite(q), axis=1)        # (a snooker walker on its own pivot: q is NaN)
+                    if not valid.all():
+                        q[~valid] = s[~valid]                       # evaluated in place of the proposal, then rejected
                 new_lp, new_bl = self.compute_log_prob(q)
                 with np.errstate(invalid="ignore"):      # -inf - -inf for walkers outside the prior
                     lnpdiff = factors + new_lp - self._lp[S]
                 accepted = np.log(self._random.rand(len(S))) < lnpdiff
+                if valid is not None:
+                    accepted &= valid
                 idx = S[accepted]
                 self._coords[idx] = q[accepted]
                 self._lp[idx] = new_lp[accepted]
@@ -352,6 +485,33 @@ class EnsembleSampler(object):
                 if self._bl is not None:
                     self._blobs.append(self._bl.copy())
             yield self._coords, self._lp, self._bl
+
+    def _propose(self, move, s, c):
+        """Proposals and log proposal factors of ``move`` for the active half ``s`` (S, D) against the complement ``c``."""
+        ns, nc, nd = len(s), len(c), self.ndim
+        rs = self._random
+        if isinstance(move, StretchMove):
+            zz = ((move.a - 1.0) * rs.rand(ns) + 1.0) ** 2.0 / move.a
+            rint = rs.randint(nc, size=(ns,))
+            return c[rint] - (c[rint] - s) * zz[:, None], (nd - 1.0) * np.log(zz)
+        j = rs.randint(nc, size=(ns,))
+        k = rs.randint(nc - 1, size=(ns,))
+        k += k >= j                                              # ordered pair, j != k
+        if isinstance(move, DEMove):
+            gamma = move.g0(nd) * (1.0 + move.sigma * rs.randn(ns))
+            return s + gamma[:, None] * (c[j] - c[k]), np.zeros(ns)
+        l = rs.randint(nc - 2, size=(ns,))
+        l += l >= np.minimum(j, k)
+        l += l >= np.maximum(j, k)                               # ordered triple, all distinct
+        z, z1, z2 = c[j], c[k], c[l]
+        with np.errstate(invalid="ignore", divide="ignore"):
+            delta = s - z
+            norm = np.sqrt(np.sum(delta * delta, axis=1))
+            e = delta / norm[:, None]
+            q = s + move.gammas * np.sum(e * (z1 - z2), axis=1)[:, None] * e
+            qn = np.sqrt(np.sum((q - z) ** 2, axis=1))
+            factors = (nd - 1.0) * (np.log(qn) - np.log(norm))
+        return q, np.where(np.isfinite(factors), factors, -np.inf)
 
     def run_mcmc(self, initial_state, nsteps, **kwargs):
         out = None
@@ -389,7 +549,7 @@ class DeviceChain(EnsembleSampler):
     ``get_autocorr_time``, ``acceptance_fraction``), so burn-in estimation and the
     reference-style post-processing work unchanged."""
 
-    def __init__(self, result, a=2.0):
+    def __init__(self, result, a=2.0, moves=None):
         chain = result["chain"]
         self.nwalkers = chain.shape[1]
         self.ndim = chain.shape[2]
@@ -397,6 +557,8 @@ class DeviceChain(EnsembleSampler):
         self.args, self.kwargs = (), {}
         self.vectorize = True
         self.a = float(a)                 # the stretch scale the chain was run with
+        self._default_move = moves is None
+        self.moves = move_table(moves, self.nwalkers, a)      # ... and the move table
         self.blobs_dtype = None
         self.backend = None
         self._random = None

@@ -556,6 +556,37 @@ int apgp_ensemble_sample(const double* xs, int64_t n, const apgp_kernel_t* kern 
                          double* coords, double* logp, double* chain, double* logp_chain,
                          int64_t* naccept, void* stream);
 
+/* Ensemble moves: the sampler with a table of red/blue moves instead of the stretch move alone.  One entry of the
+ * table is chosen per iteration for the whole ensemble (both half-steps) with probability weight / sum of weights.
+ *   STRETCH  p0 = a > 1:                      q = c_j - (c_j - s) zz, zz = ((a - 1) u + 1)^2 / a, factor (D - 1) log zz
+ *   DE       p0 = sigma >= 0, p1 = gamma0 > 0 (0: the default 2.38 / sqrt(2 ndim)):
+ *                                             q = s + gamma0 (1 + sigma n) (c_j - c_k), n ~ N(0, 1), j != k; factor 0
+ *   SNOOKER  p0 = gammas > 0:                 q = s + gammas (e . (c_k - c_l)) e, e = (s - c_j) / |s - c_j|, j, k, l
+ *                                             distinct; factor (ndim - 1) (log|q - c_j| - log|s - c_j|)
+ * s: the walker, c_*: walkers of the other half, positions taken in the kernel's scaled coordinates; a DE or snooker
+ * proposal with a non-finite coordinate is rejected.  DE needs nwalkers >= 4, the snooker nwalkers >= 6.  The random
+ * numbers (csrc/ens_moves.h) are functions of (seed, ensemble, iteration, half-step, slot); an iteration that takes the
+ * stretch move draws what apgp_ensemble_sample draws in that iteration.
+ * apgp_ensemble_sample_moves is apgp_ensemble_sample_ex with the table moves[0..nmoves) (host, 1 <= nmoves <=
+ * APGP_ENS_MAX_MOVES; weights and parameters finite and in the ranges above, else -1); moves == NULL with nmoves == 0
+ * is the one-entry table {STRETCH, 1, a_stretch}, which is what apgp_ensemble_sample and _ex run; a_stretch is not
+ * read otherwise.
+ * Added in ABI 8 without changing anything before it: APGP_ABI_VERSION stays 8.                                   */
+#define APGP_ENS_MOVE_STRETCH 0
+#define APGP_ENS_MOVE_DE 1
+#define APGP_ENS_MOVE_SNOOKER 2
+#define APGP_ENS_MAX_MOVES 8
+typedef struct apgp_ens_move {
+    int32_t kind;           /* APGP_ENS_MOVE_* */
+    double weight, p0, p1;
+} apgp_ens_move_t;
+int apgp_ensemble_sample_moves(const double* xs, int64_t n, const apgp_kernel_t* kern /*host*/, double mean,
+                               const double* lo /*host, MAX_DIM*/, const double* hi /*host, MAX_DIM*/,
+                               int32_t nwalkers, int32_t nensembles, int64_t iterations, double a_stretch,
+                               uint64_t seed, double* coords, double* logp, double* chain,
+                               double* logp_chain, int64_t* naccept, int mode,
+                               const apgp_ens_move_t* moves /*host*/, int32_t nmoves, void* stream);
+
 /* ---- candidate matrix of the sweep drawn on the device (round 5, opt-in) ------
  * The batched counterpart of the ``sampleFn`` draws utility.minimizeObjective starts from
  * (utility.py:334-338) when the prior is the box: T (m x ndim, device) row i =
