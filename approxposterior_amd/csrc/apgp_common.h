@@ -3,6 +3,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <type_traits>
+#include <utility>
 #include "../../include/apgp.h"
 
 typedef double f64x4 __attribute__((ext_vector_type(4)));
@@ -95,6 +97,52 @@ static inline int apgp_make_kernconst(const apgp_kernel_t* k, KernConst* c) {
         c->lw[d] = d < k->ndim ? 2.0 / k->inv_metric[d] : 0.0;
     }
     return 0;
+}
+
+// ---------------------------------------------------------------------------
+// The host-side set-up shared by the entry points that take "a trained model, a box, some query points" (DESIGN.md
+// section 4): a new entry point uses these (and ApgpSeqWait of scratch.h) instead of copying a neighbour's preamble.
+// ---------------------------------------------------------------------------
+// f(std::integral_constant<int, DPAD>) with kc.dpad as a compile-time constant, and what f returns (an int status or
+// nothing).  The one list of the widths the kernels are instantiated for; anything else is 32 (apgp_dpad gives nothing else).
+template <class F>
+static inline auto apgp_by_dpad(int dpad, F&& f) {
+    switch (dpad) {
+        case 2: return f(std::integral_constant<int, 2>{});
+        case 4: return f(std::integral_constant<int, 4>{});
+        case 8: return f(std::integral_constant<int, 8>{});
+        case 16: return f(std::integral_constant<int, 16>{});
+        default: return f(std::integral_constant<int, 32>{});
+    }
+}
+
+// the kernel constants of an argument struct, from a KernConst (or from another argument struct: same field names)
+template <class Args, class Src>
+static inline void apgp_fill_kernel(Args& a, const Src& kc) {
+    a.ndim = kc.ndim; a.lin_order = kc.lin_order; a.amp = kc.amp; a.lin_coef = kc.lin_coef;
+    for (int d = 0; d < APGP_MAX_DIM; ++d) { a.sc[d] = kc.sc[d]; a.lw[d] = kc.lw[d]; }
+}
+
+// the box of an argument struct, in the caller's coordinates: zero past ndim, and everywhere without a box (the entry
+// points have checked that lo and hi come together)
+template <class Args>
+static inline void apgp_fill_box(Args& a, int ndim, const double* lo, const double* hi) {
+    a.has_box = lo != NULL;
+    for (int d = 0; d < APGP_MAX_DIM; ++d) {
+        a.lo[d] = (lo && d < ndim) ? lo[d] : 0.0;
+        a.hi[d] = (hi && d < ndim) ? hi[d] : 0.0;
+    }
+}
+
+// compile-time loop: the body sees its index as a constant expression, so register arrays are indexed statically
+// whatever hipcc's unroll heuristics decide
+template <int... Is, class F>
+__device__ __forceinline__ void static_for_impl(std::integer_sequence<int, Is...>, F&& f) {
+    (f(std::integral_constant<int, Is>{}), ...);
+}
+template <int N, class F>
+__device__ __forceinline__ void static_for(F&& f) {
+    static_for_impl(std::make_integer_sequence<int, N>{}, f);
 }
 
 // ---------------------------------------------------------------------------

@@ -450,15 +450,50 @@ extern "C" int apgp_ensemble_mode(int mode) {
     return g_ens_mode.exchange(mode ? 1 : 0);
 }
 
-// one instantiation per padded dimension (and, AM, per "holds every move" / "stretch only")
-#define APGP_ENS_BY_DPAD(LAUNCH, AM)           \
-    switch (kc.dpad) {                         \
-        case 2: LAUNCH(2, 0, AM); break;       \
-        case 4: LAUNCH(4, 1, AM); break;       \
-        case 8: LAUNCH(8, 2, AM); break;       \
-        case 16: LAUNCH(16, 3, AM); break;     \
-        default: LAUNCH(32, 4, AM); break;     \
+// The launch of one instantiation: per padded dimension and, AM, per "holds every move" / "stretch only".  The LDS-resident
+// form (xlds) needs > 64 KiB of dynamic LDS: a per-device attribute, set and CHECKED once per device and instantiation.
+// (The kernels land in the code object in the order they are first named: LDS-resident form first here, AM = true first
+// in the caller.)
+template <int DP, bool AM>
+static int ens_launch_mw(const EnsMwArgs& q, dim3 grid, size_t xbytes, bool xlds, int dev, hipStream_t s) {
+    static std::mutex attr_mu;
+    static bool attr_done[64] = {false};
+    if (xlds) {
+        std::lock_guard<std::mutex> lk(attr_mu);
+        if (!attr_done[dev]) {
+            if (hipFuncSetAttribute((const void*)ensemble_mw_kernel<DP, true, AM>,
+                                    hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024) != hipSuccess) {
+                apgp_set_error("apgp_ensemble_sample_moves: hipFuncSetAttribute(96 KiB of LDS) failed");
+                return -2;
+            }
+            attr_done[dev] = true;
+        }
     }
+    if (xlds) hipLaunchKernelGGL((ensemble_mw_kernel<DP, true, AM>), grid, dim3(256), xbytes, s, q);
+    else hipLaunchKernelGGL((ensemble_mw_kernel<DP, false, AM>), grid, dim3(256), 0, s, q);
+    return 0;
+}
+template <int DP, bool AM>
+static int ens_launch(const EnsArgs& a, dim3 grid, size_t xbytes, bool xlds, int dev, hipStream_t s) {
+    static std::mutex attr_mu;
+    static bool attr_done[64] = {false};
+    if (xlds) {
+        std::lock_guard<std::mutex> lock(attr_mu);
+        if (!attr_done[dev]) {
+            const hipError_t e = hipFuncSetAttribute((const void*)ensemble_kernel<DP, true, AM>,
+                                                     hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
+            if (e != hipSuccess) {
+                apgp_set_error("apgp_ensemble_sample_moves: hipFuncSetAttribute(96 KiB of LDS) failed on device %d: %s",
+                               dev, hipGetErrorString(e));
+                return -2;
+            }
+            attr_done[dev] = true;
+        }
+    }
+    if (xlds) hipLaunchKernelGGL((ensemble_kernel<DP, true, AM>), grid, dim3(1024), xbytes, s, a);
+    else hipLaunchKernelGGL((ensemble_kernel<DP, false, AM>), grid, dim3(1024), 0, s, a);
+    return 0;
+}
 
 // fills mv from the caller's table (NULL with nmoves == 0: the stretch move at a_stretch alone) or returns the failed check
 static const char* ens_move_table(EnsMoves& mv, const apgp_ens_move_t* moves, int32_t nmoves, double a_stretch,
@@ -545,7 +580,7 @@ extern "C" int apgp_ensemble_sample_moves(const double* xs, int64_t n, const apg
         a.hi[d] = d < kc.ndim ? hi[d] * kc.sc[d] : 0.0;
     }
     hipStream_t s = (hipStream_t)stream;
-    dim3 grid((unsigned)nensembles), block(1024);
+    const dim3 grid((unsigned)nensembles);
     const size_t xbytes = (size_t)a.n * (kc.dpad + 2) * sizeof(double);
     // (D > 16: the sampler state alone takes 100 KB of LDS -- the training stream stays in L2)
     const bool xlds = xbytes <= 96 * 1024 && kc.dpad <= 16;
@@ -568,70 +603,26 @@ extern "C" int apgp_ensemble_sample_moves(const double* xs, int64_t n, const apg
                 }
                 EnsMwArgs q;
                 q.e = a; q.xchg = xchg; q.status = xchg + (words - 8); q.timeout = 5000000ull; q.G = G;      // 50 ms of the 100 MHz clock
-                dim3 gridm((unsigned)(nensembles * G)), blockm(256);
-                static std::mutex attr_mu_m;
-                static bool attr_done_m[2][5][64] = {{{false}}};
-#define APGP_LAUNCH_ENS_MW(DP, SLOT, AM)                                                                  \
-    do {                                                                                               \
-        if (xlds) {                                                                                    \
-            {                                                                                          \
-                std::lock_guard<std::mutex> lk(attr_mu_m);                                             \
-                if (!attr_done_m[AM][SLOT][devn]) {                                                        \
-                    if (hipFuncSetAttribute((const void*)ensemble_mw_kernel<DP, true, AM>,                 \
-                                            hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024) != hipSuccess) { \
-                        apgp_set_error("apgp_ensemble_sample_moves: hipFuncSetAttribute(96 KiB of LDS) failed"); \
-                        return -2;                                                                     \
-                    }                                                                                  \
-                    attr_done_m[AM][SLOT][devn] = true;                                                    \
-                }                                                                                      \
-            }                                                                                          \
-            hipLaunchKernelGGL((ensemble_mw_kernel<DP, true, AM>), gridm, blockm, xbytes, s, q);           \
-        } else {                                                                                       \
-            hipLaunchKernelGGL((ensemble_mw_kernel<DP, false, AM>), gridm, blockm, 0, s, q);               \
-        }                                                                                              \
-    } while (0)
-                if (allmoves) { APGP_ENS_BY_DPAD(APGP_LAUNCH_ENS_MW, true) }
-                else { APGP_ENS_BY_DPAD(APGP_LAUNCH_ENS_MW, false) }
-#undef APGP_LAUNCH_ENS_MW
+                const dim3 gridm((unsigned)(nensembles * G));
+                const int rc = allmoves
+                    ? apgp_by_dpad(kc.dpad, [&](auto dp) { return ens_launch_mw<decltype(dp)::value, true>(q, gridm, xbytes, xlds, devn, s); })
+                    : apgp_by_dpad(kc.dpad, [&](auto dp) { return ens_launch_mw<decltype(dp)::value, false>(q, gridm, xbytes, xlds, devn, s); });
+                if (rc != 0) return rc;
                 hipLaunchKernelGGL(ens_mark_failed_kernel, dim3(1), dim3(256), 0, s, q.status, logp, (int)(nensembles * nwalkers));
                 APGP_CHECK_LAUNCH();
                 return 0;
             }
         }
     }
-    // the LDS-resident form needs > 64 KiB of dynamic LDS: per-device attribute, set and CHECKED once per
-    // device and instantiation
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) {
         apgp_set_error("apgp_ensemble_sample_moves: hipGetDevice failed");
         return -2;
     }
-    static std::mutex attr_mu;
-    static bool attr_done[2][5][64] = {{{false}}};
-#define APGP_LAUNCH_ENS(DP, SLOT, AM)                                                                     \
-    do {                                                                                               \
-        if (xlds) {                                                                                    \
-            {                                                                                          \
-                std::lock_guard<std::mutex> lock(attr_mu);                                             \
-                if (!attr_done[AM][SLOT][dev]) {                                                           \
-                    const hipError_t e_ = hipFuncSetAttribute((const void*)ensemble_kernel<DP, true, AM>,  \
-                                                              hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024); \
-                    if (e_ != hipSuccess) {                                                            \
-                        apgp_set_error("apgp_ensemble_sample_moves: hipFuncSetAttribute(96 KiB of LDS) failed on device %d: %s", \
-                                       dev, hipGetErrorString(e_));                                    \
-                        return -2;                                                                     \
-                    }                                                                                  \
-                    attr_done[AM][SLOT][dev] = true;                                                       \
-                }                                                                                      \
-            }                                                                                          \
-            hipLaunchKernelGGL((ensemble_kernel<DP, true, AM>), grid, block, xbytes, s, a);                \
-        } else {                                                                                       \
-            hipLaunchKernelGGL((ensemble_kernel<DP, false, AM>), grid, block, 0, s, a);                    \
-        }                                                                                              \
-    } while (0)
-    if (allmoves) { APGP_ENS_BY_DPAD(APGP_LAUNCH_ENS, true) }
-    else { APGP_ENS_BY_DPAD(APGP_LAUNCH_ENS, false) }
-#undef APGP_LAUNCH_ENS
+    const int rc = allmoves
+        ? apgp_by_dpad(kc.dpad, [&](auto dp) { return ens_launch<decltype(dp)::value, true>(a, grid, xbytes, xlds, dev, s); })
+        : apgp_by_dpad(kc.dpad, [&](auto dp) { return ens_launch<decltype(dp)::value, false>(a, grid, xbytes, xlds, dev, s); });
+    if (rc != 0) return rc;
     APGP_CHECK_LAUNCH();
     return 0;
 }

@@ -264,14 +264,7 @@ extern "C" int apgp_gmm_pass(const double* X, int64_t n, int32_t ndim, int32_t n
         apgp_set_error("apgp_gmm_pass: scratch allocation failed");
         return -2;
     }
-    int rc;
-    switch (DP) {
-        case 2: rc = gmm_launch_mode<2>(a, mode, nb, lds, s); break;
-        case 4: rc = gmm_launch_mode<4>(a, mode, nb, lds, s); break;
-        case 8: rc = gmm_launch_mode<8>(a, mode, nb, lds, s); break;
-        case 16: rc = gmm_launch_mode<16>(a, mode, nb, lds, s); break;
-        default: rc = gmm_launch_mode<32>(a, mode, nb, lds, s); break;
-    }
+    const int rc = apgp_by_dpad(DP, [&](auto dp) { return gmm_launch_mode<decltype(dp)::value>(a, mode, nb, lds, s); });
     if (rc) return rc;
     APGP_CHECK_LAUNCH();
     hipLaunchKernelGGL(gmm_reduce_kernel, dim3((unsigned)a.nout), dim3(256), 0, s, (const double*)a.partial, nb, stats_out);

@@ -103,13 +103,7 @@ int apgp_gram_with_rhs(const double* X, int64_t n, const apgp_kernel_t* kern, do
     const long long nb = (n + 63) / 64;
     dim3 grid((unsigned)(nb * (nb + 1) / 2)), block(256);
     hipStream_t s = (hipStream_t)stream;
-    switch (a.kc.dpad) {
-        case 2: hipLaunchKernelGGL(gram_kernel<2>, grid, block, 0, s, a); break;
-        case 4: hipLaunchKernelGGL(gram_kernel<4>, grid, block, 0, s, a); break;
-        case 8: hipLaunchKernelGGL(gram_kernel<8>, grid, block, 0, s, a); break;
-        case 16: hipLaunchKernelGGL(gram_kernel<16>, grid, block, 0, s, a); break;
-        default: hipLaunchKernelGGL(gram_kernel<32>, grid, block, 0, s, a); break;
-    }
+    apgp_by_dpad(a.kc.dpad, [&](auto dp) { hipLaunchKernelGGL(gram_kernel<decltype(dp)::value>, grid, block, 0, s, a); });
     APGP_CHECK_LAUNCH();
     return 0;
 }
@@ -131,13 +125,7 @@ int apgp_gram_with_rhs_batch(const double* X, int64_t n, int64_t batch, const ap
     const long long nb = (n + 63) / 64;
     dim3 grid((unsigned)(nb * (nb + 1) / 2), (unsigned)batch), block(256);
     hipStream_t s = (hipStream_t)stream;
-    switch (g.m[0].kc.dpad) {
-        case 2: hipLaunchKernelGGL(gram_batch_kernel<2>, grid, block, 0, s, g); break;
-        case 4: hipLaunchKernelGGL(gram_batch_kernel<4>, grid, block, 0, s, g); break;
-        case 8: hipLaunchKernelGGL(gram_batch_kernel<8>, grid, block, 0, s, g); break;
-        case 16: hipLaunchKernelGGL(gram_batch_kernel<16>, grid, block, 0, s, g); break;
-        default: hipLaunchKernelGGL(gram_batch_kernel<32>, grid, block, 0, s, g); break;
-    }
+    apgp_by_dpad(g.m[0].kc.dpad, [&](auto dp) { hipLaunchKernelGGL(gram_batch_kernel<decltype(dp)::value>, grid, block, 0, s, g); });
     APGP_CHECK_LAUNCH();
     return 0;
 }
@@ -191,13 +179,7 @@ extern "C" int apgp_kernel_cross(const double* X1, int64_t m, const double* X2, 
     a.X1 = X1; a.X2 = X2; a.C = C; a.m = m; a.n = n; a.ldc = ldc;
     dim3 grid((unsigned)((m * n + 255) / 256)), block(256);
     hipStream_t s = (hipStream_t)stream;
-    switch (a.kc.dpad) {
-        case 2: hipLaunchKernelGGL(kernel_cross_kernel<2>, grid, block, 0, s, a); break;
-        case 4: hipLaunchKernelGGL(kernel_cross_kernel<4>, grid, block, 0, s, a); break;
-        case 8: hipLaunchKernelGGL(kernel_cross_kernel<8>, grid, block, 0, s, a); break;
-        case 16: hipLaunchKernelGGL(kernel_cross_kernel<16>, grid, block, 0, s, a); break;
-        default: hipLaunchKernelGGL(kernel_cross_kernel<32>, grid, block, 0, s, a); break;
-    }
+    apgp_by_dpad(a.kc.dpad, [&](auto dp) { hipLaunchKernelGGL(kernel_cross_kernel<decltype(dp)::value>, grid, block, 0, s, a); });
     APGP_CHECK_LAUNCH();
     return 0;
 }

@@ -8,18 +8,7 @@
 #include "scratch.h"
 #include "pred1_body.h"
 #include <atomic>
-#include <chrono>
 #include <mutex>
-#include <type_traits>
-#include <utility>
-template <int... Is, class F>
-__device__ __forceinline__ void trtri_static_for_impl(std::integer_sequence<int, Is...>, F&& f) {
-    (f(std::integral_constant<int, Is>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void trtri_static_for(F&& f) {
-    trtri_static_for_impl(std::make_integer_sequence<int, N>{}, f);
-}
 
 // ---------------------------------------------------------------------------
 // sizes
@@ -289,13 +278,13 @@ __global__ __launch_bounds__(256) void trsv_step_kernel(TrsvStepArgs a) {
 #pragma unroll
         for (int k = 0; k < 64; ++k) v[k] = TRANS ? Lb[k][lane] : Lb[lane][k];   // column / row `lane` of the block
         if (!TRANS) {
-            trtri_static_for<64>([&](auto kc) {
+            static_for<64>([&](auto kc) {
                 constexpr int k = decltype(kc)::value;
                 const double zk = trsv_bcast(ri, k) * trsv_bcast(inv, k);
                 ri = lane == k ? zk : (lane > k ? fma(-v[k], zk, ri) : ri);
             });
         } else {
-            trtri_static_for<64>([&](auto kc) {
+            static_for<64>([&](auto kc) {
                 constexpr int k = 63 - decltype(kc)::value;
                 const double xk = trsv_bcast(ri, k) * trsv_bcast(inv, k);
                 ri = lane == k ? xk : (lane < k ? fma(-v[k], xk, ri) : ri);   // (L^T)[lane][k] = L[k][lane]
@@ -396,13 +385,13 @@ __global__ __launch_bounds__(256) void trsv_step4_kernel(TrsvStepArgs a) {
 #pragma unroll
             for (int k = 0; k < 64; ++k) v[k] = TRANS ? Lb[k][lane] : Lb[lane][k];
             if (!TRANS) {
-                trtri_static_for<64>([&](auto kc) {
+                static_for<64>([&](auto kc) {
                     constexpr int k = decltype(kc)::value;
                     const double zk = trsv_bcast(ri, k) * trsv_bcast(inv, k);
                     ri = lane == k ? zk : (lane > k ? fma(-v[k], zk, ri) : ri);
                 });
             } else {
-                trtri_static_for<64>([&](auto kc) {
+                static_for<64>([&](auto kc) {
                     constexpr int k = 63 - decltype(kc)::value;
                     const double xk = trsv_bcast(ri, k) * trsv_bcast(inv, k);
                     ri = lane == k ? xk : (lane < k ? fma(-v[k], xk, ri) : ri);
@@ -448,7 +437,7 @@ __global__ __launch_bounds__(256) void trsv_step4_kernel(TrsvStepArgs a) {
 // v[k]: forward L[lane][k], transposed L[k][lane]; inv = 1 / L[lane][lane].
 template <int TRANS>
 __device__ __forceinline__ double trsv_diag_solve(double ri, const double inv, const double (&v)[64], const int lane) {
-    trtri_static_for<16>([&](auto gc) {
+    static_for<16>([&](auto gc) {
         constexpr int g = TRANS ? 15 - decltype(gc)::value : decltype(gc)::value;
         constexpr int c0 = 4 * g;
         double r[4], iv[4], z[4];
@@ -1051,13 +1040,7 @@ extern "C" int apgp_predict1_host(const double* t_host, const double* xs, int64_
     const dim3 grid((unsigned)a.nparts), block(256);
     const bool fused = winv && n <= 256 && (apgp_potrf_mode(-1) & 15) != 1;
     if (!fused)
-    switch (kc.dpad) {
-        case 2: hipLaunchKernelGGL(pred1_kstar_kernel<2>, grid, block, 0, s, a); break;
-        case 4: hipLaunchKernelGGL(pred1_kstar_kernel<4>, grid, block, 0, s, a); break;
-        case 8: hipLaunchKernelGGL(pred1_kstar_kernel<8>, grid, block, 0, s, a); break;
-        case 16: hipLaunchKernelGGL(pred1_kstar_kernel<16>, grid, block, 0, s, a); break;
-        default: hipLaunchKernelGGL(pred1_kstar_kernel<32>, grid, block, 0, s, a); break;
-    }
+        apgp_by_dpad(kc.dpad, [&](auto dp) { hipLaunchKernelGGL(pred1_kstar_kernel<decltype(dp)::value>, grid, block, 0, s, a); });
     if (fused) {
         // (launched below, with the mailbox)
     } else if (winv) {
@@ -1074,29 +1057,17 @@ extern "C" int apgp_predict1_host(const double* t_host, const double* xs, int64_
     std::lock_guard<std::mutex> lock(apgp_stream_lock(s));
     if (mail) { a.mail = mb->dev; a.seq = ++mb->seq; }
     if (fused) {
-        switch (kc.dpad) {
-            case 2: hipLaunchKernelGGL(pred1_small_kernel<2>, dim3(1), dim3(256), 0, s, a, winv, (long long)ldw); break;
-            case 4: hipLaunchKernelGGL(pred1_small_kernel<4>, dim3(1), dim3(256), 0, s, a, winv, (long long)ldw); break;
-            case 8: hipLaunchKernelGGL(pred1_small_kernel<8>, dim3(1), dim3(256), 0, s, a, winv, (long long)ldw); break;
-            case 16: hipLaunchKernelGGL(pred1_small_kernel<16>, dim3(1), dim3(256), 0, s, a, winv, (long long)ldw); break;
-            default: hipLaunchKernelGGL(pred1_small_kernel<32>, dim3(1), dim3(256), 0, s, a, winv, (long long)ldw); break;
-        }
+        apgp_by_dpad(kc.dpad, [&](auto dp) {
+            hipLaunchKernelGGL(pred1_small_kernel<decltype(dp)::value>, dim3(1), dim3(256), 0, s, a, winv, (long long)ldw);
+        });
     } else {
         hipLaunchKernelGGL(pred1_final_kernel, dim3(1), dim3(1024), 0, s, a);
     }
     APGP_CHECK_LAUNCH();
     if (mail) {
-        volatile long long* flag = (volatile long long*)(mb->host + 5);
-        const auto t0 = std::chrono::steady_clock::now();
-        unsigned spins = 0;
-        while (__atomic_load_n(flag, __ATOMIC_ACQUIRE) != a.seq) {
-            if ((++spins & 255u) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::microseconds(400)) {
-                if (hipStreamSynchronize(s) != hipSuccess || __atomic_load_n(flag, __ATOMIC_ACQUIRE) != a.seq) {
-                    apgp_set_error("apgp_predict1_host: result record not written");
-                    return -2;
-                }
-                break;
-            }
+        if (ApgpSeqWait(s, 400).wait(mb->host + 5, a.seq) != ApgpSeqWait::OK) {
+            apgp_set_error("apgp_predict1_host: result record not written");
+            return -2;
         }
         out2_host[0] = mb->host[0];
         out2_host[1] = mb->host[1];
@@ -1144,7 +1115,7 @@ __global__ __launch_bounds__(64) void trtri_diag_kernel(const double* L, long lo
     }
     __syncthreads();
     double x[64];
-    trtri_static_for<64>([&](auto ic) {
+    static_for<64>([&](auto ic) {
         constexpr int i = decltype(ic)::value;
         double srow = 0.0;
         f64x2 lr[(i + 1) / 2 > 0 ? (i + 1) / 2 : 1];

@@ -378,13 +378,9 @@ extern "C" int64_t apgp_nm_search_work_len(int64_t restarts, int64_t n) {
 
 template <int FORM>
 static void nm_launch(int dpad, hipStream_t s, const NmArgs& a, unsigned grid) {
-    switch (dpad) {
-        case 2: hipLaunchKernelGGL((nm_search_kernel<2, FORM>), dim3(grid), dim3(NM_T), 0, s, a); break;
-        case 4: hipLaunchKernelGGL((nm_search_kernel<4, FORM>), dim3(grid), dim3(NM_T), 0, s, a); break;
-        case 8: hipLaunchKernelGGL((nm_search_kernel<8, FORM>), dim3(grid), dim3(NM_T), 0, s, a); break;
-        case 16: hipLaunchKernelGGL((nm_search_kernel<16, FORM>), dim3(grid), dim3(NM_T), 0, s, a); break;
-        default: hipLaunchKernelGGL((nm_search_kernel<32, FORM>), dim3(grid), dim3(NM_T), 0, s, a); break;
-    }
+    apgp_by_dpad(dpad, [&](auto dp) {
+        hipLaunchKernelGGL((nm_search_kernel<decltype(dp)::value, FORM>), dim3(grid), dim3(NM_T), 0, s, a);
+    });
 }
 
 extern "C" int apgp_nm_search(const double* starts, int64_t restarts, const double* xs, int64_t n,
@@ -409,17 +405,12 @@ extern "C" int apgp_nm_search(const double* starts, int64_t restarts, const doub
     a.starts = starts; a.xs = xs; a.W = winv; a.L = L; a.work = work;
     a.x_out = x_out; a.f_out = f_out; a.stats = (int*)stats; a.trace = trace; a.steps = (int*)steps;
     a.n = n; a.ldw = winv ? ldw : 0; a.ldl = L ? ldl : 0; a.wstride = apgp_round_up(n, 64);
-    a.ndim = kc.ndim; a.kind = opt->kind; a.maxiter = opt->maxiter; a.maxfev = opt->maxfev;
-    a.lin_order = kc.lin_order; a.has_box = lo != NULL;
-    a.mean = mean; a.amp = kc.amp; a.lin_coef = kc.lin_coef; a.zeta = opt->zeta; a.ybest = opt->ybest;
+    apgp_fill_kernel(a, kc);
+    apgp_fill_box(a, kc.ndim, lo, hi);
+    a.kind = opt->kind; a.maxiter = opt->maxiter; a.maxfev = opt->maxfev;
+    a.mean = mean; a.zeta = opt->zeta; a.ybest = opt->ybest;
     a.xatol = opt->xatol; a.fatol = opt->fatol;
     a.rho = opt->rho; a.chi = opt->chi; a.psi = opt->psi; a.sigma = opt->sigma;
-    for (int d = 0; d < APGP_MAX_DIM; ++d) {
-        a.sc[d] = kc.sc[d];
-        a.lw[d] = kc.lw[d];
-        a.lo[d] = (lo && d < kc.ndim) ? lo[d] : 0.0;
-        a.hi[d] = (hi && d < kc.ndim) ? hi[d] : 0.0;
-    }
     hipStream_t s = (hipStream_t)stream;
     const unsigned grid = (unsigned)restarts;
     if (winv && n <= 256) nm_launch<0>(kc.dpad, s, a, grid);

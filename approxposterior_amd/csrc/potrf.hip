@@ -19,21 +19,7 @@
 #include "mma16.h"
 #include "scratch.h"
 #include <atomic>
-#include <chrono>
 #include <mutex>
-#include <type_traits>
-#include <utility>
-
-// compile-time loop: the body sees its index as a constant expression, so the register
-// arrays below are indexed statically whatever hipcc's unroll heuristics decide
-template <int... Is, class F>
-__device__ __forceinline__ void static_for_impl(std::integer_sequence<int, Is...>, F&& f) {
-    (f(std::integral_constant<int, Is>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void static_for(F&& f) {
-    static_for_impl(std::make_integer_sequence<int, N>{}, f);
-}
 
 #define PB 64
 #define CB 4     // columns per step of the diagonal-block factorisation (potrf_panel_kernel)
@@ -904,23 +890,10 @@ static int nll_two_launch_t(const NllSmallArgs& q, int batch, hipStream_t s) {
 // `batch` matrices, one workgroup each
 template <bool BATCH>
 static int nll_fused_launch_q(const NllSmallArgs& q, int dpad, int batch, hipStream_t s) {
-    if (q.n > PB) {
-        switch (dpad) {
-            case 2: return nll_two_launch_t<2, BATCH>(q, batch, s);
-            case 4: return nll_two_launch_t<4, BATCH>(q, batch, s);
-            case 8: return nll_two_launch_t<8, BATCH>(q, batch, s);
-            case 16: return nll_two_launch_t<16, BATCH>(q, batch, s);
-            default: return nll_two_launch_t<32, BATCH>(q, batch, s);
-        }
-    }
+    if (q.n > PB)
+        return apgp_by_dpad(dpad, [&](auto dp) { return nll_two_launch_t<decltype(dp)::value, BATCH>(q, batch, s); });
     const dim3 grid((unsigned)batch), block(192);
-    switch (dpad) {
-        case 2: hipLaunchKernelGGL((nll_small_kernel<2, BATCH>), grid, block, 0, s, q); break;
-        case 4: hipLaunchKernelGGL((nll_small_kernel<4, BATCH>), grid, block, 0, s, q); break;
-        case 8: hipLaunchKernelGGL((nll_small_kernel<8, BATCH>), grid, block, 0, s, q); break;
-        case 16: hipLaunchKernelGGL((nll_small_kernel<16, BATCH>), grid, block, 0, s, q); break;
-        default: hipLaunchKernelGGL((nll_small_kernel<32, BATCH>), grid, block, 0, s, q); break;
-    }
+    apgp_by_dpad(dpad, [&](auto dp) { hipLaunchKernelGGL((nll_small_kernel<decltype(dp)::value, BATCH>), grid, block, 0, s, q); });
     APGP_CHECK_LAUNCH();
     return 0;
 }
@@ -1496,21 +1469,11 @@ static int potrf_run(double* A, int64_t n, int64_t lda, int64_t batch, int64_t b
 // the host side of the mailbox: polls the sequence word (bounded spin, then the ordinary stream
 // synchronisation) and copies the record out.  Caller holds apgp_stream_lock(s).
 static int mailbox_wait(ApgpMailbox* mb, long long seq, hipStream_t s, double* out5_host) {
-    volatile long long* flag = (volatile long long*)(mb->host + 5);
-    const auto t0 = std::chrono::steady_clock::now();
-    unsigned spins = 0;
-    while (__atomic_load_n(flag, __ATOMIC_ACQUIRE) != seq) {
-        if ((++spins & 255u) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::microseconds(400)) {
-            if (hipStreamSynchronize(s) != hipSuccess) {
-                apgp_set_error("apgp_nll_eval: stream synchronisation failed");
-                return -2;
-            }
-            if (__atomic_load_n(flag, __ATOMIC_ACQUIRE) != seq) {
-                apgp_set_error("apgp_nll_eval: result record not written");
-                return -2;
-            }
-            break;
-        }
+    const int w = ApgpSeqWait(s, 400).wait(mb->host + 5, seq);
+    if (w != ApgpSeqWait::OK) {
+        apgp_set_error(w == ApgpSeqWait::SYNC_FAILED ? "apgp_nll_eval: stream synchronisation failed"
+                                                     : "apgp_nll_eval: result record not written");
+        return -2;
     }
     for (int i = 0; i < 5; ++i) out5_host[i] = mb->host[i];
     return 0;
@@ -1696,19 +1659,12 @@ static int nll_batch_side_by_side(const double* X, int64_t n, int64_t batch, con
     hipLaunchKernelGGL(potrf_finish_kernel, dim3((unsigned)nb, (unsigned)batch), dim3(256), 0, s, full);
     APGP_CHECK_LAUNCH();
     // the records: one sequence word per matrix (bounded spin, then the ordinary synchronisation)
-    bool gave_up = false, synced = false;
-    const auto t0 = std::chrono::steady_clock::now();
+    bool gave_up = false;
+    ApgpSeqWait records(s, 800);
     for (int64_t b = 0; b < batch; ++b) {
-        volatile long long* flag = (volatile long long*)(io + 8 * b + 5);
-        unsigned spins = 0;
-        while (__atomic_load_n(flag, __ATOMIC_ACQUIRE) != seq) {
-            if ((++spins & 255u) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::microseconds(800)) {
-                if (synced || hipStreamSynchronize(s) != hipSuccess || __atomic_load_n(flag, __ATOMIC_ACQUIRE) != seq) {
-                    apgp_set_error("apgp_nll_eval_batch: result record not written");
-                    return -2;
-                }
-                synced = true;
-            }
+        if (records.wait(io + 8 * b + 5, seq) != ApgpSeqWait::OK) {
+            apgp_set_error("apgp_nll_eval_batch: result record not written");
+            return -2;
         }
         for (int i = 0; i < 5; ++i) out5_host[5 * b + i] = io[8 * b + i];
         if (out5_host[5 * b + 4] == PP_ABORTED) gave_up = true;
@@ -1762,19 +1718,11 @@ extern "C" int apgp_nll_eval_batch(const double* X, int64_t n, int64_t batch, co
             q.kc = kcs[0]; q.mail = nullptr; q.seq = seq;
             q.bkc = (const KernConst*)io_dev; q.bshift = io_dev + (size_t)batch * KCD; q.brec = io_dev + (size_t)batch * (KCD + 1);
             if ((rc = nll_fused_launch_q<true>(q, kcs[0].dpad, (int)batch, s)) != 0) return rc;
-            const auto t0 = std::chrono::steady_clock::now();
-            bool synced = false;
+            ApgpSeqWait records(s, 600);
             for (int64_t b = 0; b < batch; ++b) {
-                volatile long long* flag = (volatile long long*)(rec + 8 * b + 5);
-                unsigned spins = 0;
-                while (__atomic_load_n(flag, __ATOMIC_ACQUIRE) != seq) {
-                    if ((++spins & 255u) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::microseconds(600)) {
-                        if (synced || hipStreamSynchronize(s) != hipSuccess || __atomic_load_n(flag, __ATOMIC_ACQUIRE) != seq) {
-                            apgp_set_error("apgp_nll_eval_batch: result record not written");
-                            return -2;
-                        }
-                        synced = true;
-                    }
+                if (records.wait(rec + 8 * b + 5, seq) != ApgpSeqWait::OK) {
+                    apgp_set_error("apgp_nll_eval_batch: result record not written");
+                    return -2;
                 }
                 for (int i = 0; i < 5; ++i) out5_host[5 * b + i] = rec[8 * b + i];
             }

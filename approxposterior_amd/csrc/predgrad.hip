@@ -502,25 +502,14 @@ extern "C" int apgp_predict_grad(const double* T, int64_t m, const double* xs, i
         a.rc = ns;
         a.nrc = 1;
     }
-    a.ndim = kc.ndim; a.kind = kind; a.lin_order = kc.lin_order; a.has_box = lo != NULL;
-    a.mean = mean; a.amp = kc.amp; a.lin_coef = kc.lin_coef; a.zeta = zeta; a.ybest = ybest;
-    for (int d = 0; d < APGP_MAX_DIM; ++d) {
-        a.sc[d] = kc.sc[d];
-        a.lw[d] = kc.lw[d];
-        a.lo[d] = (lo && d < kc.ndim) ? lo[d] : 0.0;
-        a.hi[d] = (hi && d < kc.ndim) ? hi[d] : 0.0;
-    }
+    apgp_fill_kernel(a, kc);
+    apgp_fill_box(a, kc.ndim, lo, hi);
+    a.kind = kind; a.mean = mean; a.zeta = zeta; a.ybest = ybest;
     hipStream_t s = (hipStream_t)stream;
     for (int64_t m0 = 0; m0 < m; m0 += ch) {
         a.m0 = m0;
         a.mc = (m - m0) < ch ? (m - m0) : ch;
-        switch (kc.dpad) {
-            case 2: pg_launch<2>(s, a, inverse); break;
-            case 4: pg_launch<4>(s, a, inverse); break;
-            case 8: pg_launch<8>(s, a, inverse); break;
-            case 16: pg_launch<16>(s, a, inverse); break;
-            default: pg_launch<32>(s, a, inverse); break;
-        }
+        apgp_by_dpad(kc.dpad, [&](auto dp) { pg_launch<decltype(dp)::value>(s, a, inverse); });
         APGP_CHECK_LAUNCH();
     }
     return 0;

@@ -15,6 +15,7 @@
 //     streams or devices do not serialise each other (round 2 had one process-wide mutex).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <chrono>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -101,6 +102,32 @@ inline ApgpMailbox* apgp_stream_mailbox(hipStream_t s) {
     }
     return &m;             // (std::map nodes are stable: the pointer stays valid)
 }
+
+// The host side of a sequence word (the mailbox's, or one per record of a batch in the staging area): wait(flag, seq) polls
+// until the kernel's last lane has written seq; once spin_us microseconds have passed since construction it falls back to
+// one hipStreamSynchronize and looks again.  One object per call: the records of a batch share the start time and the
+// one synchronisation.  Caller holds apgp_stream_lock(s) and words the error itself.
+struct ApgpSeqWait {
+    enum { OK = 0, SYNC_FAILED, NOT_WRITTEN };
+    hipStream_t s;
+    std::chrono::microseconds spin;
+    std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
+    bool synced = false;
+    ApgpSeqWait(hipStream_t s_, int spin_us) : s(s_), spin(spin_us) {}
+    int wait(const volatile double* word, long long seq) {
+        const volatile long long* flag = (const volatile long long*)word;
+        unsigned spins = 0;
+        while (__atomic_load_n(flag, __ATOMIC_ACQUIRE) != seq) {
+            if ((++spins & 255u) == 0 && std::chrono::steady_clock::now() - t0 > spin) {
+                if (synced) return NOT_WRITTEN;
+                if (hipStreamSynchronize(s) != hipSuccess) return SYNC_FAILED;
+                synced = true;
+                return __atomic_load_n(flag, __ATOMIC_ACQUIRE) != seq ? NOT_WRITTEN : OK;
+            }
+        }
+        return OK;
+    }
+};
 
 // pinned staging area of at least `doubles` doubles for the stream (host pointer; *dev = device alias); NULL if
 // pinned memory is unavailable.  Caller holds apgp_stream_lock(s) and has no kernel in flight that uses it.

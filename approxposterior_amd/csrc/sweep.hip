@@ -31,11 +31,8 @@
 #include "mma16.h"
 #include "scratch.h"
 #include "util_value.h"             // util_value: the utilities, shared with nmsearch.hip
-#include <chrono>
 #include <mutex>
 #include <stdlib.h>
-#include <type_traits>
-#include <utility>
 #include <string.h>
 
 #define SW_ROWS APGP_ROW_BLOCK       // 512 rows of W per tile
@@ -160,16 +157,6 @@ __global__ __launch_bounds__(1024) void argmin_final_kernel(const double* part_u
 // substitution form: the statically unrolled diagonal tiles are used up to this many 256-row blocks
 // (N <= 2048), the run-time-indexed body above that (see the matrix role)
 #define S2_STATIC_DIAG_NRB 8
-
-// compile-time loop (the body sees its index as a constant expression)
-template <int... Is, class F>
-__device__ __forceinline__ void s2_static_for_impl(std::integer_sequence<int, Is...>, F&& f) {
-    (f(std::integral_constant<int, Is>{}), ...);
-}
-template <int N, class F>
-__device__ __forceinline__ void s2_static_for(F&& f) {
-    s2_static_for_impl(std::make_integer_sequence<int, N>{}, f);
-}
 
 // which form of the feeder loop an instantiation gets (see the feeder role)
 // (Dpad = 32, round 5: the plain feeder -- an x chunk is 4352 bytes there, more than the four feeder wavefronts' four 1 KiB
@@ -590,7 +577,7 @@ __global__ __launch_bounds__(S2_THREADS, 1) void sweep2_kernel(SweepArgs a) {
                             load_a(av[0], nslot, 0);
                             load_b(bpar ^ 1, 0);
                         }
-                        s2_static_for<NP>([&](auto pr_) {
+                        static_for<NP>([&](auto pr_) {
                             constexpr int pr = decltype(pr_)::value;
                             if constexpr (pr >= PF && C < 15) {
                                 constexpr bool a0 = 2 * pr > C;
@@ -622,7 +609,7 @@ __global__ __launch_bounds__(S2_THREADS, 1) void sweep2_kernel(SweepArgs a) {
                         ++kc;
                     };
                     if constexpr (STATIC_DIAG) {
-                        if (a.n - S2_ROWS * jb >= S2_ROWS) s2_static_for<S2_CPB>(diag_c);
+                        if (a.n - S2_ROWS * jb >= S2_ROWS) static_for<S2_CPB>(diag_c);
                     }
                     for (; kc < nkc; ++kc) do_diag();
                 }
@@ -1735,9 +1722,10 @@ extern "C" int apgp_sweep_prune_select(const double* bmin, int64_t ncb, const in
 static void pr_fill_args(PruneArgs& p, const SweepArgs& a, double* bmin, double* part_u, long long* part_i) {
     p.T = a.T; p.xs = a.xs; p.mask = a.mask; p.bmin = bmin; p.part_u = part_u; p.part_i = part_i;
     p.m = a.m; p.ncb = pr_ncb(a.m); p.n = a.n;
-    p.ndim = a.ndim; p.kind = a.kind; p.has_box = a.has_box; p.lin_order = a.lin_order;
-    p.mean = a.mean; p.amp = a.amp; p.lin_coef = a.lin_coef; p.zeta = a.zeta; p.ybest = a.ybest;
-    for (int d = 0; d < APGP_MAX_DIM; ++d) { p.sc[d] = a.sc[d]; p.lw[d] = a.lw[d]; p.lo[d] = a.lo[d]; p.hi[d] = a.hi[d]; }
+    p.kind = a.kind; p.mean = a.mean; p.zeta = a.zeta; p.ybest = a.ybest;
+    apgp_fill_kernel(p, a);
+    p.has_box = a.has_box;
+    for (int d = 0; d < APGP_MAX_DIM; ++d) { p.lo[d] = a.lo[d]; p.hi[d] = a.hi[d]; }
     p.blk_list = NULL; p.blk_count = NULL; p.est = NULL;
 }
 
@@ -1836,16 +1824,10 @@ static int acquire_impl(bool solve, const double* T, int64_t m, int64_t idx_offs
         a.linv_bytes = (unsigned)wb; a.xs_bytes = (unsigned)xb; a.kslot_bytes = (unsigned)kb;
     }
     a.m = m; a.idx_offset = idx_offset;
-    a.ndim = kc.ndim; a.nrb = s2_nrb(n); a.kind = kind; a.n = (int)n;
-    a.has_box = lo != NULL;
-    a.mean = mean; a.amp = kc.amp; a.zeta = zeta; a.ybest = ybest;
-    a.lin_coef = kc.lin_coef; a.lin_order = kc.lin_order;
-    for (int d = 0; d < APGP_MAX_DIM; ++d) {
-        a.sc[d] = kc.sc[d];
-        a.lw[d] = kc.lw[d];
-        a.lo[d] = (lo && d < kc.ndim) ? lo[d] : 0.0;
-        a.hi[d] = (hi && d < kc.ndim) ? hi[d] : 0.0;
-    }
+    a.nrb = s2_nrb(n); a.kind = kind; a.n = (int)n;
+    a.mean = mean; a.zeta = zeta; a.ybest = ybest;
+    apgp_fill_kernel(a, kc);
+    apgp_fill_box(a, kc.ndim, lo, hi);
     a.blk_list = NULL; a.blk_count = NULL; a.list_lo = 0; a.list_hi = 0;
     hipStream_t s = (hipStream_t)stream;
     // the pruned arg-min: only the winner is asked for (mu / var / u per candidate need the full sweep), the switch
@@ -1853,24 +1835,9 @@ static int acquire_impl(bool solve, const double* T, int64_t m, int64_t idx_offs
     const int pr_mode = apgp_get_sweep_prune();
     const bool prune = pr_mode > 0 && kind != APGP_UTIL_NONE && !mu && !var && !u && part &&
                        m >= (pr_mode == 1 ? pr_min_m(n) : (int64_t)pr_mode);
-    int rc;
-    if (prune) {
-        switch (kc.dpad) {
-            case 2: rc = launch_pruned<2>(a, s, solve, part); break;
-            case 4: rc = launch_pruned<4>(a, s, solve, part); break;
-            case 8: rc = launch_pruned<8>(a, s, solve, part); break;
-            case 16: rc = launch_pruned<16>(a, s, solve, part); break;
-            default: rc = launch_pruned<32>(a, s, solve, part); break;
-        }
-    } else {
-        switch (kc.dpad) {
-            case 2: rc = launch_sweep<2>(a, s, solve); break;
-            case 4: rc = launch_sweep<4>(a, s, solve); break;
-            case 8: rc = launch_sweep<8>(a, s, solve); break;
-            case 16: rc = launch_sweep<16>(a, s, solve); break;
-            default: rc = launch_sweep<32>(a, s, solve); break;
-        }
-    }
+    const int rc = apgp_by_dpad(kc.dpad, [&](auto dp) {
+        return prune ? launch_pruned<decltype(dp)::value>(a, s, solve, part) : launch_sweep<decltype(dp)::value>(a, s, solve);
+    });
     if (rc != 0) return rc;
     if (kind != APGP_UTIL_NONE)
         hipLaunchKernelGGL(argmin_final_kernel, dim3(1), dim3(1024), 0, s, a.part_u, a.part_i, nblk, best);
@@ -1902,23 +1869,12 @@ extern "C" int apgp_prune_bounds(const double* T, int64_t m, const double* xs, i
     PruneArgs p;
     p.T = T; p.xs = xs; p.mask = mask; p.bmin = bmin_out; p.part_u = NULL; p.part_i = NULL;
     p.m = m; p.ncb = pr_ncb(m); p.n = n;
-    p.ndim = kc.ndim; p.kind = kind; p.has_box = lo != NULL; p.lin_order = kc.lin_order;
-    p.mean = mean; p.amp = kc.amp; p.lin_coef = kc.lin_coef; p.zeta = zeta; p.ybest = ybest;
-    for (int d = 0; d < APGP_MAX_DIM; ++d) {
-        p.sc[d] = kc.sc[d];
-        p.lw[d] = kc.lw[d];
-        p.lo[d] = (lo && d < kc.ndim) ? lo[d] : 0.0;
-        p.hi[d] = (hi && d < kc.ndim) ? hi[d] : 0.0;
-    }
+    p.kind = kind; p.mean = mean; p.zeta = zeta; p.ybest = ybest;
+    apgp_fill_kernel(p, kc);
+    apgp_fill_box(p, kc.ndim, lo, hi);
     p.blk_list = NULL; p.blk_count = NULL; p.est = NULL;
     hipStream_t s = (hipStream_t)stream;
-    switch (kc.dpad) {
-        case 2: launch_bound<2>(p, s, coarse != 0); break;
-        case 4: launch_bound<4>(p, s, coarse != 0); break;
-        case 8: launch_bound<8>(p, s, coarse != 0); break;
-        case 16: launch_bound<16>(p, s, coarse != 0); break;
-        default: launch_bound<32>(p, s, coarse != 0); break;
-    }
+    apgp_by_dpad(kc.dpad, [&](auto dp) { launch_bound<decltype(dp)::value>(p, s, coarse != 0); });
     APGP_CHECK_LAUNCH();
     return 0;
 }
@@ -2133,23 +2089,12 @@ extern "C" int apgp_acquire_fantasy(const double* T, int64_t m, int64_t idx_offs
     a.part_u = (double*)part;
     a.part_i = (long long*)((double*)part + nblk);
     a.m = m; a.idx_offset = idx_offset; a.ldc = ldc; a.pick_row = pick_row; a.n = n;
-    a.ndim = kc.ndim; a.j = j; a.kind = kind; a.has_box = lo != NULL; a.lin_order = kc.lin_order;
-    a.amp = kc.amp; a.diag_add = kc.diag_add; a.lin_coef = kc.lin_coef; a.zeta = zeta; a.ybest = ybest;
-    for (int d = 0; d < APGP_MAX_DIM; ++d) {
-        a.sc[d] = kc.sc[d];
-        a.lw[d] = kc.lw[d];
-        a.lo[d] = (lo && d < kc.ndim) ? lo[d] : 0.0;
-        a.hi[d] = (hi && d < kc.ndim) ? hi[d] : 0.0;
-    }
+    a.j = j; a.kind = kind; a.diag_add = kc.diag_add; a.zeta = zeta; a.ybest = ybest;
+    apgp_fill_kernel(a, kc);
+    apgp_fill_box(a, kc.ndim, lo, hi);
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid((unsigned)nblk), block(FT_THREADS);
-    switch (kc.dpad) {
-        case 2: hipLaunchKernelGGL(fantasy_kernel<2>, grid, block, 0, s, a); break;
-        case 4: hipLaunchKernelGGL(fantasy_kernel<4>, grid, block, 0, s, a); break;
-        case 8: hipLaunchKernelGGL(fantasy_kernel<8>, grid, block, 0, s, a); break;
-        case 16: hipLaunchKernelGGL(fantasy_kernel<16>, grid, block, 0, s, a); break;
-        default: hipLaunchKernelGGL(fantasy_kernel<32>, grid, block, 0, s, a); break;
-    }
+    apgp_by_dpad(kc.dpad, [&](auto dp) { hipLaunchKernelGGL(fantasy_kernel<decltype(dp)::value>, grid, block, 0, s, a); });
     hipLaunchKernelGGL(argmin_final_kernel, dim3(1), dim3(1024), 0, s, a.part_u, a.part_i, nblk, best);
     APGP_CHECK_LAUNCH();
     return 0;
@@ -2275,18 +2220,11 @@ extern "C" int apgp_predict_mean(const double* T, int64_t m, const double* xs, i
     KernConst kc;
     APGP_CHECK_ARG(apgp_make_kernconst(kern, &kc) == 0, "kernel parameters");
     MeanArgs a;
-    a.T = T; a.xs = xs; a.mu = mu; a.m = m; a.npad = apgp_npad(n); a.ndim = kc.ndim;
-    a.mean = mean; a.amp = kc.amp; a.lin_coef = kc.lin_coef; a.lin_order = kc.lin_order;
-    for (int d = 0; d < APGP_MAX_DIM; ++d) { a.sc[d] = kc.sc[d]; a.lw[d] = kc.lw[d]; }
+    a.T = T; a.xs = xs; a.mu = mu; a.m = m; a.npad = apgp_npad(n); a.mean = mean;
+    apgp_fill_kernel(a, kc);
     dim3 grid((unsigned)((m + 3) / 4)), block(256);
     hipStream_t s = (hipStream_t)stream;
-    switch (kc.dpad) {
-        case 2: hipLaunchKernelGGL(predict_mean_kernel<2>, grid, block, 0, s, a); break;
-        case 4: hipLaunchKernelGGL(predict_mean_kernel<4>, grid, block, 0, s, a); break;
-        case 8: hipLaunchKernelGGL(predict_mean_kernel<8>, grid, block, 0, s, a); break;
-        case 16: hipLaunchKernelGGL(predict_mean_kernel<16>, grid, block, 0, s, a); break;
-        default: hipLaunchKernelGGL(predict_mean_kernel<32>, grid, block, 0, s, a); break;
-    }
+    apgp_by_dpad(kc.dpad, [&](auto dp) { hipLaunchKernelGGL(predict_mean_kernel<decltype(dp)::value>, grid, block, 0, s, a); });
     APGP_CHECK_LAUNCH();
     return 0;
 }
@@ -2322,17 +2260,9 @@ extern "C" int apgp_predict_mean_host(const double* T_host, int64_t m, const dou
             const long long seq = ++mb->seq;
             hipLaunchKernelGGL(mailbox_post_kernel, dim3(1), dim3(1), 0, s, mb->dev, seq);
             APGP_CHECK_LAUNCH();
-            volatile long long* flag = (volatile long long*)(mb->host + 5);
-            const auto t0 = std::chrono::steady_clock::now();
-            unsigned spins = 0;
-            while (__atomic_load_n(flag, __ATOMIC_ACQUIRE) != seq) {
-                if ((++spins & 255u) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::microseconds(400)) {
-                    if (hipStreamSynchronize(s) != hipSuccess || __atomic_load_n(flag, __ATOMIC_ACQUIRE) != seq) {
-                        apgp_set_error("apgp_predict_mean_host: result not posted");
-                        return -2;
-                    }
-                    break;
-                }
+            if (ApgpSeqWait(s, 400).wait(mb->host + 5, seq) != ApgpSeqWait::OK) {
+                apgp_set_error("apgp_predict_mean_host: result not posted");
+                return -2;
             }
             memcpy(mu_host, io + tn, (size_t)m * sizeof(double));
             return 0;
