@@ -199,8 +199,14 @@ def test_linear_kernel_term_parity(order, fit_amp, n, d, lib_loaded):
     cond = np.linalg.cond(gpo.kernel.get_value(X) + np.exp(-8.0) * np.eye(n))
     tol = max(1e-11, 500 * cond * EPS)
     assert abs(gp.log_likelihood(y) - llo) <= tol * abs(llo)
-    g, g0 = gp.grad_log_likelihood(y), gpo.grad_log_likelihood(y)
-    assert np.allclose(g, g0, rtol=tol, atol=tol * np.abs(g0).max())
+    g0 = gpo.grad_log_likelihood(y)
+    for mode in (None, "solve"):            # ("solve": K^-1 by apgp_kinv_solve, the route above the conditioning gate)
+        gp.variance_mode = mode
+        try:
+            g = gp.grad_log_likelihood(y)
+        finally:
+            gp.variance_mode = None
+        assert np.allclose(g, g0, rtol=tol, atol=tol * np.abs(g0).max())
     T = rs.uniform(-2.2, 2.2, size=(333, d))
     mo, vo = gpo.predict(y, T, return_var=True)
     scale = np.abs(gpo.kernel.get_value(T, diag=True)).max()
@@ -681,11 +687,13 @@ def test_gradient_many_tiles(n, d, lib_loaded):
         return g
     gpo, gp = make(go), make(agp)
     want = gpo.grad_log_likelihood(y, quiet=True)
-    got = gp.grad_log_likelihood(y, quiet=True)
     K = gpo.kernel.get_value(gpo._x)
     K[np.diag_indices_from(K)] += np.exp(-9.0)
     tol = max(1e-11, 500 * np.linalg.cond(K) * EPS)
-    assert np.allclose(got, want, rtol=tol, atol=tol * np.abs(want).max())
+    for mode in (None, "solve"):            # (None: the explicit inverse for this K; "solve": apgp_kinv_solve, 21 block rows)
+        gp.variance_mode = mode
+        got = gp.grad_log_likelihood(y, quiet=True)
+        assert np.allclose(got, want, rtol=tol, atol=tol * np.abs(want).max())
 
 
 @pytest.mark.parametrize("m", [5000, 40000])
