@@ -161,25 +161,13 @@ __global__ __launch_bounds__(256) void autocorr_reduce_kernel(AcShape sh, double
 }
 
 int ac_prepare_lds(hipStream_t s) {
-    static std::mutex mu;
-    static bool done[64] = {false};
+    static ApgpLdsOnce once;
     const int dev = apgp_stream_device(s);
     if (dev < 0 || dev >= 64) {
         apgp_set_error("apgp_autocorr_block: no device for the stream");
         return -2;
     }
-    std::lock_guard<std::mutex> g(mu);
-    if (!done[dev]) {
-        const hipError_t e = hipFuncSetAttribute((const void*)autocorr_lag_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                 (int)(AC_ROWS * 64 * sizeof(double)));
-        if (e != hipSuccess) {
-            apgp_set_error("apgp_autocorr_block: hipFuncSetAttribute(%d B of LDS) failed: %s", (int)(AC_ROWS * 64 * sizeof(double)),
-                           hipGetErrorString(e));
-            return -2;
-        }
-        done[dev] = true;
-    }
-    return 0;
+    return apgp_raise_lds(once, "apgp_autocorr_block", dev, (int)(AC_ROWS * 64 * sizeof(double)), {(const void*)autocorr_lag_kernel});
 }
 
 bool ac_sizes_ok(int64_t n_t, int64_t n_w, int32_t n_d) {

@@ -456,40 +456,18 @@ extern "C" int apgp_ensemble_mode(int mode) {
 // in the caller.)
 template <int DP, bool AM>
 static int ens_launch_mw(const EnsMwArgs& q, dim3 grid, size_t xbytes, bool xlds, int dev, hipStream_t s) {
-    static std::mutex attr_mu;
-    static bool attr_done[64] = {false};
-    if (xlds) {
-        std::lock_guard<std::mutex> lk(attr_mu);
-        if (!attr_done[dev]) {
-            if (hipFuncSetAttribute((const void*)ensemble_mw_kernel<DP, true, AM>,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024) != hipSuccess) {
-                apgp_set_error("apgp_ensemble_sample_moves: hipFuncSetAttribute(96 KiB of LDS) failed");
-                return -2;
-            }
-            attr_done[dev] = true;
-        }
-    }
+    static ApgpLdsOnce once;
+    if (xlds && apgp_raise_lds(once, "apgp_ensemble_sample_moves", dev, 96 * 1024, {(const void*)ensemble_mw_kernel<DP, true, AM>}) != 0)
+        return -2;
     if (xlds) hipLaunchKernelGGL((ensemble_mw_kernel<DP, true, AM>), grid, dim3(256), xbytes, s, q);
     else hipLaunchKernelGGL((ensemble_mw_kernel<DP, false, AM>), grid, dim3(256), 0, s, q);
     return 0;
 }
 template <int DP, bool AM>
 static int ens_launch(const EnsArgs& a, dim3 grid, size_t xbytes, bool xlds, int dev, hipStream_t s) {
-    static std::mutex attr_mu;
-    static bool attr_done[64] = {false};
-    if (xlds) {
-        std::lock_guard<std::mutex> lock(attr_mu);
-        if (!attr_done[dev]) {
-            const hipError_t e = hipFuncSetAttribute((const void*)ensemble_kernel<DP, true, AM>,
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-            if (e != hipSuccess) {
-                apgp_set_error("apgp_ensemble_sample_moves: hipFuncSetAttribute(96 KiB of LDS) failed on device %d: %s",
-                               dev, hipGetErrorString(e));
-                return -2;
-            }
-            attr_done[dev] = true;
-        }
-    }
+    static ApgpLdsOnce once;
+    if (xlds && apgp_raise_lds(once, "apgp_ensemble_sample_moves", dev, 96 * 1024, {(const void*)ensemble_kernel<DP, true, AM>}) != 0)
+        return -2;
     if (xlds) hipLaunchKernelGGL((ensemble_kernel<DP, true, AM>), grid, dim3(1024), xbytes, s, a);
     else hipLaunchKernelGGL((ensemble_kernel<DP, false, AM>), grid, dim3(1024), 0, s, a);
     return 0;

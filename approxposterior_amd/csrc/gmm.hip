@@ -197,24 +197,14 @@ int gmm_launch(const GmmArgs& a, int nb, size_t lds, hipStream_t s) {
     // the limit is declared once per device and instantiation, so it is the instantiation's largest need (K = 16),
     // not this call's: a later call with more components must not launch above what was declared
     constexpr size_t lds_max = gmm_lds_bytes(DP, GMM_MAX_K);
-    static std::mutex mu;
-    static bool done[64] = {false};
+    static ApgpLdsOnce once;
     if (lds_max > 65536) {
         const int dev = apgp_stream_device(s);
         if (dev < 0 || dev >= 64) {
             apgp_set_error("apgp_gmm_pass: no device for the stream");
             return -2;
         }
-        std::lock_guard<std::mutex> g(mu);
-        if (!done[dev]) {
-            const hipError_t e = hipFuncSetAttribute((const void*)gmm_pass_kernel<DP, MODE>,
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max);
-            if (e != hipSuccess) {
-                apgp_set_error("apgp_gmm_pass: hipFuncSetAttribute(%d B of LDS) failed: %s", (int)lds_max, hipGetErrorString(e));
-                return -2;
-            }
-            done[dev] = true;
-        }
+        if (apgp_raise_lds(once, "apgp_gmm_pass", dev, (int)lds_max, {(const void*)gmm_pass_kernel<DP, MODE>}) != 0) return -2;
     }
     hipLaunchKernelGGL((gmm_pass_kernel<DP, MODE>), dim3((unsigned)nb), dim3(GMM_NT), lds, s, a);
     return 0;

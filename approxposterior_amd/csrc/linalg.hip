@@ -718,30 +718,14 @@ extern "C" int apgp_trsv(const double* L, int64_t n, int64_t ldl, const double* 
         APGP_CHECK_LAUNCH();
         return 0;
     }
-    APGP_CHECK_ARG(n <= 15360, "n <= 15360 (right-hand side is kept in LDS)");
+    // n < 256 here (both n >= 256 branches return): the single-workgroup form keeps the right-hand side in LDS
     TrsvArgs a;
     a.L = L; a.b = b; a.x = x; a.sumsq = sumsq; a.n = n; a.ldl = ldl; a.shift = shift;
     a.trans = trans;
     size_t nr = (size_t)apgp_round_up(n, 64);
     size_t lds = (nr + TRSV_B * (TRSV_B + 1) + 16 * 64) * sizeof(double);
-    {
-        // per device, checked (the single-workgroup form keeps the right-hand side in LDS)
-        static std::mutex attr_mu;
-        static bool attr_set[64] = {false};
-        int dev = 0;
-        if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) {
-            apgp_set_error("apgp_trsv: hipGetDevice failed");
-            return -2;
-        }
-        std::lock_guard<std::mutex> lock(attr_mu);
-        if (!attr_set[dev]) {
-            if (hipFuncSetAttribute((const void*)trsv_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) {
-                apgp_set_error("apgp_trsv: hipFuncSetAttribute failed");
-                return -2;
-            }
-            attr_set[dev] = true;
-        }
-    }
+    // at most (256 + 64 * 65 + 16 * 64) * 8 = 43,520 B: under the 64 KiB a launch may take without raising the kernel's limit
+    static_assert((256 + TRSV_B * (TRSV_B + 1) + 16 * 64) * sizeof(double) <= 64 * 1024, "trsv_kernel at n < 256 needs no LDS attribute");
     hipLaunchKernelGGL(trsv_kernel, dim3(1), dim3(1024), lds, (hipStream_t)stream, a);
     APGP_CHECK_LAUNCH();
     return 0;

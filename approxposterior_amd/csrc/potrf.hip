@@ -18,35 +18,37 @@
 #include "apgp_common.h"
 #include "mma16.h"
 #include "scratch.h"
+#include <algorithm>
 #include <atomic>
 #include <mutex>
 
 #define PB 64
 #define CB 4     // columns per step of the diagonal-block factorisation (potrf_panel_kernel)
 
+// (every field has a default: a field the host's one builder -- potrf_args -- does not name is 0, never indeterminate)
 struct PotrfArgs {
-    double* A;
-    double* rhs;         // optional right-hand side carried through the factorisation
-    long long n, lda;
-    long long j0;        // first column of the current block
-    double shift;        // rhs is used as (rhs - shift); applied at block step 0 .. as read
-    int* info;
+    double* A = nullptr;
+    double* rhs = nullptr;   // optional right-hand side carried through the factorisation
+    long long n = 0, lda = 0;
+    long long j0 = 0;        // first column of the current block
+    double shift = 0.0;      // rhs is used as (rhs - shift); applied at block step 0 .. as read
+    int* info = nullptr;
     // factored diagonal blocks, nb x 64 x 64 per matrix (NULL: written straight into A).  A panel
     // workgroup reads the raw block from A when it starts and stores rows of the factor when it ends;
     // sibling workgroups are not guaranteed to start together, so the factor goes here and is copied
     // into A by potrf_finish_kernel.
-    double* out5;            // optional (apgp_nll_eval): potrf_finish_kernel also writes the 5-value fit summary
-    double* mail;            // optional: ... and (matrix 0) into the stream's pinned mailbox, sequence word last
-    long long seq;
-    double* dscr;
-    long long batch_dscr;    // per matrix: nb * 64 * 64 factor blocks, then nb * 64 entries of the forward solve (same hazard)
-    long long zoff;          // offset of the latter
+    double* out5 = nullptr;  // optional (apgp_nll_eval): potrf_finish_kernel also writes the 5-value fit summary
+    double* mail = nullptr;  // optional: ... and (matrix 0) into the stream's pinned mailbox, sequence word last
+    long long seq = 0;
+    double* dscr = nullptr;
+    long long batch_dscr = 0;    // per matrix: nb * 64 * 64 factor blocks, then nb * 64 entries of the forward solve (same hazard)
+    long long zoff = 0;          // offset of the latter
     // batched factorisation (apgp_nll_eval_batch): blockIdx.y selects the matrix
-    long long batch_A, batch_rhs;   // element strides between consecutive matrices / right-hand sides
+    long long batch_A = 0, batch_rhs = 0;   // element strides between consecutive matrices / right-hand sides
     // persistent factorisation (potrf_persist.h): *abort_word == abort_id <=> the launch gave up; potrf_finish_kernel
     // then reports PP_ABORTED in the summary's info slot and the host re-runs on the multi-launch path
-    const unsigned long long* abort_word;
-    unsigned long long abort_id;
+    const unsigned long long* abort_word = nullptr;
+    unsigned long long abort_id = 0;
     // batched persistent factorisation (round 6): matrix y's abort word / mailbox record lie y * batch_abort words /
     // y * batch_mail doubles further on (0, 0: one abort word, the record of matrix 0 only -- everything before round 6)
     long long batch_abort = 0, batch_mail = 0;
@@ -54,21 +56,22 @@ struct PotrfArgs {
     // launch on the trailing matrix): the step that hands over applies its block column to the whole trailing matrix and
     // writes the first tile column back instead of carrying on with the panel (no_panel); the persistent launch sees the
     // trailing matrix as its own (A, rhs, dscr shifted) and reports failing pivots in the full matrix's numbering (info_j0)
-    int no_panel;
-    long long info_j0;
+    int no_panel = 0;
+    long long info_j0 = 0;
     // paired trailing updates (large trailing matrices, where a step is bound by the update's memory traffic): a NARROW
     // step (pair_mode 1) applies its block column to the first TWO tile columns only, the WIDE step after it (2) applies
     // both block columns to every other tile in ONE pass over the tile -- two products, each accumulated from zero and
     // subtracted in turn: the bits of two separate passes, half their traffic.  0 = every step applies its own column.
-    int pair_mode;
+    int pair_mode = 0;
     // DEFERRED tiles (round 5): a narrow step is a latency chain (first tile + panel, ~25 us) on ~2 tb workgroups with the
     // rest of the chip idle, the wide step before it is bound by its update.  A wide step therefore leaves `defer8` eighths
     // of its tiles right of the next narrow step's two tile columns (block columns >= 3 of its trailing matrix; tile e of
     // that triangle is deferred iff e % 8 < defer8) to the NEXT launch, whose `deferred8` says so: extra workgroups of the
     // narrow step apply the two earlier block columns to them, exactly as the wide step would have (same products, same
     // order: same bits), while the panel chain runs.  0 = nothing deferred.
-    int defer8, deferred8;
+    int defer8 = 0, deferred8 = 0;
 };
+static_assert(std::is_trivially_copyable<PotrfArgs>::value, "a kernel argument");
 
 // tile e (row r, column c of the lower triangle, 0 <= c <= r) of a triangle, e = r (r + 1) / 2 + c
 __device__ __forceinline__ void potrf_tri(long long e, long long& r, long long& c) {
@@ -540,24 +543,25 @@ __global__ __launch_bounds__(192) void potrf_panel_kernel(PotrfArgs a) {
 // configuration (C1: N = 50 .. 90, 722-3,122 evaluations per optimizeGP) lives.
 // ---------------------------------------------------------------------------
 struct NllSmallArgs {
-    const double* X;
-    const double* y;
-    double* K;           // n x n (ld n): the factor on return (lower triangle)
-    double* z;           // n: L^-1 (y - shift)
-    int* info;
-    double* out5;
-    long long n;
-    double shift;
-    KernConst kc;
-    double* mail;        // optional: pinned, device-mapped host record (5 doubles + sequence word)
-    long long seq;
+    const double* X = nullptr;
+    const double* y = nullptr;
+    double* K = nullptr;     // n x n (ld n): the factor on return (lower triangle)
+    double* z = nullptr;     // n: L^-1 (y - shift)
+    int* info = nullptr;
+    double* out5 = nullptr;
+    long long n = 0;
+    double shift = 0.0;
+    KernConst kc = {};
+    double* mail = nullptr;  // optional: pinned, device-mapped host record (5 doubles + sequence word)
+    long long seq = 0;
     // batched launch (apgp_nll_eval_batch at n <= 128: gridDim.x matrices of the SAME training set, one workgroup each):
     // matrix b takes its kernel constants from bkc[b] and its shift from bshift[b] (device-mapped host memory, read once
     // into LDS), works in K + b n^2, z + b n, info + b, out5 + 5 b and posts its record + sequence word at brec + 8 b
-    const KernConst* bkc;
-    const double* bshift;
-    double* brec;
+    const KernConst* bkc = nullptr;
+    const double* bshift = nullptr;
+    double* brec = nullptr;
 };
+static_assert(std::is_trivially_copyable<NllSmallArgs>::value, "a kernel argument");
 // this workgroup's matrix of a batched launch: the constants into LDS, the pointers moved on
 template <bool BATCH>
 __device__ __forceinline__ void nll_batch_select(NllSmallArgs& q, KernConst* kcb) {
@@ -863,25 +867,14 @@ __global__ __launch_bounds__(256) void nll_two_kernel(NllSmallArgs q) {
 // the kernel's dynamic LDS exceeds 64 KiB: the attribute is set once per device and instantiation
 template <int DPAD, bool BATCH>
 static int nll_two_launch_t(const NllSmallArgs& q, int batch, hipStream_t s) {
-    static bool done[64] = {false};
-    static std::mutex mu;
+    static ApgpLdsOnce once;
     const int lds = (int)(nll_two_lds_doubles<DPAD>() * sizeof(double));
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) {
         apgp_set_error("apgp_nll_eval: hipGetDevice failed");
         return -2;
     }
-    {
-        std::lock_guard<std::mutex> lock(mu);
-        if (!done[dev]) {
-            const hipError_t e = hipFuncSetAttribute((const void*)nll_two_kernel<DPAD, BATCH>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-            if (e != hipSuccess) {
-                apgp_set_error("apgp_nll_eval: hipFuncSetAttribute(%d B of LDS) failed on device %d: %s", lds, dev, hipGetErrorString(e));
-                return -2;
-            }
-            done[dev] = true;
-        }
-    }
+    if (apgp_raise_lds(once, "apgp_nll_eval", dev, lds, {(const void*)nll_two_kernel<DPAD, BATCH>}) != 0) return -2;
     hipLaunchKernelGGL((nll_two_kernel<DPAD, BATCH>), dim3((unsigned)batch), dim3(256), lds, s, q);
     APGP_CHECK_LAUNCH();
     return 0;
@@ -901,7 +894,7 @@ static int nll_fused_launch(const double* X, int64_t n, const apgp_kernel_t* ker
                             double* K, double* z, int32_t* info_dev, double* out5_dev, hipStream_t s,
                             double* mail = nullptr, long long seq = 0) {
     NllSmallArgs q;
-    q.mail = mail; q.seq = seq; q.bkc = nullptr; q.bshift = nullptr; q.brec = nullptr;
+    q.mail = mail; q.seq = seq;
     if (apgp_make_kernconst(kern, &q.kc) != 0) {
         apgp_set_error("apgp_nll_eval: bad argument: kernel parameters");
         return -1;
@@ -1211,7 +1204,13 @@ __global__ __launch_bounds__(256) void potrf_finish_kernel(PotrfArgs a) {
 // 0 = persistent where it applies (default) | 1 = multi-launch path only | 2 = persistent, workgroup 0 gives up at
 // once (exercises the fallback) | 3 = persistent wherever it can run (n <= 4096).  A test / profiling switch
 // (apgp_potrf_mode), not read from the environment.
-static std::atomic<int> g_potrf_mode{0};
+enum { POTRF_AUTO = 0, POTRF_STEPS_ONLY = 1, POTRF_GIVE_UP_TEST = 2, POTRF_PERSIST_WHEREVER = 3 };   // (the ABI's integers)
+static std::atomic<int> g_potrf_mode{POTRF_AUTO};
+// may the single-launch forms run (nll_two_kernel, the side-by-side batch)?  The two test modes keep the separate launches.
+static bool potrf_mode_fused_ok() {
+    const int mode = g_potrf_mode.load();
+    return mode == POTRF_AUTO || mode == POTRF_PERSIST_WHEREVER;
+}
 // paired trailing updates of the launch-per-step path (PotrfArgs::pair_mode) from this many trailing block rows on;
 // apgp_potrf_mode(mode | 16) switches them off (A/B and bit-identity tests), plain modes switch them on again
 #define POTRF_PAIR_MIN_TB 24
@@ -1285,56 +1284,103 @@ static int potrf_device_cus(int dev) {
 #ifndef PP_HYBRID_NB
 #define PP_HYBRID_NB 44
 #endif
+// update workgroups of a persistent launch, in per cent of its first update step's tiles (pp_update_workgroups)
+#ifndef PP_NUPD_PCT
+#define PP_NUPD_PCT 30
+#endif
 static long long potrf_plan(int64_t n, int64_t lda, hipStream_t s) {
     const int mode = g_potrf_mode.load();
-    if (mode == 1) return -1;
+    if (mode == POTRF_STEPS_ONLY) return -1;
     const int64_t nb = (n + PB - 1) / PB;
     if (nb < 2) return -1;
     const int cus = potrf_device_cus(apgp_stream_device(s));
-    if (nb <= PP_MAX_NB && (nb <= PP_AUTO_NB || mode == 3)) {
+    if (nb <= PP_MAX_NB && (nb <= PP_AUTO_NB || mode == POTRF_PERSIST_WHEREVER)) {
         if (lda * n * 8 >= (1ll << 31) || cus < nb + 1) return -1;
         return 0;
     }
-    if (mode == 2) return -1;                                            // (the fallback test runs whole persistent launches)
+    if (mode == POTRF_GIVE_UP_TEST) return -1;                           // (the fallback test runs whole persistent launches)
     const long long s0 = nb - PP_HYBRID_NB;
     if (lda * (n - s0 * PB) * 8 >= (1ll << 31) || cus < PP_HYBRID_NB + 1) return -1;
     return s0;
+}
+
+// The one place a PotrfArgs is filled: what every launch path sets alike for matrices of order n -- the matrix, its
+// right-hand side, the records, and the scratch layout of nb = ceil(n / 64) block columns (zoff, batch_dscr).  A path
+// then sets only what is its own (batch strides, dscr, the abort word, the step fields); everything else is 0.
+static PotrfArgs potrf_args(double* A, int64_t n, int64_t lda, double* rhs, int32_t* info, double* out5, double* mail,
+                            long long seq) {
+    const long long nb = (n + PB - 1) / PB;
+    PotrfArgs a;
+    a.A = A; a.rhs = rhs; a.n = n; a.lda = lda; a.info = info; a.out5 = out5; a.mail = mail; a.seq = seq;
+    a.batch_rhs = n;
+    a.zoff = nb * (long long)(PB * PB); a.batch_dscr = a.zoff + nb * PB;
+    return a;
+}
+
+// The set-up of a persistent launch of `batch` factorisations: the stream's slot-2 scratch (PP_SCRATCH_WORDS per matrix:
+// control words and granule streams), zeroed when it is new, and the id of this call -- the flags and granule tags carry
+// it, so the scratch is never cleared between calls; when its 32-bit tag wraps, the scratch starts over.  `entry` words
+// the errors.  Caller holds apgp_stream_lock(s).
+struct PpScratch { pp_u64* pw = nullptr; pp_u64 id = 0; };
+static int pp_prepare(hipStream_t s, int64_t batch, const char* entry, PpScratch& p) {
+    const size_t words = (size_t)PP_SCRATCH_WORDS * (size_t)batch;
+    bool fresh = false;
+    unsigned long long* calls = nullptr;
+    p.pw = (pp_u64*)apgp_stream_scratch_ex(2, s, words, &fresh, &calls);
+    if (!p.pw) {
+        apgp_set_error("%s: scratch allocation failed", entry);
+        return -2;
+    }
+    p.id = ++*calls;
+    if ((unsigned)p.id == 0u) { fresh = true; p.id = ++*calls; }         // (the 32-bit granule tag wrapped: start over)
+    if (fresh && hipMemsetAsync(p.pw, 0, words * 8, s) != hipSuccess) {
+        apgp_set_error("%s: memset failed", entry);
+        return -2;
+    }
+    return 0;
+}
+// matrix m's share of that scratch, and what else a persistent kernel is told beside q.a
+static void pp_fill(PersistArgs& q, const PpScratch& p, int64_t m, long long nb, int debug) {
+    q.ctl = p.pw + m * (long long)PP_SCRATCH_WORDS; q.strm = q.ctl + PP_CTL_WORDS; q.zstrm = q.strm + PP_STRM_WORDS;
+    q.a.abort_word = q.ctl + PP_CTL_ABORT; q.a.abort_id = p.id;
+    q.call_id = p.id;
+    q.timeout = 5000000ull;                                             // 50 ms of the 100 MHz clock
+    q.nb = (int)nb;
+    q.debug = debug;
+}
+// Update workgroups of a persistent launch of nb block columns with `room` CUs left beside its nb row workgroups.
+// Not one per tile of the first update step (tiles0): a tile takes ~3.5 us of a 20 us step, and every further update
+// workgroup costs the row workgroups memory latency -- PP_NUPD_PCT = 30 % of the first step's tiles + 8 measured best:
+// 0.361 vs 0.369 ms at n = 1152, 0.521 vs 0.550 at 1600, 0.689 vs 0.716 at 2048, unchanged from 2560 on, where the
+// CUs left beside the row workgroups are the limit.
+// (The single launch used to clamp tiles0 by room, then by want; the batched one want by tiles0, then by room; both
+// then raised the result to 1.  min is associative and commutative, so either order is max(1, min(tiles0, want, room)).)
+static long long pp_update_workgroups(long long nb, long long room) {
+    const long long tiles0 = (nb - 1) * (nb - 2) / 2;                   // tiles of the first update step
+    const long long want = (tiles0 * PP_NUPD_PCT + 99) / 100 + 8;
+    return std::max(1ll, std::min(tiles0, std::min(want, room)));
 }
 
 // gram (pre_init) -> ONE persistent launch -> potrf_finish_kernel (summary, factored diagonal blocks into place).
 // Caller holds apgp_stream_lock(s).  The summary's info slot reads PP_ABORTED if the launch gave up.
 // s0 > 0 (hybrid): block columns 0 .. s0 - 1 were factorised and applied to the whole trailing matrix by the
 // launch-per-step path (z blocks and running right-hand side included); this launch factorises the trailing matrix.
-// cu_budget > 0: the CUs this launch may count on (apgp_nll_eval_batch runs several launches side by side).
 static int potrf_persist_locked(double* A, int64_t n, int64_t lda, double* z, int32_t* info_dev, hipStream_t s,
-                                double* out5, double* mail, long long seq, long long s0 = 0, int cu_budget = 0) {
+                                double* out5, double* mail, long long seq, long long s0 = 0) {
+    static ApgpLdsOnce lds_once;
     const int dev = apgp_stream_device(s);
     const long long nb_all = (n + PB - 1) / PB, nb = nb_all - s0;
     PersistArgs q;
     PotrfArgs& a = q.a;
-    a.A = A; a.rhs = z; a.n = n; a.lda = lda; a.j0 = 0; a.shift = 0.0; a.info = info_dev; a.out5 = out5;
-    a.mail = mail; a.seq = seq; a.batch_A = 0; a.batch_rhs = n; a.no_panel = 0; a.info_j0 = 0; a.pair_mode = 0; a.defer8 = 0; a.deferred8 = 0;
-    a.zoff = nb_all * (long long)(PB * PB); a.batch_dscr = a.zoff + nb_all * PB;
+    a = potrf_args(A, n, lda, z, info_dev, out5, mail, seq);
     a.dscr = apgp_stream_scratch(0, s, (size_t)a.batch_dscr);
-    bool fresh = false;
-    unsigned long long* calls = nullptr;
-    pp_u64* pw = (pp_u64*)apgp_stream_scratch_ex(2, s, (size_t)PP_SCRATCH_WORDS, &fresh, &calls);
-    if (!a.dscr || !pw) {
+    if (!a.dscr) {
         apgp_set_error("apgp_potrf: scratch allocation failed");
         return -2;
     }
-    unsigned long long id = ++*calls;
-    if ((unsigned)id == 0u) { fresh = true; id = ++*calls; }             // (the 32-bit granule tag wrapped: start over)
-    if (fresh && hipMemsetAsync(pw, 0, (size_t)PP_SCRATCH_WORDS * 8, s) != hipSuccess) {
-        apgp_set_error("apgp_potrf: memset failed");
-        return -2;
-    }
-    q.ctl = pw; q.strm = pw + PP_CTL_WORDS; q.zstrm = q.strm + PP_STRM_WORDS;
-    q.call_id = id;
-    q.timeout = 5000000ull;                                             // 50 ms of the 100 MHz clock
-    q.nb = (int)nb;
-    q.debug = g_potrf_mode.load() == 2 ? 1 : 0;
-    a.abort_word = pw + PP_CTL_ABORT; a.abort_id = id;
+    PpScratch p;
+    if (pp_prepare(s, 1, "apgp_potrf", p) != 0) return -2;
+    pp_fill(q, p, 0, nb, g_potrf_mode.load() == POTRF_GIVE_UP_TEST ? 1 : 0);
     const PotrfArgs full = a;                                           // (the finish kernel works on the whole matrix)
     if (s0 > 0) {
         const long long off = s0 * PB;
@@ -1345,31 +1391,8 @@ static int potrf_persist_locked(double* A, int64_t n, int64_t lda, double* z, in
         a.dscr = full.dscr + s0 * (long long)(PB * PB);
         a.info_j0 = off;
     }
-    {
-        static std::mutex attr_mu;
-        static bool attr_set[64] = {false};
-        std::lock_guard<std::mutex> lock(attr_mu);
-        if (dev >= 0 && dev < 64 && !attr_set[dev]) {
-            if (hipFuncSetAttribute((const void*)potrf_persist_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, PP_LDS_BYTES) != hipSuccess) {
-                apgp_set_error("apgp_potrf: hipFuncSetAttribute failed");
-                return -2;
-            }
-            attr_set[dev] = true;
-        }
-    }
-    const long long tiles0 = (nb - 1) * (nb - 2) / 2;                   // tiles of the first update step: one per workgroup
-    long long nupd = tiles0;
-    const long long room = (cu_budget > 0 ? cu_budget : potrf_device_cus(dev)) - nb;
-    if (nupd > room) nupd = room;
-    // (not one workgroup per tile of the first update step: a tile takes ~3.5 us of a 20 us step, and every further
-    // update workgroup costs the row workgroups memory latency -- 30 % of the first step's tiles + 8 measured best:
-    // 0.361 vs 0.369 ms at n = 1152, 0.521 vs 0.550 at 1600, 0.689 vs 0.716 at 2048, unchanged from 2560 on, where the
-    // CUs left beside the row workgroups are the limit)
-#ifndef PP_NUPD_PCT
-#define PP_NUPD_PCT 30
-#endif
-    { const long long want = (tiles0 * PP_NUPD_PCT + 99) / 100 + 8; if (nupd > want) nupd = want; }
-    if (nupd < 1) nupd = 1;
+    if (apgp_raise_lds(lds_once, "apgp_potrf", dev, PP_LDS_BYTES, {(const void*)potrf_persist_kernel}) != 0) return -2;
+    const long long nupd = pp_update_workgroups(nb, potrf_device_cus(dev) - nb);
     hipLaunchKernelGGL(potrf_persist_kernel, dim3((unsigned)(nb + nupd)), dim3(PP_THREADS), PP_LDS_BYTES, s, q);
     hipLaunchKernelGGL(potrf_finish_kernel, dim3((unsigned)nb_all, 1u), dim3(256), 0, s, full);
     APGP_CHECK_LAUNCH();
@@ -1392,11 +1415,8 @@ static int potrf_run_locked(double* A, int64_t n, int64_t lda, int64_t batch, in
         apgp_set_error("apgp_potrf: memset failed");
         return -2;
     }
-    PotrfArgs a;
-    a.A = A; a.rhs = z; a.n = n; a.lda = lda; a.shift = 0.0; a.info = info_dev; a.out5 = out5;
-    a.mail = mail; a.seq = seq;
-    a.batch_A = batch_A; a.batch_rhs = n;
-    a.abort_word = nullptr; a.abort_id = 0; a.no_panel = 0; a.info_j0 = 0; a.pair_mode = 0; a.defer8 = 0; a.deferred8 = 0;
+    PotrfArgs a = potrf_args(A, n, lda, z, info_dev, out5, mail, seq);
+    a.batch_A = batch_A;
     if (z && !pre_init)
         for (int64_t b = 0; b < batch; ++b)
             hipLaunchKernelGGL(potrf_rhs_init_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, y, shifts[b],
@@ -1404,7 +1424,6 @@ static int potrf_run_locked(double* A, int64_t n, int64_t lda, int64_t batch, in
     const long long nb = (n + PB - 1) / PB;
     // block column 0: panel step alone; then one launch per step = trailing update of column jb +
     // panel step of column jb + 1 (potrf_step_kernel)
-    a.dscr = nullptr; a.zoff = nb * (long long)(PB * PB); a.batch_dscr = a.zoff + nb * PB;
     if (nb > 1) {
         a.dscr = apgp_stream_scratch(0, s, (size_t)a.batch_dscr * (size_t)batch);
         if (!a.dscr) {
@@ -1413,7 +1432,6 @@ static int potrf_run_locked(double* A, int64_t n, int64_t lda, int64_t batch, in
         }
     }
     {
-        a.j0 = 0;
         const long long below = n - PB;
         const unsigned pg = below > 0 ? (unsigned)((below + PB - 1) / PB) : 1u;
         hipLaunchKernelGGL(potrf_panel_kernel, dim3(pg, (unsigned)batch), dim3(3 * PB), 0, s, a);
@@ -1424,7 +1442,7 @@ static int potrf_run_locked(double* A, int64_t n, int64_t lda, int64_t batch, in
     // a wide step defers part of its tiles to the narrow step that follows it, if one does (PotrfArgs::defer8)
     const bool pairs = g_potrf_pairs.load() != 0;
     const int defer_cfg = g_potrf_defer8.load();
-    auto narrow_at = [&](long long jb_) {                                  // would step jb_ be a narrow one (after a wide one)?
+    auto narrow_at = [&](long long jb_) {                                  // is step jb_ a narrow one, unless the step before it is?
         const long long tb_ = (n - (jb_ * PB + PB) + PB - 1) / PB;
         return pairs && jb_ + 1 < nb && tb_ >= POTRF_PAIR_MIN_TB && jb_ + 1 <= last;
     };
@@ -1433,7 +1451,7 @@ static int potrf_run_locked(double* A, int64_t n, int64_t lda, int64_t batch, in
         a.j0 = jb * PB;
         a.no_panel = (stop_at > 0 && jb == stop_at - 1) ? 1 : 0;
         const long long tb = (n - (a.j0 + PB) + PB - 1) / PB;
-        a.pair_mode = prev_mode == 1 ? 2 : ((pairs && tb >= POTRF_PAIR_MIN_TB && jb + 1 <= last) ? 1 : 0);
+        a.pair_mode = prev_mode == 1 ? 2 : (narrow_at(jb) ? 1 : 0);
         prev_mode = a.pair_mode;
         a.deferred8 = a.pair_mode == 1 ? prev_defer : 0;
         const long long E = (tb - 3) * (tb - 2) / 2;                       // this step's eligible triangle (from block (3, 3) on)
@@ -1524,41 +1542,41 @@ extern "C" int apgp_nll_eval(const double* X, int64_t n, const apgp_kernel_t* ke
         // one single-workgroup launch (nll_small_kernel): same values, two launch boundaries fewer
         rc = nll_fused_launch(X, n, kern, y, mean, K, z, info_dev, out5_dev, s, mail ? mb->dev : nullptr, seq);
         if (rc != 0) return rc;
-    } else if (n <= 2 * PB && y && (g_potrf_mode.load() == 0 || g_potrf_mode.load() == 3)) {
+    } else if (n <= 2 * PB && y && potrf_mode_fused_ok()) {
         // two block columns, still one single-workgroup launch (nll_two_kernel; modes 1 / 2 keep the separate launches)
         rc = nll_fused_launch(X, n, kern, y, mean, K, z, info_dev, out5_dev, s, mail ? mb->dev : nullptr, seq);
         if (rc != 0) return rc;
     } else {
         // three launches fewer than the separate calls: the Gram launch initialises the right-hand side
         // and the info word, the Cholesky's last launch writes the summary
-        rc = apgp_gram_with_rhs(X, n, kern, K, n, y, mean, z, info_dev, stream);
-        if (rc != 0) return rc;
+        auto per_step = [&](long long sq) -> int {          // the whole evaluation on the launch-per-step path
+            int r = apgp_gram_with_rhs(X, n, kern, K, n, y, mean, z, info_dev, stream);
+            if (r != 0) return r;
+            r = potrf_run_locked(K, n, n, 1, 0, y, &mean, z, info_dev, s, true, out5_dev, mail ? mb->dev : nullptr, sq);
+            if (r != 0) return r;
+            return nll_fetch(mb, mail, sq, s, out5_dev, out5_host);
+        };
+        const bool give_up_test = g_potrf_mode.load() == POTRF_GIVE_UP_TEST;    // (always launches, never backs off)
         long long plan = potrf_plan(n, n, s);
         const int dev = apgp_stream_device(s);
-        if (plan >= 0 && g_potrf_mode.load() != 2 && pp_backoff_take(dev)) plan = -1;   // (mode 2 = the fallback test: always launches)
-        const bool persist = plan >= 0;
+        if (plan >= 0 && !give_up_test && pp_backoff_take(dev)) plan = -1;
+        if (plan < 0) return per_step(seq);
+        rc = apgp_gram_with_rhs(X, n, kern, K, n, y, mean, z, info_dev, stream);
+        if (rc != 0) return rc;
         if (plan > 0) {
             rc = potrf_run_locked(K, n, n, 1, 0, y, &mean, z, info_dev, s, true, nullptr, nullptr, 0, plan);
             if (rc != 0) return rc;
         }
-        rc = persist ? potrf_persist_locked(K, n, n, z, info_dev, s, out5_dev, mail ? mb->dev : nullptr, seq, plan)
-                     : potrf_run_locked(K, n, n, 1, 0, y, &mean, z, info_dev, s, true, out5_dev, mail ? mb->dev : nullptr, seq);
+        rc = potrf_persist_locked(K, n, n, z, info_dev, s, out5_dev, mail ? mb->dev : nullptr, seq, plan);
         if (rc != 0) return rc;
-        if (persist) {
-            rc = nll_fetch(mb, mail, seq, s, out5_dev, out5_host);
-            if (rc != 0) return rc;
-            if (out5_host[4] != PP_ABORTED) { pp_backoff_report(dev, false); return rc; }
-            // the persistent launch gave up (its workgroups were not all resident in time): the evaluation again,
-            // from the Gram matrix, on the multi-launch path
-            g_potrf_fallbacks.fetch_add(1);
-            if (g_potrf_mode.load() != 2) pp_backoff_report(dev, true);
-            const long long seq2 = mail ? ++mb->seq : 0;
-            rc = apgp_gram_with_rhs(X, n, kern, K, n, y, mean, z, info_dev, stream);
-            if (rc != 0) return rc;
-            rc = potrf_run_locked(K, n, n, 1, 0, y, &mean, z, info_dev, s, true, out5_dev, mail ? mb->dev : nullptr, seq2);
-            if (rc != 0) return rc;
-            return nll_fetch(mb, mail, seq2, s, out5_dev, out5_host);
-        }
+        rc = nll_fetch(mb, mail, seq, s, out5_dev, out5_host);
+        if (rc != 0) return rc;
+        if (out5_host[4] != PP_ABORTED) { pp_backoff_report(dev, false); return rc; }
+        // the persistent launch gave up (its workgroups were not all resident in time): the evaluation again,
+        // from the Gram matrix, on the multi-launch path
+        g_potrf_fallbacks.fetch_add(1);
+        if (!give_up_test) pp_backoff_report(dev, true);
+        return per_step(mail ? ++mb->seq : 0);
     }
     return nll_fetch(mb, mail, seq, s, out5_dev, out5_host);
 }
@@ -1577,13 +1595,29 @@ int apgp_gram_with_rhs_batch(const double* X, int64_t n, int64_t batch, const ap
 static std::atomic<long long> g_pp_side_batches{0};
 extern "C" int64_t apgp_nll_side_batches(void) { return g_pp_side_batches.load(); }
 
+// the records of a batch out of the stream's pinned staging area: record b is five doubles at rec + 8 b, its sequence
+// word the double after them (bounded spin, then the ordinary synchronisation).  *any_aborted (optional): a record reads
+// PP_ABORTED.
+static int nll_collect_records(ApgpSeqWait& records, const double* rec, int64_t batch, long long seq, double* out5_host,
+                               bool* any_aborted) {
+    for (int64_t b = 0; b < batch; ++b) {
+        if (records.wait(rec + 8 * b + 5, seq) != ApgpSeqWait::OK) {
+            apgp_set_error("apgp_nll_eval_batch: result record not written");
+            return -2;
+        }
+        for (int i = 0; i < 5; ++i) out5_host[5 * b + i] = rec[8 * b + i];
+        if (any_aborted && out5_host[5 * b + 4] == PP_ABORTED) *any_aborted = true;
+    }
+    return 0;
+}
+
 // 0: done (out5_host filled); 1: not applicable or gave up -- nothing of the result is valid, the caller runs the
 // batched launch-per-step path from the Gram matrices; < 0: error
 static int nll_batch_side_by_side(const double* X, int64_t n, int64_t batch, const apgp_kernel_t* kerns, const double* y,
                                   const double* means, double* K, double* z, int32_t* info_dev, double* out5_dev,
                                   double* out5_host, hipStream_t s) {
-    const int mode = g_potrf_mode.load();
-    if (mode != 0 && mode != 3) return 1;
+    static ApgpLdsOnce lds_once;
+    if (!potrf_mode_fused_ok()) return 1;
     if (batch < 2 || batch > PP_BATCH_MAX) return 1;
     if (potrf_plan(n, n, s) != 0) return 1;                               // one persistent launch per matrix, no hybrid
     const int dev = apgp_stream_device(s);
@@ -1599,76 +1633,35 @@ static int nll_batch_side_by_side(const double* X, int64_t n, int64_t batch, con
     if (pp_backoff_take(dev)) return 1;
     int rc = apgp_gram_with_rhs_batch(X, n, batch, kerns, K, y, means, z, info_dev, (void*)s);
     if (rc != 0) return rc;
-    PersistBatchArgs qb;
-    PotrfArgs full;
-    {
-        PotrfArgs& a = full;
-        a.A = K; a.rhs = z; a.n = n; a.lda = n; a.j0 = 0; a.shift = 0.0; a.info = info_dev; a.out5 = out5_dev;
-        a.batch_A = n * n; a.batch_rhs = n; a.no_panel = 0; a.info_j0 = 0; a.pair_mode = 0; a.defer8 = 0; a.deferred8 = 0;
-        a.zoff = nb * (long long)(PB * PB); a.batch_dscr = a.zoff + nb * PB;
-        a.dscr = apgp_stream_scratch(0, s, (size_t)a.batch_dscr * (size_t)batch);
-    }
-    bool fresh = false;
-    unsigned long long* calls = nullptr;
-    pp_u64* pw = (pp_u64*)apgp_stream_scratch_ex(2, s, (size_t)PP_SCRATCH_WORDS * (size_t)batch, &fresh, &calls);
-    if (!full.dscr || !pw) {
+    // the finish launch's arguments (gridDim.y = batch: strides between the matrices, their abort words and their records)
+    const long long seq = ++mb->seq;
+    PotrfArgs full = potrf_args(K, n, n, z, info_dev, out5_dev, io_dev, seq);
+    full.batch_A = n * n; full.batch_abort = PP_SCRATCH_WORDS; full.batch_mail = 8;
+    full.dscr = apgp_stream_scratch(0, s, (size_t)full.batch_dscr * (size_t)batch);
+    if (!full.dscr) {
         apgp_set_error("apgp_nll_eval_batch: scratch allocation failed");
         return -2;
     }
-    unsigned long long id = ++*calls;
-    if ((unsigned)id == 0u) { fresh = true; id = ++*calls; }             // (the 32-bit granule tag wrapped: start over)
-    if (fresh && hipMemsetAsync(pw, 0, (size_t)PP_SCRATCH_WORDS * 8 * (size_t)batch, s) != hipSuccess) {
-        apgp_set_error("apgp_nll_eval_batch: memset failed");
-        return -2;
-    }
-    const long long seq = ++mb->seq;
-    full.abort_word = pw + PP_CTL_ABORT; full.abort_id = id; full.batch_abort = PP_SCRATCH_WORDS;
-    full.mail = io_dev; full.batch_mail = 8; full.seq = seq;
+    PpScratch p;
+    if (pp_prepare(s, batch, "apgp_nll_eval_batch", p) != 0) return -2;
+    full.abort_word = p.pw + PP_CTL_ABORT; full.abort_id = p.id;
+    // the persistent launch's: one record per matrix, each the single call's (no strides, no mailbox)
+    PersistBatchArgs qb;
     for (int64_t b = 0; b < PP_BATCH_MAX; ++b) {
         const int64_t m = b < batch ? b : 0;                              // (unused records: copies of matrix 0's, never read)
         PersistArgs& q = qb.m[b];
-        q.a = full;
-        q.a.A = K + m * n * n; q.a.rhs = z + m * n; q.a.info = info_dev + m; q.a.out5 = out5_dev + 5 * m;
+        q.a = potrf_args(K + m * n * n, n, n, z + m * n, info_dev + m, out5_dev + 5 * m, nullptr, seq);
         q.a.dscr = full.dscr + m * full.batch_dscr;
-        q.a.batch_A = 0; q.a.batch_rhs = n; q.a.batch_abort = 0; q.a.batch_mail = 0; q.a.mail = nullptr;
-        q.ctl = pw + m * (long long)PP_SCRATCH_WORDS; q.strm = q.ctl + PP_CTL_WORDS; q.zstrm = q.strm + PP_STRM_WORDS;
-        q.a.abort_word = q.ctl + PP_CTL_ABORT; q.a.abort_id = id;
-        q.call_id = id;
-        q.timeout = 5000000ull;                                           // 50 ms of the 100 MHz clock
-        q.nb = (int)nb;
-        q.debug = 0;
+        pp_fill(q, p, m, nb, 0);
     }
-    {
-        static std::mutex attr_mu;
-        static bool attr_set[64] = {false};
-        std::lock_guard<std::mutex> alock(attr_mu);
-        if (dev >= 0 && dev < 64 && !attr_set[dev]) {
-            if (hipFuncSetAttribute((const void*)potrf_persist_batch_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, PP_LDS_BYTES) != hipSuccess) {
-                apgp_set_error("apgp_nll_eval_batch: hipFuncSetAttribute failed");
-                return -2;
-            }
-            attr_set[dev] = true;
-        }
-    }
-    const long long tiles0 = (nb - 1) * (nb - 2) / 2;
-    long long nupd = (tiles0 * PP_NUPD_PCT + 99) / 100 + 8;               // as the single launch (potrf_persist_locked) ...
-    if (nupd > tiles0) nupd = tiles0;
-    if (nupd > budget - nb) nupd = budget - nb;                           // ... within this matrix's share of the CUs
-    if (nupd < 1) nupd = 1;
+    if (apgp_raise_lds(lds_once, "apgp_nll_eval_batch", dev, PP_LDS_BYTES, {(const void*)potrf_persist_batch_kernel}) != 0) return -2;
+    const long long nupd = pp_update_workgroups(nb, budget - nb);         // (within this matrix's share of the CUs)
     hipLaunchKernelGGL(potrf_persist_batch_kernel, dim3((unsigned)(nb + nupd), (unsigned)batch), dim3(PP_THREADS), PP_LDS_BYTES, s, qb);
     hipLaunchKernelGGL(potrf_finish_kernel, dim3((unsigned)nb, (unsigned)batch), dim3(256), 0, s, full);
     APGP_CHECK_LAUNCH();
-    // the records: one sequence word per matrix (bounded spin, then the ordinary synchronisation)
     bool gave_up = false;
     ApgpSeqWait records(s, 800);
-    for (int64_t b = 0; b < batch; ++b) {
-        if (records.wait(io + 8 * b + 5, seq) != ApgpSeqWait::OK) {
-            apgp_set_error("apgp_nll_eval_batch: result record not written");
-            return -2;
-        }
-        for (int i = 0; i < 5; ++i) out5_host[5 * b + i] = io[8 * b + i];
-        if (out5_host[5 * b + 4] == PP_ABORTED) gave_up = true;
-    }
+    if ((rc = nll_collect_records(records, io, batch, seq, out5_host, &gave_up)) != 0) return rc;
     if (gave_up) {
         g_potrf_fallbacks.fetch_add(1);
         pp_backoff_report(dev, true);
@@ -1692,7 +1685,7 @@ extern "C" int apgp_nll_eval_batch(const double* X, int64_t n, int64_t batch, co
     APGP_CHECK_ARG(batch >= 1 && batch <= 65535, "1 <= batch <= 65535 required");
     APGP_CHECK_ARG(n >= 1 && n <= APGP_MAX_N, "n >= 1 required");
     int rc;
-    if (n <= 2 * PB && batch <= 64 && (g_potrf_mode.load() == 0 || g_potrf_mode.load() == 3)) {
+    if (n <= 2 * PB && batch <= 64 && potrf_mode_fused_ok()) {
         // README sizes (round 5): ONE launch of the fused evaluation, a workgroup per matrix (nll_small_kernel /
         // nll_two_kernel); constants and shifts go in -- and the records come back -- through the stream's pinned,
         // device-mapped staging area, each workgroup posting its own sequence word: no copy, no synchronisation.
@@ -1714,19 +1707,12 @@ extern "C" int apgp_nll_eval_batch(const double* X, int64_t n, int64_t batch, co
             double* rec = sh + batch;
             const long long seq = ++mb->seq;
             NllSmallArgs q;
-            q.X = X; q.y = y; q.K = K; q.z = z; q.info = info_dev; q.out5 = out5_dev; q.n = n; q.shift = 0.0;
-            q.kc = kcs[0]; q.mail = nullptr; q.seq = seq;
+            q.X = X; q.y = y; q.K = K; q.z = z; q.info = info_dev; q.out5 = out5_dev; q.n = n;
+            q.kc = kcs[0]; q.seq = seq;
             q.bkc = (const KernConst*)io_dev; q.bshift = io_dev + (size_t)batch * KCD; q.brec = io_dev + (size_t)batch * (KCD + 1);
             if ((rc = nll_fused_launch_q<true>(q, kcs[0].dpad, (int)batch, s)) != 0) return rc;
             ApgpSeqWait records(s, 600);
-            for (int64_t b = 0; b < batch; ++b) {
-                if (records.wait(rec + 8 * b + 5, seq) != ApgpSeqWait::OK) {
-                    apgp_set_error("apgp_nll_eval_batch: result record not written");
-                    return -2;
-                }
-                for (int i = 0; i < 5; ++i) out5_host[5 * b + i] = rec[8 * b + i];
-            }
-            return 0;
+            return nll_collect_records(records, rec, batch, seq, out5_host, nullptr);
         }
     }
     hipStream_t s = (hipStream_t)stream;

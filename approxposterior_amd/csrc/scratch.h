@@ -16,6 +16,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <chrono>
+#include <initializer_list>
 #include <map>
 #include <memory>
 #include <mutex>
@@ -47,6 +48,37 @@ inline int apgp_stream_device(hipStream_t s) {
     if (s != nullptr && hipStreamGetDevice(s, &dev) == hipSuccess) return dev;
     if (hipGetDevice(&dev) != hipSuccess) return -1;
     return dev;
+}
+
+// A kernel that takes more than 64 KiB of dynamic LDS needs hipFuncAttributeMaxDynamicSharedMemorySize raised first: a
+// per-device attribute of each kernel (each instantiation of a template), set -- and its result checked -- once per device.
+// The done-flags belong to the KERNELS, never to the helper: every site owns one ApgpLdsOnce as a function-local static
+// (in a function template that is one per instantiation) and passes the kernels it launches with `bytes`; two kernels
+// behind one flag would leave the second without its limit.  Kernels land in the code object in the order they are first
+// named, so a site lists them in the order its launches name them.
+// `dev` is the device the site keys by.  The rule is the STREAM's device (apgp_stream_device, as for the scratch); three
+// sites still pass the caller's current device (hipGetDevice): nll_two_launch_t (potrf.hip), s2_prepare_device
+// (sweep.hip) and apgp_ensemble_sample_moves (ensemble.hip, for both of its launch functions).  The two agree unless a
+// caller launches on another device's stream.
+// 0, or -2 with the error set: a device index outside the table, or the attribute refused.
+void apgp_set_error(const char* fmt, ...);        // gram.hip
+struct ApgpLdsOnce { std::mutex mu; bool done[64] = {false}; };
+inline int apgp_raise_lds(ApgpLdsOnce& once, const char* entry, int dev, int bytes, std::initializer_list<const void*> kernels) {
+    if (dev < 0 || dev >= 64) {
+        apgp_set_error("%s: hipFuncSetAttribute(%d B of LDS): device %d is outside 0 .. 63", entry, bytes, dev);
+        return -2;
+    }
+    std::lock_guard<std::mutex> lock(once.mu);           // (ctypes releases the GIL: host threads may race here)
+    if (once.done[dev]) return 0;
+    for (const void* k : kernels) {
+        const hipError_t e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+        if (e != hipSuccess) {
+            apgp_set_error("%s: hipFuncSetAttribute(%d B of LDS) failed on device %d: %s", entry, bytes, dev, hipGetErrorString(e));
+            return -2;
+        }
+    }
+    once.done[dev] = true;
+    return 0;
 }
 
 // *fresh (optional): the buffer was (re)allocated by this call -- its contents are undefined.

@@ -1082,32 +1082,19 @@ static constexpr size_t s2_lds_bytes() {      // (the larger of the two feeder f
 // launches on.
 template <int DPAD>
 static int s2_prepare_device() {
-    static bool done[64] = {false};
-    static std::mutex mu;                 // (ctypes releases the GIL: host threads may race here)
+    static ApgpLdsOnce once;
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) {
         apgp_set_error("apgp_acquire: hipGetDevice failed");
         return -2;
     }
-    std::lock_guard<std::mutex> lock(mu);
-    if (done[dev]) return 0;
-    const int lds = (int)s2_lds_bytes<DPAD>();
-    hipError_t e = hipSuccess;
-    const void* kernels[12] = {(const void*)sweep2_kernel<DPAD, false, 0>, (const void*)sweep2_kernel<DPAD, true, 0>,
-                               (const void*)sweep2_kernel<DPAD, false, 1>, (const void*)sweep2_kernel<DPAD, true, 1>,
-                               (const void*)sweep2_kernel<DPAD, false, 2>, (const void*)sweep2_kernel<DPAD, true, 2>,
-                               (const void*)sweep2_kernel<DPAD, false, 0, true>, (const void*)sweep2_kernel<DPAD, true, 0, true>,
-                               (const void*)sweep2_kernel<DPAD, false, 1, true>, (const void*)sweep2_kernel<DPAD, true, 1, true>,
-                               (const void*)sweep2_kernel<DPAD, false, 2, true>, (const void*)sweep2_kernel<DPAD, true, 2, true>};
-    for (int i = 0; i < 12 && e == hipSuccess; ++i)
-        e = hipFuncSetAttribute(kernels[i], hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) {
-        apgp_set_error("apgp_acquire: hipFuncSetAttribute(%d B of LDS) failed on device %d: %s", lds, dev,
-                       hipGetErrorString(e));
-        return -2;
-    }
-    done[dev] = true;
-    return 0;
+    return apgp_raise_lds(once, "apgp_acquire", dev, (int)s2_lds_bytes<DPAD>(),
+                          {(const void*)sweep2_kernel<DPAD, false, 0>, (const void*)sweep2_kernel<DPAD, true, 0>,
+                           (const void*)sweep2_kernel<DPAD, false, 1>, (const void*)sweep2_kernel<DPAD, true, 1>,
+                           (const void*)sweep2_kernel<DPAD, false, 2>, (const void*)sweep2_kernel<DPAD, true, 2>,
+                           (const void*)sweep2_kernel<DPAD, false, 0, true>, (const void*)sweep2_kernel<DPAD, true, 0, true>,
+                           (const void*)sweep2_kernel<DPAD, false, 1, true>, (const void*)sweep2_kernel<DPAD, true, 1, true>,
+                           (const void*)sweep2_kernel<DPAD, false, 2, true>, (const void*)sweep2_kernel<DPAD, true, 2, true>});
 }
 
 // one launch of the kernel that fits (form, N, LinearKernel term); LIST: its blocks come from a.blk_list
