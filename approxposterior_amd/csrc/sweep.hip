@@ -1411,16 +1411,27 @@ __global__ __launch_bounds__(PR_THREADS) void prune_bound_kernel(PruneArgs a) {
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 // (the candidates' coordinates stay in registers: Dpad / 2 x blocks packed pairs)
+// sqrt(log2(e)) to the last bit: kappa^2 ln 2 - 1 = 6e-17 is inside the derivation's "room" (the constant that stood here
+// until round 13 was 3.5e-5 too small, a relative error of 7e-5 r^2 in every kernel value that no term covered)
+static constexpr double PR32_KAPPA = 0x1.337cc2183b050p+0;
 static constexpr int pr32_cpt(int dpad) { return dpad <= 8 ? PR32_CPT : dpad == 16 ? 2 : 1; }
 
-template <int DPAD>
+// REDO: behind prune_bound_mm32_kernel (prune_mm32.h), for the blocks it left at -inf alone (its gate failed where this
+// kernel's need not); the others keep its bound.  A workgroup without such a block leaves before its first barrier.
+template <int DPAD, bool REDO = false>
 __global__ __launch_bounds__(PR_THREADS) void prune_bound32_kernel(PruneArgs a) {
     constexpr int XS = DPAD + 2;                         // packed stream row: scaled x | alpha | 0
     constexpr int PIECES = PR32_ROWS * XS / 2;           // 16-byte pieces per tile
     constexpr int NP = (PIECES + PR_THREADS - 1) / PR_THREADS;
     constexpr int HD = DPAD / 2;
     constexpr int CPT = pr32_cpt(DPAD);
-    const double kappa = 0x1.3379f6df3f4ccp+0;           // sqrt(log2(e))
+    if (REDO) {                                          // (every thread reads the same words: one decision per workgroup)
+        const long long wg0 = (long long)blockIdx.x * (PR_THREADS / 64) * CPT;
+        bool any = false;
+        for (int i = 0; i < (PR_THREADS / 64) * CPT; ++i) any |= wg0 + i < a.ncb && a.bmin[wg0 + i] == -INFINITY;
+        if (!any) return;
+    }
+    const double kappa = PR32_KAPPA;
     __shared__ __attribute__((aligned(16))) float xt[PR32_ROWS * DPAD];
     __shared__ __attribute__((aligned(16))) float at[PR32_ROWS];
     __shared__ double cen[DPAD];
@@ -1429,12 +1440,13 @@ __global__ __launch_bounds__(PR_THREADS) void prune_bound32_kernel(PruneArgs a) 
     const long long blk0 = ((long long)blockIdx.x * (PR_THREADS / 64) + w) * CPT;
     f32x2 tt[CPT][HD];
     double ktt[CPT], an[CPT];
-    bool adm[CPT];
+    bool adm[CPT], redo[CPT];
 #pragma unroll
     for (int c = 0; c < CPT; ++c) {
         // admissibility and k(t,t) exactly as the sweep's load_candidates (lin_coef == 0: k(t,t) = amp)
         const long long row = (blk0 + c) * SW_CAND + lane;
         const bool live = blk0 + c < a.ncb && row < a.m;
+        redo[c] = !REDO || (blk0 + c < a.ncb && a.bmin[blk0 + c] == -INFINITY);
         bool ok = live, has_nan = false;
         double a2 = 0.0;
 #pragma unroll
@@ -1544,16 +1556,18 @@ __global__ __launch_bounds__(PR_THREADS) void prune_bound32_kernel(PruneArgs a) 
         if (!(be == be)) be = -INFINITY;
         if (!adm[c]) b = be = INFINITY;
         for (int o = 32; o > 0; o >>= 1) { b = fmin(b, __shfl_xor(b, o)); be = fmin(be, __shfl_xor(be, o)); }
-        if (lane == 0 && blk0 + c < a.ncb) {
+        if (lane == 0 && blk0 + c < a.ncb && redo[c]) {
             a.bmin[blk0 + c] = b;
             if (a.est) a.est[blk0 + c] = be;
-            if (a.part_u) {
+            if (!REDO && a.part_u) {
                 a.part_u[blk0 + c] = INFINITY;           // a pruned block's partial: never wins
                 a.part_i[blk0 + c] = -1;
             }
         }
     }
 }
+
+#include "prune_mm32.h"
 
 // (value, block) pairs in ascending order: by value, then by block number
 __device__ __forceinline__ bool pr_less(double v, long long i, double w, long long j) { return v < w || (v == w && i < j); }
@@ -1716,14 +1730,23 @@ static void pr_fill_args(PruneArgs& p, const SweepArgs& a, double* bmin, double*
     p.blk_list = NULL; p.blk_count = NULL; p.est = NULL;
 }
 
-// the bound pass over all blocks: coarse (fp32 kernel values; pure squared-exponential kernels only) or fp64
+// the bound pass over all blocks: coarse (fp32 kernel values; pure squared-exponential kernels only) or fp64.  Coarse up to
+// Dpad = 8: the exponents on the matrix cores (prune_mm32.h), and the vector-ALU kernel behind it for the blocks whose
+// gate failed there -- as a rule none, and its workgroups leave at once.  Dpad 16 and 32 keep the vector-ALU kernel.
 template <int DPAD>
 static void launch_bound(const PruneArgs& p, hipStream_t s, bool coarse) {
     const long long per_wg = (PR_THREADS / 64) * (coarse ? pr32_cpt(DPAD) : PR_CPT);
     const dim3 grid((unsigned)((p.ncb + per_wg - 1) / per_wg));
-    if (coarse)
-        hipLaunchKernelGGL(prune_bound32_kernel<DPAD>, grid, dim3(PR_THREADS), 0, s, p);
-    else
+    if (coarse) {
+        if constexpr (DPAD <= 8) {
+            const long long mm_wg = (PR_THREADS / 64) * (PMM_G / 2);
+            hipLaunchKernelGGL(prune_bound_mm32_kernel<DPAD>, dim3((unsigned)((p.ncb + mm_wg - 1) / mm_wg)), dim3(PR_THREADS),
+                               0, s, p);
+            hipLaunchKernelGGL((prune_bound32_kernel<DPAD, true>), grid, dim3(PR_THREADS), 0, s, p);
+        } else {
+            hipLaunchKernelGGL((prune_bound32_kernel<DPAD, false>), grid, dim3(PR_THREADS), 0, s, p);
+        }
+    } else
         hipLaunchKernelGGL((prune_bound_kernel<DPAD, false>), grid, dim3(PR_THREADS), 0, s, p);
 }
 
