@@ -63,7 +63,7 @@ import numpy as np
 DPS = 60
 U = 2.0 ** -53
 E_EXP = 1.5
-SITES = ("gram", "cross", "mean")
+SITES = ("gram", "cross", "mean", "sweep")
 MUTANTS = ("no_720", "no_ln2lo", "tab4", "skip_last_odd", "pad_nonzero", "transpose")
 
 Kern = collections.namedtuple("Kern", "ndim amp diag_add inv_metric lin_coef lin_order")
@@ -356,13 +356,19 @@ def _scaled(X, sc, D, dp, mutant):
     return rows
 
 
-def value_restate(xi, xc, k, lw, diagonal, mutant=None):
-    """apgp_gram_value on two rows of scaled coordinates (contraction off: every product and sum rounds)."""
+def value_restate(xi, xc, k, lw, diagonal, mutant=None, fuse_sc=None):
+    """apgp_gram_value on two rows of scaled coordinates (contraction off: every product and sum rounds).
+    ``fuse_sc``: xi holds RAW coordinates and its scaling is contracted into the subtraction, df = fma(x, sc, -xc)
+    (site "sweep", fused)."""
     dp = len(xi)
     s = s3 = 0.0
     for d in range(0, dp, 2):
-        df0 = xi[d] - xc[d]
-        df1 = xi[d + 1] - xc[d + 1]
+        if fuse_sc is not None:
+            df0 = fma(xi[d], fuse_sc[d], -xc[d])
+            df1 = fma(xi[d + 1], fuse_sc[d + 1], -xc[d + 1])
+        else:
+            df0 = xi[d] - xc[d]
+            df1 = xi[d + 1] - xc[d + 1]
         if mutant == "skip_last_odd" and (k.ndim & 1):
             if d == k.ndim - 1:
                 df0 = 0.0
@@ -386,11 +392,17 @@ def value_restate(xi, xc, k, lw, diagonal, mutant=None):
     return v
 
 
-def restate(X1, X2, k, site="gram", mutant=None, pairs=None):
+def restate(X1, X2, k, site="gram", mutant=None, pairs=None, fused=False):
     """The device's values as an m x n float64 array (NaN where not evaluated).  ``site``: "gram" (X2 None; lower
     triangle, diag_add on the diagonal), "cross" (apgp_kernel_cross: no diagonal term) or "mean" (the k* of
     predict_mean_kernel: the same arithmetic for the squared-exponential kernel; with a linear term the device kernel
     is compiled with contraction allowed, so there the restatement is the Gram association, not a promise).
+    "sweep": the k*(t, x) of sweep2_kernel's produce_b, X1 the candidates, pure squared-exponential kernels only.  The
+    kernel is compiled with contraction allowed and holds the scaled candidate tt = t sc in registers: in the
+    steady-state loop tt is a rounded product and the value has "cross"'s bits (``fused`` False); where produce_b is
+    inlined behind load_candidates -- the first tile a workgroup generates -- hipcc contracts the scaling into the
+    subtraction, df = fma(t, sc, -xs) (``fused`` True; docs/experiments.md, round 14).  A device value has the bits of
+    one of the two.
     ``pairs``: only those entries."""
     if site not in SITES:
         raise ValueError(site)
@@ -398,9 +410,15 @@ def restate(X1, X2, k, site="gram", mutant=None, pairs=None):
     gram = site == "gram"
     if gram != (X2 is None):
         raise ValueError("site 'gram' takes X2 = None, the other sites two point sets")
+    if site == "sweep" and k.lin_coef != 0.0:
+        raise ValueError("site 'sweep' restates pure squared-exponential kernels only")
+    if fused and site != "sweep":
+        raise ValueError("only site 'sweep' has a fused variant")
     sc, lw = kernconst(k)
     dp = len(sc)
     a = _scaled(X1, sc, k.ndim, dp, mutant)
+    if fused:
+        a = [[float(X1[i, d]) if d < k.ndim else 0.0 for d in range(dp)] for i in range(len(X1))]
     b = a if gram else _scaled(np.atleast_2d(np.asarray(X2, dtype=np.float64)), sc, k.ndim, dp, mutant)
     if mutant == "pad_nonzero" and dp > k.ndim:
         a = [row[:k.ndim] + [row[0]] * (dp - k.ndim) for row in a]      # the row point's padding keeps a stale value
@@ -410,7 +428,7 @@ def restate(X1, X2, k, site="gram", mutant=None, pairs=None):
     if pairs is None:
         pairs = [(i, j) for i in range(len(a)) for j in range(i + 1 if gram else len(b))]
     for i, j in pairs:
-        out[i, j] = value_restate(a[i], b[j], k, lw, gram and i == j, mutant)
+        out[i, j] = value_restate(a[i], b[j], k, lw, gram and i == j, mutant, sc if fused else None)
     return out
 
 
