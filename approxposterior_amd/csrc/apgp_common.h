@@ -145,6 +145,19 @@ __device__ __forceinline__ void static_for(F&& f) {
     static_for_impl(std::make_integer_sequence<int, N>{}, f);
 }
 
+// 16-byte buffer store whose data registers stay untouched for two more issue slots.  gfx9's rule "a VMEM store of more
+// than 64 bits followed by a VALU write of its data registers needs a wait state" has an exception in the ISA manual --
+// and in LLVM's hazard recogniser -- for MUBUF stores whose soffset is an SGPR; on this chip the store still reads its
+// data late: hipcc recycled the data registers of the persistent Cholesky's granule forwarder (potrf_persist.h) in the
+// very next instruction (v_mov into the first dword) and, whenever no other wavefront's instruction happened to fall in
+// between, lanes 12-15 of every 16 stored the NEXT value's low word under THIS value's tag (found when the receiver moved
+// to a SIMD it shares with a wavefront that rarely yields: factor off by 1e-7 relative, silently).  The empty-looking asm
+// keeps the registers live across the nop.  Every 16-byte granule store of the library goes through this macro.
+#define APGP_STORE16(data_, rs_, voff_, soff_, aux_) do {                                              \
+        __builtin_amdgcn_raw_buffer_store_b128((data_), (rs_), (voff_), (soff_), (aux_));            \
+        asm volatile("s_nop 1" : : "v"(data_));                                                      \
+    } while (0)
+
 // ---------------------------------------------------------------------------
 // exp() for the squared-exponential kernel values.  Every kernel that evaluates
 // k(x,x') (Gram, sweep, mean-only predict, gradient) uses THIS routine, so the

@@ -373,8 +373,7 @@ __global__ __launch_bounds__(256) void ensemble_mw_kernel(EnsMwArgs q) {
                     const double mv = t == 0 ? m0 : m1;
                     const int slot = t == 0 ? i : i1;
                     const ens_u32x4 gr = {(unsigned)__double2loint(mv), tag, (unsigned)__double2hiint(mv), tag};
-                    __builtin_amdgcn_raw_buffer_store_b128(gr, rs_x, (unsigned)((par * (ENS_MAXW / 2) + slot) * 16), 0, 16);
-                    asm volatile("s_nop 1" : : "v"(gr));        // (16-byte store: its data registers stay live -- see PP_STORE16)
+                    APGP_STORE16(gr, rs_x, (unsigned)((par * (ENS_MAXW / 2) + slot) * 16), 0, 16);
                 }
             }
             // everybody's values (one granule per thread, polled until its tag is this half-step's)

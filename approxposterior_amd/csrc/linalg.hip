@@ -214,14 +214,8 @@ __global__ __launch_bounds__(1024) void trsv_kernel(TrsvArgs a) {
 }
 
 // ---------------------------------------------------------------------------
-// K3, blocked: the same solves as a sequence of small launches, four 64-row blocks per launch, for N >= 256.
-// Launch jb: every workgroup (four wavefronts) solves the 64 x 64 diagonal block against the current
-// right-hand side of block jb itself (redundantly: 1 us, and no workgroup waits for another) and
-// applies the result to ITS block of the remaining rows (forward: block rows below, a wavefront-wide sum
-// per row; transposed: block columns to the left, coalesced as they lie).  Workgroup 0 keeps
-// the solved block.  The working right-hand side lives in stream-ordered scratch (scratch.h): the
-// solution goes to x, so no workgroup overwrites what a sibling still has to read.
-// 64 launches of ~4 us at N = 4096 instead of one single-workgroup kernel of 1.6 ms.
+// K3, blocked, for N >= 256: the same solves in 64-row blocks, as one persistent launch (trsv_persist_kernel) or as
+// one small launch per 256 rows (trsv_step4_kernel) -- instead of one single-workgroup kernel of 1.6 ms at N = 4096.
 // ---------------------------------------------------------------------------
 struct TrsvStepArgs {
     const double* L;
@@ -243,82 +237,87 @@ __device__ __forceinline__ double trsv_bcast(double v, int src) {
     return __hiloint2double(hi, lo);
 }
 
-template <int TRANS>
-__global__ __launch_bounds__(256) void trsv_step_kernel(TrsvStepArgs a) {
-    // four wavefronts: all of them request their 16 rows of the diagonal block AND of the workgroup's
-    // own off-diagonal block at once (one memory latency for both), wavefront 0 solves the diagonal
-    // block while the others wait, then each applies the solved block to its 16 rows
-    __shared__ double Lb[64][65];
-    __shared__ double zb[64];
-    __shared__ double part[4][64];
-    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
-    const long long j0 = a.j0, n = a.n;
-    const int bs = (int)((n - j0) < 64 ? (n - j0) : 64);
-    const bool off = blockIdx.x != 0;
-    const long long i0 = TRANS ? j0 - 64 * (long long)blockIdx.x : j0 + 64 * (long long)blockIdx.x;
-    double dg[16], ob[16];
+// ---------------------------------------------------------------------------
+// The pieces of a 64-row block step that the blocked forms (trsv_step4_kernel, trsv_persist_kernel) share: both
+// kernels give an element the same operations in the same order -- tiles subtracted in block order, a tile's product as
+// four 16-term FMA chains added pairwise, reciprocal pivot then product, x.x added block by block in solving order --
+// so their solutions carry the same bits (tests/test_gpu_parity.py, tests/test_gpu_factor_budget.py).  The barriers
+// between the pieces differ between the kernels and stay with them; so do the loads of the diagonal block and of the
+// lane's row of it, and trsv_step4_kernel's pivot-by-pivot substitution and its chain over own[][]: shared spellings of
+// those changed that kernel's register allocation (it sits at the 256-VGPR limit) and cost it 5 .. 10 % per solve.
+// ---------------------------------------------------------------------------
+// this wavefront's 16 rows of the diagonal block on their way to LDS (coalesced: lane = column)
+__device__ __forceinline__ void trsv_diag_stage(double (*Lb)[65], const double (&dg)[16], int w, int lane) {
 #pragma unroll
-    for (int q = 0; q < 16; ++q) {
-        const int r = 16 * w + q;
-        dg[q] = (r < bs && lane <= r) ? a.L[(j0 + r) * a.ldl + j0 + lane] : ((r == lane) ? 1.0 : 0.0);
-        // own block, the 16 k of this wavefront: forward element (row i0 + lane, column j0 + 16 w + q)
-        // -- one 128-byte line per lane --, transposed element (row j0 + 16 w + q, column i0 + lane)
-        if (!TRANS) ob[q] = (off && i0 + lane < n) ? a.L[(i0 + lane) * a.ldl + j0 + r] : 0.0;
-        else ob[q] = (off && r < bs) ? a.L[(j0 + r) * a.ldl + i0 + lane] : 0.0;
-    }
-    const double rj = (w == 0 && lane < bs) ? a.r[j0 + lane] : 0.0;
-    const double rown = (w == 0 && off && i0 + lane < n) ? a.r[i0 + lane] : 0.0;   // (the entries this workgroup updates: requested now)
-#pragma unroll
-    for (int q = 0; q < 16; ++q) Lb[16 * w + q][lane] = dg[q];                 // (coalesced: lane = column)
-    __syncthreads();
-    if (w == 0) {
-        double ri = rj;
-        const double inv = 1.0 / Lb[lane][lane];
-        double v[64];
-#pragma unroll
-        for (int k = 0; k < 64; ++k) v[k] = TRANS ? Lb[k][lane] : Lb[lane][k];   // column / row `lane` of the block
-        if (!TRANS) {
-            static_for<64>([&](auto kc) {
-                constexpr int k = decltype(kc)::value;
-                const double zk = trsv_bcast(ri, k) * trsv_bcast(inv, k);
-                ri = lane == k ? zk : (lane > k ? fma(-v[k], zk, ri) : ri);
-            });
-        } else {
-            static_for<64>([&](auto kc) {
-                constexpr int k = 63 - decltype(kc)::value;
-                const double xk = trsv_bcast(ri, k) * trsv_bcast(inv, k);
-                ri = lane == k ? xk : (lane < k ? fma(-v[k], xk, ri) : ri);   // (L^T)[lane][k] = L[k][lane]
-            });
-        }
-        zb[lane] = ri;
-        if (!off) {
-            if (lane < bs) a.x[j0 + lane] = ri;
-            if (a.sumsq) {
-                double ss = lane < bs ? ri * ri : 0.0;
-                for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o);
-                if (lane == 0) *a.sumsq += ss;              // (one writer per launch, launches in stream order)
-            }
-        }
-    }
-    __syncthreads();
-    if (!off) return;
-    // forward: r_i -= L[i, j0 .. j0+63] . z (lane = row i); transposed: r_c -= sum_k L[j0 + k, c] x_k
-    // (lane = column c).  Either way 16 of the 64 k per wavefront, the four partial sums through LDS.
+    for (int q = 0; q < 16; ++q) Lb[16 * w + q][lane] = dg[q];
+}
+// a tile's product with a solved block: this wavefront's 16 of the 64 terms as one FMA chain (zw = the block's
+// solution from element 16 w on) ...
+__device__ __forceinline__ double trsv_tile_chain(const double (&ob)[16], const double* zw) {
     double acc = 0.0;
 #pragma unroll
-    for (int q = 0; q < 16; ++q) acc = fma(ob[q], zb[16 * w + q], acc);
-    part[w][lane] = acc;
-    __syncthreads();
-    if (w == 0 && i0 + lane < n) a.r[i0 + lane] = rown - ((part[0][lane] + part[1][lane]) + (part[2][lane] + part[3][lane]));
+    for (int q = 0; q < 16; ++q) acc = fma(ob[q], zw[q], acc);
+    return acc;
+}
+// ... and the four wavefronts' chains, through part[w][lane], added pairwise
+__device__ __forceinline__ double trsv_tile_sum(const double (*part)[64], int lane) {
+    return (part[0][lane] + part[1][lane]) + (part[2][lane] + part[3][lane]);
+}
+// x.x of a solved block (its bs real rows), in every lane
+__device__ __forceinline__ double trsv_block_sumsq(double ri, int lane, int bs) {
+    double ss = lane < bs ? ri * ri : 0.0;
+    for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o);
+    return ss;
 }
 
-// Round 3: FOUR 64-row blocks (256 rows) per launch.  The launch-to-launch dependency (~7 us) is what a step of the
-// chain above costs whatever it computes, so a step now takes a 256-row diagonal "super-block": every workgroup
-// solves it itself -- four 64 x 64 diagonal solves with the six 64 x 64 products between them, redundantly as
-// before -- and applies the 256 solved values to ITS 64 rows (forward) / columns (transposed) of the remaining
-// right-hand side.  Same arithmetic in the same order per element as the one-block step (a tile's product is the
-// four wavefronts' 16-term partial sums added pairwise, tiles are subtracted in block order), so the solution has
-// the same bits; a quarter of the launches.
+// The 64 x 64 diagonal block's substitution in GROUPS of four pivots: the group's four right-hand-side entries and its
+// 4 x 4 block are broadcast (v_readlane) and solved by every lane alike, then every lane applies the four solved values
+// to its own row -- per lane the same FMAs in the same order as one pivot at a time (so the same bits), but the
+// cross-lane dependency is met once per four pivots instead of once per pivot: a pivot-by-pivot step costs ~100 cycles
+// (readlane -> SGPR -> multiply -> FMA), 2.7 us per block; a group ~140.
+// v[k]: forward L[lane][k], transposed L[k][lane]; inv = 1 / L[lane][lane].
+template <int TRANS>
+__device__ __forceinline__ double trsv_diag_solve(double ri, const double inv, const double (&v)[64], const int lane) {
+    static_for<16>([&](auto gc) {
+        constexpr int g = TRANS ? 15 - decltype(gc)::value : decltype(gc)::value;
+        constexpr int c0 = 4 * g;
+        double r[4], iv[4], z[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) { r[q] = trsv_bcast(ri, c0 + q); iv[q] = trsv_bcast(inv, c0 + q); }
+        if (!TRANS) {
+            // rows c0 .. c0+3 ascending: L[c0+q][c0+m] (m < q) = lane (c0+q)'s v[c0+m]
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+#pragma unroll
+                for (int m = 0; m < q; ++m) r[q] = fma(-trsv_bcast(v[c0 + m], c0 + q), z[m], r[q]);
+                z[q] = r[q] * iv[q];
+            }
+#pragma unroll
+            for (int q = 0; q < 4; ++q) ri = lane == c0 + q ? z[q] : (lane > c0 + q ? fma(-v[c0 + q], z[q], ri) : ri);
+        } else {
+            // rows c0+3 .. c0 descending: (L^T)[c0+q][c0+m] (m > q) = L[c0+m][c0+q] = lane (c0+q)'s v[c0+m]
+#pragma unroll
+            for (int q = 3; q >= 0; --q) {
+#pragma unroll
+                for (int m = 3; m > q; --m) r[q] = fma(-trsv_bcast(v[c0 + m], c0 + q), z[m], r[q]);
+                z[q] = r[q] * iv[q];
+            }
+#pragma unroll
+            for (int q = 3; q >= 0; --q) ri = lane == c0 + q ? z[q] : (lane < c0 + q ? fma(-v[c0 + q], z[q], ri) : ri);
+        }
+    });
+    return ri;
+}
+
+// The launch-per-256-rows form (round 3): FOUR 64-row blocks per launch.  Launch sj takes the 256-row diagonal
+// "super-block" sj: every workgroup (four wavefronts) solves it itself against the current right-hand side -- four
+// 64 x 64 diagonal solves with the six 64 x 64 products between them, redundantly: no workgroup waits for another --
+// and applies the 256 solved values to ITS 64 rows (forward: below the super-block, one 128-byte line per lane) /
+// columns (transposed: left of it, coalesced as they lie) of the remaining right-hand side.  Workgroup 0 keeps the
+// solved blocks.  The working right-hand side lives in stream-ordered scratch (scratch.h): the solution goes to x, so
+// no workgroup overwrites what a sibling still has to read.  (Round 2 launched once per 64-row block: the
+// launch-to-launch dependency, ~7 us, is what a launch costs whatever it computes, so four blocks per launch take a
+// quarter of the time -- with the same arithmetic in the same order per element, hence the same bits.)
 #define TRSV_SB 4
 template <int TRANS>
 __global__ __launch_bounds__(256) void trsv_step4_kernel(TrsvStepArgs a) {
@@ -366,19 +365,18 @@ __global__ __launch_bounds__(256) void trsv_step4_kernel(TrsvStepArgs a) {
                 if (!TRANS) ob[kk] = (lane < bs) ? a.L[(j0 + lane) * a.ldl + k] : 0.0;           // (k < j0 <= n)
                 else ob[kk] = (k < n) ? a.L[k * a.ldl + j0 + lane] : 0.0;
             }
-            double acc = 0.0;
-#pragma unroll
-            for (int kk = 0; kk < 16; ++kk) acc = fma(ob[kk], zb[64 * qb + 16 * w + kk], acc);
+            const double acc = trsv_tile_chain(ob, zb + 64 * qb + 16 * w);
             __syncthreads();                                 // (part is free: the previous tile's sum was consumed)
             part[w][lane] = acc;
             __syncthreads();
-            if (w == 0) rj = rj - ((part[0][lane] + part[1][lane]) + (part[2][lane] + part[3][lane]));
+            if (w == 0) rj = rj - trsv_tile_sum(part, lane);
         }
         __syncthreads();                                     // (Lb / part free)
-#pragma unroll
-        for (int q = 0; q < 16; ++q) Lb[16 * w + q][lane] = dg[q];
+        trsv_diag_stage(Lb, dg, w, lane);
         __syncthreads();
         if (w == 0) {
+            // (pivot by pivot, not trsv_diag_solve's groups of four -- the same FMAs in the same order per lane, so the same
+            // bits: with own[][] live this kernel has no register to spare, and the grouped form measured 9 % slower here)
             double ri = rj;
             const double inv = 1.0 / Lb[lane][lane];
             double v[64];
@@ -401,8 +399,7 @@ __global__ __launch_bounds__(256) void trsv_step4_kernel(TrsvStepArgs a) {
             if (!off) {
                 if (lane < bs) a.x[j0 + lane] = ri;
                 if (a.sumsq) {
-                    double ss = lane < bs ? ri * ri : 0.0;
-                    for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o);
+                    const double ss = trsv_block_sumsq(ri, lane, bs);
                     if (lane == 0) *a.sumsq += ss;          // (one writer, sub-blocks in order, launches in stream order)
                 }
             }
@@ -424,48 +421,9 @@ __global__ __launch_bounds__(256) void trsv_step4_kernel(TrsvStepArgs a) {
         __syncthreads();
         part[w][lane] = acc;
         __syncthreads();
-        if (w == 0) racc = racc - ((part[0][lane] + part[1][lane]) + (part[2][lane] + part[3][lane]));
+        if (w == 0) racc = racc - trsv_tile_sum(part, lane);
     }
     if (w == 0 && (TRANS || i0 + lane < n)) a.r[i0 + lane] = racc;
-}
-
-// The 64 x 64 diagonal block's substitution in GROUPS of four pivots: the group's four right-hand-side entries and its
-// 4 x 4 block are broadcast (v_readlane) and solved by every lane alike, then every lane applies the four solved values
-// to its own row -- per lane the same FMAs in the same order as one pivot at a time (so the same bits), but the
-// cross-lane dependency is met once per four pivots instead of once per pivot: a pivot-by-pivot step costs ~100 cycles
-// (readlane -> SGPR -> multiply -> FMA), 2.7 us per block; a group ~140.
-// v[k]: forward L[lane][k], transposed L[k][lane]; inv = 1 / L[lane][lane].
-template <int TRANS>
-__device__ __forceinline__ double trsv_diag_solve(double ri, const double inv, const double (&v)[64], const int lane) {
-    static_for<16>([&](auto gc) {
-        constexpr int g = TRANS ? 15 - decltype(gc)::value : decltype(gc)::value;
-        constexpr int c0 = 4 * g;
-        double r[4], iv[4], z[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) { r[q] = trsv_bcast(ri, c0 + q); iv[q] = trsv_bcast(inv, c0 + q); }
-        if (!TRANS) {
-            // rows c0 .. c0+3 ascending: L[c0+q][c0+m] (m < q) = lane (c0+q)'s v[c0+m]
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-#pragma unroll
-                for (int m = 0; m < q; ++m) r[q] = fma(-trsv_bcast(v[c0 + m], c0 + q), z[m], r[q]);
-                z[q] = r[q] * iv[q];
-            }
-#pragma unroll
-            for (int q = 0; q < 4; ++q) ri = lane == c0 + q ? z[q] : (lane > c0 + q ? fma(-v[c0 + q], z[q], ri) : ri);
-        } else {
-            // rows c0+3 .. c0 descending: (L^T)[c0+q][c0+m] (m > q) = L[c0+m][c0+q] = lane (c0+q)'s v[c0+m]
-#pragma unroll
-            for (int q = 3; q >= 0; --q) {
-#pragma unroll
-                for (int m = 3; m > q; --m) r[q] = fma(-trsv_bcast(v[c0 + m], c0 + q), z[m], r[q]);
-                z[q] = r[q] * iv[q];
-            }
-#pragma unroll
-            for (int q = 3; q >= 0; --q) ri = lane == c0 + q ? z[q] : (lane < c0 + q ? fma(-v[c0 + q], z[q], ri) : ri);
-        }
-    });
-    return ri;
 }
 
 // ---------------------------------------------------------------------------
@@ -479,12 +437,10 @@ __device__ __forceinline__ double trsv_diag_solve(double ri, const double inv, c
 // whose tickets were drawn before its own, i.e. for workgroups that are already running -- no assumption about
 // dispatch order or residency, so the spins cannot deadlock (they are bounded anyway: on timeout the block is written
 // as NaN and *err set).
-// Arithmetic per element = trsv_step4_kernel's (a tile's product is the four wavefronts' 16-term FMA chains added
-// pairwise, tiles subtracted in block order, the diagonal block by the same substitution; x.x accumulated block by
-// block in solving order), so the solution carries the same bits.
+// Arithmetic per element = trsv_step4_kernel's: both are built from the block step above, so the solution carries the
+// same bits.
 // ---------------------------------------------------------------------------
 static std::atomic<int> g_trsv_multi_launch{0};
-static thread_local int tl_trsv_mode = -1;      // >= 0: this thread's current call overrides the switch (apgp_trsv_ex)
 // test / profiling switch: 1 = the launch-per-256-rows path (not read from the environment); returns the previous value
 extern "C" int apgp_trsv_mode(int multi_launch) {
     if (multi_launch < 0) return g_trsv_multi_launch.load();
@@ -547,8 +503,7 @@ __global__ __launch_bounds__(256) void trsv_persist_kernel(TrsvPArgs a) {
     };
     // the diagonal block's row / column of this lane and its reciprocal pivot are in registers BEFORE the solved blocks
     // arrive (wavefront 0): after the last one only its tile's product and the 64-step substitution remain
-#pragma unroll
-    for (int q = 0; q < 16; ++q) Lb[16 * w + q][lane] = dg[q];                 // (coalesced: lane = column)
+    trsv_diag_stage(Lb, dg, w, lane);
     __syncthreads();
     double v[64], inv = 1.0;
     if (w == 0) {
@@ -599,33 +554,23 @@ __global__ __launch_bounds__(256) void trsv_persist_kernel(TrsvPArgs a) {
             }
         }
         __syncthreads();                                         // (zb in place; part free: the previous tile's sum was consumed)
-        double acc = 0.0;
-#pragma unroll
-        for (int q = 0; q < 16; ++q) acc = fma(ob[q], zb[16 * w + q], acc);
-        part[w][lane] = acc;
+        part[w][lane] = trsv_tile_chain(ob, zb + 16 * w);
         __syncthreads();
-        if (w == 0) rj = rj - ((part[0][lane] + part[1][lane]) + (part[2][lane] + part[3][lane]));
+        if (w == 0) rj = rj - trsv_tile_sum(part, lane);
     }
     if (w != 0) return;
     const double ri = trsv_diag_solve<TRANS>(rj, inv, v, lane);
     const double xo = lane < bs ? ri : 0.0;
-    double ss = lane < bs ? ri * ri : 0.0;
-    for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o);
-    const double snew = srun + ss;                               // (*sumsq += ss, block after block in solving order)
+    const double snew = srun + trsv_block_sumsq(ri, lane, bs);                               // (*sumsq += ss, block after block in solving order)
     if (ord + 1 < nb) {
         // hand the block on: 16 bytes per value, one write-through store per lane; the running sum as the 65th value
         typedef unsigned int u32x4_t __attribute__((ext_vector_type(4)));
         const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc((void*)a.gran, 0, 256 * 65 * 16, 0x00020000);
         const u32x4_t g = {(unsigned)__double2loint(xo), a.tag, (unsigned)__double2hiint(xo), a.tag};
-        // (the data registers stay live for two more issue slots: a 16-byte MUBUF store with an SGPR soffset reads its
-        // data late on this chip although the ISA manual and LLVM's hazard recogniser exempt it -- see PP_STORE16 in
-        // potrf_persist.h, where a recycled register put wrong low words under valid tags)
-        __builtin_amdgcn_raw_buffer_store_b128(g, rs, (unsigned)(lane * 16), (unsigned)(j * 65 * 16), 16);
-        asm volatile("s_nop 1" : : "v"(g));
+        APGP_STORE16(g, rs, (unsigned)(lane * 16), (unsigned)(j * 65 * 16), 16);
         if (lane == 0) {
             const u32x4_t gs = {(unsigned)__double2loint(snew), a.tag, (unsigned)__double2hiint(snew), a.tag};
-            __builtin_amdgcn_raw_buffer_store_b128(gs, rs, (unsigned)(64 * 16), (unsigned)(j * 65 * 16), 16);
-            asm volatile("s_nop 1" : : "v"(gs));
+            APGP_STORE16(gs, rs, (unsigned)(64 * 16), (unsigned)(j * 65 * 16), 16);
         }
     }
     if (lane < bs) a.x[j0 + lane] = bad_s ? __builtin_nan("") : ri;
@@ -636,99 +581,125 @@ __global__ __launch_bounds__(256) void trsv_persist_kernel(TrsvPArgs a) {
 #define TRSV_P_WORDS (8 + 256 * 65 * 2)
 #define TRSV_P_MAX_NB 256
 
-extern "C" int apgp_trsv(const double* L, int64_t n, int64_t ldl, const double* b, double shift,
-                         int trans, double* x, double* sumsq, void* stream) {
-    APGP_CHECK_ARG(L && b && x, "null pointer");
-    APGP_CHECK_ARG(n >= 1 && n <= APGP_MAX_N && ldl >= n, "n >= 1 and ldl >= n required");
-    hipStream_t st = (hipStream_t)stream;
-    const int multi_launch = tl_trsv_mode >= 0 ? tl_trsv_mode : g_trsv_multi_launch.load();
-    if (n >= 256 && (n + 63) / 64 <= TRSV_P_MAX_NB && !multi_launch) {
-        // ONE persistent launch (trsv_persist_kernel): flags-free granule hand-offs, call-unique tags and tickets (the
-        // scratch is zeroed when it is allocated, never between calls); b may alias x (a block's owner alone touches it)
-        std::lock_guard<std::mutex> enqueue_lock(apgp_stream_lock(st));
-        bool fresh = false;
-        unsigned long long* calls = nullptr;
-        unsigned long long* pw = (unsigned long long*)apgp_stream_scratch_ex(3, st, (size_t)TRSV_P_WORDS + 8, &fresh, &calls);
-        if (!pw) {
-            apgp_set_error("apgp_trsv: scratch allocation failed");
+// The three launch recipes of apgp_trsv; each takes the arguments that trsv_run has validated.  Errors are reported under
+// the entry point's name (apgp_trsv_ex's too, as ever): APGP_CHECK_ARG / APGP_CHECK_LAUNCH would print the enclosing function's.
+static int trsv_check_launch() {
+    const hipError_t e = hipGetLastError();
+    if (e == hipSuccess) return 0;
+    apgp_set_error("apgp_trsv: HIP error: %s", hipGetErrorString(e));
+    return -2;
+}
+
+// ONE persistent launch (trsv_persist_kernel): flags-free granule hand-offs, call-unique tags and tickets (the scratch is
+// zeroed when it is allocated, never between calls); b may alias x (a block's owner alone touches it)
+static int trsv_launch_persistent(const TrsvArgs& a, hipStream_t st) {
+    std::lock_guard<std::mutex> enqueue_lock(apgp_stream_lock(st));
+    bool fresh = false;
+    unsigned long long* calls = nullptr;
+    unsigned long long* pw = (unsigned long long*)apgp_stream_scratch_ex(3, st, (size_t)TRSV_P_WORDS + 8, &fresh, &calls);
+    if (!pw) {
+        apgp_set_error("apgp_trsv: scratch allocation failed");
+        return -2;
+    }
+    // calls[0] holds both counters of this buffer: low 40 bits = tickets drawn by earlier calls (the ticket base), high
+    // bits = calls so far (the granule tag).  A fresh buffer, or one whose tag space is used up, is zeroed and starts
+    // both over.
+    unsigned long long ncall = (*calls >> 40) + 1;
+    if (fresh || (unsigned)ncall == 0u || ncall >= (1ull << 23)) {
+        if (hipMemsetAsync(pw, 0, ((size_t)TRSV_P_WORDS + 8) * 8, st) != hipSuccess) {
+            apgp_set_error("apgp_trsv: memset failed");
             return -2;
         }
-        // calls[0] doubles as the ticket base (tickets handed out so far); the tag is a second counter kept in word 1..
-        // (both live with the scratch entry: a fresh buffer starts them over)
-        if (fresh) {
-            if (hipMemsetAsync(pw, 0, ((size_t)TRSV_P_WORDS + 8) * 8, st) != hipSuccess) {
-                apgp_set_error("apgp_trsv: memset failed");
-                return -2;
-            }
-            *calls = 0;
-        }
-        const long long nb = (n + 63) / 64;
-        TrsvPArgs pa;
-        pa.L = L; pa.b = b; pa.x = x; pa.sumsq = sumsq; pa.n = n; pa.ldl = ldl; pa.shift = shift;
-        pa.ticket = pw; pa.ticket_base = *calls & 0xffffffffffull;          // low 40 bits: tickets drawn by earlier calls
-        pa.gran = pw + 8;
-        pa.timeout = 5000000ull;                                           // 50 ms of the 100 MHz clock
-        pa.err = (int*)(pw + 4);
-        unsigned long long ncall = (*calls >> 40) + 1;                     // high bits: calls so far -> the granule tag
-        if ((unsigned)ncall == 0u || ncall >= (1ull << 23)) {
-            // (the tag space of this buffer is used up: start over on a zeroed buffer)
-            if (hipMemsetAsync(pw, 0, ((size_t)TRSV_P_WORDS + 8) * 8, st) != hipSuccess) {
-                apgp_set_error("apgp_trsv: memset failed");
-                return -2;
-            }
-            *calls = 0; ncall = 1; pa.ticket_base = 0;
-        }
-        pa.tag = (unsigned)ncall;
-        if (!trans) hipLaunchKernelGGL(trsv_persist_kernel<0>, dim3((unsigned)nb), dim3(256), 0, st, pa);
-        else hipLaunchKernelGGL(trsv_persist_kernel<1>, dim3((unsigned)nb), dim3(256), 0, st, pa);
-        APGP_CHECK_LAUNCH();
-        // (only a launch that was accepted draws its tickets on the device: the host-side base moves with it, not before --
-        // a failed launch would otherwise leave every later call on this stream with tickets nobody hands out)
-        *calls = (ncall << 40) | ((pa.ticket_base + (unsigned long long)nb) & 0xffffffffffull);
-        return 0;
+        *calls = 0; ncall = 1;
     }
-    if (n >= 256) {
-        // blocked form (trsv_step4_kernel): one small launch per 256 rows (round 2, trsv_step_kernel: per 64-row block (~10 us each, bound by the
-        // launch-to-launch dependency; the single-workgroup form below costs ~10 us per block at N = 512
-        // and 26 us per block at N = 4096).  Scratch and launches
-        // of one solve are taken as a unit: host threads sharing a stream share the scratch.
-        std::lock_guard<std::mutex> enqueue_lock(apgp_stream_lock(st));   // (per device and stream)
-        double* r = apgp_stream_scratch(1, st, (size_t)n);
-        if (!r) {
-            apgp_set_error("apgp_trsv: scratch allocation failed");
-            return -2;
-        }
-        hipLaunchKernelGGL(trsv_init_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, b, shift, r, sumsq, (long long)n);
-        TrsvStepArgs sa;
-        sa.L = L; sa.r = r; sa.x = x; sa.sumsq = sumsq; sa.n = n; sa.ldl = ldl;
-        const long long nb = (n + 63) / 64;
-        const long long nsup = (nb + TRSV_SB - 1) / TRSV_SB;          // 256-row super-blocks
-        if (!trans) {
-            for (long long sj = 0; sj < nsup; ++sj) {
-                sa.j0 = sj * 64 * TRSV_SB;
-                const long long after = nb - (sj + 1) * TRSV_SB;     // 64-row blocks below the super-block
-                hipLaunchKernelGGL(trsv_step4_kernel<0>, dim3((unsigned)(1 + (after > 0 ? after : 0))), dim3(256), 0, st, sa);
-            }
-        } else {
-            for (long long sj = nsup - 1; sj >= 0; --sj) {
-                sa.j0 = sj * 64 * TRSV_SB;
-                hipLaunchKernelGGL(trsv_step4_kernel<1>, dim3((unsigned)(1 + sj * TRSV_SB)), dim3(256), 0, st, sa);
-            }
-        }
-        APGP_CHECK_LAUNCH();
-        return 0;
+    const long long nb = (a.n + 63) / 64;
+    TrsvPArgs pa;
+    pa.L = a.L; pa.b = a.b; pa.x = a.x; pa.sumsq = a.sumsq; pa.n = a.n; pa.ldl = a.ldl; pa.shift = a.shift;
+    pa.ticket = pw; pa.ticket_base = *calls & 0xffffffffffull;
+    pa.gran = pw + 8;
+    pa.timeout = 5000000ull;                                           // 50 ms of the 100 MHz clock
+    pa.err = (int*)(pw + 4);
+    pa.tag = (unsigned)ncall;
+    if (!a.trans) hipLaunchKernelGGL(trsv_persist_kernel<0>, dim3((unsigned)nb), dim3(256), 0, st, pa);
+    else hipLaunchKernelGGL(trsv_persist_kernel<1>, dim3((unsigned)nb), dim3(256), 0, st, pa);
+    if (trsv_check_launch() != 0) return -2;
+    // (only a launch that was accepted draws its tickets on the device: the host-side base moves with it, not before --
+    // a failed launch would otherwise leave every later call on this stream with tickets nobody hands out)
+    *calls = (ncall << 40) | ((pa.ticket_base + (unsigned long long)nb) & 0xffffffffffull);
+    return 0;
+}
+
+// One small launch per 256 rows (trsv_step4_kernel), ~7 us each, bound by the launch-to-launch dependency (the
+// single-workgroup form costs ~10 us per 64-row block at N = 512 and 26 us at N = 4096).  Scratch and launches of one
+// solve are taken as a unit: host threads sharing a stream share the scratch.
+static int trsv_launch_steps(const TrsvArgs& a, hipStream_t st) {
+    std::lock_guard<std::mutex> enqueue_lock(apgp_stream_lock(st));   // (per device and stream)
+    const long long n = a.n;
+    double* r = apgp_stream_scratch(1, st, (size_t)n);
+    if (!r) {
+        apgp_set_error("apgp_trsv: scratch allocation failed");
+        return -2;
     }
-    // n < 256 here (both n >= 256 branches return): the single-workgroup form keeps the right-hand side in LDS
-    TrsvArgs a;
-    a.L = L; a.b = b; a.x = x; a.sumsq = sumsq; a.n = n; a.ldl = ldl; a.shift = shift;
-    a.trans = trans;
-    size_t nr = (size_t)apgp_round_up(n, 64);
+    hipLaunchKernelGGL(trsv_init_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a.b, a.shift, r, a.sumsq, n);
+    TrsvStepArgs sa;
+    sa.L = a.L; sa.r = r; sa.x = a.x; sa.sumsq = a.sumsq; sa.n = n; sa.ldl = a.ldl;
+    const long long nb = (n + 63) / 64;
+    const long long nsup = (nb + TRSV_SB - 1) / TRSV_SB;          // 256-row super-blocks
+    if (!a.trans) {
+        for (long long sj = 0; sj < nsup; ++sj) {
+            sa.j0 = sj * 64 * TRSV_SB;
+            const long long after = nb - (sj + 1) * TRSV_SB;     // 64-row blocks below the super-block
+            hipLaunchKernelGGL(trsv_step4_kernel<0>, dim3((unsigned)(1 + (after > 0 ? after : 0))), dim3(256), 0, st, sa);
+        }
+    } else {
+        for (long long sj = nsup - 1; sj >= 0; --sj) {
+            sa.j0 = sj * 64 * TRSV_SB;
+            hipLaunchKernelGGL(trsv_step4_kernel<1>, dim3((unsigned)(1 + sj * TRSV_SB)), dim3(256), 0, st, sa);
+        }
+    }
+    return trsv_check_launch();
+}
+
+// n < 256: the single-workgroup form (trsv_kernel) keeps the right-hand side in LDS
+static int trsv_launch_single(const TrsvArgs& a, hipStream_t st) {
+    size_t nr = (size_t)apgp_round_up(a.n, 64);
     size_t lds = (nr + TRSV_B * (TRSV_B + 1) + 16 * 64) * sizeof(double);
     // at most (256 + 64 * 65 + 16 * 64) * 8 = 43,520 B: under the 64 KiB a launch may take without raising the kernel's limit
     static_assert((256 + TRSV_B * (TRSV_B + 1) + 16 * 64) * sizeof(double) <= 64 * 1024, "trsv_kernel at n < 256 needs no LDS attribute");
-    hipLaunchKernelGGL(trsv_kernel, dim3(1), dim3(1024), lds, (hipStream_t)stream, a);
-    APGP_CHECK_LAUNCH();
-    return 0;
+    hipLaunchKernelGGL(trsv_kernel, dim3(1), dim3(1024), lds, st, a);
+    return trsv_check_launch();
+}
+
+// mode 0: the persistent launch where it applies, 1: a launch per 256 rows, < 0: the process-wide switch apgp_trsv_mode
+static int trsv_run(const double* L, int64_t n, int64_t ldl, const double* b, double shift,
+                    int trans, double* x, double* sumsq, int mode, hipStream_t st) {
+    if (!(L && b && x)) {
+        apgp_set_error("apgp_trsv: bad argument: null pointer");
+        return -1;
+    }
+    if (!(n >= 1 && n <= APGP_MAX_N && ldl >= n)) {
+        apgp_set_error("apgp_trsv: bad argument: n >= 1 and ldl >= n required");
+        return -1;
+    }
+    TrsvArgs a;
+    a.L = L; a.b = b; a.x = x; a.sumsq = sumsq; a.n = n; a.ldl = ldl; a.shift = shift;
+    a.trans = trans;
+    if (n < 256) return trsv_launch_single(a, st);
+    const int multi_launch = mode >= 0 ? mode : g_trsv_multi_launch.load();
+    if ((n + 63) / 64 <= TRSV_P_MAX_NB && !multi_launch) return trsv_launch_persistent(a, st);
+    return trsv_launch_steps(a, st);
+}
+
+extern "C" int apgp_trsv(const double* L, int64_t n, int64_t ldl, const double* b, double shift,
+                         int trans, double* x, double* sumsq, void* stream) {
+    return trsv_run(L, n, ldl, b, shift, trans, x, sumsq, -1, (hipStream_t)stream);
+}
+
+// apgp_trsv with the path chosen PER CALL (trsv_run's mode) -- what a caller uses to re-run one solve whose persistent
+// launch gave up (NaN), without changing the path of other threads' or streams' calls.
+extern "C" int apgp_trsv_ex(const double* L, int64_t n, int64_t ldl, const double* b, double shift,
+                            int trans, double* x, double* sumsq, int mode, void* stream) {
+    return trsv_run(L, n, ldl, b, shift, trans, x, sumsq, mode < 0 ? -1 : (mode ? 1 : 0), (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------
@@ -742,18 +713,6 @@ __global__ void append_diag_kernel(double* ljj, const double* ss, double kdiag, 
     const double d2 = kdiag - *ss;
     if (d2 > 0.0 && d2 < INFINITY) *ljj = sqrt(d2);
     else { *ljj = 1.0; atomicCAS(info, 0, order); }
-}
-
-// apgp_trsv with the path chosen PER CALL (mode 0: the persistent launch where it applies, 1: a launch per 256 rows, < 0: the
-// process-wide switch apgp_trsv_mode) -- what a caller uses to re-run one solve whose persistent launch gave up (NaN), without
-// changing the path of other threads' or streams' calls.
-extern "C" int apgp_trsv_ex(const double* L, int64_t n, int64_t ldl, const double* b, double shift,
-                            int trans, double* x, double* sumsq, int mode, void* stream) {
-    const int saved = tl_trsv_mode;
-    tl_trsv_mode = mode < 0 ? -1 : (mode ? 1 : 0);
-    const int rc = apgp_trsv(L, n, ldl, b, shift, trans, x, sumsq, stream);
-    tl_trsv_mode = saved;
-    return rc;
 }
 
 extern "C" int apgp_append_diag(double* ljj, const double* ss, double kdiag, int32_t* info_dev, int64_t order,

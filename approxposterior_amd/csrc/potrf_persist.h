@@ -1,8 +1,8 @@
 // The blocked Cholesky of potrf.hip as ONE persistent launch (round 4): no launch boundary between the 64-column
 // steps, the trailing update off the critical path, and the 64 x 64 products of the next block column fed group by
-// group while the current one is still being factorised.  Included by potrf.hip (same translation unit: it reuses
-// the panel wavefront roles unchanged, so every element sees the arithmetic of the multi-launch path in the same
-// order and the two factorisations are bit-identical -- tests/test_gpu_parity.py compares them).
+// group while the current one is still being factorised.  Included by potrf.hip (same translation unit; every
+// element sees the operations of the multi-launch path's panel wavefronts in the same order, so the two
+// factorisations are bit-identical -- tests/test_gpu_parity.py compares them).
 //
 // Replaces, per gpUtils._nll evaluation (gpUtils.py:46-80 -> george GP.log_likelihood -> BasicSolver.compute),
 // the chain of 18 (N = 1152) .. 64 (N = 4096) dependent potrf_step_kernel launches.
@@ -10,24 +10,27 @@
 // Grid: nb "row" workgroups (one per 64-row block, 512 threads = 8 wavefronts, one per CU) + "update" workgroups.
 //
 // Row workgroup r lives through the steps s = 0 .. r.  At step s < r it holds T = tile (r, s) and D = the diagonal
-// block (s, s), both updated with the block columns < s, and runs the panel step of the multi-launch path:
-//   wavefront 0  factorises D (redundantly in every row workgroup, as before: no workgroup waits for a factor);
-//   wavefront 2  is its helper (columns 32 .. 63 of groups 0 .. 7; it hands the next group's four columns back first);
-//                afterwards it stages the NEXT step's two tiles -- tile (r, s+1) and the diagonal block (s+1, s+1),
-//                final in memory once the update workgroups have flagged them -- in LDS, coalesced, exactly where the
-//                hand-over puts the differences (pp_stage_tiles);
-//   wavefront 1  solves the 64 rows of T one 4-column group behind and publishes each solved group to LDS (the A
+// block (s, s), both updated with the block columns < s, and runs the panel step in super-groups of 16 columns
+// (round 5: potrf_persist_sg.h has these roles and says what became of round 4's):
+//   wavefront 0  factorises D, 16 columns at a time (redundantly in every row workgroup: no workgroup waits for a
+//                factor);
+//   wavefront 1  solves the 64 rows of T behind it, one 4-column group at a time, and publishes each to LDS (the A
 //                operand of this workgroup's next products); once done it stores L(r, s) to memory (write-through;
 //                the flag for the update workgroups follows at the head of the next step, when the stores have drained);
+//   wavefront 2  stages the NEXT step's two tiles -- tile (r, s+1) and the diagonal block (s+1, s+1), final in memory
+//                once the update workgroups have flagged them -- in LDS, coalesced, exactly where the hand-over puts
+//                the differences (pp_stage_tiles); it no longer shares the factorisation;
 //   wavefront 3  in workgroup s + 1 -- whose rows are the B operand of everybody's next products -- forwards every
 //                solved group to global memory as data-tagged granules (16 bytes per value: {low word, tag, high
 //                word, tag}; the consumer needs no flag, the producer no fence or wait); in every other workgroup it
 //                receives them (four 16-byte write-through-coherent loads per lane and look) into LDS; it also
 //                carries this block row's right-hand side of the forward solve z = L^-1 (y - mean);
-//   wavefronts 4-7 multiply: tile (r, s+1) -= L(r, s) L(s+1, s)^T and the next diagonal block (s+1, s+1) -=
-//                L(s+1, s) L(s+1, s)^T, one k = 4 step of v_mfma_f64_4x4x4_4b per published group (no memory access),
-//                so that when the last group of the factorisation is out only ONE k-step, the subtraction from the
-//                staged values and the workgroup's one barrier per step remain.
+//   wavefronts 4-7 apply every finished super-group of D and of T to the columns right of it (the "catch-ups", on
+//                accumulators they hold from the step's start) and, between those, multiply: tile (r, s+1) -=
+//                L(r, s) L(s+1, s)^T and the next diagonal block (s+1, s+1) -= L(s+1, s) L(s+1, s)^T, one k = 4 step
+//                of v_mfma_f64_4x4x4_4b per published group (no memory access), so that when the last group of the
+//                factorisation is out only ONE k-step, the subtraction from the staged values and the workgroup's
+//                one barrier per step remain.
 //   The critical path per 64-column step is then the factorisation itself + one granule hand-off + one k-step
 //   (the multi-launch path: launch boundary + operand loads + two 64^3 products + factorisation).
 //   At step r the workgroup factorises its own diagonal block for the output (L_rr, info, z_r): nobody waits for that.
@@ -146,17 +149,6 @@ __device__ __forceinline__ pp_u64 pp_ld(const pp_u64* p) { return __hip_atomic_l
 __device__ __forceinline__ void pp_st(pp_u64* p, pp_u64 v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ double pp_ld_f64(const double* p) { return __longlong_as_double((long long)pp_ld((const pp_u64*)p)); }
 __device__ __forceinline__ void pp_st_f64(double* p, double v) { pp_st((pp_u64*)p, (pp_u64)__double_as_longlong(v)); }
-// 16-byte buffer store whose data registers stay untouched for two more issue slots.  gfx9's rule "a VMEM store of more
-// than 64 bits followed by a VALU write of its data registers needs a wait state" has an exception in the ISA manual --
-// and in LLVM's hazard recogniser -- for MUBUF stores whose soffset is an SGPR; on this chip the store still reads its
-// data late: hipcc recycled the forwarder's data registers in the very next instruction (v_mov into the first dword)
-// and, whenever no other wavefront's instruction happened to fall in between, lanes 12-15 of every 16 stored the NEXT
-// value's low word under THIS value's tag (found when the receiver moved to a SIMD it shares with a wavefront that
-// rarely yields: factor off by 1e-7 relative, silently).  The empty-looking asm keeps the registers live across the nop.
-#define PP_STORE16(data_, rs_, voff_, soff_, aux_) do {                                              \
-        __builtin_amdgcn_raw_buffer_store_b128((data_), (rs_), (voff_), (soff_), (aux_));            \
-        asm volatile("s_nop 1" : : "v"(data_));                                                      \
-    } while (0)
 __device__ __forceinline__ void pp_drain() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
 
 // one failed poll of a global spin: sleeps; every 32nd time looks at the abort word and the clock.
@@ -177,43 +169,6 @@ __device__ __forceinline__ bool pp_give_up(PpSpin& sp, pp_u64* ctl, const pp_u64
 __device__ __forceinline__ void pp_lds_wait_ge(const int* p, int need, int* trip) {
     PANEL_SPIN_WHILE_T(lds_load_volatile(p) < need, trip);
     PANEL_FENCE();
-}
-
-// wavefront 1 of a row workgroup: panel_solve_wave with every solved 4-column group published at once to As (this
-// workgroup's A operand, chunk layout).  In the workgroup whose rows are everybody's B operand wavefront 3 forwards
-// the groups from there to the granule stream (the stores would cost the solving wavefront ~1 us per step, and its
-// groups pace everybody).  The rows themselves go to memory from As once all sixteen groups are solved (pp_role_solve).
-__device__ __forceinline__ void pp_solve_wave(const int lane, double (&x)[PB], const double (*Ls)[PB + 2], const double* invd,
-                                              int* prog_p, double* As_par, int* xprog_p, int* trip) {
-    static_for<PB / CB>([&](auto cc_) {
-        constexpr int cc = decltype(cc_)::value, c0 = CB * cc;
-        pp_lds_wait_ge(prog_p, c0 + CB, trip);           // columns c0 .. c0 + CB - 1 of L_jj published
-        f64x2 dq[CB][CB / 2], iq[CB / 2];
-#pragma unroll
-        for (int r = 0; r < CB; ++r)
-#pragma unroll
-            for (int q = 0; 2 * q < r; ++q) dq[r][q] = *(const f64x2*)(&Ls[c0 + r][c0 + 2 * q]);
-#pragma unroll
-        for (int q = 0; q < CB / 2; ++q) iq[q] = *(const f64x2*)(&invd[c0 + 2 * q]);
-        PANEL_FENCE();
-        double xs[CB];
-#pragma unroll
-        for (int k = 0; k < CB; ++k) {
-            double sacc = x[c0 + k];
-#pragma unroll
-            for (int m = 0; m < k; ++m) sacc = fma(-xs[m], (m & 1) ? dq[k][m >> 1].y : dq[k][m >> 1].x, sacc);
-            xs[k] = sacc * ((k & 1) ? iq[k >> 1].y : iq[k >> 1].x);
-            x[c0 + k] = xs[k];
-        }
-        {
-            double* dst = As_par + (cc >> 2) * PP_CHUNK + lane * 18 + 4 * (cc & 3);
-            *(f64x2*)dst = (f64x2){xs[0], xs[1]};
-            *(f64x2*)(dst + 2) = (f64x2){xs[2], xs[3]};
-            lds_store_volatile(xprog_p, cc + 1);         // (same wavefront: LDS stores stay in order)
-        }
-        PANEL_FENCE();
-        panel_trailing<c0, c0 + CB, PB, 0, PB>(x, xs, Ls);
-    });
 }
 
 // one k = 4 step (group g of the current block column) of a matrix wavefront's 32 x 32 quadrant:
@@ -429,7 +384,7 @@ __device__ PP_NOINLINE void pp_role_recv(unsigned lds_off, PpKarg karg, double r
 #pragma unroll
             for (int k = 0; k < CB; ++k) {
                 const pp_u32x4 g = {(unsigned)__double2loint(xs[k]), tag, (unsigned)__double2hiint(xs[k]), tag};
-                PP_STORE16(g, rs_strm, (unsigned)(lane * 64 + k * 16), (unsigned)((s * 16 + cc) * 4096), 16);
+                APGP_STORE16(g, rs_strm, (unsigned)(lane * 64 + k * 16), (unsigned)((s * 16 + cc) * 4096), 16);
             }
             if (cc == 15) PP_STAMPP(s, 22);
         });

@@ -190,7 +190,7 @@ __device__ PP_NOINLINE void pp_role_factor(unsigned lds_off, PpKarg karg) {
             const unsigned tag = (unsigned)q->call_id;
             const pp_u32x4 g = {(unsigned)__double2loint(ri), tag, (unsigned)__double2hiint(ri), tag};
             const __amdgpu_buffer_rsrc_t rs_z = __builtin_amdgcn_make_buffer_rsrc((void*)q->zstrm, 0, (int)(PP_ZSTRM_WORDS * 8), 0x00020000);
-            PP_STORE16(g, rs_z, (unsigned)(lane * 16), (unsigned)(s * 1024), 16);
+            APGP_STORE16(g, rs_z, (unsigned)(lane * 16), (unsigned)(s * 1024), 16);
         }
     }
     PP_STEP_LOOP_END()
@@ -309,7 +309,7 @@ __device__ PP_NOINLINE void pp_role_solve(unsigned lds_off, PpKarg karg) {
 #pragma unroll
             for (int k = 0; k < 8; ++k) {
                 const pp_u32x4 w4 = __builtin_bit_cast(pp_u32x4, v[k]);
-                PP_STORE16(w4, rs_A, off0 + (unsigned)(b8 * 8 + k) * 2u * row_b, 0, 16);
+                APGP_STORE16(w4, rs_A, off0 + (unsigned)(b8 * 8 + k) * 2u * row_b, 0, 16);
             }
             PANEL_FENCE();
         }

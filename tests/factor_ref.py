@@ -22,12 +22,12 @@ C_CHOL = 4   |A - L L^T|_ij <= u (min(i,j) + 1 + C_CHOL) (|L||L^T|)_ij.
     up: 4.
 C_TRSV = 3   |op(L) x - (b - shift)|_i <= u ((n_i + C_TRSV) (|op(L)||x|)_i + |b_i - shift|), n_i terms in row i.
     b - shift rounds once (the |b_i - shift| term; Lemma 8.4 leaves the right-hand side unperturbed otherwise).  The
-    pivot is a division in trsv_kernel (linalg.hip:156,179: one rounding), a product with a rounded reciprocal in
-    trsv_step4_kernel / trsv_persist_kernel / trsv_diag_solve (linalg.hip:383,452: two), and zacc * r with the 1.5 u
-    reciprocal square root against the 1 u diagonal in the solve that rides along apgp_potrf (potrf.hip:331: 3.5 u on
+    pivot is a division in trsv_kernel (its two substitution loops: one rounding), a product with a rounded reciprocal
+    in trsv_step4_kernel / trsv_persist_kernel (`inv = 1.0 / Lb[lane][lane]`, then `* inv`: two), and zacc * r with
+    the 1.5 u reciprocal square root against the 1 u diagonal in the solve that rides along apgp_potrf (potrf.hip:331: 3.5 u on
     the diagonal term l_ii x_i).  Off-diagonal tiles are 16-term fma chains added pairwise and subtracted in block
-    order (linalg.hip:371-375): 16 + 2 + J + i % 64 + 2 <= n_i + 1 from the second block row on; trsv_kernel's
-    transposed sweep (linalg.hip:187-193) subtracts a chain of up to 64 terms per block: kmax + 1 + (63 - i % 64) + 1
+    order (trsv_tile_chain, trsv_tile_sum): 16 + 2 + J + i % 64 + 2 <= n_i + 1 from the second block row on; trsv_kernel's
+    transposed sweep (its `r[c] -= acc` loop) subtracts a chain of up to 64 terms per block: kmax + 1 + (63 - i % 64) + 1
     = n_i + 1.  The largest excess over n_i is therefore the first row of potrf's solve, n_i = 1 with 3.5 roundings:
     + 2.5, rounded up: 3.
 C_SYRK = 1   |sum_k W_ki W_kj - truth| <= u (n - max(i,j) + C_SYRK) sum_k |W_ki||W_kj|   (grad.hip:40, syrk_wtw_kernel).
@@ -35,8 +35,8 @@ C_SYRK = 1   |sum_k W_ki W_kj - truth| <= u (n - max(i,j) + C_SYRK) sum_k |W_ki|
     (k < max(i, j), W is lower triangular) add exact zeros.  + 1 for a product that the instruction may round before
     it adds (the ISA guide does not promise a fused product).
 x.x          |ss - x.x| <= u depth sum x_i^2: one product, six shuffle levels, then 16 wavefront partials in order
-    (trsv_kernel, linalg.hip:198-211, sumsq_kernel) or one addition per 64-row block (trsv_step4_kernel / persistent,
-    linalg.hip:404-406, 612-614); sumsq_kernel's strided loop adds ceil(n / 1024) - 1.
+    (trsv_kernel's closing loop, sumsq_kernel) or one addition per 64-row block (trsv_step4_kernel / persistent,
+    trsv_block_sumsq); sumsq_kernel's strided loop adds ceil(n / 1024) - 1.
 gradient     see ``grad_record``.
 """
 import math

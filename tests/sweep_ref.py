@@ -5,7 +5,7 @@ CONDITION-FREE error budgets.  Plain Python (NumPy long double, kvalue_ref's exa
 import.
 
 Images (bit for bit)
-    ``pack_linv``    restates pack_linv_kernel (csrc/linalg.hip:1184-1214): packed tile (ib, kc) holds, at e =
+    ``pack_linv``    restates pack_linv_kernel (csrc/linalg.hip): packed tile (ib, kc) holds, at e =
                      ((s 2 + kp) 64 + p) 2 + q, W[512 ib + 16 s + (p & 15)][16 kc + 4 (2 kp + q) + (p >> 4)], zero above
                      the diagonal and from row n on; row block ib has chunks 0 .. 32 (ib + 1) - 1.
     ``pack_lsolve``  restates pack_lsolve_kernel (csrc/sweep.hip:2113-2160) operation by operation: -L where the
@@ -401,8 +401,8 @@ def solve_residual_bound(L, v, ak, ek):
 
 
 def predict1_counts(n):
-    """Roundings on a term's way in apgp_predict1_host (csrc/linalg.hip:896-955; the single-launch kernel for n <= 256
-    forms every sum in the same order, linalg.hip:957-988):
+    """Roundings on a term's way in apgp_predict1_host (csrc/linalg.hip: pred1_kstar_kernel, pred1_final_kernel;
+    the single-launch kernel for n <= 256, pred1_small_kernel, forms every sum in the same order):
       mu       kv * alpha (1), six shuffle levels, (red0 + red1) + (red2 + red3) (2), one addition per 256-row part;
       v        through winv: winv_gemv_kernel with shift = 0 (``winv_depth`` less the subtraction); through L: apgp_trsv,
                factor_ref's C_TRSV residual |L v - k*|_i <= u ((i + 1 + C_TRSV) (|L||v|)_i + |k*_i|);
@@ -533,10 +533,10 @@ def restate(W, X, alpha, T, k, mean, kf=None, mutant=None, form="inverse"):
 def trtri_bound(L, W):
     """Entrywise bound of |L W^ - I| (n x n, lower triangle) for the device's inverse, by its own recursion.
 
-    Diagonal 64-blocks (trtri_diag_kernel, csrc/linalg.hip:1077-1120): column c by substitution, x_i = -srow r_i with
+    Diagonal 64-blocks (trtri_diag_kernel, csrc/linalg.hip): column c by substitution, x_i = -srow r_i with
     srow an fma chain over the i - c non-zero terms and r_i = 1 / L_ii rounded:
         |L_D X_D - I|_ic <= u (i - c + 2) (|L_D||X_D|)_ic,  <= u |L_cc x_c| on the diagonal.
-    Merge of two halves at level s (trtri_merge_kernel, linalg.hip:1136-1181; apgp_gemm64_tile chains its instructions
+    Merge of two halves at level s (trtri_merge_kernel, linalg.hip; apgp_gemm64_tile chains its instructions
     over the k range, csrc/mma16.h:89-132): T^ = L21 W11 + E1 and W21 = -(W22 T^ + E2), each product a chain over at
     most 64 s columns, g = 64 s + 1 with the product's own rounding (negation exact).  Then
         (L W)_21 = L21 W11 + L22 W21 = -E1 - (L22 W22 - I) T^ - L22 E2,
@@ -635,7 +635,7 @@ def trtri_big_rows(n):
 
 
 # ----------------------------------------------------------------------------------------------------------------------
-# apgp_winv_apply: x = W (b - shift) or W^T b through the dense panel (csrc/linalg.hip:777-825)
+# apgp_winv_apply: x = W (b - shift) or W^T b through the dense panel (csrc/linalg.hip: winv_gemv_kernel, winv_gemvt_*_kernel)
 # ----------------------------------------------------------------------------------------------------------------------
 WA_RCH = 128
 

@@ -18,7 +18,7 @@ def _tool(name):
 def test_no_wide_store_has_its_data_registers_overwritten_at_once():
     """A 16-byte VMEM store reads its data registers late; LLVM exempts MUBUF stores with an SGPR soffset from the
     wait state, MI355X does not (round 4: wrong low words under valid tags in the persistent Cholesky's granule
-    stream, csrc/potrf_persist.h PP_STORE16).  Every wide store in the shipped library must keep its data registers
+    stream, csrc/apgp_common.h APGP_STORE16).  Every wide store in the shipped library must keep its data registers
     untouched for the next two issue slots."""
     from approxposterior_amd import _lib
     tools = "/opt/rocm/lib/llvm/bin"

@@ -1147,7 +1147,9 @@ def test_persistent_cholesky_two_streams_at_once(lib_loaded):
 
 
 @pytest.mark.parametrize("trans", [0, 1])
-@pytest.mark.parametrize("n", [256, 300, 1100, 1153, 2048, 4095, 8000])
+# (320: a second super-block of one full sub-block; 577 = 9 * 64 + 1: a third super-block of one full and one 1-row
+# sub-block -- the tile subtraction inside a super-block meets the ragged substitution)
+@pytest.mark.parametrize("n", [256, 300, 320, 577, 1100, 1153, 2048, 4095, 8000])
 def test_persistent_trsv_bit_identical_to_multi_launch(n, trans, lib_loaded):
     """K3 (george BasicSolver.apply_inverse on a vector: gpUtils.py:78, utility.py:131): the blocked triangular solve as
     ONE persistent launch (trsv_persist_kernel: a workgroup per 64-row block, solved blocks handed on as tagged granules,

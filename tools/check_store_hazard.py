@@ -4,7 +4,7 @@ A VMEM store of more than 64 bits reads its data registers a few cycles after it
 before a VALU instruction may overwrite them -- has an exception in the ISA manual, and in LLVM, for MUBUF stores whose
 soffset operand is an SGPR.  On MI355X that exception does not hold: with `buffer_store_dwordx4 v[6:9], ..., s25 offen`
 followed directly by `v_mov_b32 v6, ...` lanes 12-15 of every 16 stored the new value of v6 (round 4: the persistent
-Cholesky's granule forwarder, potrf_persist.h PP_STORE16; low words of forwarded values wrong under valid tags whenever no
+Cholesky's granule forwarder, apgp_common.h APGP_STORE16; low words of forwarded values wrong under valid tags whenever no
 other wavefront's instruction fell between the two).  This tool disassembles every gfx950 code object in libapgp.so and
 reports each wide store (x3 / x4, buffer / global / flat / scratch) whose data registers are written by one of the next
 two instructions without an intervening s_nop.

@@ -10,6 +10,11 @@ if "--lib" in sys.argv:          # an experimental build: python tools/check_trs
     i = sys.argv.index("--lib")
     _lib.LIB_PATH = os.path.abspath(sys.argv[i + 1])
     del sys.argv[i:i + 2]
+REPS = 50                        # timed calls per figure (--reps N; a tenth of them, at least 3, warm up first)
+if "--reps" in sys.argv:
+    i = sys.argv.index("--reps")
+    REPS = int(sys.argv[i + 1])
+    del sys.argv[i:i + 2]
 lib = _lib.load()
 dev = torch.device("cuda:0")
 bad = 0
@@ -69,12 +74,12 @@ for n in (512, 1152, 4096):
         res = []
         for mode in (1, 0):
             lib.apgp_trsv_mode(mode)
-            for _ in range(3):
+            for _ in range(max(3, REPS // 10)):
                 lib.apgp_trsv(L.data_ptr(), n, n, b.data_ptr(), 0.0, trans, x.data_ptr(), ss.data_ptr(), None)
             torch.cuda.synchronize(); t0 = time.perf_counter()
-            for _ in range(50):
+            for _ in range(REPS):
                 lib.apgp_trsv(L.data_ptr(), n, n, b.data_ptr(), 0.0, trans, x.data_ptr(), ss.data_ptr(), None)
-            torch.cuda.synchronize(); res.append((time.perf_counter() - t0) / 50)
+            torch.cuda.synchronize(); res.append((time.perf_counter() - t0) / REPS)
         lib.apgp_trsv_mode(0)
         print("apgp_trsv n=%4d trans=%d: multi-launch %.3f ms, persistent %.3f ms" % (n, trans, res[0] * 1e3, res[1] * 1e3), flush=True)
 print("FAILURES: %d" % bad)
