@@ -1,6 +1,7 @@
-// Proposals of the on-device ensemble sampler (ensemble.hip: ensemble_kernel and ensemble_mw_kernel call ens_propose, so
-// the two cannot drift apart), and the counter-based RNG they draw from.  tests/ensemble_moves_ref.py states the recipe;
-// this file implements that text.
+// Proposals of the on-device ensemble sampler and the counter-based RNG they draw from.  ensemble_kernel and
+// ensemble_mw_kernel (ensemble.hip) share one sampler body so that the two cannot drift apart: ens_propose here, and in
+// ensemble.hip, above the kernels, the walker load, the GP-mean row loops, the start gate, the iteration prologue, the slot
+// index, the accept step and the walker store.  tests/ensemble_moves_ref.py states the recipe; this file implements that text.
 //
 // A half-step moves slot t of the active half S (walker s) against the complement C (H = W / 2 slots), all slots in
 // parallel against the positions at its start, which are the kernel's scaled coordinates x * sc.  Every draw is a pure

@@ -39,12 +39,152 @@ struct EnsArgs {
     double sc[APGP_MAX_DIM], lo[APGP_MAX_DIM], hi[APGP_MAX_DIM], lw[APGP_MAX_DIM];
 };
 
-// XLDS: the packed training stream (Npad x (DPAD+2) doubles) is staged into LDS once
-// (it is re-read by every walker of every half-step); falls back to L2 when it does
-// not fit beside the sampler state.
+// ---------------------------------------------------------------------------
+// The sampler body: the steps the two kernels below share, each spelled once and force-inlined (as ens_propose is).  A
+// kernel is its schedule -- who evaluates which proposals and how the values reach the accept step -- around them.
+// ---------------------------------------------------------------------------
+// Lane sums of k(p, x_k) alpha_k over the training rows first, first + stride, ... (xs: the stream, in LDS or L2) for TWO
+// points t0 / t1 (scaled coordinates), butterflied over the wavefront.  Every row read serves both points: the stream is
+// 80 B per row and is read by all wavefronts of every half-step; with one point per pass the LDS, not the arithmetic, set
+// the pace.  Each point's sum runs in the order of ens_rows1.
+template <int DPAD>
+__device__ __forceinline__ void ens_rows2(const EnsArgs& a, const double* xs, const double* etab, const double (&t0)[DPAD],
+                                          const double (&t1)[DPAD], const int first, const int stride, double& r0, double& r1) {
+    double acc0 = 0.0, acc1 = 0.0;
+    const int nn = (int)a.n;
+    for (int k = first; k < nn; k += stride) {
+        const double* xr = xs + k * (DPAD + 2);
+        double xv[DPAD];
+#pragma unroll
+        for (int d = 0; d < DPAD; ++d) xv[d] = xr[d];
+        const double al = xr[DPAD];
+        double s0 = 0.0, s03 = 0.0, s1 = 0.0, s13 = 0.0;
+#pragma unroll
+        for (int d = 0; d < DPAD; d += 2) {
+            const double a0 = t0[d] - xv[d], a1 = t0[d + 1] - xv[d + 1];
+            const double b0 = t1[d] - xv[d], b1 = t1[d + 1] - xv[d + 1];
+            s0 = fma(a0, a0, s0); s03 = fma(a1, a1, s03);
+            s1 = fma(b0, b0, s1); s13 = fma(b1, b1, s13);
+        }
+        double kv0 = a.amp * apgp_exp(-(s0 + s03), etab);
+        double kv1 = a.amp * apgp_exp(-(s1 + s13), etab);
+        if (a.lin_coef != 0.0) {
+            double ls;
+            APGP_LIN_SUM(ls, DPAD, a.ndim, a.lin_order, t0[d_] * xv[d_] * a.lw[d_]);
+            kv0 = fma(a.lin_coef, ls, kv0);
+            APGP_LIN_SUM(ls, DPAD, a.ndim, a.lin_order, t1[d_] * xv[d_] * a.lw[d_]);
+            kv1 = fma(a.lin_coef, ls, kv1);
+        }
+        acc0 = fma(kv0, al, acc0);
+        acc1 = fma(kv1, al, acc1);
+    }
+    for (int o = 32; o > 0; o >>= 1) { acc0 += __shfl_xor(acc0, o); acc1 += __shfl_xor(acc1, o); }
+    r0 = acc0;
+    r1 = acc1;
+}
+// its one-point sibling, the same chain per point (start-up; and D > 8, where two points' registers do not fit 16 wavefronts)
+template <int DPAD>
+__device__ __forceinline__ double ens_rows1(const EnsArgs& a, const double* xs, const double* etab, const double* p,
+                                            const int first, const int stride) {
+    double tt[DPAD];
+#pragma unroll
+    for (int d = 0; d < DPAD; ++d) tt[d] = p[d];
+    double acc = 0.0;
+    const int nn = (int)a.n;
+    for (int k = first; k < nn; k += stride) {
+        const double* xr = xs + k * (DPAD + 2);
+        double s = 0.0, s3 = 0.0;
+#pragma unroll
+        for (int d = 0; d < DPAD; d += 2) {
+            const double df0 = tt[d] - xr[d], df1 = tt[d + 1] - xr[d + 1];
+            s = fma(df0, df0, s);
+            s3 = fma(df1, df1, s3);
+        }
+        double kv = a.amp * apgp_exp(-(s + s3), etab);
+        if (a.lin_coef != 0.0) {
+            double ls;
+            APGP_LIN_SUM(ls, DPAD, a.ndim, a.lin_order, tt[d_] * xr[d_] * a.lw[d_]);
+            kv = fma(a.lin_coef, ls, kv);
+        }
+        acc = fma(kv, xr[DPAD], acc);
+    }
+    for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+    return acc;
+}
+
+// Walker load by a workgroup of NT threads: scaled coordinates, accept counters zeroed.  XLDS: the packed training stream
+// (Npad x (DPAD+2) doubles) is staged into LDS once (it is re-read by every walker of every half-step); it stays in L2
+// when it does not fit beside the sampler state.
+template <int DPAD, bool XLDS, int NT>
+__device__ __forceinline__ void ens_load(const EnsArgs& a, const double* gc, double (*cs)[DPAD], int* nacc, double* xsl, const int t) {
+    const int W = a.nwalkers, D = a.ndim;
+    for (int e = t; e < W * DPAD; e += NT) {
+        const int w = e / DPAD, d = e % DPAD;
+        cs[w][d] = d < D ? gc[w * D + d] * a.sc[d] : 0.0;
+    }
+    if (t < W) nacc[t] = 0;
+    if (XLDS) {
+        for (long long e = t; e < a.n * (DPAD + 2); e += NT) xsl[e] = a.xs[e];
+    }
+}
+
+// the start gate: a walker c outside the prior's box has zero probability (as _gpll returns -inf): m, or -inf there
+__device__ __forceinline__ double ens_gate(const EnsArgs& a, const double* c, double m) {
+    for (int d = 0; d < a.ndim; ++d)
+        if (!(c[d] >= a.lo[d] && c[d] <= a.hi[d])) m = -INFINITY;
+    return m;
+}
+
+// walker of slot i of half `half` of the red/blue partition: the active half S of a split is half `split`, its
+// complement C half `1 - split`
+__device__ __forceinline__ int ens_slot(const int i, const int half, const int H, const int rot, const int W) {
+    const int v = i + half * H + rot;
+    return v >= W ? v - W : v;
+}
+
+// The iteration's prologue (Philox tag 5): returns the random cyclic offset of the red/blue partition and, for a mixed
+// table, sets the iteration's move, uniform over the workgroup(s).  (The move of a one-entry table, the default, is read
+// once before the loop, not per iteration.)
+__device__ __forceinline__ int ens_iteration(const EnsMoves& mv, const bool mixed, const long long it, const unsigned int k0,
+                                             const unsigned int k1, const int W, int& mkind, double& mp0, double& mp1) {
+    unsigned int cr[4] = {(unsigned int)it, (unsigned int)(it >> 32), 0xFFFFFFFFu, 0x5u};
+    philox4x32(cr, k0, k1);
+    const int rot = (int)(cr[0] % (unsigned int)W);
+    if (mixed) {
+        const int mi = ens_pick_move(mv, cr);
+        mkind = mv.kind[mi]; mp0 = mv.p0[mi]; mp1 = mv.p1[mi];
+    }
+    return rot;
+}
+
+// the accept step of slot t, whose walker is s
+template <int DPAD>
+__device__ __forceinline__ void ens_accept(const int t, const int s, double (*cs)[DPAD], double* lp, int* nacc,
+                                           const double (*qs)[DPAD], const double* lpq, const double* fac, const double* uacc,
+                                           const int* qok) {
+    const double diff = fac[t] + lpq[t] - lp[s];
+    if (qok[t] && lpq[t] == lpq[t] && log(uacc[t]) < diff) {
+#pragma unroll
+        for (int d = 0; d < DPAD; ++d) cs[s][d] = qs[t][d];
+        lp[s] = lpq[t];
+        nacc[s] += 1;
+    }
+}
+
+// Result writes.  The walkers in plain coordinates, elements first, first + stride, ... of a W x D block:
+template <int DPAD>
+__device__ __forceinline__ void ens_store_walkers(const EnsArgs& a, const double (*cs)[DPAD], double* out, const int W,
+                                                  const int D, const int first, const int stride) {
+    for (int e = first; e < W * D; e += stride) {
+        const int w = e / D, d = e % D;
+        out[e] = cs[w][d] / a.sc[d];
+    }
+}
+
+// One workgroup of 1024 threads per ensemble: slot t proposes and accepts; wavefront wv takes proposals wv and wv + 16
+// through one pass over the training stream (one proposal per pass for D > 8), its lanes striding the rows.
 template <int DPAD, bool XLDS, bool ALLMOVES>
 __global__ __launch_bounds__(1024) void ensemble_kernel(EnsArgs a) {
-    constexpr int XS = DPAD + 2;
     extern __shared__ __attribute__((aligned(16))) double xsl[];
     __shared__ double etab[APGP_EXP_TAB_N];
     __shared__ double cs[ENS_MAXW][DPAD];      // scaled walker coordinates
@@ -60,111 +200,37 @@ __global__ __launch_bounds__(1024) void ensemble_kernel(EnsArgs a) {
     const long long ens = blockIdx.x;
     apgp_exp_tab_load(etab);
     double* gc = a.coords + ens * W * D;
-    for (int e = t; e < W * DPAD; e += 1024) {
-        const int w = e / DPAD, d = e % DPAD;
-        cs[w][d] = d < D ? gc[w * D + d] * a.sc[d] : 0.0;
-    }
-    if (t < W) nacc[t] = 0;
-    if (XLDS) {
-        for (long long e = t; e < a.n * XS; e += 1024) xsl[e] = a.xs[e];
-    }
+    ens_load<DPAD, XLDS, 1024>(a, gc, cs, nacc, xsl, t);
     __syncthreads();
 
-    // GP means of TWO points (scaled coordinates p0 / p1[0..DPAD)) by one wavefront: every training
-    // row read from LDS serves both (the stream is 80 B per row and is read by all 16 wavefronts of
-    // every half-step: with one point per pass the LDS, not the arithmetic, set the pace).  Each
-    // point's sum runs in the same order as a single-point pass.
+    // GP means of two points and of one by one wavefront, its lanes striding the training rows
     auto gp_mean2 = [&](const double* p0, const double* p1, double& m0, double& m1) {
         double t0[DPAD], t1[DPAD];
 #pragma unroll
         for (int d = 0; d < DPAD; ++d) { t0[d] = p0[d]; t1[d] = p1[d]; }
-        double acc0 = 0.0, acc1 = 0.0;
-        const int nn = (int)a.n;
-        for (int k = lane; k < nn; k += 64) {
-            const double* xr = (XLDS ? (const double*)xsl : a.xs) + k * XS;
-            double xv[DPAD];
-#pragma unroll
-            for (int d = 0; d < DPAD; ++d) xv[d] = xr[d];
-            const double al = xr[DPAD];
-            double s0 = 0.0, s03 = 0.0, s1 = 0.0, s13 = 0.0;
-#pragma unroll
-            for (int d = 0; d < DPAD; d += 2) {
-                const double a0 = t0[d] - xv[d], a1 = t0[d + 1] - xv[d + 1];
-                const double b0 = t1[d] - xv[d], b1 = t1[d + 1] - xv[d + 1];
-                s0 = fma(a0, a0, s0); s03 = fma(a1, a1, s03);
-                s1 = fma(b0, b0, s1); s13 = fma(b1, b1, s13);
-            }
-            double kv0 = a.amp * apgp_exp(-(s0 + s03), etab);
-            double kv1 = a.amp * apgp_exp(-(s1 + s13), etab);
-            if (a.lin_coef != 0.0) {
-                double ls;
-                APGP_LIN_SUM(ls, DPAD, a.ndim, a.lin_order, t0[d_] * xv[d_] * a.lw[d_]);
-                kv0 = fma(a.lin_coef, ls, kv0);
-                APGP_LIN_SUM(ls, DPAD, a.ndim, a.lin_order, t1[d_] * xv[d_] * a.lw[d_]);
-                kv1 = fma(a.lin_coef, ls, kv1);
-            }
-            acc0 = fma(kv0, al, acc0);
-            acc1 = fma(kv1, al, acc1);
-        }
-        for (int o = 32; o > 0; o >>= 1) { acc0 += __shfl_xor(acc0, o); acc1 += __shfl_xor(acc1, o); }
+        double acc0, acc1;
+        ens_rows2<DPAD>(a, XLDS ? (const double*)xsl : a.xs, etab, t0, t1, lane, 64, acc0, acc1);
         m0 = acc0 + a.mean;
         m1 = acc1 + a.mean;
     };
-    // one point per pass (start-up; and D > 8, where two points' registers do not fit 16 wavefronts)
-    auto gp_mean = [&](const double* p) {
-        double tt[DPAD];
-#pragma unroll
-        for (int d = 0; d < DPAD; ++d) tt[d] = p[d];
-        double acc = 0.0;
-        const int nn = (int)a.n;
-        for (int k = lane; k < nn; k += 64) {
-            const double* xr = (XLDS ? (const double*)xsl : a.xs) + k * XS;
-            double s = 0.0, s3 = 0.0;
-#pragma unroll
-            for (int d = 0; d < DPAD; d += 2) {
-                const double df0 = tt[d] - xr[d], df1 = tt[d + 1] - xr[d + 1];
-                s = fma(df0, df0, s);
-                s3 = fma(df1, df1, s3);
-            }
-            double kv = a.amp * apgp_exp(-(s + s3), etab);
-            if (a.lin_coef != 0.0) {
-                double ls;
-                APGP_LIN_SUM(ls, DPAD, a.ndim, a.lin_order, tt[d_] * xr[d_] * a.lw[d_]);
-                kv = fma(a.lin_coef, ls, kv);
-            }
-            acc = fma(kv, xr[DPAD], acc);
-        }
-        for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
-        return acc + a.mean;
-    };
+    auto gp_mean = [&](const double* p) { return ens_rows1<DPAD>(a, XLDS ? (const double*)xsl : a.xs, etab, p, lane, 64) + a.mean; };
 
     for (int w = wv; w < W; w += 16) {
         double m = gp_mean(cs[w]);
-        // walkers that start outside the prior have zero probability (as _gpll returns -inf)
-        for (int d = 0; d < D; ++d)
-            if (!(cs[w][d] >= a.lo[d] && cs[w][d] <= a.hi[d])) m = -INFINITY;
+        m = ens_gate(a, cs[w], m);
         if (lane == 0) lp[w] = m;
     }
     __syncthreads();
 
     const unsigned int k0 = (unsigned int)a.seed, k1 = (unsigned int)(a.seed >> 32) ^ (unsigned int)(ens * 0x9E3779B9u);
-    // the move of a one-entry table (the default) is read once, not per iteration
     const bool mixed = a.mv.n > 1;
     int mkind = a.mv.kind[0];
     double mp0 = a.mv.p0[0], mp1 = a.mv.p1[0];
     for (long long it = 0; it < a.iterations; ++it) {
-        // random cyclic offset of the red/blue partition for this iteration
-        unsigned int cr[4] = {(unsigned int)it, (unsigned int)(it >> 32), 0xFFFFFFFFu, 0x5u};
-        philox4x32(cr, k0, k1);
-        const int rot = (int)(cr[0] % (unsigned int)W);
-        if (mixed) {                                            // the iteration's move: uniform over the workgroup(s)
-            const int mi = ens_pick_move(a.mv, cr);
-            mkind = a.mv.kind[mi]; mp0 = a.mv.p0[mi]; mp1 = a.mv.p1[mi];
-        }
+        const int rot = ens_iteration(a.mv, mixed, it, k0, k1, W, mkind, mp0, mp1);
         for (int split = 0; split < 2; ++split) {
-            // walker index of slot i of the active half S and of the complement C
-            auto s_idx = [&](int i) { int v = i + split * H + rot; return v >= W ? v - W : v; };
-            auto c_idx = [&](int i) { int v = i + (1 - split) * H + rot; return v >= W ? v - W : v; };
+            auto s_idx = [&](int i) { return ens_slot(i, split, H, rot, W); };
+            auto c_idx = [&](int i) { return ens_slot(i, 1 - split, H, rot, W); };
             if (t < H) {
                 qok[t] = ens_propose<DPAD, ALLMOVES>(mkind, mp0, mp1, cs, s_idx(t), c_idx, H, D, a.lo, a.hi, it, split, t, k0, k1, qs[t],
                                            fac[t], uacc[t]) ? 1 : 0;
@@ -191,31 +257,13 @@ __global__ __launch_bounds__(1024) void ensemble_kernel(EnsArgs a) {
                 }
             }
             __syncthreads();
-            if (t < H) {
-                const int s = s_idx(t);
-                const double diff = fac[t] + lpq[t] - lp[s];
-                if (qok[t] && lpq[t] == lpq[t] && log(uacc[t]) < diff) {
-#pragma unroll
-                    for (int d = 0; d < DPAD; ++d) cs[s][d] = qs[t][d];
-                    lp[s] = lpq[t];
-                    nacc[s] += 1;
-                }
-            }
+            if (t < H) ens_accept<DPAD>(t, s_idx(t), cs, lp, nacc, qs, lpq, fac, uacc, qok);
             __syncthreads();
         }
-        if (a.chain) {
-            double* out = a.chain + ((it * gridDim.x + ens) * W) * D;
-            for (int e = t; e < W * D; e += 1024) {
-                const int w = e / D, d = e % D;
-                out[e] = cs[w][d] / a.sc[d];
-            }
-        }
+        if (a.chain) ens_store_walkers<DPAD>(a, cs, a.chain + ((it * gridDim.x + ens) * W) * D, W, D, t, 1024);
         if (a.logp_chain && t < W) a.logp_chain[(it * gridDim.x + ens) * W + t] = lp[t];
     }
-    for (int e = t; e < W * D; e += 1024) {
-        const int w = e / D, d = e % D;
-        gc[e] = cs[w][d] / a.sc[d];
-    }
+    ens_store_walkers<DPAD>(a, cs, gc, W, D, t, 1024);
     if (t < W) {
         a.logp[ens * W + t] = lp[t];
         a.naccept[ens * W + t] = nacc[t];
@@ -246,7 +294,6 @@ typedef unsigned int ens_u32x4 __attribute__((ext_vector_type(4)));
 template <int DPAD, bool XLDS, bool ALLMOVES>
 __global__ __launch_bounds__(256) void ensemble_mw_kernel(EnsMwArgs q) {
     const EnsArgs& a = q.e;
-    constexpr int XS = DPAD + 2;
     extern __shared__ __attribute__((aligned(16))) double xsl[];
     __shared__ double etab[APGP_EXP_TAB_N];
     __shared__ double cs[ENS_MAXW][DPAD];
@@ -265,51 +312,17 @@ __global__ __launch_bounds__(256) void ensemble_mw_kernel(EnsMwArgs q) {
     const int g = (int)(blockIdx.x % G);
     apgp_exp_tab_load(etab);
     double* gc = a.coords + ens * W * D;
-    for (int e = t; e < W * DPAD; e += 256) {
-        const int w = e / DPAD, d = e % DPAD;
-        cs[w][d] = d < D ? gc[w * D + d] * a.sc[d] : 0.0;
-    }
-    if (t < W) nacc[t] = 0;
+    ens_load<DPAD, XLDS, 256>(a, gc, cs, nacc, xsl, t);
     if (t == 0) gaveup = 0;
-    if (XLDS) {
-        for (long long e = t; e < a.n * XS; e += 256) xsl[e] = a.xs[e];
-    }
     __syncthreads();
-    const int nn = (int)a.n;
     // GP means of one or two points by the WHOLE workgroup: row k goes to thread k mod 256 (wavefront (k / 64) mod 4), each
     // wavefront butterflies its lanes, the four partial sums are added 0 + 1 + 2 + 3
     auto gp_mean_wg = [&](const double* p0, const double* p1, const bool two, double& m0, double& m1) {
         double t0[DPAD], t1[DPAD];
 #pragma unroll
         for (int d = 0; d < DPAD; ++d) { t0[d] = p0[d]; t1[d] = two ? p1[d] : p0[d]; }
-        double acc0 = 0.0, acc1 = 0.0;
-        for (int k = t; k < nn; k += 256) {
-            const double* xr = (XLDS ? (const double*)xsl : a.xs) + k * XS;
-            double xv[DPAD];
-#pragma unroll
-            for (int d = 0; d < DPAD; ++d) xv[d] = xr[d];
-            const double al = xr[DPAD];
-            double s0 = 0.0, s03 = 0.0, s1 = 0.0, s13 = 0.0;
-#pragma unroll
-            for (int d = 0; d < DPAD; d += 2) {
-                const double a0 = t0[d] - xv[d], a1 = t0[d + 1] - xv[d + 1];
-                const double b0 = t1[d] - xv[d], b1 = t1[d + 1] - xv[d + 1];
-                s0 = fma(a0, a0, s0); s03 = fma(a1, a1, s03);
-                s1 = fma(b0, b0, s1); s13 = fma(b1, b1, s13);
-            }
-            double kv0 = a.amp * apgp_exp(-(s0 + s03), etab);
-            double kv1 = a.amp * apgp_exp(-(s1 + s13), etab);
-            if (a.lin_coef != 0.0) {
-                double ls;
-                APGP_LIN_SUM(ls, DPAD, a.ndim, a.lin_order, t0[d_] * xv[d_] * a.lw[d_]);
-                kv0 = fma(a.lin_coef, ls, kv0);
-                APGP_LIN_SUM(ls, DPAD, a.ndim, a.lin_order, t1[d_] * xv[d_] * a.lw[d_]);
-                kv1 = fma(a.lin_coef, ls, kv1);
-            }
-            acc0 = fma(kv0, al, acc0);
-            acc1 = fma(kv1, al, acc1);
-        }
-        for (int o = 32; o > 0; o >>= 1) { acc0 += __shfl_xor(acc0, o); acc1 += __shfl_xor(acc1, o); }
+        double acc0, acc1;
+        ens_rows2<DPAD>(a, XLDS ? (const double*)xsl : a.xs, etab, t0, t1, t, 256, acc0, acc1);
         if (lane == 0) { part[wv][0] = acc0; part[wv][1] = acc1; }
         __syncthreads();
         m0 = ((part[0][0] + part[1][0]) + part[2][0]) + part[3][0] + a.mean;
@@ -321,12 +334,8 @@ __global__ __launch_bounds__(256) void ensemble_mw_kernel(EnsMwArgs q) {
         double m0, m1;
         gp_mean_wg(cs[w], cs[w + 1 < W ? w + 1 : w], w + 1 < W, m0, m1);
         if (t == 0) {
-            for (int d = 0; d < D; ++d) {
-                if (!(cs[w][d] >= a.lo[d] && cs[w][d] <= a.hi[d])) m0 = -INFINITY;
-                if (w + 1 < W && !(cs[w + 1][d] >= a.lo[d] && cs[w + 1][d] <= a.hi[d])) m1 = -INFINITY;
-            }
-            lp[w] = m0;
-            if (w + 1 < W) lp[w + 1] = m1;
+            lp[w] = ens_gate(a, cs[w], m0);
+            if (w + 1 < W) lp[w + 1] = ens_gate(a, cs[w + 1], m1);
         }
     }
     __syncthreads();
@@ -334,22 +343,15 @@ __global__ __launch_bounds__(256) void ensemble_mw_kernel(EnsMwArgs q) {
     const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc((void*)(q.xchg + ens * 2 * (ENS_MAXW / 2) * 2), 0,
                                                                           2 * (ENS_MAXW / 2) * 16, 0x00020000);
     const unsigned int k0 = (unsigned int)a.seed, k1 = (unsigned int)(a.seed >> 32) ^ (unsigned int)(ens * 0x9E3779B9u);
-    // the move of a one-entry table (the default) is read once, not per iteration
     const bool mixed = a.mv.n > 1;
     int mkind = a.mv.kind[0];
     double mp0 = a.mv.p0[0], mp1 = a.mv.p1[0];
     bool dead = false;
     for (long long it = 0; it < a.iterations && !dead; ++it) {
-        unsigned int cr[4] = {(unsigned int)it, (unsigned int)(it >> 32), 0xFFFFFFFFu, 0x5u};
-        philox4x32(cr, k0, k1);
-        const int rot = (int)(cr[0] % (unsigned int)W);
-        if (mixed) {                                            // the iteration's move: uniform over the workgroup(s)
-            const int mi = ens_pick_move(a.mv, cr);
-            mkind = a.mv.kind[mi]; mp0 = a.mv.p0[mi]; mp1 = a.mv.p1[mi];
-        }
+        const int rot = ens_iteration(a.mv, mixed, it, k0, k1, W, mkind, mp0, mp1);
         for (int split = 0; split < 2; ++split) {
-            auto s_idx = [&](int i) { int v = i + split * H + rot; return v >= W ? v - W : v; };
-            auto c_idx = [&](int i) { int v = i + (1 - split) * H + rot; return v >= W ? v - W : v; };
+            auto s_idx = [&](int i) { return ens_slot(i, split, H, rot, W); };
+            auto c_idx = [&](int i) { return ens_slot(i, 1 - split, H, rot, W); };
             if (t < H) {
                 qok[t] = ens_propose<DPAD, ALLMOVES>(mkind, mp0, mp1, cs, s_idx(t), c_idx, H, D, a.lo, a.hi, it, split, t, k0, k1, qs[t],
                                            fac[t], uacc[t]) ? 1 : 0;
@@ -395,28 +397,13 @@ __global__ __launch_bounds__(256) void ensemble_mw_kernel(EnsMwArgs q) {
             }
             __syncthreads();
             if (gaveup) { dead = true; break; }
-            if (t < H) {
-                const int sw = s_idx(t);
-                const double diff = fac[t] + lpq[t] - lp[sw];
-                if (qok[t] && lpq[t] == lpq[t] && log(uacc[t]) < diff) {
-#pragma unroll
-                    for (int d = 0; d < DPAD; ++d) cs[sw][d] = qs[t][d];
-                    lp[sw] = lpq[t];
-                    nacc[sw] += 1;
-                }
-            }
+            if (t < H) ens_accept<DPAD>(t, s_idx(t), cs, lp, nacc, qs, lpq, fac, uacc, qok);
             __syncthreads();
         }
         if (dead) break;
         // the chain: every workgroup writes its share of the walkers
         const long long E_ = gridDim.x / G;
-        if (a.chain) {
-            double* out = a.chain + ((it * E_ + ens) * W) * D;
-            for (int e = g * 256 + t; e < W * D; e += G * 256) {
-                const int w = e / D, d = e % D;
-                out[e] = cs[w][d] / a.sc[d];
-            }
-        }
+        if (a.chain) ens_store_walkers<DPAD>(a, cs, a.chain + ((it * E_ + ens) * W) * D, W, D, g * 256 + t, G * 256);
         if (a.logp_chain && g == 0 && t < W) a.logp_chain[(it * E_ + ens) * W + t] = lp[t];
     }
     // A workgroup that gave up raises the launch's sticky word: its NaN marker in logp alone could be overwritten by the
@@ -425,10 +412,7 @@ __global__ __launch_bounds__(256) void ensemble_mw_kernel(EnsMwArgs q) {
     // into NaN log-probabilities for every ensemble -- the marker the host looks at can no longer be lost.
     if (dead && t == 0) atomicOr(q.status, 1ull);
     if (g == 0 || dead) {
-        for (int e = t; e < W * D; e += 256) {
-            const int w = e / D, d = e % D;
-            gc[e] = cs[w][d] / a.sc[d];
-        }
+        ens_store_walkers<DPAD>(a, cs, gc, W, D, t, 256);
         if (t < W) {
             a.logp[ens * W + t] = dead ? __longlong_as_double(0x7ff8000000000000ll) : lp[t];
             a.naccept[ens * W + t] = nacc[t];
@@ -449,27 +433,25 @@ extern "C" int apgp_ensemble_mode(int mode) {
     return g_ens_mode.exchange(mode ? 1 : 0);
 }
 
-// The launch of one instantiation: per padded dimension and, AM, per "holds every move" / "stretch only".  The LDS-resident
-// form (xlds) needs > 64 KiB of dynamic LDS: a per-device attribute, set and CHECKED once per device and instantiation.
-// (The kernels land in the code object in the order they are first named: LDS-resident form first here, AM = true first
-// in the caller.)
-template <int DP, bool AM>
-static int ens_launch_mw(const EnsMwArgs& q, dim3 grid, size_t xbytes, bool xlds, int dev, hipStream_t s) {
+// The launch of one kernel (MW: the multi-workgroup one) in one instantiation: per padded dimension and, AM, per "holds
+// every move" / "stretch only".  The LDS-resident form (xlds) needs > 64 KiB of dynamic LDS: a per-device attribute, set and
+// CHECKED once per device and instantiation.  (The kernels land in the code object in the order they are first named:
+// LDS-resident form first here, AM = true first in ens_dispatch, the multi-workgroup kernel first in its caller.)
+template <bool MW, int DP, bool AM, class Args>
+static int ens_launch(const Args& q, dim3 grid, size_t xbytes, bool xlds, int dev, hipStream_t s) {
     static ApgpLdsOnce once;
-    if (xlds && apgp_raise_lds(once, "apgp_ensemble_sample_moves", dev, 96 * 1024, {(const void*)ensemble_mw_kernel<DP, true, AM>}) != 0)
-        return -2;
-    if (xlds) hipLaunchKernelGGL((ensemble_mw_kernel<DP, true, AM>), grid, dim3(256), xbytes, s, q);
-    else hipLaunchKernelGGL((ensemble_mw_kernel<DP, false, AM>), grid, dim3(256), 0, s, q);
+    void (*kl)(Args), (*kg)(Args);
+    if constexpr (MW) { kl = ensemble_mw_kernel<DP, true, AM>; kg = ensemble_mw_kernel<DP, false, AM>; }
+    else { kl = ensemble_kernel<DP, true, AM>; kg = ensemble_kernel<DP, false, AM>; }
+    if (xlds && apgp_raise_lds(once, "apgp_ensemble_sample_moves", dev, 96 * 1024, {(const void*)kl}) != 0) return -2;
+    hipLaunchKernelGGL(xlds ? kl : kg, grid, dim3(MW ? 256 : 1024), xlds ? xbytes : 0, s, q);
     return 0;
 }
-template <int DP, bool AM>
-static int ens_launch(const EnsArgs& a, dim3 grid, size_t xbytes, bool xlds, int dev, hipStream_t s) {
-    static ApgpLdsOnce once;
-    if (xlds && apgp_raise_lds(once, "apgp_ensemble_sample_moves", dev, 96 * 1024, {(const void*)ensemble_kernel<DP, true, AM>}) != 0)
-        return -2;
-    if (xlds) hipLaunchKernelGGL((ensemble_kernel<DP, true, AM>), grid, dim3(1024), xbytes, s, a);
-    else hipLaunchKernelGGL((ensemble_kernel<DP, false, AM>), grid, dim3(1024), 0, s, a);
-    return 0;
+template <bool MW, class Args>
+static int ens_dispatch(int dpad, bool allmoves, const Args& q, dim3 grid, size_t xbytes, bool xlds, int dev, hipStream_t s) {
+    return allmoves
+        ? apgp_by_dpad(dpad, [&](auto dp) { return ens_launch<MW, decltype(dp)::value, true>(q, grid, xbytes, xlds, dev, s); })
+        : apgp_by_dpad(dpad, [&](auto dp) { return ens_launch<MW, decltype(dp)::value, false>(q, grid, xbytes, xlds, dev, s); });
 }
 
 // fills mv from the caller's table (NULL with nmoves == 0: the stretch move at a_stretch alone) or returns the failed check
@@ -522,6 +504,25 @@ static const char* ens_move_table(EnsMoves& mv, const apgp_ens_move_t* moves, in
     return nullptr;
 }
 
+// the kernels' arguments from the checked ones: the walkers live in scaled coordinates x * sc
+static EnsArgs ens_args(const double* xs, int64_t n, const KernConst& kc, double mean, const double* lo, const double* hi,
+                        int32_t nwalkers, int64_t iterations, uint64_t seed, double* coords, double* logp, double* chain,
+                        double* logp_chain, int64_t* naccept, const EnsMoves& mv) {
+    EnsArgs a;
+    a.xs = xs; a.coords = coords; a.logp = logp; a.chain = chain; a.logp_chain = logp_chain;
+    a.naccept = (long long*)naccept; a.n = apgp_npad(n); a.iterations = iterations;
+    a.ndim = kc.ndim; a.nwalkers = nwalkers; a.seed = seed; a.mean = mean; a.amp = kc.amp;
+    a.mv = mv;
+    a.lin_coef = kc.lin_coef; a.lin_order = kc.lin_order;
+    for (int d = 0; d < APGP_MAX_DIM; ++d) {
+        a.lw[d] = kc.lw[d];
+        a.sc[d] = d < kc.ndim ? kc.sc[d] : 1.0;
+        a.lo[d] = d < kc.ndim ? lo[d] * kc.sc[d] : 0.0;     // bounds in scaled coordinates
+        a.hi[d] = d < kc.ndim ? hi[d] * kc.sc[d] : 0.0;
+    }
+    return a;
+}
+
 extern "C" int apgp_ensemble_sample_moves(const double* xs, int64_t n, const apgp_kernel_t* kern, double mean,
                                           const double* lo, const double* hi, int32_t nwalkers,
                                           int32_t nensembles, int64_t iterations, double a_stretch,
@@ -544,18 +545,7 @@ extern "C" int apgp_ensemble_sample_moves(const double* xs, int64_t n, const apg
     bool allmoves = false;
     for (int m = 0; m < mv.n; ++m) allmoves = allmoves || mv.kind[m] != APGP_ENS_MOVE_STRETCH;
     const int ens_mode = mode < 0 ? g_ens_mode.load() : (mode ? 1 : 0);
-    EnsArgs a;
-    a.xs = xs; a.coords = coords; a.logp = logp; a.chain = chain; a.logp_chain = logp_chain;
-    a.naccept = (long long*)naccept; a.n = apgp_npad(n); a.iterations = iterations;
-    a.ndim = kc.ndim; a.nwalkers = nwalkers; a.seed = seed; a.mean = mean; a.amp = kc.amp;
-    a.mv = mv;
-    a.lin_coef = kc.lin_coef; a.lin_order = kc.lin_order;
-    for (int d = 0; d < APGP_MAX_DIM; ++d) {
-        a.lw[d] = kc.lw[d];
-        a.sc[d] = d < kc.ndim ? kc.sc[d] : 1.0;
-        a.lo[d] = d < kc.ndim ? lo[d] * kc.sc[d] : 0.0;     // bounds in scaled coordinates
-        a.hi[d] = d < kc.ndim ? hi[d] * kc.sc[d] : 0.0;
-    }
+    const EnsArgs a = ens_args(xs, n, kc, mean, lo, hi, nwalkers, iterations, seed, coords, logp, chain, logp_chain, naccept, mv);
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid((unsigned)nensembles);
     const size_t xbytes = (size_t)a.n * (kc.dpad + 2) * sizeof(double);
@@ -581,9 +571,7 @@ extern "C" int apgp_ensemble_sample_moves(const double* xs, int64_t n, const apg
                 EnsMwArgs q;
                 q.e = a; q.xchg = xchg; q.status = xchg + (words - 8); q.timeout = 5000000ull; q.G = G;      // 50 ms of the 100 MHz clock
                 const dim3 gridm((unsigned)(nensembles * G));
-                const int rc = allmoves
-                    ? apgp_by_dpad(kc.dpad, [&](auto dp) { return ens_launch_mw<decltype(dp)::value, true>(q, gridm, xbytes, xlds, devn, s); })
-                    : apgp_by_dpad(kc.dpad, [&](auto dp) { return ens_launch_mw<decltype(dp)::value, false>(q, gridm, xbytes, xlds, devn, s); });
+                const int rc = ens_dispatch<true>(kc.dpad, allmoves, q, gridm, xbytes, xlds, devn, s);
                 if (rc != 0) return rc;
                 hipLaunchKernelGGL(ens_mark_failed_kernel, dim3(1), dim3(256), 0, s, q.status, logp, (int)(nensembles * nwalkers));
                 APGP_CHECK_LAUNCH();
@@ -596,9 +584,7 @@ extern "C" int apgp_ensemble_sample_moves(const double* xs, int64_t n, const apg
         apgp_set_error("apgp_ensemble_sample_moves: hipGetDevice failed");
         return -2;
     }
-    const int rc = allmoves
-        ? apgp_by_dpad(kc.dpad, [&](auto dp) { return ens_launch<decltype(dp)::value, true>(a, grid, xbytes, xlds, dev, s); })
-        : apgp_by_dpad(kc.dpad, [&](auto dp) { return ens_launch<decltype(dp)::value, false>(a, grid, xbytes, xlds, dev, s); });
+    const int rc = ens_dispatch<false>(kc.dpad, allmoves, a, grid, xbytes, xlds, dev, s);
     if (rc != 0) return rc;
     APGP_CHECK_LAUNCH();
     return 0;

@@ -12,5 +12,5 @@ with tempfile.TemporaryDirectory() as wd:
             get = lambda k: (re.search(r"\.%s:\s+(\S+)" % k, blk) or [None, "?"])[1]
             name = get("name")
             if want in name:
-                print("%-70s vgpr %s agpr %s sgpr %s scratch %s lds %s kernarg %s" % (name[:70], get("vgpr_count"), blk.split()[0].strip(": "), get("sgpr_count"),
+                print("%-70s vgpr %s agpr %s sgpr %s scratch %s lds %s kernarg %s" % (name[:70], get("vgpr_count"), blk.lstrip(": ").split()[0], get("sgpr_count"),
                       get("private_segment_fixed_size"), get("group_segment_fixed_size"), get("kernarg_segment_size")))
