@@ -328,10 +328,13 @@ class ApproxPosterior(object):
                 point, value = self._agree(point, value)
         return point, value
 
-    def _selectBatch(self, utilities, nCandidates):
+    def _selectBatch(self, utilities, nCandidates, batchMethod="believer"):
         """``len(utilities)`` design points chosen jointly (:meth:`GP.acquire_batch`, the kriging believer) from
         ONE candidate draw -- the draw :meth:`_selectPoint` makes for one point; pick j minimises
-        ``utilities[j]``.  A batch of one is :meth:`_selectPoint`'s sweep: same draw, same point."""
+        ``utilities[j]``.  A batch of one is :meth:`_selectPoint`'s sweep: same draw, same point.
+        ``batchMethod="thompson"``: the points are the arg-maxes of posterior function draws over the same candidate
+        draw (:meth:`GP.thompson_batch`); slots the draws left empty are topped up by the kriging believer under
+        ``utilities``, with the rows already picked masked out."""
         total = int(nCandidates)
         kinds = [ut.utilityKind(fn) for fn in utilities]
         joint = self._jointPrior()
@@ -348,7 +351,17 @@ class ApproxPosterior(object):
             draws = np.asarray(self.priorSample(total), dtype=float).reshape(total, -1)
             cands = self.gp.parse_samples(draws)
             row = lambda g: np.array(draws[g])                                                              # noqa: E731
-        idx, _ = self.gp.acquire_batch(self.y, cands, kinds, len(kinds), bounds=gate)
+        if batchMethod == "thompson":
+            idx = self.gp.thompson_batch(self.y, cands, len(kinds), bounds=gate)
+            picked = [int(g) for g in idx if g >= 0]
+            if len(picked) < len(kinds):
+                free = np.ones(total, dtype=np.uint8)
+                free[picked] = 0
+                more, _ = self.gp.acquire_batch(self.y, cands, kinds[len(picked):], len(kinds) - len(picked),
+                                                bounds=gate, mask=free)
+                idx = np.array(picked + [int(g) for g in more], dtype=np.int64)
+        else:
+            idx, _ = self.gp.acquire_batch(self.y, cands, kinds, len(kinds), bounds=gate)
         if idx[0] < 0:
             raise RuntimeError("ERROR: Cannot find a valid solution: no candidate is allowed by the prior")
         # (a later step without an admissible candidate cannot happen: the earlier picks stay admissible)
@@ -379,7 +392,7 @@ class ApproxPosterior(object):
                       runName="apRun", numNewPoints=1, optGPEveryN=1,
                       gpHyperPrior=gpUtils.defaultHyperPrior, args=None,
                       nCandidates=None, polish=False, deviceCandidates=None, batchSize=None, pool=None,
-                      deviceSearch=None, searchJac=False, **kwargs):
+                      deviceSearch=None, searchJac=False, batchMethod="believer", **kwargs):
         """Select ``numNewPoints`` design points by minimising the (negative) utility;
         with ``computeLnLike`` evaluate the forward model at each, absorb it into the
         training set / GP and re-fit the hyper-parameters every ``optGPEveryN`` points
@@ -402,6 +415,9 @@ class ApproxPosterior(object):
         ``concurrent.futures`` executor), else serially in pick order.  They are then absorbed in pick order,
         the GP is re-fitted once per batch when a point of the batch meets the ``optGPEveryN`` rule, and the
         cache is written after each batch.  ``batchSize=1`` is the plain ``nCandidates`` search.
+        ``batchMethod="thompson"`` (with ``batchSize``) chooses the batch as the arg-maxes of ``q`` functions drawn
+        from the GP posterior instead (:meth:`GP.thompson_batch`: one pass over the candidates, no variance sweep,
+        whatever the utility); slots on which the draws agreed are filled by the kriging believer.
 
         ``deviceSearch=True`` (opt-in; kept on the object like ``deviceCandidates``) runs the Nelder-Mead point search
         -- the default without ``nCandidates``, and ``polish`` after a sweep -- on the device: all ``nMinObjRestarts``
@@ -415,6 +431,10 @@ class ApproxPosterior(object):
         the host point search -- and ``polish`` -- the utility's exact gradient (``utility.minimizeObjective(jac=True)``,
         :meth:`GP.predict_grad`) instead of SciPy's finite differences.
         """
+        if batchMethod not in ("believer", "thompson"):
+            raise ValueError('batchMethod must be "believer" or "thompson"')
+        if batchMethod == "thompson" and batchSize is None:
+            raise ValueError('batchMethod="thompson" needs batchSize: it chooses batches')
         if batchSize is not None:
             if nCandidates is None:
                 raise ValueError("batchSize needs nCandidates: batches are chosen by the device sweep")
@@ -443,7 +463,7 @@ class ApproxPosterior(object):
             return self._findBatches(numNewPoints, int(batchSize), computeLnLike, nCandidates, pool, fwdArgs,
                                      kwargs, cache, verbose, optGPEveryN, runName,
                                      dict(seed=seed, method=gpMethod, options=gpOptions, p0=gpP0,
-                                          nGPRestarts=nGPRestarts, gpHyperPrior=gpHyperPrior))
+                                          nGPRestarts=nGPRestarts, gpHyperPrior=gpHyperPrior), batchMethod)
         for count in range(numNewPoints):
             if ranks is not None:
                 # one global random stream: the candidate matrix / restart draws below are the same on
@@ -496,7 +516,7 @@ class ApproxPosterior(object):
         return np.asarray(points)
 
     def _findBatches(self, numNewPoints, q, computeLnLike, nCandidates, pool, fwdArgs, kwargs, cache, verbose,
-                     optGPEveryN, runName, fit):
+                     optGPEveryN, runName, fit, batchMethod="believer"):
         """findNextPoint with ``batchSize=q`` (single process): ``numNewPoints`` points, ``q`` per batch."""
         points, values = [], []
         forward = _ForwardModel(self._lnlike, self._lnprior, fwdArgs, kwargs)
@@ -507,7 +527,7 @@ class ApproxPosterior(object):
                 self.utility = utilities[-1]
             else:
                 utilities = [self.utility] * len(counts)
-            batch = self._selectBatch(utilities, nCandidates)
+            batch = self._selectBatch(utilities, nCandidates, batchMethod)
             points.extend(batch)
             if not computeLnLike:
                 continue
@@ -693,7 +713,7 @@ class ApproxPosterior(object):
             gpHyperPrior=gpUtils.defaultHyperPrior, eps=1.0, convergenceCheck=False,
             minObjMethod="nelder-mead", minObjOptions=None, args=None,
             nCandidates=None, onDevice=False, batched=True, deviceCandidates=None, batchSize=None, pool=None,
-            deviceSearch=None, deviceAutocorr=False, searchJac=False, **kwargs):
+            deviceSearch=None, deviceAutocorr=False, searchJac=False, batchMethod="believer", **kwargs):
         """BAPE / AGP outer loop (approx.py:229-524): ``nmax`` times, find ``m`` design
         points (re-fitting the GP every ``optGPEveryN``), sample the surrogate posterior,
         record burn-in / thinning, and -- with ``convergenceCheck`` -- stop once the
@@ -703,12 +723,17 @@ class ApproxPosterior(object):
         ``nCandidates`` switches the point search to the fused device sweep
         (``deviceCandidates``: drawn on the device, see :meth:`findNextPoint`);
         ``onDevice`` / ``batched`` are passed to :meth:`runMCMC`; ``batchSize`` / ``pool`` to
-        :meth:`findNextPoint` (design points chosen and their forward models run in batches), and ``deviceSearch``
+        :meth:`findNextPoint` (design points chosen and their forward models run in batches; ``batchMethod``:
+        "believer" or "thompson", how a batch is chosen), and ``deviceSearch``
         (the Nelder-Mead point search on the device) and ``searchJac`` (exact gradients for a gradient
         ``minObjMethod``).  ``deviceAutocorr`` is passed to :meth:`runMCMC` too (burn-in and
         thinning from the device's autocorrelation estimate; needs ``onDevice=True``)."""
         if deviceAutocorr and not onDevice:
             raise ValueError("run(deviceAutocorr=True) needs onDevice=True")
+        if batchMethod not in ("believer", "thompson"):
+            raise ValueError('batchMethod must be "believer" or "thompson"')
+        if batchMethod == "thompson" and batchSize is None:
+            raise ValueError('batchMethod="thompson" needs batchSize: it chooses batches')
         if convergenceCheck and onlyLastMCMC:
             raise RuntimeError("If convergenceCheck is True, must run an MCMC each iteration.\n"
                                "convergenceCheck = %d onlyLastMCMC = %d" % (convergenceCheck, onlyLastMCMC))
@@ -737,7 +762,8 @@ class ApproxPosterior(object):
                                minObjMethod=minObjMethod, minObjOptions=minObjOptions,
                                runName=runName, theta0=None, args=args, verbose=verbose,
                                nCandidates=nCandidates, deviceCandidates=deviceCandidates, batchSize=batchSize,
-                               pool=pool, deviceSearch=deviceSearch, searchJac=searchJac, **fit, **kwargs)
+                               pool=pool, deviceSearch=deviceSearch, searchJac=searchJac, batchMethod=batchMethod,
+                               **fit, **kwargs)
             if timing:
                 self.trainingTime.append(time.time() - clock)
             if cache:
@@ -813,14 +839,29 @@ class ApproxPosterior(object):
                  nMinObjRestarts=5, initGPOpt=True, minObjMethod="nelder-mead",
                  gpHyperPrior=gpUtils.defaultHyperPrior, minObjOptions=None,
                  findMAP=True, args=None, nCandidates=None, deviceCandidates=None, deviceSearch=None,
-                 searchJac=False, **kwargs):
+                 searchJac=False, batchSize=None, pool=None, batchMethod="believer", **kwargs):
         """Bayesian optimisation (approx.py:929-1151): one design point per iteration by
         the object's utility (use algorithm="jones"), optionally the MAP of the GP mean
         after each, stop after ``kmax`` consecutive iterations whose best value changed
         by less than ``tol``.  Returns the reference's solution dictionary (thetaBest,
         valBest, thetas, vals, nev [, thetasMAP, valsMAP, thetaMAPBest, valMAPBest]).
         ``deviceSearch`` runs the point searches and the MAP searches on the device (see :meth:`findNextPoint`);
-        ``searchJac`` gives both host searches exact gradients (with a gradient ``minObjMethod``)."""
+        ``searchJac`` gives both host searches exact gradients (with a gradient ``minObjMethod``).
+        ``batchSize=q`` (with ``nCandidates``): each iteration chooses ``q`` points as one batch and evaluates their
+        forward models together, through ``pool.map`` when ``pool`` is given (see :meth:`findNextPoint`;
+        ``batchMethod="thompson"`` draws the batch from the posterior, which suits optimisation whatever the
+        utility); ``nev`` counts forward-model evaluations, ``q`` per iteration."""
+        if batchSize is None and batchMethod != "believer":
+            raise ValueError('batchMethod needs batchSize: it chooses batches')
+        if batchSize is not None:
+            if nCandidates is None:
+                raise ValueError("batchSize needs nCandidates: batches are chosen by the device sweep")
+            if not isinstance(batchSize, (int, np.integer)) or not 1 <= batchSize <= _lib.MAX_FANTASY:
+                raise ValueError("batchSize must be an integer between 1 and %d" % _lib.MAX_FANTASY)
+            if batchMethod not in ("believer", "thompson"):
+                raise ValueError('batchMethod must be "believer" or "thompson"')
+        batch = {} if batchSize is None else dict(batchSize=int(batchSize), pool=pool, batchMethod=batchMethod)
+        perIteration = 1 if batchSize is None else int(batchSize)
         verbose, cache = verbose and self._chief(), cache and self._chief()
         if cache:
             np.savez(_cacheName(runName, "APFModelCache"), theta=self.theta, y=self.y)
@@ -839,12 +880,13 @@ class ApproxPosterior(object):
             period = 1 if iteration % optGPEveryN == 0 else 99999999
             point, value = self.findNextPoint(computeLnLike=True, cache=cache, gpMethod=gpMethod,
                                               gpOptions=gpOptions, nMinObjRestarts=nMinObjRestarts,
-                                              optGPEveryN=period, numNewPoints=1,
+                                              optGPEveryN=period, numNewPoints=perIteration,
                                               minObjMethod=minObjMethod, minObjOptions=minObjOptions,
                                               runName=runName, args=args, verbose=verbose,
                                               nCandidates=nCandidates, deviceCandidates=deviceCandidates,
-                                              deviceSearch=deviceSearch, searchJac=searchJac, **fit, **kwargs)
-            evaluations = iteration + 1
+                                              deviceSearch=deviceSearch, searchJac=searchJac, **batch, **fit,
+                                              **kwargs)
+            evaluations = (iteration + 1) * perIteration
             if verbose:
                 print("Forward model evaluation at: ", point, ", function value: ", value)
             if cache:

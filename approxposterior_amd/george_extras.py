@@ -5,7 +5,8 @@
 
 OFF the hot path (none of these is a row): ``apply_inverse``, ``get_matrix``, the covariance
 form of ``predict`` (george's default ``return_cov=True``; the reference only ever asks for the mean or
-``return_var=True``: approx.py:178, utility.py:131,178,224) and the ``nll`` / ``lnlikelihood`` aliases.  Kept for
+``return_var=True``: approx.py:178, utility.py:131,178,224), ``sample_conditional`` on top of it, and the ``nll`` /
+``lnlikelihood`` aliases.  Kept for
 scripts written against george that hold the GP object directly; mixed into :class:`approxposterior_amd.gp.GP`.
 The kernel matrices come from the HIP cross-kernel of the row append (``apgp_kernel_cross``); the dense solves and the
 (M, N) x (N, M) product are plain library calls through torch (rocBLAS) -- acceptable here, never on the path.
@@ -67,6 +68,16 @@ class GeorgeExtras(object):
 
     def grad_lnlikelihood(self, y, quiet=False):
         return self.grad_log_likelihood(y, quiet=quiet)
+
+    def sample_conditional(self, y, t, size=1):
+        """george ``GP.sample_conditional``: ``size`` draws of N(mu, cov) at the points ``t`` (M, D), with (mu, cov) of
+        ``predict(y, t, return_cov=True)``, by ``np.random.multivariate_normal`` (NumPy's global stream); (M,) for
+        ``size=1`` as in george, else (size, M).  Off the hot path and for small M: the covariance is M x M and its
+        factorisation O(M^3) on the host.  For many points use :meth:`GP.sample_paths`, whose draws are functions
+        evaluated in O(N + nFeatures) per point."""
+        mu, cov = self.predict(y, t, return_cov=True)
+        draws = np.random.multivariate_normal(mu, cov, int(size))
+        return draws[0] if int(size) == 1 else draws
 
     def _predict_cov(self, y, xs):
         """(mu, cov) of george's ``GP.predict`` defaults (return_cov=True): cov = k(t, t) - V^T V with

@@ -415,6 +415,48 @@ def _records_nll(o, n):
     return np.where(bad, np.inf, -ll)
 
 
+class PathDraws(object):
+    """``size`` functions drawn from a GP's posterior (:meth:`GP.sample_paths`): the random features ``Z``, ``b``, their
+    weights ``W``, ``Wl`` and the data weights ``V`` on the device, with the kernel struct ``ks`` and the mean they were
+    drawn for.  It belongs to the factor it was solved against: after the GP's training set, hyper-parameters or mean
+    changed, :meth:`evaluate` and :meth:`argmax` raise."""
+
+    def __init__(self, gp, Z, b, W, Wl):
+        self.gp, self.Z, self.b, self.W, self.Wl, self.V = gp, Z, b, W, Wl, None
+        self.size, self.nFeatures = int(W.shape[0]), int(W.shape[1])
+        if Z.shape != (self.nFeatures, gp.kernel.ndim) or b.shape != (self.nFeatures,) \
+                or Wl.shape != (self.size, gp.kernel.ndim):
+            raise ValueError("Z (R, D), b (R,), W (S, R) and Wl (S, D) do not fit together")
+        self.ks = gp._kernel_struct()
+        self.mean = float(gp.mean.value)
+        self._key, self._x = (gp._factor_key(), self.mean), gp._x
+
+    def _call(self, t, bounds, mask, idx_offset, with_f):
+        gp = self.gp
+        if not gp.computed or gp._x is not self._x or (gp._factor_key(), float(gp.mean.value)) != self._key:
+            raise RuntimeError("these draws belong to a factor the GP no longer holds: call sample_paths again")
+        lo, hi = _box(bounds, gp.kernel.ndim)
+        T = gp._candidates(t)
+        mask_d = mask if hasattr(mask, "data_ptr") else gp._mask(mask, T.shape[0])
+        if mask_d is not None and (tuple(mask_d.shape) != (T.shape[0],) or str(mask_d.dtype) != "torch.uint8"):
+            raise ValueError("a device mask must be a (M,) uint8 tensor")
+        if T.shape[0] == 0:
+            return np.empty((self.size, 0)), np.full(self.size, -1, dtype=np.int64), np.full(self.size, np.inf)
+        return gp._path_call(T, self.ks, self.mean, self, self.V, lo, hi, mask_d, idx_offset, with_f)
+
+    def evaluate(self, t):
+        """f_s(t) at the points ``t`` (M, D; host array or device tensor) as an (S, M) array."""
+        F = self._call(t, None, None, 0, True)[0]
+        return F if isinstance(F, np.ndarray) else F.cpu().numpy()
+
+    def argmax(self, t, bounds=None, mask=None, idx_offset=0):
+        """Each draw's arg-max over the admissible rows of ``t``: (global indices (S,), values (S,)).  The sweep's
+        contract: the lowest index on ties, NaN never wins, a row outside ``bounds``, with ``mask == 0`` or with a
+        NaN coordinate is inadmissible; index -1 and -inf where no row is admissible."""
+        _, idx, u = self._call(t, bounds, mask, idx_offset, False)
+        return idx, -u
+
+
 # ---------------------------------------------------------------------------
 # GP
 # ---------------------------------------------------------------------------
@@ -1591,6 +1633,116 @@ class GP(GeorgeExtras):
             if return_all:
                 return idx, ub, u.cpu().numpy(), mu.cpu().numpy(), var[cur].cpu().numpy()
         return idx, ub
+
+    # -- posterior function draws (DESIGN.md "Posterior function draws") ------------------
+    def _path_call(self, T, ks, mean, paths, V, lo=None, hi=None, mask_d=None, idx_offset=0, with_f=False):
+        """``apgp_path_draws`` over the rows of the device tensor ``T`` (M >= 1, D) with the weights of ``paths`` and the
+        data weights ``V`` (None: the prior draws alone).  Returns (F (S, M) device or None, indices (S,), u (S,))."""
+        torch, dev, lib = self._rt()
+        m, S = T.shape[0], paths.size
+        with self._on(torch, dev):
+            st = self._stream(torch)
+            f64 = dict(dtype=torch.float64, device=dev)
+            F = torch.empty((S, m), **f64) if with_f else None
+            part = torch.empty(max(int(lib.apgp_path_draws_work_len(m, S)), 2), **f64)
+            best = torch.empty(2 * S, **f64)
+            _lib.check(lib.apgp_path_draws(T.data_ptr(), m, int(idx_offset), _ptr(self._xs if V is not None else None),
+                                           len(self._x), ctypes.byref(ks), float(mean), _ptr(V), paths.Z.data_ptr(),
+                                           paths.b.data_ptr(), paths.W.data_ptr(), paths.Wl.data_ptr(),
+                                           paths.nFeatures, S, lo, hi, _ptr(mask_d), _ptr(F), part.data_ptr(),
+                                           best.data_ptr(), st), "apgp_path_draws")
+            bb = best.cpu().numpy().reshape(S, 2)
+        return F, bb[:, 1].copy().view(np.int64), bb[:, 0].copy()
+
+    def sample_paths(self, y, size, nFeatures=2048):
+        """``size`` functions drawn from the GP posterior given ``y``, as a :class:`PathDraws` that evaluates them --
+        and finds each one's arg-max -- over any number of points in one device pass of O(N + nFeatures) per point and
+        draw, with no N^2 contraction.  By Matheron's rule a posterior draw is a prior draw plus a data term,
+        ``f_s(t) = mean + g_s(t) + k(t, X).v_s`` with ``v_s = K^-1 (y - mean - g_s(X) - eps_s)``; the squared-exponential
+        part of the prior draw ``g_s`` is a sum of ``nFeatures`` random cosines (error O(nFeatures^-1/2) in
+        distribution: it blurs the draws' covariance, not their mean -- the data term is exact), the linear term's
+        feature map is exact.
+        The random numbers come from NumPy's global stream, in the order Z (nFeatures x D), b (nFeatures), W (size x
+        nFeatures), Wl (size x D), eps (size x N); the device only evaluates.  The set-up -- g_s(X) by the same kernel,
+        then two triangular solves per draw against the resident factor (through the explicit inverse where
+        :meth:`_trust_inverse` allows and it is resident, as ``_solve`` does) -- is O(size N^2), off the per-point path."""
+        if not self.computed:
+            raise RuntimeError("ERROR: Need to compute GP before using it!")
+        size, nFeatures = int(size), int(nFeatures)
+        if not 1 <= size <= _lib.MAX_DRAWS:
+            raise ValueError("size must be between 1 and %d (APGP_MAX_DRAWS)" % _lib.MAX_DRAWS)
+        if not 1 <= nFeatures <= _lib.MAX_FEATURES:
+            raise ValueError("nFeatures must be between 1 and %d (APGP_MAX_FEATURES)" % _lib.MAX_FEATURES)
+        y = self._check_dimensions(y)
+        n, D = len(self._x), self.kernel.ndim
+        diag_add = self._kernel_struct().diag_add
+        Z = np.random.standard_normal((nFeatures, D))
+        b = np.random.uniform(0.0, 2.0 * np.pi, nFeatures)
+        W = np.random.standard_normal((size, nFeatures))
+        Wl = np.random.standard_normal((size, D))
+        eps = np.sqrt(diag_add) * np.random.standard_normal((size, n))
+        return self._paths_from(y, Z, b, W, Wl, eps)
+
+    def _paths_from(self, y, Z, b, W, Wl, eps):
+        """The :class:`PathDraws` of given random numbers (host arrays, shapes as in :meth:`sample_paths`)."""
+        torch, dev, lib = self._rt()
+        y = self._check_dimensions(y)
+        n = len(self._x)
+        self._ensure_xs(y)              # the packed training stream (and, where the gate allows, the resident L^-1)
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev)       # noqa: E731
+        paths = PathDraws(self, up(Z), up(b), up(W), up(Wl))
+        S = paths.size
+        via_w = self._work is not None and self._trust_inverse()
+        np64 = (n + 63) // 64 * 64
+        with self._on(torch, dev):
+            st = self._stream(torch)
+            f64 = dict(dtype=torch.float64, device=dev)
+            G, _, _ = self._path_call(self._x_d, paths.ks, 0.0, paths, None, with_f=True)        # g_s(X), (S, N)
+            rhs = (up(y) - float(self.mean.value)).unsqueeze(0) - G - up(eps)
+            Vt = torch.empty((S, n), **f64)
+            z, ss = torch.empty(n, **f64), torch.empty(1, **f64)
+            wk = torch.empty(int(lib.apgp_winv_apply_work_len(n)), **f64) if via_w else None
+            for s in range(S):
+                if via_w:
+                    w = self._work.data_ptr()
+                    _lib.check(lib.apgp_winv_apply(w, np64, n, rhs[s].data_ptr(), 0.0, 0, z.data_ptr(), None, None, st),
+                               "apgp_winv_apply(paths, forward)")
+                    _lib.check(lib.apgp_winv_apply(w, np64, n, z.data_ptr(), 0.0, 1, Vt[s].data_ptr(), None,
+                                                   wk.data_ptr(), st), "apgp_winv_apply(paths, backward)")
+                else:
+                    self._trsv(st, rhs[s], 0.0, 0, z, ss, "paths")
+                    self._trsv(st, z, 0.0, 1, Vt[s], ss, "paths")
+            paths.V = Vt.t().contiguous()                     # (N, S): a training row's S weights side by side
+        return paths
+
+    def thompson_batch(self, y, t, q, bounds=None, mask=None, idx_offset=0, nFeatures=2048, maxRounds=4,
+                       return_draws=False):
+        """``q`` distinct candidates of ``t`` (M, D; host array or device tensor, as in :meth:`acquire`) chosen by
+        Thompson sampling: each is the arg-max of one function drawn from the posterior (:meth:`sample_paths`), in
+        draw order.  A round draws min(APGP_MAX_DRAWS, 2 x the missing slots) functions and evaluates them over all
+        candidates in one launch; a winner already in the batch is skipped.  After ``maxRounds`` rounds the remaining
+        slots are -1 -- a concentrated posterior legitimately keeps electing the same row.  The GP is not modified.
+        Returns the global indices (q,) int64; ``return_draws`` adds the (round, draw) pair that elected each slot."""
+        q = int(q)
+        if not 1 <= q <= _lib.MAX_DRAWS:
+            raise ValueError("q must be between 1 and %d (APGP_MAX_DRAWS)" % _lib.MAX_DRAWS)
+        if not self.computed:
+            raise RuntimeError("ERROR: Need to compute GP before using it!")
+        T = self._candidates(t)
+        mask_d = self._mask(mask, T.shape[0])
+        idx, draws = [], []
+        for rnd in range(int(maxRounds)):
+            if len(idx) == q or T.shape[0] == 0:
+                break
+            paths = self.sample_paths(y, min(_lib.MAX_DRAWS, 2 * (q - len(idx))), nFeatures)
+            winners, _ = paths.argmax(T, bounds=bounds, mask=mask_d, idx_offset=idx_offset)
+            for s, g in enumerate(winners.tolist()):
+                if g >= 0 and g not in idx and len(idx) < q:
+                    idx.append(g)
+                    draws.append((rnd, s))
+        out = np.full(q, -1, dtype=np.int64)
+        out[:len(idx)] = idx
+        return (out, draws) if return_draws else out
 
     # -- candidate matrix of the sweep drawn on the device -----------------------------
     def box_candidates(self, m, bounds, seed, idx_offset=0):

@@ -409,6 +409,41 @@ int apgp_acquire_fantasy(const double* T, int64_t m, int64_t idx_offset,
                          const uint8_t* mask, double zeta, double ybest,
                          double* u, void* part, apgp_best_t* best, void* stream);
 
+/* ---- posterior function draws (GP.sample_paths, Thompson batches) ------------------
+ * S = ndraws functions drawn from the GP posterior, evaluated at the m rows t of T (m x ndim), and the arg-max of each.
+ * By Matheron's rule a posterior draw is a prior draw plus a data term; the squared-exponential part of the prior draw
+ * is a sum of R = nfeat random cosines in the scaled coordinates ts_d = t_d sqrt(inv_metric_d / 2), the linear term has
+ * an exact feature map of ndim features:
+ *   g_s(t) = sqrt(2 amp / R) sum_{r<R} W[s,r] cos(sqrt2 Z[r,:].ts + b[r]) + sqrt(lin_coef) sum_{d<ndim} Wl[s,d] t_d^P
+ *   f_s(t) = mean + g_s(t) + k(t, X).V[:,s]
+ * The caller draws Z (R x ndim) ~ N(0,1), b (R) ~ U[0, 2 pi), W (S x R) ~ N(0,1), Wl (S x ndim) ~ N(0,1) (Wl may be NULL
+ * without a linear term) and solves V (n x S, row-major) = K^-1 (y - mean - g_s(X) - eps_s), eps_s ~ N(0, diag_add); the
+ * device only evaluates.  Only the squared-exponential part of the prior draw is approximate (O(R^-1/2) in
+ * distribution); the data term is exact, so with W = Wl = 0 f_s is the predictive mean.
+ * xs: the packed training stream (its alpha column is not read).  V == NULL: the data term is skipped (xs and n are not
+ * read) -- with T = X and mean = 0 the call evaluates g_s(X) for the right-hand sides above.
+ * F (S x m, row-major, may be NULL) receives f_s(t).  best: S records on the device; record s holds the arg-min of
+ * u = -f_s(t) over the admissible rows and its global index idx_offset + row, with the sweep's contract: ties go to the
+ * lowest index; NaN never wins; a row outside [lo, hi] (host arrays or NULL), with mask[row] == 0 (device or NULL) or
+ * with a NaN coordinate has u = +inf and F = NaN; no admissible row gives index -1 and u = +inf.
+ * part: apgp_path_draws_work_len(m, ndraws) doubles, 16-byte aligned (-1: m or ndraws beyond the limits; 0: nothing to do).
+ * 1 <= ndraws <= APGP_MAX_DRAWS, 1 <= nfeat <= APGP_MAX_FEATURES.  No atomics, a fixed order in every sum.
+ * Added in ABI 8 without changing anything before it: APGP_ABI_VERSION stays 8.                                   */
+#define APGP_MAX_DRAWS 32
+#define APGP_MAX_FEATURES 65536
+int64_t apgp_path_draws_work_len(int64_t m, int32_t ndraws);
+/* Test / profiling switch (not read from the environment) for where the contraction with the S weights runs: 0 =
+ * default (the faster form per shape: the matrix cores above 8 draws when ndim <= 8, else the vector units), 1 = the
+ * vector units always, 2 = the matrix cores wherever that kernel exists (ndraws > 1, ndim <= 8); < 0 queries.  Both
+ * forms sum in a fixed order of their own: they agree to rounding, not bit for bit.  Returns the previous value (-1:
+ * bad argument).                                                                                                   */
+int apgp_path_draws_mode(int mode);
+int apgp_path_draws(const double* T, int64_t m, int64_t idx_offset, const double* xs, int64_t n,
+                    const apgp_kernel_t* kern /*host*/, double mean, const double* V, const double* Z,
+                    const double* b, const double* W, const double* Wl, int32_t nfeat, int32_t ndraws,
+                    const double* lo /*host*/, const double* hi /*host*/, const uint8_t* mask, double* F,
+                    void* part, apgp_best_t* best, void* stream);
+
 /* ---- ONE candidate: george GP.predict(y, t[1 x D], return_var=True) ----------
  * What the reference's scalar utilities evaluate once per Nelder-Mead step
  * (utility.py:131,178,224 <- minimizeObjective, utility.py:336-372; the default
