@@ -48,14 +48,16 @@
 //     point).  It needs B, which the staging threads carry with the tiles (max over the rows < n), so it is decided
 //     after the last tile.  Gate failed: e32 = +inf, the block's bound is -inf.
 //   * flushes: a kernel value, an alpha or a product below 2^-126 may become 0: 2^-120 (sum |alpha| + N), absolute, so
-//     this term keeps sum |alpha| (summed in fp32 over 16 rows, then fp64; times 1 + 2^-16).
+//     this term keeps sum |alpha|.  It is a property of the fit, not of a candidate: the staging lanes add |alpha| of
+//     the row they convert, in fp64 from the fp64 alpha, once per row and workgroup (N eps relative), and the sum is
+//     taken times 1 + 2^-16, which also covers |fl32(alpha)| <= |alpha| (1 + u) where the fp32 alphas are meant.
 // |mu32 - mu| <= e32 = amp ((e^eta - 1) S32 + 2^-120 (sum|alpha| + N)); the slack is prune_bound_kernel's with
 // S <= amp sum|alpha| plus 2 e32.  At C3 (A + B ~ 9.5, S32 <= 5e4 against sum|alpha| = 1.9e6) that is below 8, where
 // sum|alpha| in the place of S32 would give several hundred and prune nothing.
 //
 // A block whose bound came out -inf (gate failed: data far wider than the length scale; or a NaN bound) is left to
 // prune_bound32_kernel<DPAD, true>, launched behind this kernel: the -inf in bmin is the mark, no other scratch.
-// Variants measured: docs/experiments.md, round 13.
+// Variants measured: docs/experiments.md, round 13; what the fp32 MFMA leaves to the vector ALU beside it: round 17.
 #pragma once
 
 #ifndef PMM_G
@@ -84,7 +86,7 @@ __global__ __launch_bounds__(PR_THREADS, PMM_G <= 4 ? 2 : 1) void prune_bound_mm
     const double kappa = PR32_KAPPA;                     // sqrt(log2(e))
     __shared__ __attribute__((aligned(16))) float xt[PMM_ROWS * RS];
     __shared__ __attribute__((aligned(16))) float at[PMM_ROWS];
-    __shared__ double wmax[PR_THREADS / 64];
+    __shared__ double wmax[PR_THREADS / 64], wsal[PR_THREADS / 64];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, h = lane >> 5, l32 = lane & 31;
     const long long blk0 = ((long long)blockIdx.x * (PR_THREADS / 64) + w) * (G / 2);
     double cen[DPAD], c2 = 0.0;
@@ -160,7 +162,7 @@ __global__ __launch_bounds__(PR_THREADS, PMM_G <= 4 ? 2 : 1) void prune_bound_mm
                 bf[d] = in ? (float)(df * kappa) : 0.0f;
                 n2 = fma((double)bf[d], (double)bf[d], n2);
             }
-            if (in) bm2 = fmax(bm2, b2);
+            if (in) { bm2 = fmax(bm2, b2); sal += fabs(pre[DPAD / 2].x); }
             float rowv[RS];
 #pragma unroll
             for (int i = 0; i < RS; ++i) rowv[i] = 0.0f;
@@ -186,21 +188,19 @@ __global__ __launch_bounds__(PR_THREADS, PMM_G <= 4 ? 2 : 1) void prune_bound_mm
             }
 #pragma unroll
             for (int r = 0; r < SH::R; ++r) pop[4 * SH::Q4 + r] = xr[SH::Q4 * 8 + h * SH::R + r];
-            float al[16], pa = 0.0f;                     // alpha of accumulator r's row: (r & 3) + 8 (r >> 2) + 4 h
+            float al[16];                                // alpha of accumulator r's row: (r & 3) + 8 (r >> 2) + 4 h
 #pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                *(f32x4*)(al + 4 * q) = *(const f32x4*)(at + rt * 32 + 8 * q + 4 * h);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) pa += fabsf(al[4 * q + j]);
-            }
-            sal += (double)pa;
+            for (int q = 0; q < 4; ++q) *(f32x4*)(al + 4 * q) = *(const f32x4*)(at + rt * 32 + 8 * q + 4 * h);
             auto product = [&](int g) {
                 f32x16 c = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
                 for (int s = 0; s < KH; ++s) c = __builtin_amdgcn_mfma_f32_32x32x2f32(pop[s], qop[g][s], c, 0, 0, 0);
                 return c;
             };
-            // two accumulator tiles in flight: the exponentials of one group run under the products of the next
+            // Written as a two-tile pipeline, but hipcc issues all G groups' products first and the vector work behind
+            // them (64 accumulators fit), and nothing is lost by that: v_mfma_f32_32x32x2_f32 holds the vector lanes
+            // for its 64 cycles, so an exponential placed between two products costs what it costs behind them
+            // (tools/probes/mfma32_shadow.hip; docs/experiments.md, round 17).
             f32x16 cur = product(0);
 #pragma unroll
             for (int g = 0; g < G; ++g) {
@@ -220,15 +220,16 @@ __global__ __launch_bounds__(PR_THREADS, PMM_G <= 4 ? 2 : 1) void prune_bound_mm
         }
         __syncthreads();                                 // the tile has been consumed
     }
-    // B = max |x - c| over the training rows: the stagers' maxima, over the workgroup
-    for (int o = 32; o > 0; o >>= 1) bm2 = fmax(bm2, __shfl_xor(bm2, o));
-    if (lane == 0) wmax[w] = bm2;
+    // B = max |x - c| and sum |alpha| over the training rows: the stagers' maxima and sums, over the workgroup (every
+    // workgroup adds the same rows in the same order: one value of sum |alpha| per call)
+    for (int o = 32; o > 0; o >>= 1) { bm2 = fmax(bm2, __shfl_xor(bm2, o)); sal += __shfl_xor(sal, o); }
+    if (lane == 0) { wmax[w] = bm2; wsal[w] = sal; }
     __syncthreads();
+    sal = 0.0;
 #pragma unroll
-    for (int i = 0; i < PR_THREADS / 64; ++i) bm2 = fmax(bm2, wmax[i]);
+    for (int i = 0; i < PR_THREADS / 64; ++i) { bm2 = fmax(bm2, wmax[i]); sal += wsal[i]; }
     const double bn = sqrt(bm2);
     const double u32 = 0x1p-24, eps = 0x1p-53;
-    sal += __shfl_xor(sal, 32);
     const double sa = sal * (1.0 + 0x1p-16);
     double bb = INFINITY, bbe = INFINITY;
 #pragma unroll

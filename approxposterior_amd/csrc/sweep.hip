@@ -1574,70 +1574,126 @@ __device__ __forceinline__ bool pr_less(double v, long long i, double w, long lo
 
 #define PR_NONE 0x7fffffffffffffffll                     // block number of an empty shortlist entry, value +inf
 
-// a sorted shortlist of the PR_SEED smallest pairs seen, in registers (every index is a compile-time constant)
-__device__ __forceinline__ void pr_short_insert(double (&lv)[PR_SEED], long long (&li)[PR_SEED], double v, long long p) {
-    if (!pr_less(v, p, lv[PR_SEED - 1], li[PR_SEED - 1])) return;
-    lv[PR_SEED - 1] = v; li[PR_SEED - 1] = p;
-#pragma unroll
-    for (int s = PR_SEED - 1; s > 0; --s) {
-        const bool up = pr_less(lv[s], li[s], lv[s - 1], li[s - 1]);
-        const double tv = lv[s]; const long long tp = li[s];
-        lv[s] = up ? lv[s - 1] : tv; li[s] = up ? li[s - 1] : tp;
-        lv[s - 1] = up ? tv : lv[s - 1]; li[s - 1] = up ? tp : li[s - 1];
-    }
-}
-
-// The PR_SEED smallest pairs of a wavefront's 64 shortlists, in order: lane r < PR_SEED returns the r-th (PR_NONE if
-// there are fewer).  PR_SEED rounds: the smallest head wins, its lane drops it.
-__device__ __forceinline__ void pr_wave_merge(double (&lv)[PR_SEED], long long (&li)[PR_SEED], double& mv, long long& mi) {
+// The PR_SEED smallest of the E pairs that each lane of a wavefront holds, in order: lane r < PR_SEED returns the r-th
+// (PR_NONE if there are fewer).  PR_SEED rounds: every lane offers its smallest pair, the smallest offer wins and its
+// lane drops it.  The pairs stay where they are (every index is a compile-time constant), so nothing is sorted or moved
+// and nothing spills; block numbers are distinct, which makes the winner unique.
+template <int E>
+__device__ __forceinline__ void pr_wave_select(double (&lv)[E], long long (&li)[E], double& mv, long long& mi) {
     const int lane = threadIdx.x & 63;
     mv = INFINITY; mi = PR_NONE;
     for (int r = 0; r < PR_SEED; ++r) {
-        double bv = lv[0];
-        long long bi = li[0];
+        double hv = lv[0];
+        long long hi = li[0];
+#pragma unroll
+        for (int j = 1; j < E; ++j)
+            if (pr_less(lv[j], li[j], hv, hi)) { hv = lv[j]; hi = li[j]; }
+        double bv = hv;
+        long long bi = hi;
         for (int o = 32; o > 0; o >>= 1) {
             const double ov = __shfl_xor(bv, o);
             const long long oi = __shfl_xor(bi, o);
             if (pr_less(ov, oi, bv, bi)) { bv = ov; bi = oi; }
         }
+        if (bi == PR_NONE) break;                        // (the same in every lane) nothing is left
         if (lane == r) { mv = bv; mi = bi; }
-        if (bi != PR_NONE && li[0] == bi) {
+        if (hi == bi) {
 #pragma unroll
-            for (int s = 0; s + 1 < PR_SEED; ++s) { lv[s] = lv[s + 1]; li[s] = li[s + 1]; }
-            lv[PR_SEED - 1] = INFINITY; li[PR_SEED - 1] = PR_NONE;
+            for (int j = 0; j < E; ++j)
+                if (li[j] == bi) { lv[j] = INFINITY; li[j] = PR_NONE; }
         }
     }
 }
 
+#define PR_SEED_E 16                                     // values per thread and chunk: C3's 15,625 blocks are one chunk
+#define PR_LIST (16 * PR_SEED)                           // pairs in the workgroup's list
+
 // The PR_SEED blocks with the smallest bmin below +inf (fewer if fewer have an admissible row), ascending by (value,
-// block number), one workgroup, ONE pass over bmin: every thread keeps a sorted shortlist of its strided share, each
-// wavefront merges its 64 shortlists, the first wavefront merges the 16 results.
+// block number).  One workgroup, one pass over bmin in chunks of PR_SEED_E x 1024 values, a thread's strided share of a
+// chunk in registers, nothing sorted, no scratch:
+//   * filter.  The smallest pair of each of the 16 wavefronts are 16 different pairs, so the PR_SEED-th smallest of all
+//     is not above the largest of them, tau (+inf while a wavefront has no value below +inf); tau only falls from chunk
+//     to chunk.  The pairs <= tau go to a list in LDS: about 50 of C3's 15,625 values.
+//   * rank.  A pair's place in the result is the number of listed pairs below it; thread t counts for pair t.
+//   * a list that overflows (values in an order that defeats the filter; a wavefront's whole share at +inf) is
+//     dropped: every wavefront selects the PR_SEED smallest of what its lanes hold, chunk after chunk (from the second
+//     on only values below its PR_SEED-th so far enter), and the list is the 16 wavefronts' results.
 __global__ __launch_bounds__(1024) void prune_seed_kernel(const double* bmin, long long ncb, long long* seeds,
                                                           long long* counts) {
-    __shared__ double sv[16 * PR_SEED];
-    __shared__ long long si[16 * PR_SEED];
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-    double lv[PR_SEED], mv;
-    long long li[PR_SEED], mi;
+    __shared__ double sv[PR_LIST], wv[16];
+    __shared__ long long si[PR_LIST], wi[16];
+    __shared__ int cnt, nsel;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    if (tid == 0) { cnt = 0; nsel = 0; }
+    double tv = INFINITY;                                // tau: (+inf, PR_NONE) is above every pair
+    long long ti = PR_NONE;
+    for (long long base = 0; base < ncb; base += PR_SEED_E * 1024) {
+        double lv[PR_SEED_E], hv = INFINITY;
+        long long hp = PR_NONE;
 #pragma unroll
-    for (int s = 0; s < PR_SEED; ++s) { lv[s] = INFINITY; li[s] = PR_NONE; }
-    for (long long p = threadIdx.x; p < ncb; p += 1024) {
-        const double v = bmin[p];
-        if (v < INFINITY) pr_short_insert(lv, li, v, p);
+        for (int j = 0; j < PR_SEED_E; ++j) {
+            const long long p = base + tid + 1024 * j;
+            const double v = p < ncb ? bmin[p] : INFINITY;
+            lv[j] = v < INFINITY ? v : INFINITY;         // (a NaN is not below +inf)
+            if (lv[j] < hv) { hv = lv[j]; hp = p; }      // p ascends with j: the lowest block number on ties
+        }
+        for (int o = 32; o > 0; o >>= 1) {
+            const double ov = __shfl_xor(hv, o);
+            const long long op = __shfl_xor(hp, o);
+            if (pr_less(ov, op, hv, hp)) { hv = ov; hp = op; }
+        }
+        __syncthreads();                                 // (the previous chunk's minima have been read)
+        if (lane == 0) { wv[w] = hv; wi[w] = hp; }
+        __syncthreads();
+        double cv = wv[0];
+        long long ci = wi[0];
+#pragma unroll
+        for (int i = 1; i < 16; ++i)
+            if (pr_less(cv, ci, wv[i], wi[i])) { cv = wv[i]; ci = wi[i]; }
+        if (pr_less(cv, ci, tv, ti)) { tv = cv; ti = ci; }
+#pragma unroll
+        for (int j = 0; j < PR_SEED_E; ++j) {
+            const long long p = base + tid + 1024 * j;
+            if (lv[j] < INFINITY && !pr_less(tv, ti, lv[j], p)) {
+                const int slot = atomicAdd(&cnt, 1);
+                if (slot < PR_LIST) { sv[slot] = lv[j]; si[slot] = p; }
+            }
+        }
     }
-    pr_wave_merge(lv, li, mv, mi);
-    if (lane < PR_SEED) { sv[w * PR_SEED + lane] = mv; si[w * PR_SEED + lane] = mi; }
     __syncthreads();
-    if (w != 0) return;
+    int n = cnt;
+    if (n > PR_LIST) {
+        double lv[PR_SEED_E + 1], mv = INFINITY;
+        long long li[PR_SEED_E + 1], mi = PR_NONE;
+        for (long long base = 0; base < ncb; base += PR_SEED_E * 1024) {
+            const double qv = __shfl(mv, PR_SEED - 1);   // the wavefront's PR_SEED-th so far (+inf, PR_NONE: none yet)
+            const long long qi = __shfl(mi, PR_SEED - 1);
+            bool any = false;
 #pragma unroll
-    for (int s = 0; s < PR_SEED; ++s) { lv[s] = INFINITY; li[s] = PR_NONE; }
-    for (int e = lane; e < 16 * PR_SEED; e += 64)
-        if (si[e] != PR_NONE) pr_short_insert(lv, li, sv[e], si[e]);
-    pr_wave_merge(lv, li, mv, mi);
-    const bool have = lane < PR_SEED && mi != PR_NONE;
-    if (have) seeds[lane] = mi;
-    const int ns = __popcll(__ballot(have));
-    if (lane == 0) { counts[0] = ns; counts[1] = 0; counts[3] = 0; }
+            for (int j = 0; j < PR_SEED_E; ++j) {
+                const long long p = base + tid + 1024 * j;
+                const double v = p < ncb ? bmin[p] : INFINITY;
+                const bool in = v < INFINITY && pr_less(v, p, qv, qi);
+                lv[j] = in ? v : INFINITY; li[j] = in ? p : PR_NONE;
+                any |= in;
+            }
+            if (!__any(any)) continue;
+            lv[PR_SEED_E] = mv; li[PR_SEED_E] = mi;
+            pr_wave_select(lv, li, mv, mi);
+        }
+        if (lane < PR_SEED) { sv[w * PR_SEED + lane] = mv; si[w * PR_SEED + lane] = mi; }
+        n = PR_LIST;
+        __syncthreads();
+    }
+    if (tid < n && si[tid] != PR_NONE) {
+        const double v = sv[tid];
+        const long long p = si[tid];
+        int rank = 0;
+        for (int e = 0; e < n; ++e) rank += pr_less(sv[e], si[e], v, p) ? 1 : 0;
+        if (rank < PR_SEED) { seeds[rank] = p; atomicAdd(&nsel, 1); }
+    }
+    __syncthreads();
+    if (tid == 0) { counts[0] = nsel; counts[1] = 0; counts[3] = 0; }
 }
 
 // tau = the smallest utility the seed blocks found (part_u of the seeds; tau_in if part_u == NULL: a planted
