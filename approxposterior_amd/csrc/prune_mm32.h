@@ -1,43 +1,73 @@
-// Coarse bound of the pruned arg-min with the exponents formed on the fp32 matrix cores (included from sweep.hip behind
+// Coarse bound of the pruned arg-min with the exponents formed on the bf16 matrix cores (included from sweep.hip behind
 // prune_bound32_kernel; DESIGN.md section 4, "The bound in two stages").  Same PruneArgs, same outputs as
 // prune_bound32_kernel: bmin, est (b without slack), the (+inf, -1) pre-fill of the arg-min partials.
 //
 // With a = (t sc - c) kappa and b = (x - c) kappa as there (c = the first training row, kappa^2 = log2(e)), the exponent
-// of k = amp 2^-|a - b|^2 is a rank-(Dpad + 2) product,
-//     -|a - b|^2 = sum_e P[row][e] Q[e][candidate],   P = (-|b|^2, 1, 2 b_1 .. 2 b_Dpad),  Q = (1, -|a|^2, a_1 .. a_Dpad),
-// and v_mfma_f32_32x32x2_f32 forms it for 32 training rows x 32 candidates in (Dpad + 2) / 2 instructions: bit for bit an
-// fp32 fma chain over the entries, one rounding per entry.  Only the exponential and the two products with alpha and
-// |alpha| stay on the vector ALU.
-//   * operands: the candidates are the N side, lane l holds candidate l % 32 of a 32-candidate group in registers for
-//     the whole kernel (PMM_G groups = PMM_G / 2 candidate blocks per wavefront, which share every LDS read of a
-//     training row); the training rows are the M side, converted once per workgroup into an LDS tile of PMM_ROWS rows.
-//     Lane half h = l / 32 takes entries h KH .. h KH + KH - 1 (KH = Dpad / 2 + 1), stored so that a lane reads its
-//     KH floats in one 16-byte read per four entries and the rest behind them.
-//   * a lane's 16 accumulators are 16 training rows (r & 3) + 8 (r >> 2) + 4 h of ONE candidate: exp2 in place, the
-//     alphas of four consecutive rows in one 16-byte read, fp32 partial sums over the 16 rows, then into fp64 -- the
-//     accumulation error does not grow with N.  Lanes l and l + 32 hold the two halves of a candidate's sums and are
-//     combined once at the end.
-//   * rows past n, rows that are not live and rows with a NaN or a coordinate beyond fp32 enter the operands as 0 (a NaN
-//     in a candidate's column would stay in that column, but nothing is left to that); they decide admissibility in
-//     fp64 alone, as in load_candidates.
+// of k = amp 2^-|a - b|^2 is a rank-(Dpad + 2) product of fp32 entries,
+//     -|a - b|^2 = sum_e P[row][e] Q[e][candidate],   P = (-|b|^2, 1, 2 b_1 .. 2 b_Dpad),  Q = (1, -|a|^2, a_1 .. a_Dpad).
+// v_mfma_f32_32x32x2_f32 forms it at the fp32 vector rate and holds the vector lanes while it runs (docs/experiments.md,
+// round 17); v_mfma_f32_32x32x16_bf16 is 16 times faster and leaves them free.  So every fp32 entry p is written as the
+// EXACT sum of three bf16 numbers, h = bf16(p), m = bf16(p - h), l = p - h - m (round to nearest; |m| <= 2^-8 |p|,
+// |l| <= 2^-17 |p|; tests/test_prune_mmbf16_ref.py), and P[e] Q[e] becomes nine bf16 products of which six are kept:
+//     big    h h                                  one per entry: Dpad + 2
+//     small  h m, m h, m m, h l, l h              five per coordinate entry; m 1, l 1 for the two norm entries (1 = h)
+//     dropped  m l, l m, l l                      <= (2^-24 + 2^-34) |p q| per coordinate entry
+// The k slots of the instruction are filled 16 at a time (PmmShape::slot): the small products FIRST, lowest order first
+// (h l and l h, the norms' l; m m; h m and m h, the norms' m), into an accumulator that starts at 0, padded with zeros to
+// a multiple of 16; the big products in the LAST instruction.  Dpad = 8: 44 small products in three instructions and ten
+// big ones in the fourth; Dpad = 4: 2 + 1; Dpad = 2: 1 + 1.  Only the exponential and the two products with alpha and
+// |alpha| stay on the vector ALU, and run under the next group's matrix products or the other wavefront's.
+//   * operands: the candidates are the N (B) side, lane l holds candidate l % 32 of a 32-candidate group in registers
+//     for the whole kernel, k slots 8 (l / 32) .. + 7 of every instruction: 4 VGPRs per instruction and group (PMM_G
+//     groups = PMM_G / 2 candidate blocks per wavefront, which share every LDS read of a training row); the training
+//     rows are the M (A) side, split once per workgroup into an LDS tile of PMM_ROWS rows of 16 NI bf16 values, of which
+//     a lane reads its 8 per instruction in one 16-byte read.  The row pitch is 32 NI + 16 bytes, an ODD number of
+//     16-byte units: ds_read_b128 serves 16 lanes per pass, the rows {0-3, 12-15, 20-27} or {4-11, 16-19, 28-31} of one
+//     lane half, which are 16 different rows modulo 16, so with an odd pitch their 16-byte pieces fall on 16 different
+//     four-bank groups of the 64 banks: conflict-free (an even pitch, 128 bytes for Dpad = 8, would be 8-way).
+//   * a lane's 16 accumulators are 16 training rows (r & 3) + 8 (r >> 2) + 4 h of ONE candidate (the C layout does not
+//     depend on the operand type): exp2 in place, the alphas of four consecutive rows in one 16-byte read, fp32 partial
+//     sums over the 16 rows, then into fp64 -- the accumulation error does not grow with N.  Lanes l and l + 32 hold
+//     the two halves of a candidate's sums and are combined once at the end.
+//   * rows past n, rows that are not live and rows with a NaN or a coordinate beyond fp32 enter with their coordinates
+//     and their norm 0 in all three parts (a NaN in a candidate's column would stay in that column, but nothing is left
+//     to that); the entries "1" stay 1, so a padding row's exponent is -|a|^2 <= 0 and its kernel value meets alpha = 0.
+//     Such rows decide admissibility in fp64 alone, as in load_candidates.  Inside the gate below no part can be
+//     infinite: eta <= 2^-8 means (A + B)^2 < 2^13, every entry of P and Q is below 2^14 in absolute value, and
+//     rounding a finite fp32 number below 2^127 to bf16 stays finite; outside it (a^2 up to 2^100 is let in) an
+//     infinite or NaN exponent gives a NaN bound, which is the same -inf mark.
 //   * exact part: admissibility, k(t,t), util_value and the slack in fp64, as in prune_bound32_kernel.
+//
+// What the instruction does with its 16 products and C (tools/probes/mfma_bf16_acc.hip, profiles/r18_mfma_bf16_acc.txt;
+// DESIGN.md section 2): it works in two halves, k slots 0 .. 7 and then 8 .. 15.  Per half the products (exact, 16 bits)
+// are aligned to E = the largest sum of the two operands' exponents among the non-zero products (so the largest product
+// lies in [2^(E-2), 2^E)) and cut TOWARD ZERO to multiples of q = 2^(E-26); the accumulator, where it has bits below q,
+// is cut to a multiple of q toward -inf; the cut values are summed exactly and rounded to nearest once.  Nothing is
+// flushed: bf16 subnormal operands, subnormal products, sums and C all count.  A zero product loses nothing and a half
+// with no non-zero product returns its accumulator.  With pmax the largest product of the half, q <= 2^-24 pmax = u pmax:
+//     per half  |error| <= (non-zero products + 1) u pmax + u |partial sum|.
 //
 // Error of mu32.  u = 2^-24, eps = 2^-53, A = |t sc - c|, B = max over the training rows of |x - c| (both without kappa:
 // kappa^2 ln 2 = 1, so (A + B)^2 IS the scale of the exponent in natural units), K = Dpad + 2.  In the expanded form
-// the exponent's error is no longer relative to r^2 but to (A + B)^2, whatever k is:
+// the exponent's error is not relative to r^2 but to (A + B)^2, whatever k is:
 //   * conversions.  a^ = fl32(a), b^ = fl32(b) are off by u |a_d|, u |b_d| per coordinate, so |a^ - b^| and |a - b| = r
 //     differ by <= u (A + B) and the squares by <= (2 r + u (A + B)) u (A + B) <= 2.01 u (A + B)^2  (r <= A + B).
 //   * norms.  |a^|^2 and |b^|^2 are summed in fp64 from the CONVERTED coordinates (so that the three parts cancel to
-//     -|a^ - b^|^2 exactly before rounding) and rounded once to fp32, no low parts: u (A^2 + B^2) <= u (A + B)^2.
-//     2 b^_d is exact.
-//   * chain.  One rounding per entry, relative to the partial sum, and every partial sum in any order of the entries is
-//     at most |a^|^2 + |b^|^2 + 2 |a^| |b^| = (|a^| + |b^|)^2 in absolute value: K u (A + B)^2 (1 + K u).  The bound
-//     does not depend on the order in which the instruction adds its two entries.
-//     Together (K + 3.01) u (A + B)^2, taken as (K + 4) u (A + B)^2 with room for the fp64 roundings of a, b, kappa and
-//     the norms (2^-29 u each) and the factors (1 + u)^K.
+//     -|a^ - b^|^2 exactly) and rounded once to fp32: u (A^2 + B^2) <= u (A + B)^2.  2 b^_d is exact, and so is the
+//     split of every entry.
+//   * dropped products.  (2^-24 + 2^-34) sum_d |2 b^_d a^_d| <= (2^-24 + 2^-34) (|a^| + |b^|)^2 / 2 <= 0.51 u (A + B)^2.
+//   * accumulation.  The absolute values of all products of an entry sum to <= |p q| (1 + 2^-7), and sum_e |P_e Q_e| =
+//     (|a^| + |b^|)^2, so every partial sum and every product is at most (1 + 2^-7) (A + B)^2 (natural units), and every
+//     small product and every partial sum of the small chain at most 2^-7 of that.  Last instruction: K non-zero
+//     products and two accumulator cuts at u pmax each, two roundings: (K + 4) u (A + B)^2.  Small chain: per half nine
+//     cuts of <= u 2^-8 and a rounding of <= u 2^-7, 11 u 2^-8 (A + B)^2, in at most six halves: 0.26 u (A + B)^2.
+//     Together (K + 4.26) u (A + B)^2: the order of the slots matters only in that the K products of full size meet
+//     the accumulator once, in the last instruction.
+//     With the above (K + 7.78) u (A + B)^2, taken as (K + 8) u (A + B)^2 with room for the factors (1 + 2^-7), the
+//     fp64 roundings of a, b, kappa and the norms (2^-29 u each).
 //   * centring, as for prune_bound32_kernel: t sc - c may be contracted to one fma, an ABSOLUTE shift delta of a with
 //     |delta| <= 1.21 eps (|c| + A); it moves the exponent by <= 2 r |delta| + |delta|^2 <= 2.5 eps (A + B) (|c| + A).
-//   * so k lies in [k^ e^-eta0, k^ e^eta0] with eta0 = (K + 4) u (A + B)^2 + 2.5 eps (A + B) (|c| + A), k^ the exact
+//   * so k lies in [k^ e^-eta0, k^ e^eta0] with eta0 = (K + 8) u (A + B)^2 + 2.5 eps (A + B) (|c| + A), k^ the exact
 //     power of the computed exponent.  v_exp_f32 (1 ulp, allowed 4 u), alpha -> fp32 (u) and the 16 fma of one fp32
 //     partial sum (16 u of sum |alpha| k^, the terms of S32 below) are relative too: with
 //         eta = eta0 + 24 u       (4.1 + 1.01 + 16.1 and room)
@@ -47,44 +77,102 @@
 //   * gate: eta <= 2^-8 keeps e^eta - 1 a small multiple of eta (and k^ <= e^eta where a candidate sits on a training
 //     point).  It needs B, which the staging threads carry with the tiles (max over the rows < n), so it is decided
 //     after the last tile.  Gate failed: e32 = +inf, the block's bound is -inf.
-//   * flushes: a kernel value, an alpha or a product below 2^-126 may become 0: 2^-120 (sum |alpha| + N), absolute, so
-//     this term keeps sum |alpha|.  It is a property of the fit, not of a candidate: the staging lanes add |alpha| of
-//     the row they convert, in fp64 from the fp64 alpha, once per row and workgroup (N eps relative), and the sum is
-//     taken times 1 + 2^-16, which also covers |fl32(alpha)| <= |alpha| (1 + u) where the fp32 alphas are meant.
+//   * flushes: a kernel value, an alpha or a product with alpha below 2^-126 may become 0: 2^-120 (sum |alpha| + N),
+//     absolute, so this term keeps sum |alpha|.  The matrix instruction flushes nothing; a part of an entry below 2^-126
+//     that the conversion to bf16 might flush moves the exponent by less than 2^-100, which is inside the room of the
+//     24 u.  sum |alpha| is a property of the fit, not of a candidate: the staging lanes add |alpha| of the row they
+//     convert, in fp64 from the fp64 alpha, once per row and workgroup (N eps relative), and the sum is taken times
+//     1 + 2^-16, which also covers |fl32(alpha)| <= |alpha| (1 + u) where the fp32 alphas are meant.
 // |mu32 - mu| <= e32 = amp ((e^eta - 1) S32 + 2^-120 (sum|alpha| + N)); the slack is prune_bound_kernel's with
-// S <= amp sum|alpha| plus 2 e32.  At C3 (A + B ~ 9.5, S32 <= 5e4 against sum|alpha| = 1.9e6) that is below 8, where
+// S <= amp sum|alpha| plus 2 e32.  At C3 the maxima A + B ~ 9.5 and S32 <= 5e4 (against sum|alpha| = 1.9e6) put it
+// below 10 (the fp32 chain's: below 8; "coarse kept 0" holds below 45); replayed on 256 of C3's candidates it is at most
+// 2.6, 1.0 in the median, 1.27 times the fp32 chain's on the same candidates (profiles/r18_seeds_branch.json), where
 // sum|alpha| in the place of S32 would give several hundred and prune nothing.
 //
 // A block whose bound came out -inf (gate failed: data far wider than the length scale; or a NaN bound) is left to
 // prune_bound32_kernel<DPAD, true>, launched behind this kernel: the -inf in bmin is the mark, no other scratch.
-// Variants measured: docs/experiments.md, round 13; what the fp32 MFMA leaves to the vector ALU beside it: round 17.
+// Variants measured: docs/experiments.md, round 13 (the fp32 form), round 17 (what the fp32 MFMA leaves to the vector
+// ALU), round 18 (this form).
 #pragma once
+#include <utility>
 
 #ifndef PMM_G
-#define PMM_G 4             // 32-candidate groups per wavefront (8 measured: docs/experiments.md, round 13)
+#define PMM_G 4             // 32-candidate groups per wavefront (2 measured: docs/experiments.md, round 18)
 #endif
 #define PMM_ROWS 128        // training rows per LDS tile: one 32-row matrix tile staged by each wavefront
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+
+struct PmmSlot { int e, pp, qp; };                       // entry; part of P, part of Q (0 h, 1 m, 2 l); e < 0: a zero slot
 
 template <int DPAD>
 struct PmmShape {
-    static constexpr int K = DPAD + 2, KH = K / 2, Q4 = KH / 4, R = KH % 4;
-    static constexpr int RS = (2 * KH + 3) & ~3;                  // floats per LDS row (16-byte rows)
-    // where entry e of a row stands in its LDS row: per four steps the quad of half 0, the quad of half 1; the rest after
-    static constexpr int pos(int e) {
-        const int h = e / KH, s = e % KH;
-        return s < 4 * Q4 ? (s / 4) * 8 + h * 4 + (s & 3) : Q4 * 8 + h * R + (s - 4 * Q4);
+    static constexpr int K = DPAD + 2;
+    static constexpr int NS = 5 * DPAD + 4;              // small products
+    static constexpr int NIS = (NS + 15) / 16, NI = NIS + 1;      // instructions: the small chain, and the big products
+    static constexpr int PITCH = 16 * NI + 8;            // bf16 values per LDS row: an odd number of 16-byte units
+    static_assert(K <= 16, "the big products stand in one instruction");
+    // what stands in k slot i of the chain (slot i % 16 of instruction i / 16); P[1] = Q[0] = 1 have an h part only
+    static constexpr PmmSlot slot(int i) {
+        if (i >= 16 * NIS) return i - 16 * NIS < K ? PmmSlot{i - 16 * NIS, 0, 0} : PmmSlot{-1, 0, 0};
+        if (i < 2 * DPAD) return PmmSlot{2 + i / 2, (i & 1) ? 2 : 0, (i & 1) ? 0 : 2};             // h l, l h
+        i -= 2 * DPAD;
+        if (i < 2) return i == 0 ? PmmSlot{0, 2, 0} : PmmSlot{1, 0, 2};                            // the norms' l
+        i -= 2;
+        if (i < DPAD) return PmmSlot{2 + i, 1, 1};                                                 // m m
+        i -= DPAD;
+        if (i < 2 * DPAD) return PmmSlot{2 + i / 2, (i & 1) ? 1 : 0, (i & 1) ? 0 : 1};             // h m, m h
+        i -= 2 * DPAD;
+        if (i < 2) return i == 0 ? PmmSlot{0, 1, 0} : PmmSlot{1, 0, 1};                            // the norms' m
+        return PmmSlot{-1, 0, 0};
     }
 };
+
+// part 0, 1, 2 = h, m, l of p = h + m + l, each a bf16 number (p - h and p - h - m are exact in fp32)
+template <int PART>
+__device__ __forceinline__ float pmm_part(float p) {
+    const float h = (float)(__bf16)p;
+    if constexpr (PART == 0) return h;
+    const float r = p - h, m = (float)(__bf16)r;
+    return PART == 1 ? m : r - m;
+}
+
+// Fragment F (k slots 8 F .. 8 F + 7 of the chain) of an operand row out of its fp32 entries (SIDE 0: P, 1: Q).  The slot
+// numbers are template arguments and every slot splits its entry anew (the compiler merges the repeats): with the parts
+// in an array indexed by slot() the array stayed in scratch memory.
+template <int DPAD, int SIDE, int I>
+__device__ __forceinline__ __bf16 pmm_slot_value(const float (&entry)[DPAD + 2]) {
+    constexpr PmmSlot s = PmmShape<DPAD>::slot(I);
+    if constexpr (s.e < 0) return (__bf16)0.0f;
+    else return (__bf16)pmm_part<SIDE ? s.qp : s.pp>(entry[s.e]);            // (exact: every part is a bf16 number)
+}
+template <int DPAD, int SIDE, int F, int... J>
+__device__ __forceinline__ bf16x8 pmm_frag(const float (&entry)[DPAD + 2], std::integer_sequence<int, J...>) {
+    return bf16x8{pmm_slot_value<DPAD, SIDE, 8 * F + J>(entry)...};
+}
+// a training row's 2 NI fragments into its LDS row
+template <int DPAD, int... F>
+__device__ __forceinline__ void pmm_store_row(__bf16* dst, const float (&entry)[DPAD + 2],
+                                              std::integer_sequence<int, F...>) {
+    ((*(bf16x8*)(dst + 8 * F) = pmm_frag<DPAD, 0, F>(entry, std::make_integer_sequence<int, 8>{})), ...);
+}
+// a candidate's fragments of lane half h: k slots 8 h .. 8 h + 7 of every instruction (both halves' fragments are formed
+// and one is selected per lane: twice the split work, once per candidate and kernel, outside the row loop)
+template <int DPAD, int... T>
+__device__ __forceinline__ void pmm_cand(bf16x8 (&qop)[PmmShape<DPAD>::NI], const float (&entry)[DPAD + 2], int h,
+                                         std::integer_sequence<int, T...>) {
+    ((qop[T] = h ? pmm_frag<DPAD, 1, 2 * T + 1>(entry, std::make_integer_sequence<int, 8>{})
+                 : pmm_frag<DPAD, 1, 2 * T>(entry, std::make_integer_sequence<int, 8>{})), ...);
+}
 
 template <int DPAD>
 __global__ __launch_bounds__(PR_THREADS, PMM_G <= 4 ? 2 : 1) void prune_bound_mm32_kernel(PruneArgs a) {
     using SH = PmmShape<DPAD>;
     constexpr int XS = DPAD + 2;                         // packed stream row: scaled x | alpha | 0
-    constexpr int KH = SH::KH, RS = SH::RS, G = PMM_G;
+    constexpr int K = SH::K, NI = SH::NI, PITCH = SH::PITCH, G = PMM_G;
     static_assert(PMM_G % 2 == 0 && PMM_ROWS == 32 * (PR_THREADS / 64), "one 32-row tile staged per wavefront");
     const double kappa = PR32_KAPPA;                     // sqrt(log2(e))
-    __shared__ __attribute__((aligned(16))) float xt[PMM_ROWS * RS];
+    __shared__ __attribute__((aligned(16))) __bf16 xt[PMM_ROWS * PITCH];
     __shared__ __attribute__((aligned(16))) float at[PMM_ROWS];
     __shared__ double wmax[PR_THREADS / 64], wsal[PR_THREADS / 64];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, h = lane >> 5, l32 = lane & 31;
@@ -93,7 +181,7 @@ __global__ __launch_bounds__(PR_THREADS, PMM_G <= 4 ? 2 : 1) void prune_bound_mm
 #pragma unroll
     for (int d = 0; d < DPAD; ++d) { cen[d] = a.xs[d]; c2 = fma(cen[d], cen[d], c2); }
     const double cn = sqrt(c2);                          // |c|
-    float qop[G][KH];                                    // the candidates' side of the product, this lane half's entries
+    bf16x8 qop[G][NI];                                   // the candidates' side of the product, this lane half's k slots
     double an[G];
     bool adm[G];
 #pragma unroll
@@ -119,21 +207,16 @@ __global__ __launch_bounds__(PR_THREADS, PMM_G <= 4 ? 2 : 1) void prune_bound_mm
         adm[g] = ok && !has_nan;
         an[g] = sqrt(a2);
         const bool use = live && !has_nan && a2 <= 0x1p100;      // else 0: the gate fails on an, or the row is inadmissible
-        float af[DPAD];
+        float q[K];                                      // Q's entries
         double n2 = 0.0;
 #pragma unroll
         for (int d = 0; d < DPAD; ++d) {
-            af[d] = use ? (float)(ce[d] * kappa) : 0.0f;
-            n2 = fma((double)af[d], (double)af[d], n2);
+            q[d + 2] = use ? (float)(ce[d] * kappa) : 0.0f;
+            n2 = fma((double)q[d + 2], (double)q[d + 2], n2);
         }
-        const float na = -(float)n2;
-#pragma unroll
-        for (int s = 0; s < KH; ++s) {
-            const int e0 = s, e1 = KH + s;               // entry of half 0, of half 1
-            const float q0 = e0 == 0 ? 1.0f : e0 == 1 ? na : af[e0 >= 2 ? e0 - 2 : 0];
-            const float q1 = af[e1 - 2];                 // (KH >= 2: half 1 holds coordinates only)
-            qop[g][s] = h ? q1 : q0;
-        }
+        q[0] = 1.0f;
+        q[1] = -(float)n2;
+        pmm_cand<DPAD>(qop[g], q, h, std::make_integer_sequence<int, NI>{});
     }
     double accm[G], accs[G], sal = 0.0, bm2 = 0.0;
 #pragma unroll
@@ -152,55 +235,44 @@ __global__ __launch_bounds__(PR_THREADS, PMM_G <= 4 ? 2 : 1) void prune_bound_mm
     for (long long ti = 0; ti < ntile; ++ti) {
         if (stager) {
             const bool in = ti * PMM_ROWS + srow < a.n;  // rows of the padding: operands 0, alpha 0, no part in B
-            float bf[DPAD];
+            float pe[K];                                 // P's entries
             double n2 = 0.0, b2 = 0.0;
 #pragma unroll
             for (int d = 0; d < DPAD; ++d) {
                 const double x = (d & 1) ? pre[d >> 1].y : pre[d >> 1].x;
                 const double df = x - cen[d];
                 b2 = fma(df, df, b2);
-                bf[d] = in ? (float)(df * kappa) : 0.0f;
-                n2 = fma((double)bf[d], (double)bf[d], n2);
+                const float bf = in ? (float)(df * kappa) : 0.0f;
+                n2 = fma((double)bf, (double)bf, n2);
+                pe[d + 2] = 2.0f * bf;
             }
             if (in) { bm2 = fmax(bm2, b2); sal += fabs(pre[DPAD / 2].x); }
-            float rowv[RS];
-#pragma unroll
-            for (int i = 0; i < RS; ++i) rowv[i] = 0.0f;
-            rowv[SH::pos(0)] = -(float)n2;
-            rowv[SH::pos(1)] = 1.0f;
-#pragma unroll
-            for (int d = 0; d < DPAD; ++d) rowv[SH::pos(d + 2)] = 2.0f * bf[d];
-#pragma unroll
-            for (int i = 0; i < RS; i += 4)
-                *(f32x4*)(xt + srow * RS + i) = f32x4{rowv[i], rowv[i + 1], rowv[i + 2], rowv[i + 3]};
+            pe[0] = -(float)n2;
+            pe[1] = 1.0f;
+            pmm_store_row<DPAD>(xt + srow * PITCH, pe, std::make_integer_sequence<int, 2 * NI>{});
             at[srow] = in ? (float)pre[DPAD / 2].x : 0.0f;
         }
         __syncthreads();
         if (ti + 1 < ntile) fetch(ti + 1);
 #pragma unroll 1
         for (int rt = 0; rt < PMM_ROWS / 32; ++rt) {
-            const float* xr = xt + (rt * 32 + l32) * RS;
-            float pop[KH];                               // the training rows' side, this lane half's entries
+            const __bf16* xr = xt + (rt * 32 + l32) * PITCH + 8 * h;
+            bf16x8 pop[NI];                              // the training rows' side, this lane half's k slots
 #pragma unroll
-            for (int q = 0; q < SH::Q4; ++q) {
-                const f32x4 v = *(const f32x4*)(xr + q * 8 + h * 4);
-                pop[4 * q] = v.x; pop[4 * q + 1] = v.y; pop[4 * q + 2] = v.z; pop[4 * q + 3] = v.w;
-            }
-#pragma unroll
-            for (int r = 0; r < SH::R; ++r) pop[4 * SH::Q4 + r] = xr[SH::Q4 * 8 + h * SH::R + r];
+            for (int t = 0; t < NI; ++t) pop[t] = *(const bf16x8*)(xr + 16 * t);
             float al[16];                                // alpha of accumulator r's row: (r & 3) + 8 (r >> 2) + 4 h
 #pragma unroll
             for (int q = 0; q < 4; ++q) *(f32x4*)(al + 4 * q) = *(const f32x4*)(at + rt * 32 + 8 * q + 4 * h);
             auto product = [&](int g) {
                 f32x16 c = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
-                for (int s = 0; s < KH; ++s) c = __builtin_amdgcn_mfma_f32_32x32x2f32(pop[s], qop[g][s], c, 0, 0, 0);
+                for (int t = 0; t < NI; ++t) c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pop[t], qop[g][t], c, 0, 0, 0);
                 return c;
             };
-            // Written as a two-tile pipeline, but hipcc issues all G groups' products first and the vector work behind
-            // them (64 accumulators fit), and nothing is lost by that: v_mfma_f32_32x32x2_f32 holds the vector lanes
-            // for its 64 cycles, so an exponential placed between two products costs what it costs behind them
-            // (tools/probes/mfma32_shadow.hip; docs/experiments.md, round 17).
+            // Written as a two-tile pipeline, but hipcc issues all G groups' chains first and the vector work behind them
+            // (64 accumulators fit).  Unlike the fp32 form this one leaves the vector issue free for most of its
+            // cycles, so the exponentials run under the products of the SIMD's other wavefront
+            // (tools/probes/mfma_bf16_shadow.hip; docs/experiments.md, round 18).
             f32x16 cur = product(0);
 #pragma unroll
             for (int g = 0; g < G; ++g) {
@@ -240,7 +312,7 @@ __global__ __launch_bounds__(PR_THREADS, PMM_G <= 4 ? 2 : 1) void prune_bound_mm
         const double mu = fma(a.amp, sm, a.mean);
         double b = util_value(a.kind, mu, ktt, a.zeta, a.ybest);
         const double ab = an[g] + bn;
-        const double eta = (DPAD + 6.0) * u32 * ab * ab + 2.5 * eps * ab * (cn + an[g]) + 24.0 * u32;
+        const double eta = (DPAD + 10.0) * u32 * ab * ab + 2.5 * eps * ab * (cn + an[g]) + 24.0 * u32;
         double e32 = a.amp * (expm1(eta) * (1.0 + 0x1p-20) * s32 + 0x1p-120 * (sa + (double)a.n));
         if (!(eta <= 0x1p-8)) e32 = INFINITY;
         // prune_bound_kernel's slack with S <= amp sum|alpha|, and the fp32 part on top
