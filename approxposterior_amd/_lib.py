@@ -109,6 +109,16 @@ SIGNATURES = {
     "apgp_prune_bounds": (ctypes.c_int, [_P, _I64, _P, _I64, _KP, _F64, _I32, ctypes.POINTER(_F64), ctypes.POINTER(_F64),
                                          _P, _F64, _F64, ctypes.c_int, _P, _P]),
     "apgp_sweep_prune_seeds": (ctypes.c_int, [_P, _I64, _P, _P, _P]),
+    "apgp_prune_rows_len": (_I64, [_I64, _I32]),
+    "apgp_pack_prune_rows": (ctypes.c_int, [_P, _I64, _KP, _P, _P]),
+    "apgp_acquire_rows": (ctypes.c_int, [_P, _I64, _I64, _P, _P, _I64, _KP, _F64, _I32,
+                                         ctypes.POINTER(_F64), ctypes.POINTER(_F64), _P,
+                                         _F64, _F64, _P, _P, _P, _P, _P, _P, _P]),
+    "apgp_acquire_solve_rows": (ctypes.c_int, [_P, _I64, _I64, _P, _P, _I64, _KP, _F64, _I32,
+                                               ctypes.POINTER(_F64), ctypes.POINTER(_F64), _P,
+                                               _F64, _F64, _P, _P, _P, _P, _P, _P, _P]),
+    "apgp_prune_bounds_rows": (ctypes.c_int, [_P, _I64, _P, _I64, _KP, _F64, _I32, ctypes.POINTER(_F64),
+                                              ctypes.POINTER(_F64), _P, _F64, _F64, ctypes.c_int, _P, _P, _P]),
     "apgp_acquire_fantasy_work_len": (_I64, [_I64]),
     "apgp_acquire_fantasy": (ctypes.c_int, [_P, _I64, _I64, _P, _I64, _KP, _P, _I64, _I32, _P, _I64,
                                             _P, _P, _P, _I32, ctypes.POINTER(_F64), ctypes.POINTER(_F64), _P,

@@ -20,7 +20,9 @@
 //   * operands: the candidates are the N (B) side, lane l holds candidate l % 32 of a 32-candidate group in registers
 //     for the whole kernel, k slots 8 (l / 32) .. + 7 of every instruction: 4 VGPRs per instruction and group (PMM_G
 //     groups = PMM_G / 2 candidate blocks per wavefront, which share every LDS read of a training row); the training
-//     rows are the M (A) side, split once per workgroup into an LDS tile of PMM_ROWS rows of 16 NI bf16 values, of which
+//     rows are the M (A) side, split once per fit (apgp_pack_prune_rows -> pmm_pack_rows_kernel: the stream holds every
+//     tile's LDS image and the kernel copies it, PRE = true; a caller without the stream gets PRE = false, where every
+//     workgroup splits the rows itself, same bits) into LDS tiles of PMM_ROWS rows of 16 NI bf16 values, of which
 //     a lane reads its 8 per instruction in one 16-byte read.  The row pitch is 32 NI + 16 bytes, an ODD number of
 //     16-byte units: ds_read_b128 serves 16 lanes per pass, the rows {0-3, 12-15, 20-27} or {4-11, 16-19, 28-31} of one
 //     lane half, which are 16 different rows modulo 16, so with an odd pitch their 16-byte pieces fall on 16 different
@@ -75,13 +77,14 @@
 //     beside mu32, one v_fmac more per value; summed like mu32 it is below the exact sum by <= 17 u of it and is taken
 //     times 1 + 2^-16, expm1 times 1 + 2^-20.
 //   * gate: eta <= 2^-8 keeps e^eta - 1 a small multiple of eta (and k^ <= e^eta where a candidate sits on a training
-//     point).  It needs B, which the staging threads carry with the tiles (max over the rows < n), so it is decided
-//     after the last tile.  Gate failed: e32 = +inf, the block's bound is -inf.
+//     point).  It needs B, which the staging threads carry with the tiles (max over the rows < n; the pre-split stream
+//     has it in its header), so it is decided after the last tile.  Gate failed: e32 = +inf, the block's bound is -inf.
 //   * flushes: a kernel value, an alpha or a product with alpha below 2^-126 may become 0: 2^-120 (sum |alpha| + N),
 //     absolute, so this term keeps sum |alpha|.  The matrix instruction flushes nothing; a part of an entry below 2^-126
 //     that the conversion to bf16 might flush moves the exponent by less than 2^-100, which is inside the room of the
 //     24 u.  sum |alpha| is a property of the fit, not of a candidate: the staging lanes add |alpha| of the row they
-//     convert, in fp64 from the fp64 alpha, once per row and workgroup (N eps relative), and the sum is taken times
+//     convert, in fp64 from the fp64 alpha, once per row and workgroup (N eps relative; the pre-split stream's header
+//     carries the same sum, added in the same order: the same bits), and the sum is taken times
 //     1 + 2^-16, which also covers |fl32(alpha)| <= |alpha| (1 + u) where the fp32 alphas are meant.
 // |mu32 - mu| <= e32 = amp ((e^eta - 1) S32 + 2^-120 (sum|alpha| + N)); the slack is prune_bound_kernel's with
 // S <= amp sum|alpha| plus 2 e32.  At C3 the maxima A + B ~ 9.5 and S32 <= 5e4 (against sum|alpha| = 1.9e6) put it
@@ -92,7 +95,7 @@
 // A block whose bound came out -inf (gate failed: data far wider than the length scale; or a NaN bound) is left to
 // prune_bound32_kernel<DPAD, true>, launched behind this kernel: the -inf in bmin is the mark, no other scratch.
 // Variants measured: docs/experiments.md, round 13 (the fp32 form), round 17 (what the fp32 MFMA leaves to the vector
-// ALU), round 18 (this form).
+// ALU), round 18 (this form), round 19 (the rows split once per fit).
 #pragma once
 #include <utility>
 
@@ -112,6 +115,9 @@ struct PmmShape {
     static constexpr int NIS = (NS + 15) / 16, NI = NIS + 1;      // instructions: the small chain, and the big products
     static constexpr int PITCH = 16 * NI + 8;            // bf16 values per LDS row: an odd number of 16-byte units
     static_assert(K <= 16, "the big products stand in one instruction");
+    // the pre-split stream (apgp_pack_prune_rows): a 16-byte header (bm2, sal), then per PMM_ROWS-row tile the LDS image
+    // of the rows (XPIECES 16-byte pieces) and the tile's fp32 alphas (APIECES)
+    static constexpr int XPIECES = PMM_ROWS * PITCH / 8, APIECES = PMM_ROWS / 4, PIECES = XPIECES + APIECES;
     // what stands in k slot i of the chain (slot i % 16 of instruction i / 16); P[1] = Q[0] = 1 have an h part only
     static constexpr PmmSlot slot(int i) {
         if (i >= 16 * NIS) return i - 16 * NIS < K ? PmmSlot{i - 16 * NIS, 0, 0} : PmmSlot{-1, 0, 0};
@@ -165,15 +171,79 @@ __device__ __forceinline__ void pmm_cand(bf16x8 (&qop)[PmmShape<DPAD>::NI], cons
                  : pmm_frag<DPAD, 1, 2 * T>(entry, std::make_integer_sequence<int, 8>{})), ...);
 }
 
+// The pre-split stream of a fit (apgp_pack_prune_rows): a 16-byte header, then every tile's LDS image as the staging lanes
+// of prune_bound_mm32_kernel<DPAD, false> write it (the pad of a row zeroed) and the tile's fp32 alphas.  The header holds
+// bm2 = max |x - c|^2 over the rows < n and sal = sum |alpha| with the bits that kernel reduces them to: the same lanes
+// add the same rows in the same order, the same shuffle tree, the wavefronts' sums in order.  One workgroup.
 template <int DPAD>
+__global__ __launch_bounds__(PR_THREADS) void pmm_pack_rows_kernel(const double* xs, long long n, unsigned char* rows) {
+    using SH = PmmShape<DPAD>;
+    constexpr int XS = DPAD + 2, PITCH = SH::PITCH;
+    const double kappa = PR32_KAPPA;
+    __shared__ double wmax[PR_THREADS / 64], wsal[PR_THREADS / 64];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, h = lane >> 5, l32 = lane & 31;
+    double cen[DPAD];
+#pragma unroll
+    for (int d = 0; d < DPAD; ++d) cen[d] = xs[d];
+    double sal = 0.0, bm2 = 0.0;
+    const long long ntile = (n + PMM_ROWS - 1) / PMM_ROWS;
+    const int srow = w * 32 + l32;
+    if (h == 0) {
+        for (long long ti = 0; ti < ntile; ++ti) {
+            const f64x2* src = (const f64x2*)(xs + (ti * PMM_ROWS + srow) * XS);
+            f64x2 pre[XS / 2];
+#pragma unroll
+            for (int i = 0; i < XS / 2; ++i) pre[i] = src[i];
+            const bool in = ti * PMM_ROWS + srow < n;
+            unsigned char* tile = rows + 16 + ti * (16ll * SH::PIECES);
+            __bf16* xrow = (__bf16*)tile + srow * PITCH;
+            // (the conversion is the staging lanes' of prune_bound_mm32_kernel<DPAD, false>, statement for statement: as a
+            // shared function it changed that kernel's code; tests/test_gpu_prune_rows.py holds the two to the same bits)
+            float pe[DPAD + 2];                          // P's entries
+            double n2 = 0.0, b2 = 0.0;
+#pragma unroll
+            for (int d = 0; d < DPAD; ++d) {
+                const double x = (d & 1) ? pre[d >> 1].y : pre[d >> 1].x;
+                const double df = x - cen[d];
+                b2 = fma(df, df, b2);
+                const float bf = in ? (float)(df * kappa) : 0.0f;
+                n2 = fma((double)bf, (double)bf, n2);
+                pe[d + 2] = 2.0f * bf;
+            }
+            if (in) { bm2 = fmax(bm2, b2); sal += fabs(pre[DPAD / 2].x); }
+            pe[0] = -(float)n2;
+            pe[1] = 1.0f;
+            pmm_store_row<DPAD>(xrow, pe, std::make_integer_sequence<int, 2 * SH::NI>{});
+            ((float*)(tile + 16 * SH::XPIECES))[srow] = in ? (float)pre[DPAD / 2].x : 0.0f;
+            *(bf16x8*)(xrow + 16 * SH::NI) = bf16x8{(__bf16)0.0f, (__bf16)0.0f, (__bf16)0.0f, (__bf16)0.0f,
+                                                    (__bf16)0.0f, (__bf16)0.0f, (__bf16)0.0f, (__bf16)0.0f};      // the pad
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) { bm2 = fmax(bm2, __shfl_xor(bm2, o)); sal += __shfl_xor(sal, o); }
+    if (lane == 0) { wmax[w] = bm2; wsal[w] = sal; }
+    __syncthreads();
+    if (tid == 0) {
+        sal = 0.0;
+#pragma unroll
+        for (int i = 0; i < PR_THREADS / 64; ++i) { bm2 = fmax(bm2, wmax[i]); sal += wsal[i]; }
+        ((double*)rows)[0] = bm2;
+        ((double*)rows)[1] = sal;
+    }
+}
+
+// PRE: the training rows come pre-split (PruneArgs::prune_rows, pmm_pack_rows_kernel): staging is a copy of the next
+// tile's image into the other of two LDS buffers, one barrier per tile, and bm2 and sal come from the stream's header.
+template <int DPAD, bool PRE = false>
 __global__ __launch_bounds__(PR_THREADS, PMM_G <= 4 ? 2 : 1) void prune_bound_mm32_kernel(PruneArgs a) {
     using SH = PmmShape<DPAD>;
     constexpr int XS = DPAD + 2;                         // packed stream row: scaled x | alpha | 0
     constexpr int K = SH::K, NI = SH::NI, PITCH = SH::PITCH, G = PMM_G;
     static_assert(PMM_G % 2 == 0 && PMM_ROWS == 32 * (PR_THREADS / 64), "one 32-row tile staged per wavefront");
     const double kappa = PR32_KAPPA;                     // sqrt(log2(e))
-    __shared__ __attribute__((aligned(16))) __bf16 xt[PMM_ROWS * PITCH];
-    __shared__ __attribute__((aligned(16))) float at[PMM_ROWS];
+    static_assert(SH::XPIECES * 8 == PMM_ROWS * PITCH && SH::APIECES * 4 == PMM_ROWS, "the stream's tile is the LDS image");
+    constexpr int NB = PRE ? 2 : 1;                      // LDS buffers
+    __shared__ __attribute__((aligned(16))) __bf16 xt[NB * PMM_ROWS * PITCH];
+    __shared__ __attribute__((aligned(16))) float at[NB * PMM_ROWS];
     __shared__ double wmax[PR_THREADS / 64], wsal[PR_THREADS / 64];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, h = lane >> 5, l32 = lane & 31;
     const long long blk0 = ((long long)blockIdx.x * (PR_THREADS / 64) + w) * (G / 2);
@@ -222,47 +292,17 @@ __global__ __launch_bounds__(PR_THREADS, PMM_G <= 4 ? 2 : 1) void prune_bound_mm
 #pragma unroll
     for (int g = 0; g < G; ++g) { accm[g] = 0.0; accs[g] = 0.0; }
     const long long ntile = (a.n + PMM_ROWS - 1) / PMM_ROWS;
-    // staging: lane l32 of half 0 of wavefront w converts row 32 w + l32 of the tile
-    const bool stager = h == 0;
-    const int srow = w * 32 + l32;
-    f64x2 pre[XS / 2];
-    auto fetch = [&](long long ti) {                     // (rows < ntile * PMM_ROWS <= npad: inside the packed stream)
-        const f64x2* src = (const f64x2*)(a.xs + (ti * PMM_ROWS + srow) * XS);
-#pragma unroll
-        for (int i = 0; i < XS / 2; ++i) pre[i] = stager ? src[i] : f64x2{0.0, 0.0};
-    };
-    fetch(0);
-    for (long long ti = 0; ti < ntile; ++ti) {
-        if (stager) {
-            const bool in = ti * PMM_ROWS + srow < a.n;  // rows of the padding: operands 0, alpha 0, no part in B
-            float pe[K];                                 // P's entries
-            double n2 = 0.0, b2 = 0.0;
-#pragma unroll
-            for (int d = 0; d < DPAD; ++d) {
-                const double x = (d & 1) ? pre[d >> 1].y : pre[d >> 1].x;
-                const double df = x - cen[d];
-                b2 = fma(df, df, b2);
-                const float bf = in ? (float)(df * kappa) : 0.0f;
-                n2 = fma((double)bf, (double)bf, n2);
-                pe[d + 2] = 2.0f * bf;
-            }
-            if (in) { bm2 = fmax(bm2, b2); sal += fabs(pre[DPAD / 2].x); }
-            pe[0] = -(float)n2;
-            pe[1] = 1.0f;
-            pmm_store_row<DPAD>(xt + srow * PITCH, pe, std::make_integer_sequence<int, 2 * NI>{});
-            at[srow] = in ? (float)pre[DPAD / 2].x : 0.0f;
-        }
-        __syncthreads();
-        if (ti + 1 < ntile) fetch(ti + 1);
+    // one staged tile: its PMM_ROWS / 32 matrix tiles against the G candidate groups
+    auto consume = [&](int xo, int ao) {          // (element offsets of the LDS buffer in xt and at)
 #pragma unroll 1
         for (int rt = 0; rt < PMM_ROWS / 32; ++rt) {
-            const __bf16* xr = xt + (rt * 32 + l32) * PITCH + 8 * h;
+            const __bf16* xr = xt + xo + (rt * 32 + l32) * PITCH + 8 * h;
             bf16x8 pop[NI];                              // the training rows' side, this lane half's k slots
 #pragma unroll
             for (int t = 0; t < NI; ++t) pop[t] = *(const bf16x8*)(xr + 16 * t);
             float al[16];                                // alpha of accumulator r's row: (r & 3) + 8 (r >> 2) + 4 h
 #pragma unroll
-            for (int q = 0; q < 4; ++q) *(f32x4*)(al + 4 * q) = *(const f32x4*)(at + rt * 32 + 8 * q + 4 * h);
+            for (int q = 0; q < 4; ++q) *(f32x4*)(al + 4 * q) = *(const f32x4*)(at + ao + rt * 32 + 8 * q + 4 * h);
             auto product = [&](int g) {
                 f32x16 c = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
 #pragma unroll
@@ -290,16 +330,90 @@ __global__ __launch_bounds__(PR_THREADS, PMM_G <= 4 ? 2 : 1) void prune_bound_mm
                 cur = nxt;
             }
         }
-        __syncthreads();                                 // the tile has been consumed
-    }
-    // B = max |x - c| and sum |alpha| over the training rows: the stagers' maxima and sums, over the workgroup (every
-    // workgroup adds the same rows in the same order: one value of sum |alpha| per call)
-    for (int o = 32; o > 0; o >>= 1) { bm2 = fmax(bm2, __shfl_xor(bm2, o)); sal += __shfl_xor(sal, o); }
-    if (lane == 0) { wmax[w] = bm2; wsal[w] = sal; }
-    __syncthreads();
-    sal = 0.0;
+    };
+    if constexpr (PRE) {
+        // every thread copies pieces tid, tid + 256, .. of a tile (the last round is partial: a clamped load, a guarded
+        // store); loaded before the tile in LDS is consumed, written behind it.  Past the last tile the last one is copied
+        // again, into the buffer nobody reads any more: no branch around the loads.
+        typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+        constexpr int NPC = SH::PIECES, NL = (NPC + PR_THREADS - 1) / PR_THREADS;
+        const u32x4* img = (const u32x4*)((const unsigned char*)a.prune_rows + 16);
+        u32x4 pre[NL];
+        auto fetch = [&](long long ti) {
+            const u32x4* src = img + ti * NPC;
 #pragma unroll
-    for (int i = 0; i < PR_THREADS / 64; ++i) { bm2 = fmax(bm2, wmax[i]); sal += wsal[i]; }
+            for (int j = 0; j < NL; ++j) {
+                const int e = tid + j * PR_THREADS;
+                pre[j] = src[e < NPC ? e : NPC - 1];
+            }
+        };
+        auto put = [&](int b) {
+            u32x4* xd = (u32x4*)(xt + b * PMM_ROWS * PITCH);
+            u32x4* ad = (u32x4*)(at + b * PMM_ROWS);
+#pragma unroll
+            for (int j = 0; j < NL; ++j) {
+                const int e = tid + j * PR_THREADS;
+                if ((j + 1) * PR_THREADS <= SH::XPIECES || e < SH::XPIECES) xd[e] = pre[j];
+                else if (e < NPC) ad[e - SH::XPIECES] = pre[j];
+            }
+        };
+        fetch(0);
+        put(0);
+        __syncthreads();
+        for (long long ti = 0; ti < ntile; ++ti) {
+            const int b = (int)(ti & 1);
+            fetch(ti + 1 < ntile ? ti + 1 : ntile - 1);
+            consume(b * PMM_ROWS * PITCH, b * PMM_ROWS);
+            put(b ^ 1);
+            __syncthreads();                             // the next tile is in; this one has been consumed
+        }
+        bm2 = ((const double*)a.prune_rows)[0];
+        sal = ((const double*)a.prune_rows)[1];
+    } else {
+        // staging: lane l32 of half 0 of wavefront w converts row 32 w + l32 of the tile
+        const bool stager = h == 0;
+        const int srow = w * 32 + l32;
+        f64x2 pre[XS / 2];
+        auto fetch = [&](long long ti) {                 // (rows < ntile * PMM_ROWS <= npad: inside the packed stream)
+            const f64x2* src = (const f64x2*)(a.xs + (ti * PMM_ROWS + srow) * XS);
+#pragma unroll
+            for (int i = 0; i < XS / 2; ++i) pre[i] = stager ? src[i] : f64x2{0.0, 0.0};
+        };
+        fetch(0);
+        for (long long ti = 0; ti < ntile; ++ti) {
+            if (stager) {
+                const bool in = ti * PMM_ROWS + srow < a.n;  // rows of the padding: operands 0, alpha 0, no part in B
+                float pe[K];                             // P's entries
+                double n2 = 0.0, b2 = 0.0;
+#pragma unroll
+                for (int d = 0; d < DPAD; ++d) {
+                    const double x = (d & 1) ? pre[d >> 1].y : pre[d >> 1].x;
+                    const double df = x - cen[d];
+                    b2 = fma(df, df, b2);
+                    const float bf = in ? (float)(df * kappa) : 0.0f;
+                    n2 = fma((double)bf, (double)bf, n2);
+                    pe[d + 2] = 2.0f * bf;
+                }
+                if (in) { bm2 = fmax(bm2, b2); sal += fabs(pre[DPAD / 2].x); }
+                pe[0] = -(float)n2;
+                pe[1] = 1.0f;
+                pmm_store_row<DPAD>(xt + srow * PITCH, pe, std::make_integer_sequence<int, 2 * NI>{});
+                at[srow] = in ? (float)pre[DPAD / 2].x : 0.0f;
+            }
+            __syncthreads();
+            if (ti + 1 < ntile) fetch(ti + 1);
+            consume(0, 0);
+            __syncthreads();                             // the tile has been consumed
+        }
+        // B = max |x - c| and sum |alpha| over the training rows: the stagers' maxima and sums, over the workgroup (every
+        // workgroup adds the same rows in the same order: one value of sum |alpha| per call)
+        for (int o = 32; o > 0; o >>= 1) { bm2 = fmax(bm2, __shfl_xor(bm2, o)); sal += __shfl_xor(sal, o); }
+        if (lane == 0) { wmax[w] = bm2; wsal[w] = sal; }
+        __syncthreads();
+        sal = 0.0;
+#pragma unroll
+        for (int i = 0; i < PR_THREADS / 64; ++i) { bm2 = fmax(bm2, wmax[i]); sal += wsal[i]; }
+    }
     const double bn = sqrt(bm2);
     const double u32 = 0x1p-24, eps = 0x1p-53;
     const double sa = sal * (1.0 + 0x1p-16);

@@ -1217,6 +1217,9 @@ struct PruneArgs {
     // coarse stage: per block the smallest b WITHOUT the slack (NULL: not wanted) -- where the minimum probably lies,
     // which is what the seeds are chosen by; a seed need not come from a valid bound
     double* est;
+    // coarse stage up to Dpad = 8: the training rows split into bf16 parts once per fit (apgp_pack_prune_rows), or NULL:
+    // every workgroup splits them itself
+    const void* prune_rows;
 };
 
 // LIST: the refine stage of a call that bounded coarsely first (prune_bound32_kernel): only the blocks of a device list,
@@ -1776,19 +1779,21 @@ extern "C" int apgp_sweep_prune_select(const double* bmin, int64_t ncb, const in
     return 0;
 }
 
-static void pr_fill_args(PruneArgs& p, const SweepArgs& a, double* bmin, double* part_u, long long* part_i) {
+static void pr_fill_args(PruneArgs& p, const SweepArgs& a, double* bmin, double* part_u, long long* part_i,
+                         const void* prune_rows) {
     p.T = a.T; p.xs = a.xs; p.mask = a.mask; p.bmin = bmin; p.part_u = part_u; p.part_i = part_i;
     p.m = a.m; p.ncb = pr_ncb(a.m); p.n = a.n;
     p.kind = a.kind; p.mean = a.mean; p.zeta = a.zeta; p.ybest = a.ybest;
     apgp_fill_kernel(p, a);
     p.has_box = a.has_box;
     for (int d = 0; d < APGP_MAX_DIM; ++d) { p.lo[d] = a.lo[d]; p.hi[d] = a.hi[d]; }
-    p.blk_list = NULL; p.blk_count = NULL; p.est = NULL;
+    p.blk_list = NULL; p.blk_count = NULL; p.est = NULL; p.prune_rows = prune_rows;
 }
 
 // the bound pass over all blocks: coarse (fp32 kernel values; pure squared-exponential kernels only) or fp64.  Coarse up to
 // Dpad = 8: the exponents on the matrix cores (prune_mm32.h), and the vector-ALU kernel behind it for the blocks whose
 // gate failed there -- as a rule none, and its workgroups leave at once.  Dpad 16 and 32 keep the vector-ALU kernel.
+// With PruneArgs::prune_rows the matrix-core kernel copies the pre-split rows instead of splitting them (same bits).
 template <int DPAD>
 static void launch_bound(const PruneArgs& p, hipStream_t s, bool coarse) {
     const long long per_wg = (PR_THREADS / 64) * (coarse ? pr32_cpt(DPAD) : PR_CPT);
@@ -1796,8 +1801,11 @@ static void launch_bound(const PruneArgs& p, hipStream_t s, bool coarse) {
     if (coarse) {
         if constexpr (DPAD <= 8) {
             const long long mm_wg = (PR_THREADS / 64) * (PMM_G / 2);
-            hipLaunchKernelGGL(prune_bound_mm32_kernel<DPAD>, dim3((unsigned)((p.ncb + mm_wg - 1) / mm_wg)), dim3(PR_THREADS),
-                               0, s, p);
+            const dim3 mm_grid((unsigned)((p.ncb + mm_wg - 1) / mm_wg));
+            if (p.prune_rows)
+                hipLaunchKernelGGL((prune_bound_mm32_kernel<DPAD, true>), mm_grid, dim3(PR_THREADS), 0, s, p);
+            else
+                hipLaunchKernelGGL((prune_bound_mm32_kernel<DPAD, false>), mm_grid, dim3(PR_THREADS), 0, s, p);
             hipLaunchKernelGGL((prune_bound32_kernel<DPAD, true>), grid, dim3(PR_THREADS), 0, s, p);
         } else {
             hipLaunchKernelGGL((prune_bound32_kernel<DPAD, false>), grid, dim3(PR_THREADS), 0, s, p);
@@ -1813,7 +1821,7 @@ static void launch_bound(const PruneArgs& p, hipStream_t s, bool coarse) {
 // exceeds the spread of the bounds (an ill-conditioned fit: sum |alpha| is huge against the spread of mu) the bounds
 // themselves order the blocks by little more than |t - c|, the seeds would be arbitrary and tau prune nothing.
 template <int DPAD>
-static int launch_pruned(const SweepArgs& a, hipStream_t s, bool solve, void* part) {
+static int launch_pruned(const SweepArgs& a, hipStream_t s, bool solve, void* part, const void* prune_rows) {
     const int rc = s2_prepare_device<DPAD>();
     if (rc != 0) return rc;
     const long long ncb = pr_ncb(a.m);
@@ -1823,7 +1831,7 @@ static int launch_pruned(const SweepArgs& a, hipStream_t s, bool solve, void* pa
     long long* counts = seeds + PR_SEED;
     const bool coarse = a.lin_coef == 0.0;
     PruneArgs p;
-    pr_fill_args(p, a, bmin, a.part_u, a.part_i);
+    pr_fill_args(p, a, bmin, a.part_u, a.part_i, prune_rows);
     if (coarse) p.est = (double*)(counts + 8);
     launch_bound<DPAD>(p, s, coarse);
     hipLaunchKernelGGL(prune_seed_kernel, dim3(1), dim3(1024), 0, s, coarse ? (const double*)p.est : (const double*)bmin, ncb,
@@ -1858,7 +1866,7 @@ static int acquire_impl(bool solve, const double* T, int64_t m, int64_t idx_offs
                         const double* xs, int64_t n, const apgp_kernel_t* kern, double mean,
                         int32_t kind, const double* lo, const double* hi, const uint8_t* mask,
                         double zeta, double ybest, double* mu, double* var, double* u, void* part,
-                        apgp_best_t* best, void* stream) {
+                        apgp_best_t* best, const void* prune_rows, void* stream) {
     APGP_CHECK_ARG(T && packed_linv && xs && kern, "null pointer");
     APGP_CHECK_ARG(m >= 1 && m <= APGP_MAX_M && n >= 1 && n <= APGP_MAX_N, "m >= 1 and n >= 1 required");
     APGP_CHECK_ARG(kind >= APGP_UTIL_AGP && kind <= APGP_UTIL_NONE, "unknown utility kind");
@@ -1902,7 +1910,8 @@ static int acquire_impl(bool solve, const double* T, int64_t m, int64_t idx_offs
     const bool prune = pr_mode > 0 && kind != APGP_UTIL_NONE && !mu && !var && !u && part &&
                        m >= (pr_mode == 1 ? pr_min_m(n) : (int64_t)pr_mode);
     const int rc = apgp_by_dpad(kc.dpad, [&](auto dp) {
-        return prune ? launch_pruned<decltype(dp)::value>(a, s, solve, part) : launch_sweep<decltype(dp)::value>(a, s, solve);
+        return prune ? launch_pruned<decltype(dp)::value>(a, s, solve, part, prune_rows)
+                     : launch_sweep<decltype(dp)::value>(a, s, solve);
     });
     if (rc != 0) return rc;
     if (kind != APGP_UTIL_NONE)
@@ -1917,32 +1926,95 @@ extern "C" int apgp_acquire(const double* T, int64_t m, int64_t idx_offset, cons
                             double zeta, double ybest, double* mu, double* var, double* u, void* part,
                             apgp_best_t* best, void* stream) {
     return acquire_impl(false, T, m, idx_offset, packed_linv, xs, n, kern, mean, kind, lo, hi, mask, zeta, ybest,
-                        mu, var, u, part, best, stream);
+                        mu, var, u, part, best, NULL, stream);
+}
+
+// apgp_acquire with the fit's pre-split rows of the coarse bound (apgp_pack_prune_rows; NULL: apgp_acquire itself)
+extern "C" int apgp_acquire_rows(const double* T, int64_t m, int64_t idx_offset, const double* packed_linv,
+                                 const double* xs, int64_t n, const apgp_kernel_t* kern, double mean,
+                                 int32_t kind, const double* lo, const double* hi, const uint8_t* mask,
+                                 double zeta, double ybest, double* mu, double* var, double* u, void* part,
+                                 apgp_best_t* best, const void* prune_rows, void* stream) {
+    return acquire_impl(false, T, m, idx_offset, packed_linv, xs, n, kern, mean, kind, lo, hi, mask, zeta, ybest,
+                        mu, var, u, part, best, prune_rows, stream);
 }
 
 // Test hooks of the pruned arg-min (include/apgp.h): one bound pass over all blocks into the caller's buffer, and the
 // seed step alone.
-extern "C" int apgp_prune_bounds(const double* T, int64_t m, const double* xs, int64_t n, const apgp_kernel_t* kern,
-                                 double mean, int32_t kind, const double* lo, const double* hi, const uint8_t* mask,
-                                 double zeta, double ybest, int coarse, double* bmin_out, void* stream) {
-    APGP_CHECK_ARG(T && xs && kern && bmin_out, "null pointer");
-    APGP_CHECK_ARG(m >= 1 && m <= APGP_MAX_M && n >= 1 && n <= APGP_MAX_N, "m >= 1 and n >= 1 required");
-    APGP_CHECK_ARG(kind >= APGP_UTIL_AGP && kind < APGP_UTIL_NONE, "unknown utility kind");
-    APGP_CHECK_ARG((lo == NULL) == (hi == NULL), "lo and hi must be given together");
+// The coarse bound's training rows split into bf16 parts, once per fit (prune_mm32.h: pmm_pack_rows_kernel).  Doubles:
+// the 16-byte header and per PMM_ROWS-row tile the LDS image and the alphas; 0 where the coarse bound does not use it.
+extern "C" int64_t apgp_prune_rows_len(int64_t n, int32_t ndim) {
+    if (n < 0 || n > APGP_MAX_N || ndim < 1 || ndim > APGP_MAX_DIM) return -1;
+    const int dpad = apgp_dpad(ndim);
+    if (n == 0 || dpad > 8) return 0;
+    const int64_t ntile = (n + PMM_ROWS - 1) / PMM_ROWS;
+    return apgp_by_dpad(dpad, [&](auto dp) -> int64_t {
+        if constexpr (decltype(dp)::value <= 8) return 2 + ntile * 2 * PmmShape<decltype(dp)::value>::PIECES;
+        else return 0;
+    });
+}
+
+extern "C" int apgp_pack_prune_rows(const double* xs, int64_t n, const apgp_kernel_t* kern, void* rows, void* stream) {
+    APGP_CHECK_ARG(xs && kern && rows, "null pointer");
+    APGP_CHECK_ARG(n >= 1 && n <= APGP_MAX_N, "n >= 1 required");
     KernConst kc;
     APGP_CHECK_ARG(apgp_make_kernconst(kern, &kc) == 0, "kernel parameters");
-    APGP_CHECK_ARG(!coarse || kc.lin_coef == 0.0, "the coarse bound takes pure squared-exponential kernels only");
+    APGP_CHECK_ARG(kc.dpad <= 8, "no pre-split rows beyond 8 dimensions (apgp_prune_rows_len is 0)");
+    apgp_by_dpad(kc.dpad, [&](auto dp) {
+        if constexpr (decltype(dp)::value <= 8)
+            hipLaunchKernelGGL(pmm_pack_rows_kernel<decltype(dp)::value>, dim3(1), dim3(PR_THREADS), 0, (hipStream_t)stream,
+                               xs, (long long)n, (unsigned char*)rows);
+    });
+    APGP_CHECK_LAUNCH();
+    return 0;
+}
+
+// (who: the entry point's name, which the refusals of apgp_prune_bounds have always carried)
+static int prune_bounds_impl(const char* who, const double* T, int64_t m, const double* xs, int64_t n,
+                             const apgp_kernel_t* kern, double mean, int32_t kind, const double* lo, const double* hi,
+                             const uint8_t* mask, double zeta, double ybest, int coarse, double* bmin_out,
+                             const void* prune_rows, void* stream) {
+#define PB_CHECK_ARG(cond, msg)                                     \
+    do {                                                            \
+        if (!(cond)) {                                              \
+            apgp_set_error("%s: bad argument: %s", who, msg);       \
+            return -1;                                              \
+        }                                                           \
+    } while (0)
+    PB_CHECK_ARG(T && xs && kern && bmin_out, "null pointer");
+    PB_CHECK_ARG(m >= 1 && m <= APGP_MAX_M && n >= 1 && n <= APGP_MAX_N, "m >= 1 and n >= 1 required");
+    PB_CHECK_ARG(kind >= APGP_UTIL_AGP && kind < APGP_UTIL_NONE, "unknown utility kind");
+    PB_CHECK_ARG((lo == NULL) == (hi == NULL), "lo and hi must be given together");
+    KernConst kc;
+    PB_CHECK_ARG(apgp_make_kernconst(kern, &kc) == 0, "kernel parameters");
+    PB_CHECK_ARG(!coarse || kc.lin_coef == 0.0, "the coarse bound takes pure squared-exponential kernels only");
+#undef PB_CHECK_ARG
     PruneArgs p;
     p.T = T; p.xs = xs; p.mask = mask; p.bmin = bmin_out; p.part_u = NULL; p.part_i = NULL;
     p.m = m; p.ncb = pr_ncb(m); p.n = n;
     p.kind = kind; p.mean = mean; p.zeta = zeta; p.ybest = ybest;
     apgp_fill_kernel(p, kc);
     apgp_fill_box(p, kc.ndim, lo, hi);
-    p.blk_list = NULL; p.blk_count = NULL; p.est = NULL;
+    p.blk_list = NULL; p.blk_count = NULL; p.est = NULL; p.prune_rows = prune_rows;
     hipStream_t s = (hipStream_t)stream;
     apgp_by_dpad(kc.dpad, [&](auto dp) { launch_bound<decltype(dp)::value>(p, s, coarse != 0); });
     APGP_CHECK_LAUNCH();
     return 0;
+}
+
+extern "C" int apgp_prune_bounds(const double* T, int64_t m, const double* xs, int64_t n, const apgp_kernel_t* kern,
+                                 double mean, int32_t kind, const double* lo, const double* hi, const uint8_t* mask,
+                                 double zeta, double ybest, int coarse, double* bmin_out, void* stream) {
+    return prune_bounds_impl(__func__, T, m, xs, n, kern, mean, kind, lo, hi, mask, zeta, ybest, coarse, bmin_out, NULL,
+                             stream);
+}
+
+extern "C" int apgp_prune_bounds_rows(const double* T, int64_t m, const double* xs, int64_t n, const apgp_kernel_t* kern,
+                                      double mean, int32_t kind, const double* lo, const double* hi, const uint8_t* mask,
+                                      double zeta, double ybest, int coarse, double* bmin_out, const void* prune_rows,
+                                      void* stream) {
+    return prune_bounds_impl(__func__, T, m, xs, n, kern, mean, kind, lo, hi, mask, zeta, ybest, coarse, bmin_out,
+                             prune_rows, stream);
 }
 
 extern "C" int apgp_sweep_prune_seeds(const double* bmin, int64_t ncb, int64_t* seeds, int64_t* counts, void* stream) {
@@ -1970,7 +2042,16 @@ extern "C" int apgp_acquire_solve(const double* T, int64_t m, int64_t idx_offset
                                   double zeta, double ybest, double* mu, double* var, double* u, void* part,
                                   apgp_best_t* best, void* stream) {
     return acquire_impl(true, T, m, idx_offset, packed_lsolve, xs, n, kern, mean, kind, lo, hi, mask, zeta, ybest,
-                        mu, var, u, part, best, stream);
+                        mu, var, u, part, best, NULL, stream);
+}
+
+extern "C" int apgp_acquire_solve_rows(const double* T, int64_t m, int64_t idx_offset, const double* packed_lsolve,
+                                       const double* xs, int64_t n, const apgp_kernel_t* kern, double mean,
+                                       int32_t kind, const double* lo, const double* hi, const uint8_t* mask,
+                                       double zeta, double ybest, double* mu, double* var, double* u, void* part,
+                                       apgp_best_t* best, const void* prune_rows, void* stream) {
+    return acquire_impl(true, T, m, idx_offset, packed_lsolve, xs, n, kern, mean, kind, lo, hi, mask, zeta, ybest,
+                        mu, var, u, part, best, prune_rows, stream);
 }
 
 // ---------------------------------------------------------------------------

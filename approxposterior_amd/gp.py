@@ -519,6 +519,7 @@ class GP(GeorgeExtras):
         self._packed_solve = None  # packed tiles of the substitution form (apgp_pack_lsolve)
         self._work = None         # trtri work (dense L^-1 in first panel)
         self._xs = None           # packed training stream (depends on alpha)
+        self._prune_rows = None   # its rows split for the coarse prune bound (apgp_pack_prune_rows); lives and dies with _xs
         self._xs_key = None
         for key in ("nll", "one", "mean", "pgrad"):
             self._replays.pop(key, None)
@@ -775,6 +776,7 @@ class GP(GeorgeExtras):
             self._kernel_struct(ks)
             # (as _reset_device_state: whatever was derived from the previous factor is stale)
             self._alpha = self._packed = self._packed_solve = self._work = self._xs = self._xs_key = None
+            self._prune_rows = None
             self._computed = False
             r.args[4] = float(self.mean.value)
             try:
@@ -949,7 +951,7 @@ class GP(GeorgeExtras):
                     self._ztz_host = self._trsv(st, self._y_d, float(self.mean.value), 0, self._z, ztz, "forward",
                                                 retry_ss=ztz)
                 self._alpha = None
-                self._xs = None
+                self._xs = self._prune_rows = None
                 self._alpha_y = np.array(y, copy=True)
                 self._alpha_mean = self.mean.value
             if need_alpha and self._alpha is None:
@@ -961,7 +963,7 @@ class GP(GeorgeExtras):
                                "apgp_winv_apply(backward)")
                 else:
                     self._trsv(st, self._z, 0.0, 1, self._alpha, torch.empty(1, dtype=torch.float64, device=dev), "backward")
-                self._xs = None
+                self._xs = self._prune_rows = None
         return self._ztz_host
 
     def log_likelihood(self, y, quiet=False):
@@ -1166,6 +1168,13 @@ class GP(GeorgeExtras):
             _lib.check(lib.apgp_pack_train(self._x_d.data_ptr(), self._alpha.data_ptr(), n,
                                            ctypes.byref(ks), self._xs.data_ptr(), st),
                        "apgp_pack_train")
+            # the rows split into bf16 parts for the coarse bound of the pruned arg-min: once per fit, not per call
+            rows_len = int(lib.apgp_prune_rows_len(n, ks.ndim))
+            self._prune_rows = None
+            if rows_len > 0:
+                self._prune_rows = torch.empty(rows_len, dtype=torch.float64, device=dev)
+                _lib.check(lib.apgp_pack_prune_rows(self._xs.data_ptr(), n, ctypes.byref(ks),
+                                                    self._prune_rows.data_ptr(), st), "apgp_pack_prune_rows")
 
     # -- predict (george GP.predict) ----------------------------
     def predict(self, y, t, return_cov=True, return_var=False, cache=True, **kwargs):
@@ -1396,15 +1405,16 @@ class GP(GeorgeExtras):
                 e0 = torch.cuda.Event(enable_timing=True)
                 e0.record()
             args = (self._xs.data_ptr(), n, ctypes.byref(ks), float(self.mean.value), kind_id, lo, hi, _ptr(mask_d),
-                    float(zeta), float(np.max(y)), _ptr(mu), _ptr(var), _ptr(u), part.data_ptr(), best.data_ptr(), st)
+                    float(zeta), float(np.max(y)), _ptr(mu), _ptr(var), _ptr(u), part.data_ptr(), best.data_ptr(),
+                    _ptr(self._prune_rows), st)
             prune_was = None if self.sweep_prune is None else lib.apgp_set_sweep_prune(int(self.sweep_prune))
             try:
                 if use_solve:
-                    _lib.check(lib.apgp_acquire_solve(T.data_ptr(), m, int(idx_offset), self._packed_solve.data_ptr(),
-                                                      *args), "apgp_acquire_solve")
+                    _lib.check(lib.apgp_acquire_solve_rows(T.data_ptr(), m, int(idx_offset),
+                                                           self._packed_solve.data_ptr(), *args), "apgp_acquire_solve_rows")
                 else:
-                    _lib.check(lib.apgp_acquire(T.data_ptr(), m, int(idx_offset), self._packed.data_ptr(), *args),
-                               "apgp_acquire")
+                    _lib.check(lib.apgp_acquire_rows(T.data_ptr(), m, int(idx_offset), self._packed.data_ptr(), *args),
+                               "apgp_acquire_rows")
             finally:
                 if prune_was is not None:
                     lib.apgp_set_sweep_prune(prune_was)
@@ -1473,10 +1483,11 @@ class GP(GeorgeExtras):
         with self._on(torch, dev):
             self._ensure_xs(y)
             bmin = torch.empty((m + 63) // 64, dtype=torch.float64, device=dev)
-            _lib.check(lib.apgp_prune_bounds(T.data_ptr(), m, self._xs.data_ptr(), len(self._x), ctypes.byref(ks),
-                                             float(self.mean.value), kind_id, lo, hi, _ptr(mask_d), float(zeta),
-                                             float(np.max(y)), int(bool(coarse)), bmin.data_ptr(), self._stream(torch)),
-                       "apgp_prune_bounds")
+            _lib.check(lib.apgp_prune_bounds_rows(T.data_ptr(), m, self._xs.data_ptr(), len(self._x), ctypes.byref(ks),
+                                                  float(self.mean.value), kind_id, lo, hi, _ptr(mask_d), float(zeta),
+                                                  float(np.max(y)), int(bool(coarse)), bmin.data_ptr(),
+                                                  _ptr(self._prune_rows), self._stream(torch)),
+                       "apgp_prune_bounds_rows")
         return bmin.cpu().numpy()
 
     def nelder_mead_search(self, y, starts, kind, bounds=None, zeta=0.01, options=None, trace=False):

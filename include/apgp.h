@@ -382,6 +382,40 @@ int apgp_prune_bounds(const double* T, int64_t m, const double* xs, int64_t n,
                       double zeta, double ybest, int coarse, double* bmin_out, void* stream);
 int apgp_sweep_prune_seeds(const double* bmin, int64_t ncb, int64_t* seeds, int64_t* counts, void* stream);
 
+/* The coarse bound's training rows, split once per fit.  Up to 8 dimensions the single-precision stage forms its
+ * exponents on the bf16 matrix cores from every training row split into three bf16 parts; without the stream below
+ * every workgroup of every call splits all rows itself.  The split depends on xs (apgp_pack_train) alone, not on the
+ * candidates, the utility, the mean or the amplitude: pack it once per fit, behind apgp_pack_train.
+ * apgp_prune_rows_len: doubles in the stream (16-byte aligned device memory); 0 beyond 8 dimensions, where the coarse
+ * bound does not use it (pass NULL then).  Layout: a 16-byte header -- max |x - c|^2 over the rows (c = the first row)
+ * and sum |alpha|, both fp64 with the bits the bound kernel reduces them to itself -- and per 128-row tile the kernel's
+ * image of the rows (bf16) followed by the tile's 128 fp32 alphas.
+ * apgp_pack_prune_rows: one launch; rows receives the stream.
+ * apgp_acquire_rows, apgp_acquire_solve_rows, apgp_prune_bounds_rows: their namesakes with the stream as one more
+ * argument (prune_rows; NULL: the namesake itself).  Results are the namesakes', bit for bit.
+ * Added in ABI 8 without changing anything before it: APGP_ABI_VERSION stays 8.             */
+int64_t apgp_prune_rows_len(int64_t n, int32_t ndim);
+int apgp_pack_prune_rows(const double* xs, int64_t n, const apgp_kernel_t* kern /*host*/, void* rows, void* stream);
+int apgp_acquire_rows(const double* T, int64_t m, int64_t idx_offset,
+                      const double* packed_linv, const double* xs, int64_t n,
+                      const apgp_kernel_t* kern /*host*/, double mean, int32_t kind,
+                      const double* lo /*host*/, const double* hi /*host*/,
+                      const uint8_t* mask, double zeta, double ybest,
+                      double* mu, double* var, double* u,
+                      void* part, apgp_best_t* best, const void* prune_rows, void* stream);
+int apgp_acquire_solve_rows(const double* T, int64_t m, int64_t idx_offset,
+                            const double* packed_lsolve, const double* xs, int64_t n,
+                            const apgp_kernel_t* kern /*host*/, double mean, int32_t kind,
+                            const double* lo /*host*/, const double* hi /*host*/,
+                            const uint8_t* mask, double zeta, double ybest,
+                            double* mu, double* var, double* u,
+                            void* part, apgp_best_t* best, const void* prune_rows, void* stream);
+int apgp_prune_bounds_rows(const double* T, int64_t m, const double* xs, int64_t n,
+                           const apgp_kernel_t* kern /*host*/, double mean, int32_t kind,
+                           const double* lo /*host*/, const double* hi /*host*/, const uint8_t* mask,
+                           double zeta, double ybest, int coarse, double* bmin_out, const void* prune_rows,
+                           void* stream);
+
 /* ---- fantasy update of a sweep (batch design points, kriging believer) -----------
  * After a sweep over T (mu, var = v_0 written) and picks x_1 .. x_j, conditioning the GP on
  * x_j = T[pick_row] observed at y = mu(x_j) (hyper-parameters unchanged) leaves mu as it is
