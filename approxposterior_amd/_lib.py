@@ -25,6 +25,8 @@ NM_STEPS = {1: "reflect", 2: "expand", 3: "reflect_exp", 4: "contract_out", 5: "
             6: "shrink_out", 7: "shrink_in", 8: "maxfev"}
 GMM_EM, GMM_SCORE, GMM_KMEANS = 0, 1, 2
 GMM_MAX_COMP = 16
+IMP_BLOCK = 256        # APGP_IMP_BLOCK: candidates per workgroup pass of apgp_importance_pass
+IMP_MAX_BLOCKS = 2048  # APGP_IMP_MAX_BLOCKS: beyond IMP_BLOCK * IMP_MAX_BLOCKS rows a workgroup takes further tiles
 
 
 class ApgpError(RuntimeError):
@@ -158,6 +160,12 @@ SIGNATURES = {
     "apgp_gmm_params_len": (_I64, [_I32, _I32]),
     "apgp_gmm_stats_len": (_I64, [_I32, _I32]),
     "apgp_gmm_pass": (ctypes.c_int, [_P, _I64, _I32, _I32, _P, _I32, _P, _P, _P, _P]),
+    "apgp_mix_params_len": (_I64, [_I32, _I32]),
+    "apgp_mix_candidates": (ctypes.c_int, [_P, _P, _I64, _I32, _I32, _P, ctypes.c_uint64, _I64, _P]),
+    "apgp_importance_stats_len": (_I64, [_I32]),
+    "apgp_importance_work_len": (_I64, [_I64]),
+    "apgp_importance_pass": (ctypes.c_int, [_P, _I64, _P, _P, _I64, _KP, _F64, ctypes.POINTER(_F64), ctypes.POINTER(_F64),
+                                            _P, _P, _P, _P, _P]),
     "apgp_autocorr_work_len": (_I64, [_I64, _I64, _I32]),
     "apgp_autocorr_block": (ctypes.c_int, [_P, _I64, _I64, _I32, _I64, _I64, _I64, _I64, _I32, _P, _P, _P]),
 }

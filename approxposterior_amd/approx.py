@@ -55,6 +55,7 @@ import numpy as np
 from . import _lib
 from . import dist as apdist
 from . import gp as george
+from . import gmmUtils
 from . import gpUtils
 from . import mcmc as emcee   # drop-in for the ``emcee`` names used below
 from . import mcmcUtils
@@ -669,6 +670,7 @@ class ApproxPosterior(object):
             self._dumpChain(runName)
         iburn, ithin = mcmcUtils.estimateBurnin(self.sampler, estBurnin=estBurnin,
                                                 thinChains=thinChains, verbose=verbose)
+        self._chainCut = (iburn, ithin)     # (evidence(proposal="gmm") fits its proposal to the chain cut this way)
         return self.sampler, iburn, ithin
 
     def _hostSampler(self, samplerKwargs, args, kwargs, batched, seed=None):
@@ -703,6 +705,92 @@ class ApproxPosterior(object):
         blobs = sampler.get_blobs()
         out = (sampler.get_chain(), sampler.get_log_prob(), sampler._naccepted)
         return out if blobs is None else out + (blobs,)
+
+    # ------------------------------------------------------- evidence by importance sampling
+    def _mixtureProposal(self, proposal):
+        """(weights, means, covariances) of a mixture proposal: a tuple of the three, or an object with ``weights_``,
+        ``means_``, ``covariances_`` of ``covariance_type == "full"`` (sklearn's GaussianMixture, ``fitGMM``'s result)."""
+        if isinstance(proposal, (tuple, list)):
+            if len(proposal) != 3:
+                raise ValueError("a mixture proposal is the tuple (weights, means, covariances)")
+            return proposal
+        if all(hasattr(proposal, a) for a in ("weights_", "means_", "covariances_")):
+            if getattr(proposal, "covariance_type", "full") != "full":
+                raise ValueError("evidence: a mixture proposal needs covariance_type == 'full', not %r"
+                                 % (proposal.covariance_type,))
+            return proposal.weights_, proposal.means_, proposal.covariances_
+        raise ValueError("evidence: proposal must be 'prior', 'box', 'gmm', a (weights, means, covariances) tuple or a "
+                         "fitted full-covariance mixture, not %r" % (proposal,))
+
+    def evidence(self, nSamples=2 ** 20, proposal="prior", seed=None, chunk=2 ** 20, samples=None, maxComp=3,
+                 covScale=1.0):
+        """The model evidence and chain-free posterior moments of the surrogate by importance sampling on the device.
+        The GP models the unnormalised log-posterior (``y = lnlike + lnprior``), so ``Z = int exp(mu(t)) dt`` over the
+        prior's support is the evidence; with ``nSamples`` draws from a proposal ``q`` the weights ``exp(mu - ln q)``
+        give ``logZ`` with a standard error, the posterior mean and covariance -- an independent check on
+        :meth:`runMCMC`'s chain -- and an effective sample size that says when to distrust both.  Returns
+        :func:`utility.importanceSummary`'s dict (``logZ``, ``logZErr``, ``ess``, ``mean``, ``cov``, ``nInside``).
+
+        ``proposal``: ``"box"`` -- uniform on ``self.bounds`` (``GP.box_candidates``), ``ln q = -sum log(hi - lo)``;
+        ``"prior"`` -- draws from ``lnprior``, which must be a :class:`~approxposterior_amd.priors.JointPrior`
+        (``ValueError`` otherwise), ``ln q`` its log-density; a mixture -- a tuple ``(weights, means, covariances)``
+        or an object with ``weights_``, ``means_``, ``covariances_`` of ``covariance_type == "full"``, covariances
+        scaled by ``covScale`` (``GP.mixture_candidates``); ``"gmm"`` -- :func:`gmmUtils.fitGMM` ``(samples,
+        maxComp=maxComp)`` (needs scikit-learn), ``samples`` defaulting to the last :meth:`runMCMC` chain after its
+        burn-in and thinning (``ValueError`` when there is none).
+
+        Rows are gated by ``lnprior.support()`` for a JointPrior, else by ``self.bounds``; a gated row weighs nothing
+        and still counts in ``nSamples``.  The moments are taken about the training point with the largest ``y``.
+        Rows are processed ``chunk`` at a time; chunk j draws rows ``j chunk ..`` of the global proposal matrix, a
+        function of (seed, row) alone, so the estimate does not depend on ``chunk`` beyond the rounding of
+        :func:`utility.mergeImportance`.  ``seed=None`` takes one from NumPy's global stream.  Under a process group
+        every rank computes the same numbers from the same seed.
+
+        ``logZErr`` measures the scatter of the weights that were drawn.  A proposal with lighter tails than
+        ``exp(mu)`` rarely draws the rows that carry the weight, and ``logZErr`` comes out misleadingly small: watch
+        ``ess`` (a small fraction of ``nSamples`` is the warning) and widen a mixture proposal with ``covScale``."""
+        nSamples, chunk = int(nSamples), int(chunk)
+        if nSamples < 1 or chunk < 1:
+            raise ValueError("evidence: nSamples and chunk must be positive")
+        joint = self._jointPrior()
+        gate = self.bounds if joint is None else [tuple(r) for r in joint.support()]
+        logVolume, mixture = 0.0, None
+        if isinstance(proposal, str) and proposal == "prior":
+            if joint is None:
+                raise ValueError("evidence(proposal='prior') draws from lnprior on the device: lnprior must be a "
+                                 "priors.JointPrior. Use proposal='box', 'gmm' or a mixture.")
+        elif isinstance(proposal, str) and proposal == "box":
+            b = np.asarray(self.bounds, dtype=np.float64).reshape(-1, 2)
+            logVolume = float(np.sum(np.log(b[:, 1] - b[:, 0])))
+        elif isinstance(proposal, str) and proposal == "gmm":
+            if samples is None:
+                cut = getattr(self, "_chainCut", None)
+                if getattr(self, "sampler", None) is None or cut is None:
+                    raise ValueError("evidence(proposal='gmm') fits its proposal to posterior samples: pass samples= or "
+                                     "call runMCMC first")
+                samples = self.sampler.get_chain(discard=cut[0], flat=True, thin=cut[1])
+            mixture = self._mixtureProposal(gmmUtils.fitGMM(samples, maxComp=maxComp))
+        else:
+            mixture = self._mixtureProposal(proposal)
+        if seed is None:
+            if self._ranks() is not None:       # one NumPy stream on every rank, as runMCMC arranges: the same seed
+                apdist.sync_random_state(0, self.group, enabled=self.distributed)
+            seed = int(np.random.randint(0, 2 ** 31 - 1))
+        centre = np.array(self.theta[int(np.argmax(self.y))], dtype=np.float64).ravel()
+        record = None
+        for off in range(0, nSamples, chunk):
+            mc = min(chunk, nSamples - off)
+            if mixture is not None:
+                T, lnq = self.gp.mixture_candidates(mc, mixture[0], mixture[1], mixture[2], seed, idx_offset=off,
+                                                    covScale=covScale)
+            elif proposal == "prior":
+                T = self.gp.prior_candidates(mc, joint, seed, idx_offset=off)
+                lnq = self.gp.prior_lnprior(T, joint)
+            else:
+                T, lnq = self.gp.box_candidates(mc, self.bounds, seed, idx_offset=off), None      # ln q: logVolume
+            part = self.gp.importance_pass(self.y, T, lnq=lnq, bounds=gate, centre=centre)
+            record = part if record is None else ut.mergeImportance(record, part)
+        return ut.importanceSummary(record, nSamples, logVolume=logVolume)
 
     # ---------------------------------------------------------------------- outer loop
     def run(self, m=10, nmax=2, seed=None, timing=False, verbose=True,

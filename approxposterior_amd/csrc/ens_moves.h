@@ -49,8 +49,16 @@ __device__ __forceinline__ double u01(unsigned int a, unsigned int b) {
 
 // Box-Muller normal from two uniforms in (0, 1).  Not inlined (as prior_gauss in ensemble.hip): inlined, the constants of
 // log and cospi are hoisted out of the iteration loop into 25 registers that stay live through the GP mean.
-static __device__ __attribute__((noinline)) double ens_normal(double u1, double u2) {
+static inline __device__ __attribute__((noinline)) double ens_normal(double u1, double u2) {
     return sqrt(-2.0 * log(u1)) * cospi(2.0 * u2);
+}
+
+// The Gaussian inverse CDF of the prior draws (ensemble.hip prior_candidates_kernel) and of the mixture proposal (evidence.hip):
+// mu + (sigma sqrt 2) erfcinv(2 (1 - u)), every operation rounded in NumPy's order (tests/prior_ref.py).
+// (not inlined: inside the row loop the compiler hoists erfcinv's coefficients into some 400 registers)
+static inline __device__ __attribute__((noinline)) double prior_gauss(double mu, double sigma, double u) {
+    const double w = __dmul_rn(2.0, __dsub_rn(1.0, u));
+    return __dadd_rn(mu, __dmul_rn(__dmul_rn(sigma, 1.4142135623730951), erfcinv(w)));
 }
 
 // the move table of a launch: kinds, cumulative normalised weights and the two parameters of include/apgp.h

@@ -664,12 +664,7 @@ struct PriorArgs {
     double lc[APGP_MAX_DIM];   // log-density constant of the factor
 };
 
-// (not inlined: inside the row loop the compiler hoists erfcinv's coefficients into some 400 registers)
-__device__ __attribute__((noinline)) double prior_gauss(double mu, double sigma, double u) {
-    const double w = __dmul_rn(2.0, __dsub_rn(1.0, u));
-    return __dadd_rn(mu, __dmul_rn(__dmul_rn(sigma, 1.4142135623730951), erfcinv(w)));
-}
-
+// (prior_gauss: csrc/ens_moves.h, shared with the mixture proposal of evidence.hip)
 __device__ __forceinline__ double prior_draw(const PriorArgs& a, int d, double u) {
     if (a.kind[d] == APGP_PRIOR_UNIFORM) return fma(a.p1[d], u, a.p0[d]);
     return prior_gauss(a.p0[d], a.p1[d], u);

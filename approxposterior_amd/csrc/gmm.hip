@@ -18,6 +18,7 @@
 // all sum_rows w * a * b for two slots a, b of the row), computes one row per thread, then each thread owns a set of
 // outputs and sums them over the tile's rows; the per-thread totals run over the workgroup's tiles in order.
 #include "apgp_common.h"
+#include "gmm_logpdf.h"
 #include "scratch.h"
 #include <mutex>
 
@@ -47,26 +48,6 @@ struct GmmArgs {
     int K;
     int nout;
 };
-
-// log N(x | mu_k, Sigma_k) + log w_k through the precision Cholesky factor
-template <int DP>
-__device__ __forceinline__ double gmm_logpdf(const double* x, const double* P, int D) {
-    const double* c = P + 2;
-    const double* U = P + 2 + DP;
-    double z[DP];
-#pragma unroll
-    for (int i = 0; i < DP; ++i) z[i] = x[i] - c[i];
-    double quad = 0.0;
-#pragma unroll
-    for (int j = 0; j < DP; ++j) {
-        double y = 0.0;
-#pragma unroll
-        for (int i = 0; i <= j; ++i) y = fma(z[i], U[j * (j + 1) / 2 + i], y);
-        quad = fma(y, y, quad);
-    }
-    const double log2pi = 1.8378770664093454836;
-    return (-0.5 * ((double)D * log2pi + quad) + P[1]) + P[0];
-}
 
 template <int DP, int MODE>
 __global__ __launch_bounds__(GMM_NT) void gmm_pass_kernel(GmmArgs a) {

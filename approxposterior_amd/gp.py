@@ -36,6 +36,7 @@ from operator import is_
 
 import numpy as np
 from numpy.linalg import LinAlgError
+from scipy.linalg import solve_triangular
 
 from . import _lib
 from .george_extras import GeorgeExtras
@@ -384,6 +385,13 @@ def _box(bounds, D, optional=True):
     return arr(*b[:, 0]), arr(*b[:, 1])
 
 
+def _triu_colmajor(D):
+    """(rows, cols) of the upper triangle packed column by column: U[i][j] at j(j+1)/2 + i (include/apgp.h)."""
+    j = np.repeat(np.arange(D), np.arange(1, D + 1))
+    i = np.concatenate([np.arange(c + 1) for c in range(D)])
+    return i, j
+
+
 def _seed64(seed):
     return int(seed) & 0xFFFFFFFFFFFFFFFF
 
@@ -493,6 +501,7 @@ class GP(GeorgeExtras):
         self._x_d = None              # device copy of the training set
         self._mean_work = None        # scratch of the small predictions and of the evaluations: survives refits
         self._p1_work = None
+        self._imp_work = None         # scratch of importance_pass
         self._pg_work = None
         self._nll_scratch = None
         self._nll_stream = None       # the stream the private buffers of the last _nll evaluation were made on
@@ -1798,6 +1807,133 @@ class GP(GeorgeExtras):
                                                  p1.ctypes.data, _seed64(seed), int(idx_offset),
                                                  self._stream(torch)), "apgp_prior_candidates")
         return T
+
+    # -- evidence by importance sampling (DESIGN.md "Evidence by importance sampling") ------
+    @staticmethod
+    def _mixture_params(weights, means, covariances, covScale):
+        """The host record of ``apgp_mix_candidates`` (include/apgp.h) of a full-covariance mixture: per component the
+        cumulative weight (summed sequentially, the last forced to 1.0), the ``apgp_gmm_pass`` record (log weight,
+        log det U, centre, U packed) and the lower Cholesky factor A of ``covScale`` x covariance packed row by row."""
+        w = np.asarray(weights, dtype=np.float64).ravel()
+        mu = np.atleast_2d(np.asarray(means, dtype=np.float64))
+        cov = np.asarray(covariances, dtype=np.float64)
+        K, D = mu.shape
+        if w.shape != (K,) or cov.shape != (K, D, D):
+            raise ValueError("a mixture needs weights (K,), means (K, D) and full covariances (K, D, D)")
+        if not 1 <= K <= _lib.GMM_MAX_COMP:
+            raise ValueError("a mixture proposal has between 1 and %d components" % _lib.GMM_MAX_COMP)
+        if not (np.all(np.isfinite(w)) and np.all(w >= 0.0) and w.sum() > 0.0 and float(covScale) > 0.0):
+            raise ValueError("mixture weights must be finite and non-negative with a positive sum, covScale positive")
+        w = w / w.sum()
+        cum = np.empty(K)
+        run = 0.0
+        for k in range(K):
+            run = min(run + w[k], 1.0)
+            cum[k] = run
+        cum[K - 1] = 1.0
+        iu, ju = _triu_colmajor(D)
+        il, jl = np.tril_indices(D)
+        rec = np.empty((K, 3 + D + D * (D + 1)))
+        with np.errstate(divide="ignore"):
+            logw = np.log(w)
+        for k in range(K):
+            try:
+                A = np.linalg.cholesky(float(covScale) * cov[k])
+            except np.linalg.LinAlgError:
+                raise ValueError("covariance %d of the mixture is not positive definite" % k)
+            if not np.all(np.isfinite(A)):
+                raise ValueError("covariance %d of the mixture is not positive definite" % k)
+            U = solve_triangular(A, np.eye(D), lower=True).T        # precision = U U^T
+            rec[k] = np.concatenate([[cum[k], logw[k], np.sum(np.log(np.diag(U)))], mu[k], U[iu, ju], A[il, jl]])
+        return K, D, rec
+
+    def mixture_candidates(self, m, weights, means, covariances, seed, idx_offset=0, covScale=1.0):
+        """Rows ``idx_offset .. idx_offset + m - 1`` of the global matrix of draws from the Gaussian mixture
+        (``weights`` (K,), ``means`` (K, D), full ``covariances`` (K, D, D) scaled by ``covScale``) keyed by ``seed``
+        -- a row depends on (seed, row number) only -- and the mixture's log-density at every draw: device tensors
+        ``(T (m, D), lnq (m,))``.  The factors come from NumPy on the host; ``ValueError`` for a covariance that is not
+        positive definite."""
+        torch, dev, lib = self._rt()
+        K, D, rec = self._mixture_params(weights, means, covariances, covScale)
+        if D != self.kernel.ndim:
+            raise ValueError("the mixture must have the GP's dimension")
+        m = int(m)
+        with self._on(torch, dev):
+            T = torch.empty((m, D), dtype=torch.float64, device=dev)
+            lnq = torch.empty(m, dtype=torch.float64, device=dev)
+            if m == 0:
+                return T, lnq
+            rec = np.ascontiguousarray(rec.ravel())
+            assert rec.size == lib.apgp_mix_params_len(D, K)
+            _lib.check(lib.apgp_mix_candidates(T.data_ptr(), lnq.data_ptr(), m, D, K, rec.ctypes.data, _seed64(seed),
+                                               int(idx_offset), self._stream(torch)), "apgp_mix_candidates")
+        return T, lnq
+
+    def prior_lnprior(self, T, prior):
+        """``prior``'s log-density (a :class:`~approxposterior_amd.priors.JointPrior`) at the rows of the device
+        tensor ``T`` (M, D), as a device tensor (M,)."""
+        torch, dev, lib = self._rt()
+        T = self._candidates(T)
+        kind, p0, p1 = self._prior_records(prior, self.kernel.ndim)
+        with self._on(torch, dev):
+            out = torch.empty(T.shape[0], dtype=torch.float64, device=dev)
+            if T.shape[0]:
+                _lib.check(lib.apgp_prior_lnprior(T.data_ptr(), T.shape[0], self.kernel.ndim, kind.ctypes.data,
+                                                  p0.ctypes.data, p1.ctypes.data, out.data_ptr(), self._stream(torch)),
+                           "apgp_prior_lnprior")
+        return out
+
+    def importance_pass(self, y, T, lnq=None, bounds=None, centre=None, return_logw=False):
+        """One importance-sampling record over the rows of ``T`` (M >= 1, D; host array or device tensor) drawn from a
+        proposal with log-density ``lnq`` (M,; device tensor or host array; None: zeros):
+        ``logw = mu(t) - lnq`` where every coordinate is finite and inside ``bounds`` and ``mu`` and ``lnq`` are finite,
+        else -inf.  Returns a dict of NumPy values -- ``lmax``, ``S0 = sum e``, ``S2 = sum e^2``, ``cnt``, ``s1 = sum e
+        (t - c)``, ``S = sum e (t - c)(t - c)^T`` (D, D), ``centre`` -- with ``e = exp(logw - lmax)`` and ``c`` =
+        ``centre`` (default: the training point with the largest ``y``); ``utility.importanceSummary`` reads it,
+        ``utility.mergeImportance`` joins two.  ``return_logw`` adds the device tensor of ``logw``.  One device pass:
+        the means, the weights and the moments never visit the host."""
+        torch, dev, lib = self._rt()
+        if not self.computed:
+            raise RuntimeError("ERROR: Need to compute GP before using it!")
+        y = self._check_dimensions(y)
+        D = self.kernel.ndim
+        T = self._candidates(T)
+        m = int(T.shape[0])
+        if m < 1:
+            raise ValueError("importance_pass needs at least one row")
+        c = np.array(self._x[int(np.argmax(y))] if centre is None else centre, dtype=np.float64).ravel()
+        if c.shape != (D,) or not np.all(np.isfinite(c)):
+            raise ValueError("centre must be D finite numbers")
+        lo, hi = _box(bounds, D)
+        ks = self._kernel_struct()
+        with self._on(torch, dev):
+            st = self._stream(torch)
+            self._ensure_xs(y)
+            f64 = dict(dtype=torch.float64, device=dev)
+            if lnq is not None and not hasattr(lnq, "data_ptr"):
+                lnq = torch.from_numpy(np.ascontiguousarray(lnq, dtype=np.float64)).to(dev)
+            if lnq is not None and (tuple(lnq.shape) != (m,) or str(lnq.dtype) != "torch.float64" or not lnq.is_cuda
+                                    or not lnq.is_contiguous()):
+                raise ValueError("lnq must be a contiguous (M,) float64 tensor on the device")
+            logw = torch.empty(m, **f64) if return_logw else None
+            nstat = int(lib.apgp_importance_stats_len(D))
+            stats = torch.empty(nstat, **f64)
+            need = int(lib.apgp_importance_work_len(m)) - (m if return_logw else 0)
+            if self._imp_work is None or self._imp_work.numel() < need:
+                self._imp_work = torch.empty(need, **f64)
+            cc = (ctypes.c_double * _lib.MAX_DIM)(*c)
+            _lib.check(lib.apgp_importance_pass(T.data_ptr(), m, _ptr(lnq), self._xs.data_ptr(), len(self._x),
+                                                ctypes.byref(ks), float(self.mean.value), lo, hi,
+                                                ctypes.addressof(cc), _ptr(logw), stats.data_ptr(),
+                                                self._imp_work.data_ptr(), st), "apgp_importance_pass")
+            r = stats.cpu().numpy()
+        iu, ju = _triu_colmajor(D)
+        S = np.zeros((D, D))
+        S[iu, ju] = r[4 + D:]
+        S[ju, iu] = r[4 + D:]
+        rec = {"lmax": float(r[0]), "S0": float(r[1]), "S2": float(r[2]), "cnt": float(r[3]), "s1": r[4:4 + D].copy(),
+               "S": S, "centre": c}
+        return (rec, logw) if return_logw else rec
 
     # -- on-device ensemble MCMC over the GP mean ------------------------------------
     def sample_ensemble(self, y, initial_state, iterations, bounds, a=2.0, seed=0, store=True, prior=None,

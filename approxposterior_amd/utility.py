@@ -22,7 +22,8 @@ from scipy.optimize import minimize
 from scipy.stats import norm
 
 __all__ = ["logsubexp", "AGPUtility", "BAPEUtility", "JonesUtility",
-           "minimizeObjective", "sweepObjective", "utilityKind", "searchKind", "klNumerical"]
+           "minimizeObjective", "sweepObjective", "utilityKind", "searchKind", "klNumerical",
+           "mergeImportance", "importanceSummary"]
 
 
 def klNumerical(x, p, q):
@@ -269,3 +270,59 @@ def sweepObjective(fn, y, gp, candidates, bounds=None, mask=None, zeta=0.01,
     if returnAll:
         return best, bu, out[2], out[3], out[4]
     return best, bu
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# importance-sampling records (GP.importance_pass, ApproxPosterior.evidence)
+# ---------------------------------------------------------------------------------------------------------------------
+def mergeImportance(a, b):
+    """The record of the rows of ``a`` and ``b`` together.  A record (``GP.importance_pass``) is a dict with ``lmax``
+    (the largest log-weight, -inf for no admissible row), ``S0 = sum e``, ``S2 = sum e^2``, ``cnt``, ``s1 = sum e (t - c)``
+    (D,), ``S = sum e (t - c)(t - c)^T`` (D, D) and the centre ``centre`` (D,), with ``e = exp(logw - lmax)``.  The merge
+    works in log space: with ``l = max`` of the two ``lmax``, the zeroth and first moments and ``S`` of each side are
+    rescaled by ``exp(lmax - l)`` and ``S2`` by ``exp(2 (lmax - l))`` -- one of the two factors is exactly 1 -- so records
+    whose ``lmax`` lie hundreds apart merge without overflow.  Associative up to rounding; an empty record is the neutral
+    element.  Both records must be taken about the same centre (``ValueError`` otherwise)."""
+    ca, cb = np.asarray(a["centre"], dtype=float), np.asarray(b["centre"], dtype=float)
+    if ca.shape != cb.shape or not np.array_equal(ca, cb):
+        raise ValueError("mergeImportance: the two records are taken about different centres")
+    la, lb = float(a["lmax"]), float(b["lmax"])
+    l = max(la, lb)
+    out = {"lmax": l, "centre": ca.copy(), "cnt": float(a["cnt"]) + float(b["cnt"])}
+    fa = np.exp(la - l) if la > -np.inf else 0.0
+    fb = np.exp(lb - l) if lb > -np.inf else 0.0
+    out["S0"] = fa * float(a["S0"]) + fb * float(b["S0"])
+    out["S2"] = (fa * fa) * float(a["S2"]) + (fb * fb) * float(b["S2"])
+    out["s1"] = fa * np.asarray(a["s1"], dtype=float) + fb * np.asarray(b["s1"], dtype=float)
+    out["S"] = fa * np.asarray(a["S"], dtype=float) + fb * np.asarray(b["S"], dtype=float)
+    return out
+
+
+def importanceSummary(record, m, logVolume=0.0):
+    """What an importance-sampling record over ``m`` proposal draws says, as a dict:
+
+    ``logZ``     ``lmax + log S0 - log m + logVolume``: the log of the mean weight.  ``logVolume`` is for weights taken
+                 without a constant proposal density (``lnq=None`` under a uniform proposal: pass the log of the box volume)
+    ``logZErr``  ``sqrt(max(m S2 / S0^2 - 1, 0) / m)``, the delta-method standard error of ``logZ``
+    ``ess``      ``S0^2 / S2``, the effective sample size
+    ``mean``     ``c + s1 / S0``
+    ``cov``      ``S / S0 - (s1 / S0)(s1 / S0)^T``
+    ``nInside``  ``cnt``, the rows with a finite weight
+
+    A record with no admissible row gives ``logZ = -inf``, ``ess = 0`` and NaN for the rest.  ``logZErr`` is the sampling
+    error GIVEN the draws' weight variance: a proposal with lighter tails than exp(mu) under-samples the rows that carry
+    the weight, and ``logZErr`` comes out misleadingly small -- watch ``ess`` and widen the proposal."""
+    m = float(m)
+    c = np.asarray(record["centre"], dtype=float)
+    S0, S2 = float(record["S0"]), float(record["S2"])
+    if not S0 > 0.0:
+        nan = np.full(c.shape, np.nan)
+        return {"logZ": -np.inf, "logZErr": np.nan, "ess": 0.0, "mean": nan, "cov": np.full(c.shape * 2, np.nan),
+                "nInside": int(record["cnt"])}
+    d = np.asarray(record["s1"], dtype=float) / S0
+    return {"logZ": float(record["lmax"]) + np.log(S0) - np.log(m) + float(logVolume),
+            "logZErr": float(np.sqrt(max(m * S2 / (S0 * S0) - 1.0, 0.0) / m)),
+            "ess": S0 * S0 / S2,
+            "mean": c + d,
+            "cov": np.asarray(record["S"], dtype=float) / S0 - np.outer(d, d),
+            "nInside": int(record["cnt"])}

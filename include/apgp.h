@@ -706,6 +706,58 @@ int64_t apgp_gmm_stats_len(int32_t ndim, int32_t ncomp);
 int apgp_gmm_pass(const double* X, int64_t n, int32_t ndim, int32_t ncomp, const double* params, int32_t mode,
                   double* stats_out, double* row_lp, int32_t* row_label, void* stream);
 
+/* ---- Evidence and posterior moments by importance sampling --------------------------------
+ * The surrogate models the unnormalised log-posterior (y = lnlike + lnprior), so Z = int exp(mu(t)) dt over the prior's
+ * support is the model evidence.  With M draws t_i from a proposal q and log w_i = mu(t_i) - ln q(t_i), one record of
+ * weighted sums gives log Z, its standard error, the effective sample size and the posterior mean and covariance.
+ *
+ * apgp_mix_candidates: rows idx_offset .. idx_offset + m - 1 of the global matrix of draws from a Gaussian mixture into T
+ * (m x ndim, device) and ln q of each STORED row into lnq (m, device, may be NULL).  params (HOST, apgp_mix_params_len
+ * doubles): per component k, 3 + D + D(D+1) doubles
+ *   [cumw_k, log w_k, log det U_k, c_k (D), U_k packed as apgp_gmm_pass takes it (U[i][j] at j(j+1)/2 + i, i <= j),
+ *    A_k packed row by row (A[i][j] at i(i+1)/2 + j, j <= i)]
+ * cumw: the cumulative weights, summed sequentially by the caller, the last one forced to 1.0; c_k the centre; A_k the
+ * lower Cholesky factor of the covariance (the draw); U_k the precision Cholesky factor (precision = U U^T) and its
+ * log-determinant (the density), i.e. entries 1 .. of a component are its apgp_gmm_pass record.
+ * A row depends on (seed, global row) only, as in apgp_box_candidates: Philox4x32-10, key = seed, counter (row low, row
+ * high, j, "MIXT"); j = 0: u = u01(words 0, 1) picks the first k with u < cumw[k]; j = 1 + d / 2: words 0, 1 / 2, 3 are
+ * the uniforms of dimensions d, d + 1, each turned into a standard normal by the inverse-CDF expression of a Gaussian
+ * prior factor (sqrt 2 erfcinv(2 (1 - u))); t = c_k + A_k z.  ln q = logsumexp_k(log w_k + log N(t | c_k, Sigma_k)) at the
+ * stored t, by the arithmetic of apgp_gmm_pass's score.
+ * 1 <= ncomp <= 16, 1 <= ndim <= APGP_MAX_DIM, 0 <= m <= APGP_MAX_M (m = 0: nothing is done); bad arguments -- among
+ * them cumulative weights that fall or do not end at 1.0, a non-finite entry, a non-positive diagonal of A -- are refused
+ * (-1) before anything reaches the device.  The parameters are uploaded into per-stream scratch (apgp_release_scratch;
+ * not during capture) by a copy ordered on `stream` that has completed when the call returns.
+ *
+ * apgp_importance_pass: for the m rows t of T (m x ndim, device) and lnq (m, device; NULL: zeros), with the surrogate as
+ * apgp_predict_mean takes it (xs, n, kern, mean), a gate lo / hi (host, NULL: none) and a centre c (host, ndim doubles):
+ *   mu = k(t, X).alpha + mean
+ *   logw = mu - lnq   if every coordinate is finite and inside [lo, hi] and mu and lnq are finite, else -inf
+ * (a gated row still counts in m).  stats_out (device, apgp_importance_stats_len = 4 + D + D(D+1)/2 doubles):
+ *   [lmax, S0, S2, cnt, s1 (D), S (D(D+1)/2, packed as apgp_gmm_pass packs S)]
+ *   lmax = max logw (-inf if no row is admissible), e_i = exp(logw_i - lmax), S0 = sum e_i, S2 = sum e_i^2, cnt = the
+ *   number of rows with finite logw, s1_d = sum e_i (t_d - c_d), S_de = sum e_i (t_d - c_d)(t_e - c_e).
+ * With no admissible row the record is (-inf, 0, 0, 0, zeros).  e_i is 0 where logw_i - lmax < -700.
+ * logw_out (m, device, may be NULL) receives logw.  work: apgp_importance_work_len(m) doubles (device).
+ * A candidate per thread, APGP_IMP_BLOCK candidates per workgroup, at most APGP_IMP_MAX_BLOCKS workgroups: beyond
+ * APGP_IMP_BLOCK * APGP_IMP_MAX_BLOCKS rows a workgroup takes further tiles of candidates.  Each k(t, x) carries the bits
+ * of apgp_predict_mean's; the sum over the training rows runs in another order (four interleaved partial sums), so mu
+ * agrees with apgp_predict_mean's to rounding, not bit for bit.  No atomics and a fixed order in every sum: the same
+ * input gives the same bits, and the record depends on nothing but the inputs and m.
+ * 1 <= m <= APGP_MAX_M, 1 <= n <= 2^24; the *_len functions return -1 outside the limits.
+ * Added in ABI 8 without changing anything before it: APGP_ABI_VERSION stays 8.                                      */
+#define APGP_IMP_BLOCK 256
+#define APGP_IMP_MAX_BLOCKS 2048
+int64_t apgp_mix_params_len(int32_t ndim, int32_t ncomp);
+int apgp_mix_candidates(double* T, double* lnq, int64_t m, int32_t ndim, int32_t ncomp, const double* params /*host*/,
+                        uint64_t seed, int64_t idx_offset, void* stream);
+int64_t apgp_importance_stats_len(int32_t ndim);
+int64_t apgp_importance_work_len(int64_t m);
+int apgp_importance_pass(const double* T, int64_t m, const double* lnq, const double* xs, int64_t n,
+                         const apgp_kernel_t* kern /*host*/, double mean, const double* lo /*host*/,
+                         const double* hi /*host*/, const double* centre /*host*/, double* logw_out,
+                         double* stats_out, double* work, void* stream);
+
 /* ---- Chain diagnostics: a block of the walker-averaged autocorrelation function ------------
  * (mcmc.integrated_time(onDevice=True).)  x (device, fp64) is an ensemble chain laid out (steps, n_w, n_d) row-major as
  * GP.sample_ensemble stores it; step t of the series is row row0 + t * row_stride of it (a get_chain(discard=, thin=)
