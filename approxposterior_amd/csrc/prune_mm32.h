@@ -87,7 +87,7 @@
 //     carries the same sum, added in the same order: the same bits), and the sum is taken times
 //     1 + 2^-16, which also covers |fl32(alpha)| <= |alpha| (1 + u) where the fp32 alphas are meant.
 // |mu32 - mu| <= e32 = amp ((e^eta - 1) S32 + 2^-120 (sum|alpha| + N)); the slack is prune_bound_kernel's with
-// S <= amp sum|alpha| plus 2 e32.  At C3 the maxima A + B ~ 9.5 and S32 <= 5e4 (against sum|alpha| = 1.9e6) put it
+// S <= amp sum|alpha| plus 2 e32 (pr_slack).  At C3 the maxima A + B ~ 9.5 and S32 <= 5e4 (against sum|alpha| = 1.9e6) put it
 // below 10 (the fp32 chain's: below 8; "coarse kept 0" holds below 45); replayed on 256 of C3's candidates it is at most
 // 2.6, 1.0 in the median, 1.27 times the fp32 chain's on the same candidates (profiles/r18_seeds_branch.json), where
 // sum|alpha| in the place of S32 would give several hundred and prune nothing.
@@ -197,8 +197,11 @@ __global__ __launch_bounds__(PR_THREADS) void pmm_pack_rows_kernel(const double*
             const bool in = ti * PMM_ROWS + srow < n;
             unsigned char* tile = rows + 16 + ti * (16ll * SH::PIECES);
             __bf16* xrow = (__bf16*)tile + srow * PITCH;
-            // (the conversion is the staging lanes' of prune_bound_mm32_kernel<DPAD, false>, statement for statement: as a
-            // shared function it changed that kernel's code; tests/test_gpu_prune_rows.py holds the two to the same bits)
+            // (the conversion is the staging lanes' of prune_bound_mm32_kernel<DPAD, false>, statement for statement;
+            // tests/test_gpu_prune_rows.py holds the two to the same bits.  Tried twice as one force-inlined function
+            // of (row, in, centre) -> (LDS row image, fp32 alpha, bm2, sal): hipcc then packs the bf16 pairs of both
+            // kernels another way (v_perm_b32 / v_alignbit_b32 for some v_cvt_pk_bf16_f32, fewer v_cndmask_b32) and this
+            // kernel's VGPR count moves, 76 -> 58 at Dpad = 8: profiles/r20_bound_asm_compare.txt)
             float pe[DPAD + 2];                          // P's entries
             double n2 = 0.0, b2 = 0.0;
 #pragma unroll
@@ -429,27 +432,11 @@ __global__ __launch_bounds__(PR_THREADS, PMM_G <= 4 ? 2 : 1) void prune_bound_mm
         const double eta = (DPAD + 10.0) * u32 * ab * ab + 2.5 * eps * ab * (cn + an[g]) + 24.0 * u32;
         double e32 = a.amp * (expm1(eta) * (1.0 + 0x1p-20) * s32 + 0x1p-120 * (sa + (double)a.n));
         if (!(eta <= 0x1p-8)) e32 = INFINITY;
-        // prune_bound_kernel's slack with S <= amp sum|alpha|, and the fp32 part on top
-        double slack = 2.0 * e32 + 2.0 * (4.0 * (double)(a.n + 16) + 8.0 * DPAD + 32.0) * eps * (a.amp * sa) +
-                       64.0 * eps * (1.0 + fabs(mu) + fabs(a.ybest) + fabs(a.zeta) + ktt + fabs(b));
-        if (a.kind == APGP_UTIL_BAPE) slack += 16.0 * eps / (1.0 - exp(0.0 - ktt));
-        double be = b;
-        b -= slack;
-        if (!(b == b)) b = -INFINITY;
-        if (!(be == be)) be = -INFINITY;
-        if (!adm[g]) b = be = INFINITY;
-        for (int o = 16; o > 0; o >>= 1) { b = fmin(b, __shfl_xor(b, o)); be = fmin(be, __shfl_xor(be, o)); }
-        bb = fmin(bb, b); bbe = fmin(bbe, be);
+        bbe = fmin(bbe, pr_block_min<32>(b, adm[g]));
+        bb = fmin(bb, pr_block_min<32>(b - pr_slack<DPAD>(a, 2.0 * e32, a.amp * sa, mu, ktt, b), adm[g]));
         if (g & 1) {                                     // both 32-candidate groups of block blk0 + g / 2 are in
             const long long blk = blk0 + (g >> 1);
-            if (lane == 0 && blk < a.ncb) {
-                a.bmin[blk] = bb;
-                if (a.est) a.est[blk] = bbe;
-                if (a.part_u) {
-                    a.part_u[blk] = INFINITY;            // a pruned block's partial: never wins
-                    a.part_i[blk] = -1;
-                }
-            }
+            if (lane == 0 && blk < a.ncb) pr_store_block<true>(a, blk, bb, bbe);
             bb = INFINITY; bbe = INFINITY;
         }
     }

@@ -1222,6 +1222,45 @@ struct PruneArgs {
     const void* prune_rows;
 };
 
+// Slack of a coarse bound: prune_bound_kernel's (derived there) with S <= amp sum|alpha| for its S, added in that
+// kernel's order onto base = 2 e32, what the coarse mu may be off by times |du/dmu| <= 2.
+template <int DPAD>
+__device__ __forceinline__ double pr_slack(const PruneArgs& a, double base, double S, double mu, double ktt, double b) {
+    const double eps = 0x1p-53;
+    double slack = base + 2.0 * (4.0 * (double)(a.n + 16) + 8.0 * DPAD + 32.0) * eps * S +
+                   64.0 * eps * (1.0 + fabs(mu) + fabs(a.ybest) + fabs(a.zeta) + ktt + fabs(b));
+    if (a.kind == APGP_UTIL_BAPE) slack += 16.0 * eps / (1.0 - exp(0.0 - ktt));
+    return slack;
+}
+
+// The end of a bound: a row's b (with or without its slack) -> the minimum over the W lanes that hold a block's rows (64)
+// or half of them (32).  A bound that is NaN bounds nothing: -inf, the block is evaluated; a row that is not admissible
+// cannot win: +inf.
+template <int W>
+__device__ __forceinline__ double pr_block_min(double b, bool adm) {
+    if (!(b == b)) b = -INFINITY;
+    if (!adm) b = INFINITY;
+    for (int o = W / 2; o > 0; o >>= 1) b = fmin(b, __shfl_xor(b, o));
+    return b;
+}
+
+// a block's arg-min partial before any sweep has seen the block: a pruned block's never wins
+__device__ __forceinline__ void pr_prefill(const PruneArgs& a, long long blk) {
+    if (a.part_u) {
+        a.part_u[blk] = INFINITY;
+        a.part_i[blk] = -1;
+    }
+}
+
+// what one lane writes for block blk of a coarse stage: the block minimum of the bounds, of the b without slack where
+// asked for (PruneArgs::est), and with PREFILL the partial
+template <bool PREFILL>
+__device__ __forceinline__ void pr_store_block(const PruneArgs& a, long long blk, double b, double be) {
+    a.bmin[blk] = b;
+    if (a.est) a.est[blk] = be;
+    if (PREFILL) pr_prefill(a, blk);
+}
+
 // LIST: the refine stage of a call that bounded coarsely first (prune_bound32_kernel): only the blocks of a device list,
 // bmin[blk] = max(coarse, this bound) -- both are valid, the larger prunes more --, and no pre-fill of the partials.  The
 // launch is sized for the longest list; a workgroup beyond the count leaves before its first barrier.
@@ -1247,7 +1286,10 @@ __global__ __launch_bounds__(PR_THREADS) void prune_bound_kernel(PruneArgs a) {
     bool adm[PR_CPT];
 #pragma unroll
     for (int c = 0; c < PR_CPT; ++c) {
-        // admissibility and k(t,t) exactly as the sweep's load_candidates
+        // admissibility and k(t,t) exactly as the sweep's load_candidates.  (The three bound kernels each write this load
+        // out: as one force-inlined function -- coordinates returned in an array or handed to a callback, the arguments by
+        // reference, value or pointer -- hipcc reads the whole PruneArgs up front, keeps it in SGPRs that spill into VGPR
+        // lanes, and the VGPR counts move: docs/experiments.md, round 20.)
         const long long row = blk[c] * SW_CAND + lane;
         const bool live = blk[c] < a.ncb && row < a.m;
         bool ok = live, has_nan = false;
@@ -1346,23 +1388,23 @@ __global__ __launch_bounds__(PR_THREADS) void prune_bound_kernel(PruneArgs a) {
         //    absolute error eps / (1 - exp(-var))), u_i exceeds b_i by more than it loses; BAPE at a tiny k(t,t)
         //    itself gets the term 16 eps / (1 - exp(-k(t,t))).
         //    (Jones with var_i <= 0 or NaN is 0.0: b_i = -EI <= 0 up to the same rounding.)
-        // A bound that is NaN bounds nothing: -inf, the block is evaluated.
+        // The expression stands here and in pr_slack (the coarse kernels'): here hipcc contracts the two products into ONE
+        // fma; through pr_slack with base 0.0 it rounds the first product on its own (fma(.., S, 0.0), then the second
+        // fma), which moves the last bit of the slack and, where b is as small as the slack (Jones), of bmin.
         const double eps = 0x1p-53;
         double slack = 2.0 * (4.0 * (double)(a.n + 16) + 8.0 * DPAD + 32.0) * eps * S +
                        64.0 * eps * (1.0 + fabs(mu) + fabs(a.ybest) + fabs(a.zeta) + ktt[c] + fabs(b));
         if (a.kind == APGP_UTIL_BAPE) slack += 16.0 * eps / (1.0 - exp(0.0 - ktt[c]));
         b -= slack;
-        if (!(b == b)) b = -INFINITY;
-        if (!adm[c]) b = INFINITY;
-        for (int o = 32; o > 0; o >>= 1) b = fmin(b, __shfl_xor(b, o));
+        b = pr_block_min<64>(b, adm[c]);
         if (lane == 0 && blk[c] < a.ncb) {
             if (LIST) {
                 a.bmin[blk[c]] = fmax(a.bmin[blk[c]], b);
             } else {
                 a.bmin[blk[c]] = b;
-                if (a.part_u) {
-                    a.part_u[blk[c]] = INFINITY;     // a pruned block's partial: never wins
-                    a.part_i[blk[c]] = -1;
+                if (a.part_u) {                      // pr_prefill, written out: behind the call hipcc forms this
+                    a.part_u[blk[c]] = INFINITY;     // kernel's slack with other instructions (docs/experiments.md,
+                    a.part_i[blk[c]] = -1;           // round 20)
                 }
             }
         }
@@ -1404,7 +1446,7 @@ __global__ __launch_bounds__(PR_THREADS) void prune_bound_kernel(PruneArgs a) {
 //   * sum |alpha| itself is summed the same way (fp32 over 8 rows, then fp64): below the true one by <= 2^-20 of it;
 //     it is taken times 1 + 2^-16.
 // |mu32 - mu| <= e32 = amp ((u (4 A + Dpad / 2 + 18) + 2 eps (|c| + A)) sum|alpha| + 2^-120 (sum|alpha| + N)); the slack is
-// prune_bound_kernel's with S <= amp sum|alpha| plus 2 e32 (|du/dmu| <= 2).  Not finite: -inf, the block goes on to
+// prune_bound_kernel's with S <= amp sum|alpha| plus 2 e32 (pr_slack; |du/dmu| <= 2).  Not finite: -inf, the block goes on to
 // the fp64 bound.
 // Variants measured: docs/experiments.md, round 9.
 // ---------------------------------------------------------------------------
@@ -1549,24 +1591,10 @@ __global__ __launch_bounds__(PR_THREADS) void prune_bound32_kernel(PruneArgs a) 
         double e32 = a.amp * ((u32 * (4.0 * an[c] + 0.5 * DPAD + 18.0) + 2.0 * eps * (cn + an[c])) * sa +
                               0x1p-120 * (sa + (double)a.n));
         if (!(u32 * (8.0 * an[c] + DPAD + 8.0) + eps * (cn + an[c]) <= 0x1p-8)) e32 = INFINITY;
-        // prune_bound_kernel's slack with S <= amp sum|alpha|, and the fp32 part on top
-        double slack = 2.0 * e32 + 2.0 * (4.0 * (double)(a.n + 16) + 8.0 * DPAD + 32.0) * eps * (a.amp * sa) +
-                       64.0 * eps * (1.0 + fabs(mu) + fabs(a.ybest) + fabs(a.zeta) + ktt[c] + fabs(b));
-        if (a.kind == APGP_UTIL_BAPE) slack += 16.0 * eps / (1.0 - exp(0.0 - ktt[c]));
-        double be = b;
-        b -= slack;
-        if (!(b == b)) b = -INFINITY;
-        if (!(be == be)) be = -INFINITY;
-        if (!adm[c]) b = be = INFINITY;
-        for (int o = 32; o > 0; o >>= 1) { b = fmin(b, __shfl_xor(b, o)); be = fmin(be, __shfl_xor(be, o)); }
-        if (lane == 0 && blk0 + c < a.ncb && redo[c]) {
-            a.bmin[blk0 + c] = b;
-            if (a.est) a.est[blk0 + c] = be;
-            if (!REDO && a.part_u) {
-                a.part_u[blk0 + c] = INFINITY;           // a pruned block's partial: never wins
-                a.part_i[blk0 + c] = -1;
-            }
-        }
+        const double be = pr_block_min<64>(b, adm[c]);
+        b = pr_block_min<64>(b - pr_slack<DPAD>(a, 2.0 * e32, a.amp * sa, mu, ktt[c], b), adm[c]);
+        // (REDO: the partials were pre-filled by the kernel in front)
+        if (lane == 0 && blk0 + c < a.ncb && redo[c]) pr_store_block<!REDO>(a, blk0 + c, b, be);
     }
 }
 
@@ -1779,29 +1807,35 @@ extern "C" int apgp_sweep_prune_select(const double* bmin, int64_t ncb, const in
     return 0;
 }
 
-static void pr_fill_args(PruneArgs& p, const SweepArgs& a, double* bmin, double* part_u, long long* part_i,
-                         const void* prune_rows) {
-    p.T = a.T; p.xs = a.xs; p.mask = a.mask; p.bmin = bmin; p.part_u = part_u; p.part_i = part_i;
-    p.m = a.m; p.ncb = pr_ncb(a.m); p.n = a.n;
-    p.kind = a.kind; p.mean = a.mean; p.zeta = a.zeta; p.ybest = a.ybest;
-    apgp_fill_kernel(p, a);
-    p.has_box = a.has_box;
-    for (int d = 0; d < APGP_MAX_DIM; ++d) { p.lo[d] = a.lo[d]; p.hi[d] = a.hi[d]; }
+// the one place that fills a PruneArgs.  Kern: a KernConst, or an argument struct that apgp_fill_kernel has filled;
+// lo, hi: the box in the caller's coordinates, or NULL both
+template <class Kern>
+static PruneArgs pr_args(const double* T, int64_t m, const double* xs, int64_t n, const uint8_t* mask, const Kern& kern,
+                         double mean, int32_t kind, const double* lo, const double* hi, double zeta, double ybest,
+                         double* bmin, double* part_u, long long* part_i, const void* prune_rows) {
+    PruneArgs p;
+    p.T = T; p.xs = xs; p.mask = mask; p.bmin = bmin; p.part_u = part_u; p.part_i = part_i;
+    p.m = m; p.ncb = pr_ncb(m); p.n = n;
+    p.kind = kind; p.mean = mean; p.zeta = zeta; p.ybest = ybest;
+    apgp_fill_kernel(p, kern);
+    apgp_fill_box(p, p.ndim, lo, hi);
     p.blk_list = NULL; p.blk_count = NULL; p.est = NULL; p.prune_rows = prune_rows;
+    return p;
 }
 
 // the bound pass over all blocks: coarse (fp32 kernel values; pure squared-exponential kernels only) or fp64.  Coarse up to
 // Dpad = 8: the exponents on the matrix cores (prune_mm32.h), and the vector-ALU kernel behind it for the blocks whose
 // gate failed there -- as a rule none, and its workgroups leave at once.  Dpad 16 and 32 keep the vector-ALU kernel.
 // With PruneArgs::prune_rows the matrix-core kernel copies the pre-split rows instead of splitting them (same bits).
+// With PruneArgs::blk_list (fp64 only): the refine stage, over the blocks of that list; the launch is sized for all blocks.
 template <int DPAD>
 static void launch_bound(const PruneArgs& p, hipStream_t s, bool coarse) {
-    const long long per_wg = (PR_THREADS / 64) * (coarse ? pr32_cpt(DPAD) : PR_CPT);
-    const dim3 grid((unsigned)((p.ncb + per_wg - 1) / per_wg));
+    // cpt candidate blocks per wavefront
+    auto grid_of = [&](int cpt) { return dim3((unsigned)((p.ncb + (PR_THREADS / 64) * cpt - 1) / ((PR_THREADS / 64) * cpt))); };
+    const dim3 grid = grid_of(coarse ? pr32_cpt(DPAD) : PR_CPT);
     if (coarse) {
         if constexpr (DPAD <= 8) {
-            const long long mm_wg = (PR_THREADS / 64) * (PMM_G / 2);
-            const dim3 mm_grid((unsigned)((p.ncb + mm_wg - 1) / mm_wg));
+            const dim3 mm_grid = grid_of(PMM_G / 2);
             if (p.prune_rows)
                 hipLaunchKernelGGL((prune_bound_mm32_kernel<DPAD, true>), mm_grid, dim3(PR_THREADS), 0, s, p);
             else
@@ -1810,7 +1844,9 @@ static void launch_bound(const PruneArgs& p, hipStream_t s, bool coarse) {
         } else {
             hipLaunchKernelGGL((prune_bound32_kernel<DPAD, false>), grid, dim3(PR_THREADS), 0, s, p);
         }
-    } else
+    } else if (p.blk_list)
+        hipLaunchKernelGGL((prune_bound_kernel<DPAD, true>), grid, dim3(PR_THREADS), 0, s, p);
+    else
         hipLaunchKernelGGL((prune_bound_kernel<DPAD, false>), grid, dim3(PR_THREADS), 0, s, p);
 }
 
@@ -1830,8 +1866,8 @@ static int launch_pruned(const SweepArgs& a, hipStream_t s, bool solve, void* pa
     long long* seeds = list + ncb;
     long long* counts = seeds + PR_SEED;
     const bool coarse = a.lin_coef == 0.0;
-    PruneArgs p;
-    pr_fill_args(p, a, bmin, a.part_u, a.part_i, prune_rows);
+    PruneArgs p = pr_args(a.T, a.m, a.xs, a.n, a.mask, a, a.mean, a.kind, a.has_box ? a.lo : NULL, a.has_box ? a.hi : NULL,
+                          a.zeta, a.ybest, bmin, a.part_u, a.part_i, prune_rows);
     if (coarse) p.est = (double*)(counts + 8);
     launch_bound<DPAD>(p, s, coarse);
     hipLaunchKernelGGL(prune_seed_kernel, dim3(1), dim3(1024), 0, s, coarse ? (const double*)p.est : (const double*)bmin, ncb,
@@ -1841,9 +1877,7 @@ static int launch_pruned(const SweepArgs& a, hipStream_t s, bool solve, void* pa
                        counts + 3);
     if (coarse) {
         p.blk_list = list; p.blk_count = counts + 3;
-        const long long per_wg = (PR_THREADS / 64) * PR_CPT;
-        hipLaunchKernelGGL((prune_bound_kernel<DPAD, true>), dim3((unsigned)((ncb + per_wg - 1) / per_wg)), dim3(PR_THREADS),
-                           0, s, p);
+        launch_bound<DPAD>(p, s, false);
         hipLaunchKernelGGL(prune_select_kernel, dim3(1), dim3(1024), 0, s, bmin, ncb, seeds, counts, a.part_u, 0.0, list,
                            (long long*)NULL);
     }
@@ -1873,7 +1907,6 @@ static int acquire_impl(bool solve, const double* T, int64_t m, int64_t idx_offs
     APGP_CHECK_ARG(kind == APGP_UTIL_NONE || best, "best required for an acquisition");
     APGP_CHECK_ARG(part || (kind == APGP_UTIL_NONE && n <= S2_ROWS),
                    "part (apgp_acquire_work_len doubles) required");
-    (void)solve;
     APGP_CHECK_ARG((lo == NULL) == (hi == NULL), "lo and hi must be given together");
     KernConst kc;
     APGP_CHECK_ARG(apgp_make_kernconst(kern, &kc) == 0, "kernel parameters");
@@ -1989,13 +2022,7 @@ static int prune_bounds_impl(const char* who, const double* T, int64_t m, const 
     PB_CHECK_ARG(apgp_make_kernconst(kern, &kc) == 0, "kernel parameters");
     PB_CHECK_ARG(!coarse || kc.lin_coef == 0.0, "the coarse bound takes pure squared-exponential kernels only");
 #undef PB_CHECK_ARG
-    PruneArgs p;
-    p.T = T; p.xs = xs; p.mask = mask; p.bmin = bmin_out; p.part_u = NULL; p.part_i = NULL;
-    p.m = m; p.ncb = pr_ncb(m); p.n = n;
-    p.kind = kind; p.mean = mean; p.zeta = zeta; p.ybest = ybest;
-    apgp_fill_kernel(p, kc);
-    apgp_fill_box(p, kc.ndim, lo, hi);
-    p.blk_list = NULL; p.blk_count = NULL; p.est = NULL; p.prune_rows = prune_rows;
+    const PruneArgs p = pr_args(T, m, xs, n, mask, kc, mean, kind, lo, hi, zeta, ybest, bmin_out, NULL, NULL, prune_rows);
     hipStream_t s = (hipStream_t)stream;
     apgp_by_dpad(kc.dpad, [&](auto dp) { launch_bound<decltype(dp)::value>(p, s, coarse != 0); });
     APGP_CHECK_LAUNCH();
