@@ -7,7 +7,8 @@
 //
 // One kernel implements it: sweep2_kernel, the two-role kernel further down (matrix wavefronts
 // + feeder wavefronts); a short last round of the persistent grid is split by row block and
-// finished by sweep_finish_kernel.
+// finished by sweep_finish_kernel.  In the pruned arg-min's seed launch the heavy row blocks of such a split go as two
+// row-half items each, put together by sweep_fold_kernel before sweep_finish_kernel ("row-half items" below).
 //
 // Data flow per workgroup (512 threads = 4 matrix + 4 feeder wavefronts, 64 candidates):
 //   * matrix / feeder wavefront w owns candidates [16 w, 16 w + 16) (one MFMA column block).
@@ -158,6 +159,73 @@ __global__ __launch_bounds__(1024) void argmin_final_kernel(const double* part_u
 // (N <= 2048), the run-time-indexed body above that (see the matrix role)
 #define S2_STATIC_DIAG_NRB 8
 
+// ---- row-half items (the seed launch of the pruned arg-min) ----------------------------------
+// A split launch lasts as long as its heaviest item, candidate block x row block nrb - 1 with its 16 nrb tiles, while the
+// item of row block 0 walks 16: with one workgroup per CU the chip is half idle.  The rows of a row block are
+// independent, so row blocks jb >= J0 go as TWO items, sub-block pairs [4 h, 4 h + 4) each (h = 0, 1): half the image
+// bytes, the four-pair tile bodies on acc[0 .. 7].  The bits stay those of the whole item because the chain
+// qr[r] = fma(acc[s][r], acc[s][r], qr[r]), s = 0 .. 15, is continued, not re-associated: the h = 0 item stores its
+// chain over s = 0 .. 7 (S2_HQ_PRE doubles), the h = 1 item its 32 accumulators per lane (S2_HQ_ACC doubles), and
+// sweep_fold_kernel runs the chain on from the prefix through the stored values, then the same gather and
+// reductions (s2_q_gather), and writes the share sweep_finish_kernel reads.  No workgroup waits for another.
+#define S2_HQ_PRE (4 * 256)              // doubles per (position, row block): 4 per matrix lane
+#define S2_HQ_ACC (32 * 256)             // doubles per (position, row block): 8 sub-blocks x 4 rotations per matrix lane
+// The fold inputs lie s2_fold_off doubles behind sp_q, at the end of the caller's scratch (apgp_acquire_work_len): behind
+// the split shares and the pruned sweep's 3 ncb + S2_PRUNE_WORDS words, at an even offset (16-byte accesses).  A function
+// of the launch's own arguments (ncb = SweepArgs::blk_end in a list launch; split = 2 + J0 there), not a pointer in
+// SweepArgs: the kernel's argument block, and with it every other instantiation's code, stays what it was.
+#define S2_SPLIT_MAX 184                 // blocks of a last round that are split by row block (see launch_sweep)
+#define S2_PRUNE_WORDS 24                // PR_SEED seed block numbers + 8 counters
+__host__ __device__ inline long long s2_fold_off(int nrb, long long ncb) {
+    return (2ll * S2_SPLIT_MAX * SW_CAND * nrb + 3 * ncb + S2_PRUNE_WORDS + 1) & ~1ll;
+}
+__host__ __device__ inline double* s2_fold_item(double* sp_q, int nrb, long long ncb, long long pos, int jb) {
+    return sp_q + s2_fold_off(nrb, ncb) + (pos * nrb + jb) * (S2_HQ_PRE + S2_HQ_ACC);
+}
+// cost of a half item's tile against a whole item's: 0.70 measured (N = 2048, one item per CU: 217 against 311 us; the
+// feeders' k* and the tile's barrier do not halve with the rows), that is delta = 0.4 (docs/experiments.md, Round 22)
+#define S2_HALF_COST 7
+#define S2_WHOLE_COST 10
+__host__ __device__ inline int s2_nkc_of(int jb, int n) {
+    const int v = S2_CPB * (jb + 1), lim = (n + SW_KC - 1) / SW_KC;
+    return v < lim ? v : lim;
+}
+// row block jb goes as two half items: at or above J0, and with rows in its lower half
+__host__ __device__ inline bool s2_halved(int jb, int j0, int n) { return jb >= j0 && n - S2_ROWS * jb > S2_ROWS / 2; }
+__host__ __device__ inline int s2_nhalved(int nrb, int j0, int n) {
+    int c = 0;
+    for (int jb = j0 < 0 ? 0 : j0; jb < nrb; ++jb) c += s2_halved(jb, j0, n) ? 1 : 0;
+    return c;
+}
+// Row item idx of nrb + s2_nhalved(..), heaviest first by the cost model: the merge of two descending runs -- the row
+// blocks >= J0 from the last down (their halves, h = 1 first: its diagonal tiles are the fuller ones; a last block
+// without a lower half as one item of four-pair tiles) and the whole row blocks below J0.  h = -1: a whole item.
+__host__ __device__ inline void s2_row_item(int idx, int nrb, int j0, int n, int& jb, int& h) {
+    int hj = nrb - 1, hh = 1, wj = (j0 < nrb ? j0 : nrb) - 1;
+    for (int i = 0;; ++i) {
+        if (hj >= j0 && (wj < 0 || S2_HALF_COST * s2_nkc_of(hj, n) >= S2_WHOLE_COST * s2_nkc_of(wj, n))) {
+            const bool two = s2_halved(hj, j0, n);
+            if (i == idx) { jb = hj; h = two ? hh : -1; return; }
+            if (two && hh == 1) hh = 0; else { --hj; hh = 1; }
+        } else {
+            if (i == idx || wj < 0) { jb = wj < 0 ? 0 : wj; h = -1; return; }    // (wj < 0: idx past the last item)
+            --wj;
+        }
+    }
+}
+// gather of the four rotations' sums of squares back to their candidates and the reduction over the 4 row-lanes
+// (rotation r's accumulators belong to the candidate of lane (lane & 48) | ((lane + 4 r) & 15)): the fold's copy of the
+// lines at the end of the kernel's row block.  (The kernel keeps its own text: called from there, this function moved
+// instructions in every instantiation.)
+__device__ __forceinline__ double s2_q_gather(const double (&qr)[4], int lane) {
+    double qs = qr[0];
+#pragma unroll
+    for (int r = 1; r < 4; ++r) qs += __shfl(qr[r], (lane & 48) | ((lane - 4 * r) & 15));
+    qs += __shfl_xor(qs, 16);
+    qs += __shfl_xor(qs, 32);
+    return qs;
+}
+
 // which form of the feeder loop an instantiation gets (see the feeder role)
 // (Dpad = 32, round 5: the plain feeder -- an x chunk is 4352 bytes there, more than the four feeder wavefronts' four 1 KiB
 // LDS-DMA pieces of the structured form, whose hand-counted vmcnt waits assume exactly one piece per wavefront)
@@ -171,8 +239,11 @@ static constexpr bool s2_structured_feeder(int dpad, bool solve) { return dpad =
 // so that the full sweep's code is what it was before the list existed (this kernel's speed hangs on how hipcc
 // allocates its scalars: DESIGN.md section 6, the NaN-refusal episode).  The indirection sits where a block's
 // candidates are loaded; the tile loop never sees it.
-template <int DPAD, bool LIN, int MODE, bool LIST = false>
+// RHALF (MODE 0, LIST, split launches only): row blocks >= J0 = a.split - 2 go as two row-half items (above).  Again an
+// instantiation of its own: every other one keeps its code.
+template <int DPAD, bool LIN, int MODE, bool LIST = false, bool RHALF = false>
 __global__ __launch_bounds__(S2_THREADS, 1) void sweep2_kernel(SweepArgs a) {
+    static_assert(!RHALF || (MODE == 0 && LIST), "row-half items: inverse form, list launches");
     constexpr bool SOLVE = MODE != 0;
     constexpr bool STATIC_DIAG = MODE == 2;
     constexpr int XS = DPAD + 2;
@@ -201,7 +272,8 @@ __global__ __launch_bounds__(S2_THREADS, 1) void sweep2_kernel(SweepArgs a) {
     if constexpr (LIST) {
         lst_end = *a.blk_count;
         if (lst_end <= a.list_lo || lst_end > a.list_hi) return;    // (the whole grid: another launch has this count)
-        const long long nwg = a.split ? lst_end * ((a.n + S2_ROWS - 1) / S2_ROWS) : lst_end;
+        long long nwg = a.split ? lst_end * ((a.n + S2_ROWS - 1) / S2_ROWS) : lst_end;
+        if constexpr (RHALF) nwg += lst_end * s2_nhalved((a.n + S2_ROWS - 1) / S2_ROWS, a.split - 2, a.n);
         if ((long long)blockIdx.x >= nwg) return;                   // (before the first barrier, the whole workgroup)
     }
 #define S2_BLK_BEGIN (LIST ? 0ll : a.blk_begin)
@@ -232,14 +304,17 @@ __global__ __launch_bounds__(S2_THREADS, 1) void sweep2_kernel(SweepArgs a) {
     // Split mode (short last round / small launches): ONE (candidate block, row block) item,
     // heaviest row blocks first; the shares go to sp_q / sp_mu and sweep_finish_kernel.
     int jb_lo = 0, jb_hi = nrb2;
+    int rh = -1;                                  // RHALF: half h of row block jb_lo (pairs [4 h, 4 h + 4)); -1: a whole item
     long long blk0 = S2_BLK_BEGIN + blockIdx.x, blk_step = gridDim.x;
     if (a.split) {
         const int nsplit = (int)(S2_BLK_END - S2_BLK_BEGIN);
         blk0 = S2_BLK_BEGIN + (int)blockIdx.x % nsplit;
-        jb_lo = nrb2 - 1 - (int)blockIdx.x / nsplit;
+        if constexpr (RHALF) s2_row_item((int)blockIdx.x / nsplit, nrb2, a.split - 2, a.n, jb_lo, rh);
+        else jb_lo = nrb2 - 1 - (int)blockIdx.x / nsplit;
         jb_hi = jb_lo + 1;
         blk_step = S2_BLK_END;
     }
+    const int rsh = rh > 0 ? S2_NP / 2 : 0;       // RHALF: first sub-block pair of this item
     auto successor = [&](int& jb, int& kc, long long& blk) {
         ++kc;
         if (kc >= nkc_of(jb)) { ++jb; kc = 0; }
@@ -310,8 +385,10 @@ __global__ __launch_bounds__(S2_THREADS, 1) void sweep2_kernel(SweepArgs a) {
                         }
                     };
                     int p0 = (kc - ndiag0) >> 1;
+                    if constexpr (RHALF) p0 -= rsh;     // (a half item's pairs sit in pieces 0 .. 3 and acc[0 .. 7])
                     if (p0 < 0) p0 = 0;
                     int p1 = (a.n - S2_ROWS * jb + 31) >> 5;
+                    if constexpr (RHALF) p1 -= rsh;
                     if (p1 > NP) p1 = NP;
 #pragma unroll
                     for (int pr = 0; pr < NPA; ++pr) {
@@ -372,6 +449,15 @@ __global__ __launch_bounds__(S2_THREADS, 1) void sweep2_kernel(SweepArgs a) {
                     bpar ^= 1;
                 };
                 auto do_tile = [&](auto pred_tag) { do_tile_n(pred_tag, std::integral_constant<int, NP>{}); };
+                if constexpr (RHALF) {
+                    // a half item: its straight tiles with the four-pair body (rows past the end are zero in the
+                    // packed factor), its diagonal tiles with the predicated four-pair body; kc == nkc after them, and
+                    // none of the loops below runs.  (Plain loops in sequence, as there.)
+                    const int nhalf4 = rh >= 0 ? ndiag0 : 0;
+                    for (; kc < nhalf4; ++kc) do_tile_n(std::false_type{}, std::integral_constant<int, 4>{});
+                    const int nhalfp = rh >= 0 ? nkc : 0;
+                    for (; kc < nhalfp; ++kc) do_tile_n(std::true_type{}, std::integral_constant<int, 4>{});
+                }
                 const int nstraight = (a.n - S2_ROWS * jb >= S2_ROWS) ? ndiag0 : 0;
                 for (; kc < nstraight; ++kc) do_tile(std::false_type{});
                 if constexpr (!SOLVE) {
@@ -379,7 +465,7 @@ __global__ __launch_bounds__(S2_THREADS, 1) void sweep2_kernel(SweepArgs a) {
                     // compile time (the predicated body costs 3.4 k cycles for four pairs' 2.05 k of MFMAs,
                     // profiles/r03aa; N = 1152: 23.9 -> 22.8 ms, bit-identical).  Plain loops in sequence: as
                     // if / else alternatives that join with the 128 accumulators live, hipcc spilled them.
-                    const int npart4 = (nstraight == 0 && a.n - S2_ROWS * jb <= 128) ? ndiag0 : 0;
+                    const int npart4 = (nstraight == 0 && a.n - S2_ROWS * jb <= 128) ? ndiag0 : 0;      // (kc == nkc after a half item)
                     for (; kc < npart4; ++kc) do_tile_n(std::false_type{}, std::integral_constant<int, 4>{});
                     const int npart6 = (nstraight == 0 && a.n - S2_ROWS * jb <= 192) ? ndiag0 : 0;
                     for (; kc < npart6; ++kc) do_tile_n(std::false_type{}, std::integral_constant<int, 6>{});
@@ -622,6 +708,27 @@ __global__ __launch_bounds__(S2_THREADS, 1) void sweep2_kernel(SweepArgs a) {
 #pragma unroll
                     for (int s_ = 0; s_ < 2 * NP; ++s_) qr[r] = fma(acc[s_][r], acc[s_][r], qr[r]);
                 }
+                if constexpr (RHALF) {
+                    if (rh >= 0) {
+                        // the fold's inputs instead of a share (acc[8 .. 15] are zero: qr is the chain over s = 0 .. 7);
+                        // [16-byte piece][matrix thread]: a wavefront's store is 1 KiB in one piece
+                        double* item = s2_fold_item(a.sp_q, nrb2, a.blk_end, blk0, jb);
+                        if (rh == 0) {
+                            f64x2* P = (f64x2*)item + t;
+                            f64x2 v0, v1;
+                            v0.x = qr[0]; v0.y = qr[1]; v1.x = qr[2]; v1.y = qr[3];
+                            P[0] = v0; P[256] = v1;
+                        } else {
+                            f64x2* A = (f64x2*)(item + S2_HQ_PRE) + t;
+#pragma unroll
+                            for (int s_ = 0; s_ < NP; ++s_) {
+                                f64x2 v0, v1;
+                                v0.x = acc[s_][0]; v0.y = acc[s_][1]; v1.x = acc[s_][2]; v1.y = acc[s_][3];
+                                A[(2 * s_) * 256] = v0; A[(2 * s_ + 1) * 256] = v1;
+                            }
+                        }
+                    }
+                }
                 double qs = qr[0];
 #pragma unroll
                 for (int r = 1; r < 4; ++r) qs += __shfl(qr[r], (lane & 48) | ((lane - 4 * r) & 15));
@@ -774,8 +881,10 @@ __global__ __launch_bounds__(S2_THREADS, 1) void sweep2_kernel(SweepArgs a) {
             if (kq == 0) {
                 // (LIST: the shares are indexed by the block's position in the list -- a split workgroup has one block)
                 const long long e = ((LIST ? blk0 : blk_fin - a.blk_begin) * SW_CAND + hw * 16 + cl) * nrb2 + jb_lo;
-                a.sp_q[e] = Shq[hw * 16 + cl];
-                a.sp_mu[e] = mu_fin;
+                // (RHALF: a half item's share of sum V^2 comes from sweep_fold_kernel; both halves hold the same share of
+                // mu, the upper one stores it)
+                if (!RHALF || rh < 0) a.sp_q[e] = Shq[hw * 16 + cl];
+                if (!RHALF || rh <= 0) a.sp_mu[e] = mu_fin;
             }
             __syncthreads();                      // E2
             return;
@@ -831,6 +940,16 @@ __global__ __launch_bounds__(S2_THREADS, 1) void sweep2_kernel(SweepArgs a) {
         auto dma_tile = [&](int slot, int jb, int kc) {
             double* dst = Aring + slot * S2_TILE + hw_s * 128;
             const unsigned toffs = tile_off(jb, kc);
+            if constexpr (RHALF) {
+                // a half item: pieces 4 h .. 4 h + 3 of the image into pieces 0 .. 3 of the slot
+                if (rh >= 0) {
+#pragma unroll
+                    for (int q = 0; q < 4; ++q)
+                        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_w, (lds_void*)(dst + q * 512), 16, (unsigned)lane * 16u,
+                                                                 toffs + (unsigned)((q + rsh) * 4096) + (unsigned)hw_s * 1024u, 0, 0);
+                    return;
+                }
+            }
 #pragma unroll
             for (int q = 0; q < 8; ++q)
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_w, (lds_void*)(dst + q * 512), 16, (unsigned)lane * 16u,
@@ -933,6 +1052,16 @@ __global__ __launch_bounds__(S2_THREADS, 1) void sweep2_kernel(SweepArgs a) {
         auto dma_tile = [&](int slot, int jb, int kc) {
             double* dst = Aring + slot * S2_TILE + hw_s * 128;
             const unsigned toffs = tile_off(jb, kc);
+            if constexpr (RHALF) {
+                // a half item: pieces 4 h .. 4 h + 3 of the image into pieces 0 .. 3 of the slot
+                if (rh >= 0) {
+#pragma unroll
+                    for (int q = 0; q < 4; ++q)
+                        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_w, (lds_void*)(dst + q * 512), 16, (unsigned)lane * 16u,
+                                                                 toffs + (unsigned)((q + rsh) * 4096) + (unsigned)hw_s * 1024u, 0, 0);
+                    return;
+                }
+            }
 #pragma unroll
             for (int q = 0; q < 8; ++q)
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_w, (lds_void*)(dst + q * 512), 16, (unsigned)lane * 16u,
@@ -1062,9 +1191,38 @@ __global__ __launch_bounds__(64) void sweep_finish_kernel(SweepArgs a) {
     if (c == 0) { a.part_u[blk] = bu; a.part_i[blk] = bi; }
 }
 
+// The fold of the row-half items (between the seed launch and sweep_finish_kernel): one workgroup per (list position,
+// row block), its 256 threads the matrix threads of the item.  For a row block that went as two halves it runs the
+// chain of squares on from the upper half's prefix through the lower half's 32 stored accumulators, in the whole
+// item's order, and writes the share the whole item would have written.  Sized for the cap; leaves on the device count.
+__global__ __launch_bounds__(256) void sweep_fold_kernel(SweepArgs a) {
+    const long long cnt = *a.blk_count;
+    const int pos = (int)blockIdx.x / a.nrb, jb = (int)blockIdx.x % a.nrb;
+    if (cnt <= a.list_lo || cnt > a.list_hi || pos >= cnt || !s2_halved(jb, a.split - 2, a.n)) return;
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const double* base = s2_fold_item(a.sp_q, a.nrb, a.blk_end, pos, jb);
+    const f64x2* P = (const f64x2*)base + t;
+    const f64x2* A = (const f64x2*)(base + S2_HQ_PRE) + t;
+    double qr[4];
+    {
+        const f64x2 v0 = P[0], v1 = P[256];
+        qr[0] = v0.x; qr[1] = v0.y; qr[2] = v1.x; qr[3] = v1.y;
+    }
+#pragma unroll
+    for (int s_ = 0; s_ < S2_NP; ++s_) {
+        const f64x2 v0 = A[(2 * s_) * 256], v1 = A[(2 * s_ + 1) * 256];
+        qr[0] = fma(v0.x, v0.x, qr[0]);
+        qr[1] = fma(v0.y, v0.y, qr[1]);
+        qr[2] = fma(v1.x, v1.x, qr[2]);
+        qr[3] = fma(v1.y, v1.y, qr[3]);
+    }
+    double qtot = 0.0;
+    qtot += s2_q_gather(qr, lane);                // (as the kernel: the share is 0 + the row block's sum)
+    if ((lane >> 4) == 0) a.sp_q[((long long)pos * SW_CAND + w * 16 + (lane & 15)) * a.nrb + jb] = qtot;
+}
+
 // blocks of the last round that are split by row block (measured break-even at N = 4096:
-// ~190 of 256 -- the split launch regenerates every k* and its largest item is 1/nrb of a block)
-#define S2_SPLIT_MAX 184
+// ~190 of 256 -- the split launch regenerates every k* and its largest item is 1/nrb of a block): S2_SPLIT_MAX, above
 
 static inline int s2_nrb(int64_t n) { return (int)((n + S2_ROWS - 1) / S2_ROWS); }
 // chunks per workgroup slot whose B operands are revisited by a later 256-row block
@@ -1094,7 +1252,8 @@ static int s2_prepare_device() {
                            (const void*)sweep2_kernel<DPAD, false, 2>, (const void*)sweep2_kernel<DPAD, true, 2>,
                            (const void*)sweep2_kernel<DPAD, false, 0, true>, (const void*)sweep2_kernel<DPAD, true, 0, true>,
                            (const void*)sweep2_kernel<DPAD, false, 1, true>, (const void*)sweep2_kernel<DPAD, true, 1, true>,
-                           (const void*)sweep2_kernel<DPAD, false, 2, true>, (const void*)sweep2_kernel<DPAD, true, 2, true>});
+                           (const void*)sweep2_kernel<DPAD, false, 2, true>, (const void*)sweep2_kernel<DPAD, true, 2, true>,
+                           (const void*)sweep2_kernel<DPAD, false, 0, true, true>, (const void*)sweep2_kernel<DPAD, true, 0, true, true>});
 }
 
 // one launch of the kernel that fits (form, N, LinearKernel term); LIST: its blocks come from a.blk_list
@@ -1148,9 +1307,63 @@ static int launch_sweep(const SweepArgs& a0, hipStream_t s, bool solve) {
 // round trip: up to `cap` blocks (inverse form, N > 256) go split by row block -- a grid sized for cap blocks whose
 // surplus workgroups leave at once --, more than cap over the persistent grid; both launches are enqueued and the
 // count decides on the device which of them works.
+// ---- which row blocks of the seed launch go as two halves ----
+// -1: the rule below; v >= 0: J0 = v (0: every row block with a lower half, v >= nrb: none -- the launch without halves)
+static int g_seed_rowsplit = -1;
+
+extern "C" int apgp_set_seed_rowsplit(int v) {
+    return __atomic_exchange_n(&g_seed_rowsplit, v < 0 ? -1 : v, __ATOMIC_RELAXED);
+}
+
+extern "C" int apgp_get_seed_rowsplit(void) { return __atomic_load_n(&g_seed_rowsplit, __ATOMIC_RELAXED); }
+
+// Time of a launch of cap x (row items for J0) workgroups on SW_GRID CUs, one at a time per CU, in the order the
+// kernel numbers them (s2_row_item: heaviest first), each to the CU that falls free first; in units of the cost model
+// (S2_WHOLE_COST per tile of a whole item, S2_HALF_COST per tile of a half item or of a last block of <= 128 rows).
+static long long seed_launch_cost(int nrb, int cap, int n, int j0) {
+    long long load[SW_GRID] = {0};
+    const int nitem = nrb + s2_nhalved(nrb, j0, n);
+    long long last = 0;
+    for (int i = 0; i < nitem; ++i) {
+        int jb = 0, h = -1;
+        s2_row_item(i, nrb, j0, n, jb, h);
+        const bool light = h >= 0 || n - S2_ROWS * jb <= S2_ROWS / 2;
+        const long long c = (long long)(light ? S2_HALF_COST : S2_WHOLE_COST) * s2_nkc_of(jb, n);
+        for (int k = 0; k < cap; ++k) {
+            int best = 0;
+            for (int q = 1; q < SW_GRID; ++q)
+                if (load[q] < load[best]) best = q;
+            load[best] += c;
+            if (load[best] > last) last = load[best];
+        }
+    }
+    return last;
+}
+
+// The rule: J0 of {0, nrb / 2, nrb} with the shortest modelled launch (ties: the fewest items).  Remembered for the last
+// (nrb, cap, n): a fit's calls repeat them.
+static int seed_j0(int nrb, int cap, int n) {
+    const int v = apgp_get_seed_rowsplit();
+    if (v >= 0) return v < nrb ? v : nrb;
+    static std::mutex mu;
+    static int k_nrb = -1, k_cap = -1, k_n = -1, k_j0 = 0;
+    std::lock_guard<std::mutex> g(mu);
+    if (k_nrb != nrb || k_cap != cap || k_n != n) {
+        int best = nrb;
+        long long best_c = seed_launch_cost(nrb, cap, n, nrb);
+        for (int j0 : {nrb / 2, 0}) {
+            const long long c = seed_launch_cost(nrb, cap, n, j0);
+            if (c < best_c) { best = j0; best_c = c; }
+        }
+        k_nrb = nrb; k_cap = cap; k_n = n; k_j0 = best;
+    }
+    return k_j0;
+}
+
+// `rowsplit` (the seed launch): row blocks from seed_j0 on go as two row-half items each, folded by sweep_fold_kernel.
 template <int DPAD>
 static void launch_sweep_list(const SweepArgs& a0, hipStream_t s, bool solve, const long long* list,
-                              const long long* count, long long max_count, long long cap) {
+                              const long long* count, long long max_count, long long cap, bool rowsplit = false) {
     SweepArgs a = a0;
     const int nrb2 = s2_nrb(a.n);
     a.nrb = nrb2;
@@ -1162,7 +1375,20 @@ static void launch_sweep_list(const SweepArgs& a0, hipStream_t s, bool solve, co
         SweepArgs b = a;
         b.split = 1; b.ncache = 0; b.kslot_bytes = SW_BCH * 8;
         b.list_lo = 0; b.list_hi = cap;
-        s2_launch<DPAD, true>(b, s, solve, (unsigned)(cap * nrb2));
+        const int j0 = rowsplit ? seed_j0(nrb2, (int)cap, b.n) : nrb2;
+        const int nhalf = s2_nhalved(nrb2, j0, b.n);
+        if (nhalf > 0) {
+            const size_t lds = s2_lds_bytes<DPAD>();
+            const unsigned grid = (unsigned)(cap * (nrb2 + nhalf));
+            b.split = 2 + j0;
+            if (b.lin_coef != 0.0)
+                hipLaunchKernelGGL((sweep2_kernel<DPAD, true, 0, true, true>), dim3(grid), dim3(S2_THREADS), lds, s, b);
+            else
+                hipLaunchKernelGGL((sweep2_kernel<DPAD, false, 0, true, true>), dim3(grid), dim3(S2_THREADS), lds, s, b);
+            hipLaunchKernelGGL(sweep_fold_kernel, dim3((unsigned)(cap * nrb2)), dim3(256), 0, s, b);
+        } else {
+            s2_launch<DPAD, true>(b, s, solve, (unsigned)(cap * nrb2));
+        }
         hipLaunchKernelGGL(sweep_finish_kernel, dim3((unsigned)cap), dim3(64), 0, s, b);
     }
     if (!can_split || max_count > cap) {
@@ -1872,7 +2098,7 @@ static int launch_pruned(const SweepArgs& a, hipStream_t s, bool solve, void* pa
     launch_bound<DPAD>(p, s, coarse);
     hipLaunchKernelGGL(prune_seed_kernel, dim3(1), dim3(1024), 0, s, coarse ? (const double*)p.est : (const double*)bmin, ncb,
                        seeds, counts);
-    launch_sweep_list<DPAD>(a, s, solve, seeds, counts, ncb < PR_SEED ? ncb : PR_SEED, PR_SEED);
+    launch_sweep_list<DPAD>(a, s, solve, seeds, counts, ncb < PR_SEED ? ncb : PR_SEED, PR_SEED, true);
     hipLaunchKernelGGL(prune_select_kernel, dim3(1), dim3(1024), 0, s, bmin, ncb, seeds, counts, a.part_u, 0.0, list,
                        counts + 3);
     if (coarse) {
@@ -1889,11 +2115,17 @@ static int launch_pruned(const SweepArgs& a, hipStream_t s, bool solve, void* pa
 // parked operands | 2 x S2_SPLIT_MAX x SW_CAND x nrb row-block shares of the split last round (s2_work_len up to
 // here) | pruned sweep: ncb block bounds bmin | ncb surviving block numbers | PR_SEED seed block numbers | 8 words:
 // seed count, survivor count, bit pattern of tau, blocks the coarse bound kept (list A; list B is written over it) |
-// ncb block minima of the coarse stage's b without slack]
+// ncb block minima of the coarse stage's b without slack | PR_SEED x nrb x (S2_HQ_PRE + S2_HQ_ACC) fold inputs of the seed
+// launch's row-half items (from pr_work_len, an even offset: 16-byte accesses; n > S2_ROWS only)]
+static_assert(S2_PRUNE_WORDS == PR_SEED + 8, "the fold inputs start behind the seed numbers and the counters");
+static inline long long pr_work_len(int64_t m, int64_t n) {       // (sp_q lies 2 S2_SPLIT_MAX SW_CAND nrb before s2_work_len)
+    return s2_work_len(m, n) - 2ll * S2_SPLIT_MAX * SW_CAND * s2_nrb(n) + s2_fold_off(s2_nrb(n), pr_ncb(m));
+}
+
 extern "C" int64_t apgp_acquire_work_len(int64_t m, int64_t n) {
     if (m < 1 || n < 1) return 0;
     if (m > APGP_MAX_M || n > APGP_MAX_N) return -1;
-    return s2_work_len(m, n) + 3 * pr_ncb(m) + PR_SEED + 8;
+    return pr_work_len(m, n) + (s2_nrb(n) >= 2 ? (long long)PR_SEED * s2_nrb(n) * (S2_HQ_PRE + S2_HQ_ACC) : 0);
 }
 
 static int acquire_impl(bool solve, const double* T, int64_t m, int64_t idx_offset, const double* packed_linv,

@@ -490,7 +490,11 @@ class GP(GeorgeExtras):
         # arg-min-only sweeps skip candidate blocks that cannot win (apgp_set_sweep_prune): None: the library's
         # process-wide setting (default on); False / 0: the full sweep; True / 1: on; >= 2: on from that many candidates
         self.sweep_prune = None
-        self.sweep_prune_stats = False    # True: keep (seed blocks, surviving blocks, bits of tau, blocks the coarse
+        # the pruned sweep's seed launch sends the 256-row blocks of W from this one on as two 128-row workgroups each
+        # (apgp_set_seed_rowsplit; same bits whatever the value): None: the library's process-wide setting (default:
+        # its rule); -1: the rule; 0: every row block; >= ceil(n / 256): none
+        self.seed_rowsplit = None
+        self.sweep_prune_stats = False   # True: keep (seed blocks, surviving blocks, bits of tau, blocks the coarse
         self.last_prune_counts = None     # bound left) of the last pruned sweep here, as a device int64[4] tensor
         self._computed = False
         self._x = None
@@ -1417,6 +1421,7 @@ class GP(GeorgeExtras):
                     float(zeta), float(np.max(y)), _ptr(mu), _ptr(var), _ptr(u), part.data_ptr(), best.data_ptr(),
                     _ptr(self._prune_rows), st)
             prune_was = None if self.sweep_prune is None else lib.apgp_set_sweep_prune(int(self.sweep_prune))
+            rowsplit_was = None if self.seed_rowsplit is None else lib.apgp_set_seed_rowsplit(int(self.seed_rowsplit))
             try:
                 if use_solve:
                     _lib.check(lib.apgp_acquire_solve_rows(T.data_ptr(), m, int(idx_offset),
@@ -1427,6 +1432,8 @@ class GP(GeorgeExtras):
             finally:
                 if prune_was is not None:
                     lib.apgp_set_sweep_prune(prune_was)
+                if rowsplit_was is not None:
+                    lib.apgp_set_seed_rowsplit(rowsplit_was)
             if self.sweep_prune_stats and kind_id != _lib.UTIL_NONE and mu is None and var is None and u is None:
                 off = int(lib.apgp_sweep_prune_counts_offset(m, n))
                 self.last_prune_counts = part[off:off + 4].view(torch.int64).clone()

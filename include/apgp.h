@@ -305,7 +305,10 @@ int apgp_pack_train(const double* X, const double* alpha, int64_t n,
  *       one row block so that later row blocks do not regenerate them, and the
  *       per-row-block shares of the candidate blocks of a short last round
  *       (those are split over one workgroup per row block), and the block
- *       bounds, block lists and counters of the pruned arg-min (below).
+ *       bounds, block lists and counters of the pruned arg-min (below), and
+ *       last, for n > 256, the fold inputs of its seed step's row-half
+ *       workgroups (16 seed blocks x ceil(n / 256) row blocks x 9216 doubles:
+ *       the upper half's sums so far and the lower half's accumulators).
  * best: device apgp_best_t, written by the final reduction kernel.
  * ybest = max(y) and zeta are used by JONES only.                            */
 int64_t apgp_acquire_work_len(int64_t m, int64_t n);
@@ -364,9 +367,17 @@ int apgp_acquire_solve(const double* T, int64_t m, int64_t idx_offset,
  * bmin: ncb block bounds; seeds: 16 int64 block numbers of which the first counts[0] are read;
  * counts: int64[3], [0] read, [1] and [2] written (survivor count, bit pattern of tau); list: ncb
  * int64, receives the blocks with bmin < +inf, bmin <= tau that are no seeds, in ascending order.
- * All pointers device memory.                                                              */
+ * All pointers device memory.
+ * apgp_set_seed_rowsplit(v): process-wide switch of the seed step's launch, returns the previous value.  That
+ * launch is one workgroup per (seed block, 256-row block of W); a row block at or above J0 that has rows in its
+ * lower half goes as TWO workgroups of 128 rows each, and a fold step puts their sums together in the whole row
+ * block's order -- the bits do not depend on J0.  -1 (default): J0 by the library's rule (a model of the launch on
+ * the chip's 256 CUs); v >= 0: J0 = v (0: every such row block, v >= ceil(n / 256): none).  Inverse form only;
+ * apgp_acquire_solve ignores it.  Added in ABI 8 without changing anything before it: APGP_ABI_VERSION stays 8.  */
 int apgp_set_sweep_prune(int v);
 int apgp_get_sweep_prune(void);
+int apgp_set_seed_rowsplit(int v);
+int apgp_get_seed_rowsplit(void);
 int64_t apgp_sweep_prune_counts_offset(int64_t m, int64_t n);
 int apgp_sweep_prune_select(const double* bmin, int64_t ncb, const int64_t* seeds, int64_t* counts,
                             double tau, int64_t* list, void* stream);
