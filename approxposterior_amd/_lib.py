@@ -60,6 +60,7 @@ class EnsMove(ctypes.Structure):
 
 ENS_MOVE_STRETCH, ENS_MOVE_DE, ENS_MOVE_SNOOKER = 0, 1, 2
 ENS_MAX_MOVES = 8     # APGP_ENS_MAX_MOVES
+PT_MAX_TEMPS = 64     # APGP_PT_MAX_TEMPS: rungs of a tempering ladder
 
 _P = ctypes.c_void_p
 _I64 = ctypes.c_int64
@@ -151,6 +152,10 @@ SIGNATURES = {
                                                   _I32, _I32, _I64, _F64, ctypes.c_uint64, _P, _P, _P, _P, _P, ctypes.c_int,
                                                   ctypes.POINTER(EnsMove), _I32, _P]),
     "apgp_ensemble_mode": (ctypes.c_int, [ctypes.c_int]),
+    "apgp_tempered_work_len": (_I64, [_I32, _I32, _I32, _I32]),
+    "apgp_tempered_sample": (ctypes.c_int, [_P, _I64, _KP, _F64, ctypes.POINTER(_F64), ctypes.POINTER(_F64), _I32, _I32, _I32,
+                                            ctypes.POINTER(_F64), _I64, _I64, ctypes.c_uint64, _P, _P, _P, _I32, _P, _P, _P,
+                                            _P, _P, ctypes.POINTER(EnsMove), _I32, _P, _P]),
     "apgp_box_candidates": (ctypes.c_int, [_P, _I64, _I32, ctypes.POINTER(_F64), ctypes.POINTER(_F64), ctypes.c_uint64,
                                            _I64, _P]),
     "apgp_prior_candidates": (ctypes.c_int, [_P, _I64, _I32, _P, _P, _P, ctypes.c_uint64, _I64, _P]),

@@ -600,7 +600,7 @@ class ApproxPosterior(object):
 
     def runMCMC(self, samplerKwargs=None, mcmcKwargs=None, runName="apRun",
                 cache=True, estBurnin=True, thinChains=True, verbose=False,
-                args=None, batched=True, onDevice=False, deviceAutocorr=False, **kwargs):
+                args=None, batched=True, onDevice=False, deviceAutocorr=False, tempering=None, **kwargs):
         """Sample the GP-surrogate posterior with the stretch-move ensemble sampler and
         estimate burn-in / thinning (approx.py:757-859): ``(sampler, iburn, ithin)``.
         ``samplerKwargs["moves"]`` (``mcmc.moves.DEMove()``, ``DESnookerMove()``, weighted lists, as emcee's ``moves``)
@@ -618,10 +618,21 @@ class ApproxPosterior(object):
         ``deviceAutocorr=True`` (opt-in, needs ``onDevice=True``): the chain also stays on the device and
         ``estimateBurnin`` gets its autocorrelation time from there (``mcmc.integrated_time(onDevice=True)``); under a
         process group every rank uploads the gathered chain once and computes the same ``(iburn, ithin)``.
+        ``tempering`` (opt-in, needs ``onDevice=True``): parallel tempering (``GP.sample_tempered``) for a multimodal
+        surrogate -- an int (the rungs of the default ladder, ``mcmc.tempering_ladder``) or a dict with any of ``betas``,
+        ``ntemps``, ``betaMin``, ``swapEvery``, ``ladders``.  ``self.sampler`` is then a :class:`mcmc.TemperedChain`:
+        the cold rungs behind the usual accessors (burn-in, blobs, caching and ``evidence(proposal="gmm")`` work on
+        them as they do on a ``DeviceChain``), plus the ladder's diagnostics and ``log_evidence()``.
+        ``NotImplementedError`` under a process group.
         """
         if deviceAutocorr and not onDevice:
             raise ValueError("runMCMC(deviceAutocorr=True) diagnoses the chain of the device sampler: it needs onDevice=True")
+        if tempering is not None and not onDevice:
+            raise ValueError("runMCMC(tempering=...) tempers the device sampler: it needs onDevice=True")
         ranks = self._ranks()
+        if tempering is not None and ranks is not None:
+            raise NotImplementedError("tempering under a process group: the ladders would have to be sharded over the "
+                                      "ranks and their rung means gathered")
         if ranks is not None:
             apdist.sync_random_state(0, self.group, enabled=self.distributed)
             verbose, cache = verbose and ranks[0] == 0, cache and ranks[0] == 0
@@ -636,7 +647,10 @@ class ApproxPosterior(object):
                 p0 = p0.reshape(samplerKwargs["nwalkers"], self.ndim)
             if p0.shape != (samplerKwargs["nwalkers"], self.ndim):
                 raise ValueError("incompatible input dimensions")
-        if onDevice or ranks is not None:
+        if tempering is not None:
+            self.sampler = self._sampleTempered(np.random.randint(0, 2 ** 31 - 1), samplerKwargs, mcmcKwargs, tempering,
+                                                deviceAutocorr)
+        elif onDevice or ranks is not None:
             # one ensemble per rank, seeded base + rank, gathered once along the walker axis
             # (no ranks -- no process group, or distributed=False inside somebody else's: the local chain, seed
             # ``base``, and no collective whatever group the process has open)
@@ -672,6 +686,35 @@ class ApproxPosterior(object):
                                                 thinChains=thinChains, verbose=verbose)
         self._chainCut = (iburn, ithin)     # (evidence(proposal="gmm") fits its proposal to the chain cut this way)
         return self.sampler, iburn, ithin
+
+    def _sampleTempered(self, seed, samplerKwargs, mcmcKwargs, tempering, keepDevice):
+        """The :class:`mcmc.TemperedChain` of ``runMCMC(tempering=...)``: ``tempering`` is the number of rungs of the
+        default ladder or a dict (``betas`` | ``ntemps``, ``betaMin``; ``swapEvery``, ``ladders``).  The default ladder
+        ends at beta = 0 where the box is finite."""
+        spec = {"ntemps": tempering} if isinstance(tempering, (int, np.integer)) and not isinstance(tempering, bool) \
+            else tempering
+        known = ("betas", "ntemps", "betaMin", "swapEvery", "ladders")
+        if not isinstance(spec, dict) or any(k not in known for k in spec):
+            raise ValueError("tempering must be an int (rungs) or a dict with keys from %s" % (known,))
+        joint = self._jointPrior()
+        box = np.asarray(self.bounds if joint is None else joint.support(), dtype=np.float64).reshape(-1, 2)
+        if "betas" in spec:
+            if "ntemps" in spec or "betaMin" in spec:
+                raise ValueError("tempering: betas is the whole ladder; ntemps and betaMin describe the default one")
+            betas = np.asarray(spec["betas"], dtype=np.float64)
+        else:
+            ladder = {} if "betaMin" not in spec else {"betaMin": spec["betaMin"]}
+            betas = emcee.tempering_ladder(spec.get("ntemps", 4), zero=bool(np.all(np.isfinite(box))), **ladder)
+        extra = {} if joint is None else {"prior": joint}
+        if "swapEvery" in spec:
+            extra["swapEvery"] = spec["swapEvery"]
+        moves, a = samplerKwargs.get("moves"), samplerKwargs.get("a", 2.0)
+        if moves is None and float(a) != 2.0:
+            moves = emcee.StretchMove(a)
+        res = self.gp.sample_tempered(self.y, mcmcKwargs["initial_state"], mcmcKwargs["iterations"], self.bounds, betas,
+                                      seed=seed, ladders=spec.get("ladders", 1), moves=moves, keep_device=bool(keepDevice),
+                                      **extra)
+        return emcee.TemperedChain(res, a=a, moves=samplerKwargs.get("moves"))
 
     def _hostSampler(self, samplerKwargs, args, kwargs, batched, seed=None):
         setup = dict(samplerKwargs)
@@ -801,7 +844,7 @@ class ApproxPosterior(object):
             gpHyperPrior=gpUtils.defaultHyperPrior, eps=1.0, convergenceCheck=False,
             minObjMethod="nelder-mead", minObjOptions=None, args=None,
             nCandidates=None, onDevice=False, batched=True, deviceCandidates=None, batchSize=None, pool=None,
-            deviceSearch=None, deviceAutocorr=False, searchJac=False, batchMethod="believer", **kwargs):
+            deviceSearch=None, deviceAutocorr=False, searchJac=False, batchMethod="believer", tempering=None, **kwargs):
         """BAPE / AGP outer loop (approx.py:229-524): ``nmax`` times, find ``m`` design
         points (re-fitting the GP every ``optGPEveryN``), sample the surrogate posterior,
         record burn-in / thinning, and -- with ``convergenceCheck`` -- stop once the
@@ -815,9 +858,12 @@ class ApproxPosterior(object):
         "believer" or "thompson", how a batch is chosen), and ``deviceSearch``
         (the Nelder-Mead point search on the device) and ``searchJac`` (exact gradients for a gradient
         ``minObjMethod``).  ``deviceAutocorr`` is passed to :meth:`runMCMC` too (burn-in and
-        thinning from the device's autocorrelation estimate; needs ``onDevice=True``)."""
+        thinning from the device's autocorrelation estimate; needs ``onDevice=True``), and so is ``tempering``
+        (parallel tempering of the device sampler; needs ``onDevice=True``)."""
         if deviceAutocorr and not onDevice:
             raise ValueError("run(deviceAutocorr=True) needs onDevice=True")
+        if tempering is not None and not onDevice:
+            raise ValueError("run(tempering=...) tempers the device sampler: it needs onDevice=True")
         if batchMethod not in ("believer", "thompson"):
             raise ValueError('batchMethod must be "believer" or "thompson"')
         if batchMethod == "thompson" and batchSize is None:
@@ -865,7 +911,8 @@ class ApproxPosterior(object):
                                            runName="%s%d" % (runName, iteration), cache=cache,
                                            estBurnin=estBurnin, thinChains=thinChains,
                                            verbose=verbose, args=args, onDevice=onDevice,
-                                           batched=batched, deviceAutocorr=deviceAutocorr, **kwargs)
+                                           batched=batched, deviceAutocorr=deviceAutocorr, tempering=tempering,
+                                           **kwargs)
             self.iburns.append(iburn)
             self.ithins.append(ithin)
             if timing:

@@ -1,7 +1,8 @@
 // Proposals of the on-device ensemble sampler and the counter-based RNG they draw from.  ensemble_kernel and
-// ensemble_mw_kernel (ensemble.hip) share one sampler body so that the two cannot drift apart: ens_propose here, and in
-// ensemble.hip, above the kernels, the walker load, the GP-mean row loops, the start gate, the iteration prologue, the slot
-// index, the accept step and the walker store.  tests/ensemble_moves_ref.py states the recipe; this file implements that text.
+// ensemble_mw_kernel (ensemble.hip) and tempered_kernel (tempering.hip) share one sampler body so that they cannot drift
+// apart: ens_propose here, and in ens_body.h the walker load, the GP-mean row loops, the start gate, the iteration prologue,
+// the slot index, the accept step and the walker store.  tests/ensemble_moves_ref.py states the recipe; this file implements
+// that text.
 //
 // A half-step moves slot t of the active half S (walker s) against the complement C (H = W / 2 slots), all slots in
 // parallel against the positions at its start, which are the kernel's scaled coordinates x * sc.  Every draw is a pure
@@ -14,7 +15,9 @@
 //   tag 3: differential evolution -- j = word 0 % H, k = word 1 % (H - 1), k += (k >= j): an ordered pair j != k;
 //   tag 4: differential evolution -- n = sqrt(-2 log u01(words 0, 1)) cospi(2 u01(words 2, 3)): Box-Muller, the cosine
 //          with its argument reduced exactly (2 u is exact);
-//   tag 6: snooker -- j, k as tag 3, l = word 2 % (H - 2), l += (l >= min(j, k)), l += (l >= max(j, k)).
+//   tag 6: snooker -- j, k as tag 3, l = word 2 % (H - 2), l += (l >= min(j, k)), l += (l >= max(j, k));
+//   tag 7: parallel tempering (tempering.hip) -- counter (round low, round high, walker, 7) under the keys of the pair's
+//          lower rung: u01(words 0, 1) is the exchange uniform.
 // Moves:
 //   stretch(a):           z = (a - 1) u + 1, zz = z z / a, q = c_j - (c_j - s) zz, factor (D - 1) log zz;
 //   DE(sigma, g0):        gamma = g0 (1 + sigma n), q = s + gamma (c_j - c_k), factor 0;

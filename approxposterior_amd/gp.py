@@ -2042,6 +2042,118 @@ class GP(GeorgeExtras):
                 out["blobs"] = np.where(np.isneginf(blobs), np.nan, blobs)
         return out
 
+    def sample_tempered(self, y, initial_state, iterations, bounds, betas, swapEvery=10, seed=0, ladders=1, storeRungs=1,
+                        moves=None, prior=None, keep_device=False, swapLog=False):
+        """Parallel tempering of :meth:`sample_ensemble` on the device (``apgp_tempered_sample``): ``ladders``
+        independent ladders of ``len(betas)`` ensembles ("rungs"); rung k samples ``exp(betas[k] * mu)`` on the box
+        with the moves of :meth:`sample_ensemble`, and neighbouring rungs propose to exchange walkers every
+        ``swapEvery`` iterations.  ``betas`` starts at 1 (the cold rung is the posterior), stays in [0, 1] and does
+        not increase; a final 0 -- the rung that samples the box uniformly, which needs finite ``bounds`` -- makes
+        ``mcmc.TemperedChain.log_evidence`` possible.
+
+        ``initial_state`` is (W, D), used for every rung, (T, W, D), used for every ladder, or (L, T, W, D).
+        Returns the keys of :meth:`sample_ensemble` for the cold rungs, the ladders' side by side on the walker axis
+        (``chain`` (iterations, L*W, D), ``log_prob``, ``coords``, ``final_log_prob``, ``naccept``; ``blobs`` with
+        ``prior``, ``chain_device`` with ``keep_device``), and ``betas``, ``rung_naccept`` (L, T, W), ``swap_proposed``
+        and ``swap_accepted`` (L, T - 1), ``rung_mean_log_prob`` (iterations, L, T) -- the walker mean of mu per rung,
+        reduced on the device --, ``rung_coords`` (L, T, W, D), ``rung_final_log_prob`` (L, T, W), ``swap_every``.
+        ``storeRungs=S`` > 1 also stores rungs 0 .. S - 1: ``rung_chain`` (iterations, L, S, W, D) and
+        ``rung_log_prob`` (iterations, L, S, W).  ``swapLog`` adds ``swap_log`` (rounds, L, T - 1, W) uint8: 0 = not
+        proposed, 1 = rejected, 2 = accepted.  ``moves`` and ``prior`` as for :meth:`sample_ensemble`."""
+        self.recompute()
+        torch, dev, lib = self._rt()
+        y = self._check_dimensions(y)
+        D = self.kernel.ndim
+        betas = np.ascontiguousarray(np.asarray(betas, dtype=np.float64).ravel())
+        T, L, S = len(betas), int(ladders), int(storeRungs)
+        if T < 1 or betas[0] != 1.0:
+            raise ValueError("betas must start at 1: the cold rung is the posterior")
+        if L < 1:
+            raise ValueError("ladders must be at least 1")
+        if not 1 <= S <= T:
+            raise ValueError("storeRungs must lie between 1 and the number of rungs")
+        p0 = np.asarray(initial_state, dtype=np.float64)
+        if p0.ndim not in (2, 3, 4) or p0.shape[-1] != D or (p0.ndim >= 3 and p0.shape[-3] != T) or \
+                (p0.ndim == 4 and p0.shape[0] != L):
+            raise ValueError("initial_state must be (W, D), (T, W, D) or (L, T, W, D)")
+        W = p0.shape[-2]
+        # (a writable copy in C order: the default order of a copy follows the broadcast view's zero strides)
+        p0 = np.array(np.broadcast_to(p0, (L, T, W, D)), order="C")
+        if not np.all(np.isfinite(p0)):
+            raise ValueError("At least one parameter value was NaN or infinite")
+        if prior is not None:
+            records = self._prior_records(prior, D)
+            bounds = prior.support()
+        lo, hi = _box(bounds, D, optional=False)
+        n = len(self._x)
+        ks = self._kernel_struct()
+        iterations, swapEvery = int(iterations), int(swapEvery)
+        if swapEvery < 1:
+            raise ValueError("swapEvery must be at least 1")
+        rounds = max(0, -(-iterations // swapEvery) - 1)
+        table, ntable = None, 0
+        if moves is not None:
+            from . import mcmc
+            pairs = mcmc.move_table(moves, W)
+            table, ntable = (_lib.EnsMove * len(pairs))(), len(pairs)
+            for rec, (mv, w) in zip(table, pairs):
+                rec.kind, rec.p0, rec.p1 = mv.record(D)
+                rec.weight = w
+        need = int(lib.apgp_tempered_work_len(W, T, L, D))
+        with self._on(torch, dev):
+            st = self._stream(torch)
+            self._ensure_xs(y)
+            f64, i64 = dict(dtype=torch.float64, device=dev), dict(dtype=torch.int64, device=dev)
+            coords = torch.from_numpy(p0).to(dev)
+            logp = torch.empty((L, T, W), **f64)
+            nacc = torch.empty((L, T, W), **i64)
+            chain = torch.empty((iterations, L, S, W, D), **f64)
+            lchain = torch.empty((iterations, L, T, W), **f64)
+            sprop, sacc = torch.zeros((L, max(T - 1, 1)), **i64), torch.zeros((L, max(T - 1, 1)), **i64)
+            slog = torch.zeros((rounds, L, max(T - 1, 1), W), dtype=torch.uint8, device=dev) if swapLog else None
+            work = torch.empty(max(need, 1), **f64)
+            bb = (ctypes.c_double * T)(*betas)
+            _lib.check(lib.apgp_tempered_sample(self._xs.data_ptr(), n, ctypes.byref(ks), float(self.mean.value), lo, hi,
+                                                W, T, L, bb, iterations, swapEvery, _seed64(seed), coords.data_ptr(),
+                                                logp.data_ptr(), chain.data_ptr(), S, lchain.data_ptr(), nacc.data_ptr(),
+                                                sprop.data_ptr(), sacc.data_ptr(), _ptr(slog), table, ntable,
+                                                work.data_ptr(), st), "apgp_tempered_sample")
+            final = logp.cpu().numpy()
+            if np.any(np.isnan(final)):
+                raise FloatingPointError("the tempered sampler returned NaN log-probabilities: the GP mean is not finite at "
+                                         "the walkers' positions")
+            cold = chain[:, :, 0].contiguous() if S > 1 else chain.view(iterations, L, W, D)
+            rc = coords.cpu().numpy()
+            rn = nacc.cpu().numpy()
+            out = {"coords": rc[:, 0].reshape(L * W, D), "final_log_prob": final[:, 0].reshape(L * W),
+                   "naccept": rn[:, 0].reshape(L * W),
+                   "chain": cold.cpu().numpy().reshape(iterations, L * W, D),
+                   "log_prob": lchain[:, :, 0].cpu().numpy().reshape(iterations, L * W),
+                   "betas": betas.copy(), "swap_every": swapEvery, "rung_naccept": rn, "rung_coords": rc,
+                   "rung_final_log_prob": final,
+                   "swap_proposed": sprop.cpu().numpy()[:, :T - 1], "swap_accepted": sacc.cpu().numpy()[:, :T - 1],
+                   "rung_mean_log_prob": lchain.mean(dim=3).cpu().numpy()}
+            span = np.array([hi[d] - lo[d] for d in range(D)])
+            if np.all(np.isfinite(span)) and np.all(span > 0.0):
+                out["log_volume"] = float(np.sum(np.log(span)))
+            if S > 1:
+                out["rung_chain"] = chain.cpu().numpy()
+                out["rung_log_prob"] = lchain[:, :, :S].cpu().numpy()
+            if swapLog:
+                out["swap_log"] = slog.cpu().numpy()[:, :, :T - 1]
+            if keep_device:
+                out["chain_device"] = cold.view(iterations, L * W, D)
+            if prior is not None:
+                lp = torch.empty(iterations * L * W, **f64)
+                if iterations:
+                    kind, q0, q1 = records
+                    _lib.check(lib.apgp_prior_lnprior(cold.data_ptr(), iterations * L * W, D, kind.ctypes.data,
+                                                      q0.ctypes.data, q1.ctypes.data, lp.data_ptr(), st),
+                               "apgp_prior_lnprior")
+                blobs = lp.cpu().numpy().reshape(iterations, L * W)
+                out["blobs"] = np.where(np.isneginf(blobs), np.nan, blobs)
+        return out
+
     # -- K4: gradient of the log-likelihood ------------------------------------------
     def grad_log_likelihood(self, y, quiet=False):
         """george GP.grad_log_likelihood (gpUtils.py:110): zeros on failure when quiet."""

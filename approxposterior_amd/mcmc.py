@@ -584,3 +584,100 @@ class DeviceChain(EnsembleSampler):
         discard, thin = int(discard), int(thin)
         kwargs["onDevice"] = True
         return thin * integrated_time(self._chain_device[discard + thin - 1::thin], **kwargs)
+
+
+PT_MAX_TEMPS = 64     # APGP_PT_MAX_TEMPS
+
+
+def tempering_ladder(ntemps, betaMin=1.0e-3, zero=True):
+    """Inverse temperatures of a tempering ladder of ``ntemps`` rungs: beta_0 = 1, then geometrically down to
+    ``betaMin`` (0 < betaMin < 1) and, with ``zero``, a final rung beta = 0 -- the rung that samples the prior's box
+    uniformly, which :meth:`TemperedChain.log_evidence` needs.  ``ntemps`` counts the zero rung.  One rung is [1]; with
+    ``zero``, two rungs are [1, 0]."""
+    ntemps = int(ntemps)
+    if not 1 <= ntemps <= PT_MAX_TEMPS:
+        raise ValueError("ntemps must lie between 1 and %d" % PT_MAX_TEMPS)
+    if not 0.0 < float(betaMin) < 1.0:
+        raise ValueError("betaMin must lie strictly between 0 and 1")
+    geo = ntemps - 1 if (zero and ntemps > 1) else ntemps      # rungs of the geometric part
+    betas = np.ones(geo) if geo == 1 else float(betaMin) ** (np.arange(geo) / (geo - 1.0))
+    betas[0] = 1.0
+    if geo > 1:
+        betas[-1] = float(betaMin)
+    return np.append(betas, 0.0) if geo < ntemps else betas
+
+
+def _trapezoid_weights(betas):
+    """w with sum_k w_k f(beta_k) = the trapezoid rule of f over [beta_last, beta_0] for non-increasing ``betas``."""
+    b = np.asarray(betas, dtype=np.float64)
+    w = np.zeros(len(b))
+    if len(b) > 1:
+        gaps = b[:-1] - b[1:]
+        w[:-1] += 0.5 * gaps
+        w[1:] += 0.5 * gaps
+    return w
+
+
+class TemperedChain(DeviceChain):
+    """Result of a parallel-tempering run (``GP.sample_tempered``): the cold rungs (beta = 1, the posterior) of all
+    ladders behind the accessors of :class:`DeviceChain`, the ladder's own diagnostics, and the evidence by
+    thermodynamic integration."""
+
+    def __init__(self, result, a=2.0, moves=None):
+        super(TemperedChain, self).__init__(result, a=a, moves=moves)
+        self.betas = np.asarray(result["betas"], dtype=np.float64)
+        self.swap_every = result.get("swap_every")
+        self._rung_naccept = np.asarray(result["rung_naccept"], dtype=float)                 # (L, T, W)
+        self._swap_proposed = np.asarray(result["swap_proposed"], dtype=float)               # (L, T - 1)
+        self._swap_accepted = np.asarray(result["swap_accepted"], dtype=float)
+        self._rung_mean = np.asarray(result["rung_mean_log_prob"], dtype=np.float64)         # (iterations, L, T)
+        self._log_volume = result.get("log_volume")
+        self.nladders = self._rung_mean.shape[1]
+        self.ntemps = len(self.betas)
+
+    @property
+    def swap_acceptance_fraction(self):
+        """Accepted / proposed exchanges per neighbouring pair, summed over the ladders (T - 1,); NaN where none was proposed."""
+        prop, acc = self._swap_proposed.sum(axis=0), self._swap_accepted.sum(axis=0)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.where(prop > 0, acc / prop, np.nan)
+
+    @property
+    def rung_acceptance_fraction(self):
+        """Acceptance fraction of the moves per rung, averaged over ladders and walkers (T,)."""
+        return self._rung_naccept.mean(axis=(0, 2)) / max(self.iteration, 1)
+
+    def rung_means(self, discard=0):
+        """Mean of mu per ladder and rung over the iterations after ``discard`` (L, T)."""
+        rows = self._rung_mean[int(discard):]
+        if len(rows) == 0:
+            raise ValueError("discard leaves no iterations")
+        return rows.mean(axis=0)
+
+    def log_evidence(self, discard=0, logVolume=None):
+        """``(logZ, discErr, mcErr)`` by thermodynamic integration: ``logZ = log V + int_0^1 E_beta[mu] d beta``, V the
+        volume of the box (``logVolume``; default: the box the chain ran in), the integral by the trapezoid rule over
+        the rungs' means of mu after ``discard`` iterations.  ``discErr`` is the distance to the same rule over every
+        other rung (the end rungs kept): the size of the discretisation error, not a bound.  ``mcErr`` is the standard
+        error between the ladders' own estimates when there are several ladders, else the rungs' batch-means standard
+        errors (``mcmcUtils.batchMeansMCSE``) combined with the trapezoid weights.  ``ValueError`` unless the ladder
+        ends at beta = 0."""
+        if self.betas[-1] != 0.0 or self.betas[0] != 1.0:
+            raise ValueError("log_evidence integrates over beta from 0 to 1: the ladder must start at 1 and end at 0")
+        if logVolume is None:
+            logVolume = self._log_volume
+        if logVolume is None:
+            raise ValueError("log_evidence needs logVolume, the log-volume of the prior's box")
+        per = self.rung_means(discard)                                   # (L, T)
+        w = _trapezoid_weights(self.betas)
+        mean = per.mean(axis=0)
+        integral = float(np.dot(w, mean))
+        keep = sorted(set(range(0, self.ntemps, 2)) | {self.ntemps - 1})
+        coarse = float(np.dot(_trapezoid_weights(self.betas[keep]), mean[keep]))
+        if self.nladders > 1:
+            mc = float(np.std(per @ w, ddof=1) / np.sqrt(self.nladders))
+        else:
+            from .mcmcUtils import batchMeansMCSE
+            se = np.asarray(batchMeansMCSE(self._rung_mean[int(discard):, 0, :]), dtype=np.float64)
+            mc = float(np.sqrt(np.sum((w * se) ** 2)))
+        return float(logVolume) + integral, abs(integral - coarse), mc

@@ -667,6 +667,43 @@ int apgp_ensemble_sample_moves(const double* xs, int64_t n, const apgp_kernel_t*
                                double* logp_chain, int64_t* naccept, int mode,
                                const apgp_ens_move_t* moves /*host*/, int32_t nmoves, void* stream);
 
+/* Parallel tempering: nladders independent ladders of ntemps ensembles ("rungs") each.  Rung k of ladder l is ensemble
+ * e = l ntemps + k; it targets exp(betas[k] mu) on the box, betas (host) finite, in [0, 1] and not increasing.
+ *   Moves: exactly those of apgp_ensemble_sample_moves for ensemble e -- the same keys (k1 ^= e 0x9E3779B9), the same
+ *     counters with the GLOBAL iteration number, the same proposals; moves == NULL with nmoves == 0 is the stretch move
+ *     at a = 2.  The kernel keeps two values per walker, mu and the tempered value beta mu, which is -inf wherever mu
+ *     is not finite, at every beta (0 included); the accept step is the ensemble sampler's, fed the tempered values.
+ *     beta = 1 multiplies exactly: a beta = 1 rung makes the decisions apgp_ensemble_sample_moves(mode = 1) makes, bit
+ *     for bit.
+ *   Exchanges: round r = 0, 1, ... follows every swap_every iterations, except after the last.  It pairs rungs
+ *     (k, k + 1) with k = r (mod 2); an unpaired top or bottom rung sits the round out.  Walker i of rung k is exchanged
+ *     with walker i of rung k + 1 iff both mu are finite and log u < (beta_k - beta_{k+1}) (mu_{k+1,i} - mu_{k,i}), u =
+ *     u01 of Philox words 0, 1 under the keys of ensemble l ntemps + k with counter (r, r >> 32, i, 7).  Coordinates and
+ *     mu move together; naccept stays with the rung.
+ *   Outputs: coords (L x T x W x D, in = initial state, out = final state), logp (L x T x W: the final UNtempered mu),
+ *     naccept (L x T x W); chain (iterations x L x nstore x W x D, the first nstore rungs of every ladder; may be NULL,
+ *     0 <= nstore <= ntemps); logp_chain (iterations x L x T x W: untempered mu of ALL rungs, may be NULL); swap_prop /
+ *     swap_acc (L x (T - 1), required for ntemps > 1): exchanges proposed (both mu finite) and accepted per pair;
+ *     swap_log (uint8, rounds x L x (T - 1) x W with rounds = ceil(iterations / swap_every) - 1, may be NULL): every
+ *     decision, 0 = not proposed, 1 = rejected, 2 = accepted.
+ *   Schedule: one launch per segment of swap_every iterations, a workgroup per (ladder, rung), nothing waits inside a
+ *     launch and the call enqueues every launch without synchronising.  State passes between launches through two
+ *     halves of work (device, apgp_tempered_work_len doubles; -1 for sizes the call refuses) in the kernel's scaled
+ *     coordinates.  Not to be called twice at once with the same work.
+ * -1 before anything reaches the device: every check of apgp_ensemble_sample_moves; ntemps outside 1 ..
+ * APGP_PT_MAX_TEMPS; betas not finite, outside [0, 1] or increasing; beta = 0 with an infinite box edge; swap_every < 1;
+ * nstore outside 0 .. ntemps; nladders ntemps beyond the grid limit 2^31 - 1.
+ * Added in ABI 8 without changing anything before it: APGP_ABI_VERSION stays 8.                                   */
+#define APGP_PT_MAX_TEMPS 64
+int64_t apgp_tempered_work_len(int32_t nwalkers, int32_t ntemps, int32_t nladders, int32_t ndim);
+int apgp_tempered_sample(const double* xs, int64_t n, const apgp_kernel_t* kern /*host*/, double mean,
+                         const double* lo /*host, MAX_DIM*/, const double* hi /*host, MAX_DIM*/,
+                         int32_t nwalkers, int32_t ntemps, int32_t nladders, const double* betas /*host, ntemps*/,
+                         int64_t iterations, int64_t swap_every, uint64_t seed, double* coords, double* logp,
+                         double* chain, int32_t nstore, double* logp_chain, int64_t* naccept, int64_t* swap_prop,
+                         int64_t* swap_acc, uint8_t* swap_log, const apgp_ens_move_t* moves /*host*/, int32_t nmoves,
+                         double* work, void* stream);
+
 /* ---- candidate matrix of the sweep drawn on the device (round 5, opt-in) ------
  * The batched counterpart of the ``sampleFn`` draws utility.minimizeObjective starts from
  * (utility.py:334-338) when the prior is the box: T (m x ndim, device) row i =
