@@ -15,6 +15,8 @@ MAX_DIM = 32
 MAX_FANTASY = 32      # APGP_MAX_FANTASY: points per batch of GP.acquire_batch
 MAX_DRAWS = 32        # APGP_MAX_DRAWS: posterior function draws per apgp_path_draws call
 MAX_FEATURES = 65536  # APGP_MAX_FEATURES: random Fourier features of a draw
+MAX_REFS = 4096       # APGP_MAX_REFS: reference points per apgp_acquire_integrated call
+INTEGRATED_MAX_DIM = 16   # APGP_INTEGRATED_MAX_DIM: dimensions apgp_acquire_integrated takes
 
 UTIL_AGP, UTIL_BAPE, UTIL_JONES, UTIL_NONE = 0, 1, 2, 3
 UTIL_NEG_MEAN = 4     # -mu (ApproxPosterior.findMAP's objective): apgp_nm_search only
@@ -132,6 +134,10 @@ SIGNATURES = {
     "apgp_path_draws_mode": (ctypes.c_int, [ctypes.c_int]),
     "apgp_path_draws": (ctypes.c_int, [_P, _I64, _I64, _P, _I64, _KP, _F64, _P, _P, _P, _P, _P, _I32, _I32,
                                        ctypes.POINTER(_F64), ctypes.POINTER(_F64), _P, _P, _P, _P, _P]),
+    "apgp_integrated_work_len": (_I64, [_I64, _I32]),
+    "apgp_integrated_mode": (ctypes.c_int, [ctypes.c_int]),
+    "apgp_acquire_integrated": (ctypes.c_int, [_P, _I64, _I64, _P, _I64, _KP, _P, _I32, _P, _P, _P,
+                                               ctypes.POINTER(_F64), ctypes.POINTER(_F64), _P, _P, _I64, _P, _P, _P, _P]),
     "apgp_predict1_work_len": (_I64, [_I64]),
     "apgp_predict1_host": (ctypes.c_int, [_P, _P, _I64, _KP, _F64, _P, _I64, _P, _I64, _P, _P, _P]),
     "apgp_nm_search_work_len": (_I64, [_I64, _I64]),

@@ -368,6 +368,49 @@ class ApproxPosterior(object):
         # (a later step without an admissible candidate cannot happen: the earlier picks stay admissible)
         return [row(int(g)) for g in idx if g >= 0]
 
+    def _integrationRefs(self, integrated):
+        """(refs (J, D), density) of ``findNextPoint(integrated=...)``: an array is used as given, as samples of the
+        surrogate posterior; an int J takes J thinned, flattened samples of ``self.sampler``'s chain after its estimated
+        burn-in -- or, before any chain exists, J ``priorSample`` draws, uniform weights."""
+        if not isinstance(integrated, (int, np.integer)):
+            return np.asarray(integrated, dtype=np.float64), "posterior"
+        J = int(integrated)
+        cut = getattr(self, "_chainCut", None)
+        if self.sampler is None or cut is None:
+            return np.asarray(self.priorSample(J), dtype=np.float64).reshape(J, -1), "uniform"
+        flat = self.sampler.get_chain(discard=cut[0], flat=True, thin=cut[1])
+        if len(flat) < J:       # (a short chain: every post-burn-in sample, unthinned, then all of it)
+            flat = self.sampler.get_chain(discard=cut[0], flat=True)
+        if len(flat) < J:
+            flat = self.sampler.get_chain(flat=True)
+        rows = np.linspace(0, len(flat) - 1, min(J, len(flat))).astype(np.int64)
+        return np.asarray(flat[rows], dtype=np.float64), "posterior"
+
+    def _selectIntegrated(self, nCandidates, integrated):
+        """One design point by the integrated acquisition (:meth:`GP.acquire_integrated`) over the candidate draw
+        :meth:`_selectPoint` makes, behind the same gate."""
+        total = int(nCandidates)
+        joint = self._jointPrior()
+        gate = self.bounds if joint is None else [tuple(r) for r in joint.support()]
+        if self.deviceCandidates and joint is not None:
+            seed = int(np.random.randint(0, 2 ** 31 - 1))
+            cands = self.gp.prior_candidates(total, joint, seed)
+            row = lambda g: self.gp.prior_candidates(1, joint, seed, idx_offset=g).cpu().numpy()[0]       # noqa: E731
+        elif self.deviceCandidates:
+            seed = int(np.random.randint(0, 2 ** 31 - 1))
+            cands = self.gp.box_candidates(total, self.bounds, seed)
+            row = lambda g: self.gp.box_candidates(1, self.bounds, seed, idx_offset=g).cpu().numpy()[0]   # noqa: E731
+        else:
+            draws = np.asarray(self.priorSample(total), dtype=float).reshape(total, -1)
+            cands = self.gp.parse_samples(draws)
+            row = lambda g: np.array(draws[g])                                                              # noqa: E731
+        refs, density = self._integrationRefs(integrated)
+        weights = self.gp.integration_weights(self.y, refs, density)
+        best, value = self.gp.acquire_integrated(self.y, cands, refs, logWeights=weights, bounds=gate)
+        if best < 0:
+            raise RuntimeError("ERROR: Cannot find a valid solution: no candidate is allowed by the prior")
+        return row(best), value
+
     def _absorbPoint(self, point, value):
         """Append (point, value) to the training set and move the GP onto it: same
         kernel / mean / white-noise objects and hyper-parameters (approx.py:693-717); the
@@ -393,7 +436,7 @@ class ApproxPosterior(object):
                       runName="apRun", numNewPoints=1, optGPEveryN=1,
                       gpHyperPrior=gpUtils.defaultHyperPrior, args=None,
                       nCandidates=None, polish=False, deviceCandidates=None, batchSize=None, pool=None,
-                      deviceSearch=None, searchJac=False, batchMethod="believer", **kwargs):
+                      deviceSearch=None, searchJac=False, batchMethod="believer", integrated=None, **kwargs):
         """Select ``numNewPoints`` design points by minimising the (negative) utility;
         with ``computeLnLike`` evaluate the forward model at each, absorb it into the
         training set / GP and re-fit the hyper-parameters every ``optGPEveryN`` points
@@ -431,11 +474,32 @@ class ApproxPosterior(object):
         ``searchJac=True`` (opt-in, with a gradient ``minObjMethod`` such as "l-bfgs-b"; not with ``deviceSearch``) gives
         the host point search -- and ``polish`` -- the utility's exact gradient (``utility.minimizeObjective(jac=True)``,
         :meth:`GP.predict_grad`) instead of SciPy's finite differences.
+
+        ``integrated`` (with ``nCandidates``) replaces the utility's pick by the integrated acquisition
+        (:meth:`GP.acquire_integrated`): the candidate whose evaluation most reduces the variance of the posterior
+        estimate exp(f) integrated over reference points.  An int J takes J thinned samples of the last
+        :meth:`runMCMC` chain after its estimated burn-in (before any chain: J ``priorSample`` draws, uniform weights);
+        a (J, D) array is used as given, as posterior samples.  Same candidate draw and gate as the utility sweep;
+        absorbing and re-fitting are unchanged.  Not with ``batchSize``, ``polish`` or a process group.
         """
         if batchMethod not in ("believer", "thompson"):
             raise ValueError('batchMethod must be "believer" or "thompson"')
         if batchMethod == "thompson" and batchSize is None:
             raise ValueError('batchMethod="thompson" needs batchSize: it chooses batches')
+        if integrated is not None:
+            if nCandidates is None:
+                raise ValueError("integrated needs nCandidates: the integrated acquisition is a device pass over candidates")
+            if isinstance(integrated, (bool, np.bool_)) or (isinstance(integrated, (int, np.integer))
+                                                           and not 1 <= integrated <= _lib.MAX_REFS):
+                raise ValueError("integrated must be a number of reference points between 1 and %d, or a (J, D) array"
+                                 % _lib.MAX_REFS)
+            if batchSize is not None:
+                raise ValueError("integrated cannot be combined with batchSize: it chooses one point at a time")
+            if polish:
+                raise ValueError("integrated cannot be combined with polish=True")
+            if self._ranks() is not None:
+                raise NotImplementedError("integrated under a process group: every rank would need the same "
+                                          "reference points and the winners' records gathered")
         if batchSize is not None:
             if nCandidates is None:
                 raise ValueError("batchSize needs nCandidates: batches are chosen by the device sweep")
@@ -472,8 +536,11 @@ class ApproxPosterior(object):
                 apdist.sync_random_state(0, self.group, enabled=self.distributed)
             if self.algorithm == "alternate":      # AGP, BAPE, AGP, ... (approx.py:656-661)
                 self.utility = (ut.AGPUtility, ut.BAPEUtility)[count % 2]
-            point, _ = self._selectPoint(self.utility, theta0, nMinObjRestarts, minObjMethod,
-                                         minObjOptions, nCandidates, polish, searchJac=searchJac)
+            if integrated is not None:
+                point, _ = self._selectIntegrated(nCandidates, integrated)
+            else:
+                point, _ = self._selectPoint(self.utility, theta0, nMinObjRestarts, minObjMethod,
+                                             minObjOptions, nCandidates, polish, searchJac=searchJac)
             points.append(point)
             if not computeLnLike:
                 continue
@@ -844,7 +911,8 @@ class ApproxPosterior(object):
             gpHyperPrior=gpUtils.defaultHyperPrior, eps=1.0, convergenceCheck=False,
             minObjMethod="nelder-mead", minObjOptions=None, args=None,
             nCandidates=None, onDevice=False, batched=True, deviceCandidates=None, batchSize=None, pool=None,
-            deviceSearch=None, deviceAutocorr=False, searchJac=False, batchMethod="believer", tempering=None, **kwargs):
+            deviceSearch=None, deviceAutocorr=False, searchJac=False, batchMethod="believer", tempering=None,
+            integrated=None, **kwargs):
         """BAPE / AGP outer loop (approx.py:229-524): ``nmax`` times, find ``m`` design
         points (re-fitting the GP every ``optGPEveryN``), sample the surrogate posterior,
         record burn-in / thinning, and -- with ``convergenceCheck`` -- stop once the
@@ -859,7 +927,8 @@ class ApproxPosterior(object):
         (the Nelder-Mead point search on the device) and ``searchJac`` (exact gradients for a gradient
         ``minObjMethod``).  ``deviceAutocorr`` is passed to :meth:`runMCMC` too (burn-in and
         thinning from the device's autocorrelation estimate; needs ``onDevice=True``), and so is ``tempering``
-        (parallel tempering of the device sampler; needs ``onDevice=True``)."""
+        (parallel tempering of the device sampler; needs ``onDevice=True``).  ``integrated`` is passed to
+        :meth:`findNextPoint` (the integrated acquisition; needs ``nCandidates``)."""
         if deviceAutocorr and not onDevice:
             raise ValueError("run(deviceAutocorr=True) needs onDevice=True")
         if tempering is not None and not onDevice:
@@ -897,7 +966,7 @@ class ApproxPosterior(object):
                                runName=runName, theta0=None, args=args, verbose=verbose,
                                nCandidates=nCandidates, deviceCandidates=deviceCandidates, batchSize=batchSize,
                                pool=pool, deviceSearch=deviceSearch, searchJac=searchJac, batchMethod=batchMethod,
-                               **fit, **kwargs)
+                               **({} if integrated is None else {"integrated": integrated}), **fit, **kwargs)
             if timing:
                 self.trainingTime.append(time.time() - clock)
             if cache:

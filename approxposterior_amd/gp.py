@@ -1661,6 +1661,92 @@ class GP(GeorgeExtras):
                 return idx, ub, u.cpu().numpy(), mu.cpu().numpy(), var[cur].cpu().numpy()
         return idx, ub
 
+    # -- integrated acquisition (DESIGN.md "Integrated acquisition") ------------------
+    def _references(self, refs):
+        R = np.ascontiguousarray(np.asarray(refs, dtype=np.float64))
+        if R.ndim != 2 or R.shape[1] != self.kernel.ndim or not 1 <= len(R) <= _lib.MAX_REFS:
+            raise ValueError("refs must be a (J, D) array of 1 <= J <= %d reference points (APGP_MAX_REFS)" % _lib.MAX_REFS)
+        if not np.all(np.isfinite(R)):
+            raise ValueError("refs must be finite")
+        return R
+
+    def integration_weights(self, y, refs, density="posterior"):
+        """The log-weights ``a_j = log w_j + 2 mu(r_j) + var(r_j)`` of :meth:`acquire_integrated` for reference points
+        ``refs`` (J, D) that are samples of the surrogate posterior (``density="posterior"``: w_j proportional to
+        exp(-mu), a_j = mu_j + var_j) or uniform in the box (``"uniform"``: a_j = 2 mu_j + var_j), from one
+        ``predict(return_var=True)`` over them.  Only differences of the a_j matter."""
+        if density not in ("posterior", "uniform"):
+            raise ValueError("density must be 'posterior' or 'uniform'")
+        R = self._references(refs)
+        mu, var = self.predict(y, R, return_cov=False, return_var=True)
+        mu, var = np.asarray(mu, dtype=np.float64), np.asarray(var, dtype=np.float64)
+        return (mu if density == "posterior" else 2.0 * mu) + var
+
+    def acquire_integrated(self, y, t, refs, logWeights=None, bounds=None, mask=None, idx_offset=0, return_all=False):
+        """The candidate of ``t`` (M, D; host array or device tensor, as in :meth:`acquire`) whose evaluation most
+        reduces the integrated variance of the posterior estimate exp(f) (the expected integrated variance of
+        Jarvenpaa et al. 2021), the integral taken over the reference points ``refs`` (J, D) with the log-weights
+        ``logWeights`` (J; None: :meth:`integration_weights` for samples of the surrogate posterior):
+
+            u(t) = -log sum_j exp(a_j + c_j(t)^2 / (var(t) + diag_add)),   c_j(t) = k(t, r_j) - k(t, X) K^-1 k(X, r_j)
+
+        One prediction sweep gives var(t); B = K^-1 k(X, R) is solved once for all J columns against the resident
+        factor (O(N^2 J), off the per-candidate path); one pass (``apgp_acquire_integrated``) forms all M x J posterior
+        covariances and reduces them, O(N J) per candidate.  The GP is not modified.
+
+        Returns ``(index, u)`` -- index -1 and +inf without an admissible candidate -- and with ``return_all``
+        additionally the arrays ``(u, mu, var)``."""
+        if not self.computed:
+            raise RuntimeError("ERROR: Need to compute GP before using it!")
+        if self.kernel.ndim > _lib.INTEGRATED_MAX_DIM:
+            raise NotImplementedError("the integrated acquisition pass takes at most %d dimensions" % _lib.INTEGRATED_MAX_DIM)
+        R = self._references(refs)
+        J = len(R)
+        if logWeights is None:
+            a = self.integration_weights(y, R, "posterior")
+        else:
+            a = np.ascontiguousarray(np.asarray(logWeights, dtype=np.float64)).reshape(-1)
+            if a.shape != (J,):
+                raise ValueError("logWeights must have one entry per reference point")
+        if np.any(np.isnan(a)) or np.any(a == np.inf) or not np.any(a > -np.inf):
+            raise ValueError("logWeights must not be NaN or +inf, and not all -inf")
+        torch, dev, lib = self._rt()
+        y = self._check_dimensions(y)
+        n, D = len(self._x), self.kernel.ndim
+        lo, hi = _box(bounds, D)
+        T = self._candidates(t)
+        m = T.shape[0]
+        mask_d = self._mask(mask, m)
+        if m == 0:
+            return (-1, float("inf")) + ((np.empty(0),) * 3 if return_all else ())
+        s = self._sweep(y, T, _lib.UTIL_NONE, idx_offset=idx_offset, with_mu=return_all, with_var=True)
+        ks = self._kernel_struct()
+        with self._on(torch, dev):
+            st = self._stream(torch)
+            f64 = dict(dtype=torch.float64, device=dev)
+            R_d = torch.from_numpy(R).to(dev)
+            a_d = torch.from_numpy(a).to(dev)
+            kxr = torch.empty((n, J), **f64)
+            if self._x_d is None or self._x_d.shape[0] != n:
+                self._x_d = torch.from_numpy(self._x).to(dev)
+            _lib.check(lib.apgp_kernel_cross(self._x_d.data_ptr(), n, R_d.data_ptr(), J, ctypes.byref(ks),
+                                             kxr.data_ptr(), J, st), "apgp_kernel_cross")
+            # B = K^-1 k(X, R) = L^-T (L^-1 k(X, R)): all J right-hand sides at once (row-major (N, J): what the pass reads)
+            L = torch.tril(self._L[:n, :n])                   # (bytes above the diagonal are undefined)
+            z = torch.linalg.solve_triangular(L, kxr, upper=False)
+            B = torch.linalg.solve_triangular(L.t(), z, upper=True).contiguous()
+            u = torch.empty(m, **f64) if return_all else None
+            part = torch.empty(max(int(lib.apgp_integrated_work_len(m, J)), 2), **f64)
+            best = torch.empty(2, **f64)
+            _lib.check(lib.apgp_acquire_integrated(T.data_ptr(), m, int(idx_offset), self._xs.data_ptr(), n,
+                                                   ctypes.byref(ks), R_d.data_ptr(), J, B.data_ptr(), a_d.data_ptr(),
+                                                   s.var.data_ptr(), lo, hi, _ptr(mask_d), None, 0, _ptr(u),
+                                                   part.data_ptr(), best.data_ptr(), st), "apgp_acquire_integrated")
+            rec = _best_record(best)
+            if return_all:
+                return rec + (u.cpu().numpy(), s.mu.cpu().numpy(), s.var.cpu().numpy())
+        return rec
+
     # -- posterior function draws (DESIGN.md "Posterior function draws") ------------------
     def _path_call(self, T, ks, mean, paths, V, lo=None, hi=None, mask_d=None, idx_offset=0, with_f=False):
         """``apgp_path_draws`` over the rows of the device tensor ``T`` (M >= 1, D) with the weights of ``paths`` and the

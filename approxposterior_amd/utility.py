@@ -21,7 +21,7 @@ import numpy as np
 from scipy.optimize import minimize
 from scipy.stats import norm
 
-__all__ = ["logsubexp", "AGPUtility", "BAPEUtility", "JonesUtility",
+__all__ = ["logsubexp", "AGPUtility", "BAPEUtility", "JonesUtility", "EIVUtility",
            "minimizeObjective", "sweepObjective", "utilityKind", "searchKind", "klNumerical",
            "mergeImportance", "importanceSummary"]
 
@@ -80,6 +80,29 @@ def JonesUtility(theta, y, gp, priorFn, zeta=0.01):
         return 0.0
     z = (mu - yBest - zeta) / std
     return -((mu - yBest - zeta) * norm.cdf(z) + std * norm.pdf(z))
+
+
+def EIVUtility(theta, y, gp, priorFn, refs, logWeights):
+    """The expected integrated variance of the posterior estimate exp(f) after one more evaluation at ``theta``
+    (Jarvenpaa et al. 2021), reduced to what depends on theta: -log sum_j exp(a_j + cov(theta, r_j)^2 / (var(theta) +
+    noise)) over the reference points ``refs`` (J, D) with log-weights ``logWeights`` (``GP.integration_weights``);
+    +inf where the prior is not finite.  The scalar host form of ``GP.acquire_integrated``, from one
+    ``gp.predict(..., return_cov=True)`` over [theta; refs]; hand ``refs`` and ``logWeights`` to
+    :func:`minimizeObjective` through ``args``.  An integrated rule, not a pointwise one: it has no sweep kind."""
+    if not np.isfinite(priorFn(theta)):
+        return np.inf
+    if not gp.computed:
+        raise RuntimeError("ERROR: Need to compute GP before using it!")
+    pts = np.vstack([np.asarray(theta, dtype=float).reshape(1, -1), np.asarray(refs, dtype=float)])
+    _, cov = gp.predict(y, pts, return_cov=True)
+    s = cov[0, 0] + gp._kernel_struct().diag_add
+    if not (s > 0.0 and np.isfinite(s)):
+        return np.inf
+    e = np.asarray(logWeights, dtype=float) + cov[0, 1:] ** 2 / s
+    mx = np.max(e)
+    if not np.isfinite(mx):
+        return -mx
+    return -(mx + np.log(np.sum(np.exp(e - mx))))
 
 
 _KINDS = {AGPUtility: "agp", BAPEUtility: "bape", JonesUtility: "jones"}

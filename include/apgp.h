@@ -489,6 +489,37 @@ int apgp_path_draws(const double* T, int64_t m, int64_t idx_offset, const double
                     const double* lo /*host*/, const double* hi /*host*/, const uint8_t* mask, double* F,
                     void* part, apgp_best_t* best, void* stream);
 
+/* ---- integrated acquisition (GP.acquire_integrated; DESIGN.md "Integrated acquisition") ------------------
+ * The expected integrated variance of the posterior estimate exp(f) after one more evaluation at t (noise diag_add,
+ * hyper-parameters unchanged), integrated over J = nref reference points r_j and reduced to what depends on t:
+ *   u(t) = -log sum_j exp(a_j + c_j(t)^2 / s(t)),  c_j(t) = k(t, r_j) - sum_n k(t, x_n) B[n, j],  s(t) = var(t) + diag_add
+ * for the m rows t of T (m x ndim), and its arg-min.  The caller solves B (n x nref, row-major: a training row's J
+ * weights side by side) = K^-1 k(X, R) and supplies a (nref log-weights: log w_j + 2 mu(r_j) + var(r_j); -inf: the column
+ * contributes nothing, not one bit) and var (m; the sweep's output).  R: nref x ndim in the caller's coordinates.
+ * xs: the packed training stream (its alpha column is not read).
+ * C (may be NULL): column-major, ldc >= m; column j receives c_j(t).  u (may be NULL): m values.  best: one record on the
+ * device with the sweep's contract: ties go to the lowest global index idx_offset + row; NaN and +inf never win; a row
+ * outside [lo, hi] (host arrays or NULL), with mask[row] == 0 (device or NULL), with a NaN coordinate or with s(t) not
+ * positive or not finite has u = +inf and NaN in its row of C; no admissible row gives index -1 and u = +inf.
+ * The log-sum-exp is a running (max, sum) over j ascending.  No atomics, a fixed order in every sum; a row's u and C do
+ * not depend on the other rows of the call.
+ * part: apgp_integrated_work_len(m, nref) doubles, 16-byte aligned (-1: m or nref beyond the limits; 0 for m = 0).
+ * Added in ABI 8 without changing anything before it: APGP_ABI_VERSION stays 8.                                   */
+#define APGP_MAX_REFS 4096
+#define APGP_INTEGRATED_MAX_DIM 16      /* ndim above it is refused (-1): the pass has no kernel for D padded to 32 */
+int64_t apgp_integrated_work_len(int64_t m, int32_t nref);
+/* Test / profiling switch (not read from the environment) for where the contraction with the columns of B runs: 0 =
+ * default (the matrix cores when ndim <= 8, else the vector units), 1 = the vector units always; < 0 queries.  The two
+ * forms sum in a fixed order of their own: they agree to rounding, not bit for bit.  Returns the previous value (-1:
+ * bad argument).                                                                                                   */
+int apgp_integrated_mode(int mode);
+int apgp_acquire_integrated(const double* T, int64_t m, int64_t idx_offset,
+                            const double* xs, int64_t n, const apgp_kernel_t* kern /*host*/,
+                            const double* R, int32_t nref, const double* B, const double* a,
+                            const double* var, const double* lo /*host*/, const double* hi /*host*/,
+                            const uint8_t* mask, double* C, int64_t ldc, double* u,
+                            void* part, apgp_best_t* best, void* stream);
+
 /* ---- ONE candidate: george GP.predict(y, t[1 x D], return_var=True) ----------
  * What the reference's scalar utilities evaluate once per Nelder-Mead step
  * (utility.py:131,178,224 <- minimizeObjective, utility.py:336-372; the default
