@@ -222,7 +222,7 @@ def lsolve_slot_mask(n):
 # ----------------------------------------------------------------------------------------------------------------------
 # input families (seeded)
 # ----------------------------------------------------------------------------------------------------------------------
-LIN_COEF = {0: 0.05, 1: 0.3, 2: 0.1}
+LIN_COEF = {0: 0.05, 1: 0.3, 2: 0.1, 3: 0.04}      # (order 3: tests/predgrad_ref.py's cases)
 
 
 def planted_w(n):

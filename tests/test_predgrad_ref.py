@@ -12,6 +12,10 @@
                                 tests/test_gpu_parity.py holds mu / var / u to (200 cond eps x its scale, propagated
                                 through the utility's own derivatives)
     + 200 cond eps S            the restatement's own error, as above.
+* the stage budgets of tests/predgrad_ref.py's docstring, which tests/test_gpu_predict_grad_budget.py holds the device to
+  kernel by kernel: the scratch layout and the loop strides the counts rest on are read off csrc/predgrad.hip; the
+  float64 restatement of the device order and NumPy / SciPy's own order sit within every budget on every input of the GPU
+  test; every mutant of the restatement breaks one; the utility case leaves out at most a tenth of its rows.
 * ``minimizeObjective(jac=True)`` on a NumPy stub GP: SciPy gets ``jac=True`` and (u, du), the refusals are raised, and
   ``jac=False`` consumes the random stream and returns what the loop without the keyword did.
 """
@@ -282,3 +286,126 @@ def test_jac_false_is_the_search_as_it_was(method):
         assert np.array_equal(got[0], want[0]) and np.array_equal(np.asarray(got[1]), np.asarray(want[1]))
         assert np.array_equal(np.random.get_state()[1], state_want)
     assert not gp.grad_calls
+
+
+# ---- the stage budgets of apgp_predict_grad (tests/test_gpu_predict_grad_budget.py's bars, held on the CPU) ------------
+SRC = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "approxposterior_amd", "csrc",
+                   "predgrad.hip")
+
+
+def _define(text, name):
+    import re
+    m = re.search(r"^#define\s+%s\s+(.+?)\s*(?://.*)?$" % name, text, re.M)
+    assert m, "csrc/predgrad.hip no longer defines %s: tests/predgrad_ref.py's layout has to follow" % name
+    return m.group(1).strip()
+
+
+def test_scratch_layout_is_the_source_s():
+    """``work_views`` and the stage depths are read off csrc/predgrad.hip: a change of one of these lines changes what
+    the call leaves in ``work`` or how deep a sum is, and predgrad_ref has to follow before the GPU tests mean anything."""
+    text = open(SRC).read()
+    for name, want in (("PG_T", ref.PG_T), ("PG_PB", ref.PG_PB), ("PG_PBS", ref.PG_PBS), ("PG_FR", ref.PG_FR),
+                       ("PG_NRC", ref.PG_NRC), ("PG_B", ref.PG_B)):
+        assert int(_define(text, name)) == want, "%s is %s in the source, %d in predgrad_ref" % (name, _define(text, name), want)
+    assert _define(text, "PG_PER_POINT") == "(2 + PG_NRC)" and ref.PG_PER_POINT == 2 + ref.PG_NRC
+    assert _define(text, "PG_CHUNK_DOUBLES") == "(1ll << 24)" and ref.PG_CHUNK_DOUBLES == 1 << 24
+    for line, what in (
+            ("int64_t ch = PG_CHUNK_DOUBLES / (PG_PER_POINT * ns) / PG_PB * PG_PB;", "pg_chunk"),
+            ("if (ch > 4096) ch = 4096;", "pg_chunk's cap (PG_CHUNK_MAX)"),
+            ("if (ch < PG_PB) ch = PG_PB;", "pg_chunk's floor"),
+            ("const int64_t mr = apgp_round_up(m, PG_PB);", "pg_chunk's round-up of m"),
+            ("a.kbuf = work; a.vbuf = work + ch * ns; a.wbuf = work + 2 * ch * ns;", "the order of kbuf, vbuf, wbuf"),
+            ("a.vsrc = inverse ? a.vbuf : a.kbuf;", "v on the solve route"),
+            ("a.wstride = ch * ns;", "the stride of the partial planes"),
+            ("a.rc = apgp_round_up((n + PG_NRC - 1) / PG_NRC, 64);", "the rc rule"),
+            ("if (a.rc < 512) a.rc = 512;", "the rc rule's floor (PG_RC_MIN)"),
+            ("a.nrc = (int)((n + a.rc - 1) / a.rc);", "nrc"),
+            ("a.rc = ns;", "rc on the solve route"),
+            ("for (long long k = 2 * lane; k <= i1; k += 128) {", "the forward product's stride (FWD_STRIDE)"),
+            ("for (long long i = ibeg + rs; i < iend; i += 4) {", "the transposed product's four chains"),
+            ("for (long long k = t; k < a.n; k += PG_T) {", "the finish kernel's strided chain"),
+            ("for (long long r = k / a.rc; r < a.nrc; ++r) wk += wp[r * a.wstride + k];", "the sum of the partial planes"),
+            ("for (long long i = j0 + PG_B + w; i < n; i += 4) {", "the backward substitution's four chains")):
+        assert line in text, "csrc/predgrad.hip: %s changed; update tests/predgrad_ref.py (layout and counts)" % what
+    assert ref.PG_CHUNK_MAX == 4096 and ref.PG_RC_MIN == 512 and ref.FWD_STRIDE == 128
+    # what the GPU test's shapes are chosen for
+    got = {n: ref.row_chunks(n, "inverse") for n in (512, 513, 1025, 2049, 4096, 4097)}
+    assert got == {512: (512, 1), 513: (512, 2), 1025: (512, 3), 2049: (512, 5), 4096: (512, 8), 4097: (576, 8)}
+    assert ref.row_chunks(449, "solve") == (512, 1)
+    assert ref.chunk(4100, 65) == 4096 and ref.chunk(9, 4097) == 16 and ref.chunk(1, 1) == 8
+    assert all(ref.chunk(c[2], c[0]) >= c[2] for cs in ref.budget_cases().values() for c in cs), "one chunk per case"
+    # the views
+    m, n = 9, 513
+    ns, ch = ref.ns_of(n), ref.chunk(m, n)
+    work = np.arange(ref.work_len(m, n), dtype=np.float64)
+    vw = ref.work_views(work, m, n, "inverse")
+    assert vw["k"][2, 5] == 2 * ns + 5 and vw["v"][2, 5] == ch * ns + 2 * ns + 5
+    assert vw["w"].shape == (2, m, ns) and vw["w"][1, 3, 7] == (2 + 1) * ch * ns + 3 * ns + 7
+    vs = ref.work_views(work, m, n, "solve")
+    assert vs["k"] is None and vs["v"][2, 5] == 2 * ns + 5 and vs["w"].shape == (1, m, ns) and vs["w"][0, 1, 0] == 2 * ch * ns + ns
+    with pytest.raises(ValueError):
+        ref.work_views(work[:-1], 17, n, "inverse")
+
+
+ALL_CASES = sorted(set(c for cs in ref.budget_cases().values() for c in cs),
+                   key=lambda c: (c[3], c[0], c[1], c[2], -1 if c[4] is None else c[4]))
+
+
+@pytest.mark.parametrize("c", ALL_CASES, ids=ref.case_id)
+def test_restatement_and_scipy_within_every_stage_budget(c):
+    """The clean restatement of the device order and NumPy / SciPy's own order, on every input of the GPU test."""
+    case = ref.Case(*c, util=(c[2] == ref.UTIL_M))
+    for name, rec in (("restated", ref.restate(case)), ("scipy", ref.scipy_route(case))):
+        r = ref.judge(case, rec)
+        print(ref.case_id(c), name, "  ".join("%s %.3f" % kv for kv in sorted(r.items())))
+        assert max(r.values()) <= 1.0, (name, r)
+
+
+@pytest.mark.parametrize("mutant", sorted(ref.MUTANTS))
+def test_every_mutant_breaks_a_budget(mutant):
+    route, n, D, order = ref.MUTANTS[mutant]
+    c = (n, D, ref.M_OF[route], route, order)
+    assert c in ALL_CASES, "a mutant is shown on an input of the GPU test"
+    case = ref.Case(*c)
+    assert max(ref.judge(case, ref.restate(case)).values()) <= 1.0
+    r = ref.judge(case, ref.restate(case, mutant))
+    broken = {k: v for k, v in r.items() if v > 1.0}
+    print(mutant, ref.case_id(c), "breaks", "  ".join("%s %.3g" % kv for kv in sorted(broken.items())))
+    assert broken, (mutant, r)
+
+
+@pytest.mark.parametrize("route", ["inverse", "solve"])
+def test_utility_case_leaves_out_at_most_a_tenth_and_the_chain_budget_holds(route):
+    """From the truth alone (long double, no device): the rows of the utility case outside the box or with sigma^2 <= 0
+    are at most UTIL_CAP of it, both kinds occur, no sigma^2 is so close to zero that a device within its budget could
+    land on the other side, and NumPy's chain rule sits within the chain budget while a dropped term does not."""
+    case = ref.Case(ref.UTIL_N, ref.UTIL_D, ref.UTIL_M, route, util=True)
+    n = case.n
+    with np.errstate(all="ignore"):
+        kh = ref.kr.truth_ld(case.T, case.X, case.k)
+    A = np.tril(case.A)
+    v = (kh @ A.astype(ref.LD).T) if route == "inverse" else ref.sr.solve_ld(A, kh.T).T
+    var = (ref.sr.ktt_truth(case.T, case.k)[0] - (v * v).sum(1)).astype(np.float64)
+    inside, judged = ref.util_rows(case, var)
+    out, flat = int((~inside).sum()), int((inside & ~judged).sum())
+    print(route, "outside the box: %d, sigma^2 <= 0: %d, of %d; smallest |sigma^2| %.3g" % (out, flat, case.m, np.abs(var).min()))
+    assert out == ref.UTIL_OUT and flat >= 1
+    assert out + flat <= ref.UTIL_CAP * case.m
+    assert np.abs(var[inside]).min() >= 1e-6                       # (the variance budget is below 1e-12 here)
+    rec = ref.restate(case)
+    assert np.array_equal(ref.util_rows(case, rec["var"])[1], judged)
+    mu, vr, dmu, dvar = (rec[key][judged] for key in ("mu", "var", "dmu", "dvar"))
+    for kind in ref.UTIL_KINDS:
+        _, g_mu, g_var, fl = ref.utility(kind, mu, vr, zeta=ref.UTIL_ZETA, ybest=ref.UTIL_YBEST)
+        assert not fl.any()
+        du = g_mu[:, None] * dmu + g_var[:, None] * dvar
+        r = ref.du_ratio(kind, du, mu, vr, dmu, dvar, ref.UTIL_ZETA, ref.UTIL_YBEST)
+        print(route, kind, "NumPy's chain rule / budget %.3f" % r.max())
+        assert r.max() <= 1.0
+        if kind in ("agp", "bape"):                                # a derivative factor demoted to fp32
+            bad = g_mu[:, None] * dmu + g_var.astype(np.float32).astype(np.float64)[:, None] * dvar
+            assert ref.du_ratio(kind, bad, mu, vr, dmu, dvar, ref.UTIL_ZETA, ref.UTIL_YBEST).max() > 1.0
+        if kind == "jones":                                        # zeta left out of z
+            _, b_mu, b_var, _ = ref.utility(kind, mu, vr, zeta=0.0, ybest=ref.UTIL_YBEST)
+            bad = b_mu[:, None] * dmu + b_var[:, None] * dvar
+            assert ref.du_ratio(kind, bad, mu, vr, dmu, dvar, ref.UTIL_ZETA, ref.UTIL_YBEST).max() > 1.0
