@@ -63,6 +63,14 @@ class EnsMove(ctypes.Structure):
 ENS_MOVE_STRETCH, ENS_MOVE_DE, ENS_MOVE_SNOOKER = 0, 1, 2
 ENS_MAX_MOVES = 8     # APGP_ENS_MAX_MOVES
 PT_MAX_TEMPS = 64     # APGP_PT_MAX_TEMPS: rungs of a tempering ladder
+HMC_MAX_LEAP = 1024   # APGP_HMC_MAX_LEAP: leapfrog steps per iteration of apgp_hmc_sample
+HMC_G_ROWS = (1, 4)   # wavefronts per chain apgp_hmc_sample offers (g_rows; 0 = the library's rule)
+
+
+class HmcOptions(ctypes.Structure):
+    """``apgp_hmc_options_t``."""
+    _fields_ = [("eps", ctypes.c_double), ("jitter", ctypes.c_double), ("nleap", ctypes.c_int32),
+                ("g_rows", ctypes.c_int32), ("iteration0", ctypes.c_int64), ("mass", ctypes.c_double * MAX_DIM)]
 
 _P = ctypes.c_void_p
 _I64 = ctypes.c_int64
@@ -162,6 +170,9 @@ SIGNATURES = {
     "apgp_tempered_sample": (ctypes.c_int, [_P, _I64, _KP, _F64, ctypes.POINTER(_F64), ctypes.POINTER(_F64), _I32, _I32, _I32,
                                             ctypes.POINTER(_F64), _I64, _I64, ctypes.c_uint64, _P, _P, _P, _I32, _P, _P, _P,
                                             _P, _P, ctypes.POINTER(EnsMove), _I32, _P, _P]),
+    "apgp_hmc_sample": (ctypes.c_int, [_P, _I64, _KP, _F64, ctypes.POINTER(_F64), ctypes.POINTER(_F64), _I32, _I64,
+                                       ctypes.POINTER(HmcOptions), ctypes.c_uint64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "apgp_hmc_rule": (ctypes.c_int, [_I32, _I64, _I32]),
     "apgp_box_candidates": (ctypes.c_int, [_P, _I64, _I32, ctypes.POINTER(_F64), ctypes.POINTER(_F64), ctypes.c_uint64,
                                            _I64, _P]),
     "apgp_prior_candidates": (ctypes.c_int, [_P, _I64, _I32, _P, _P, _P, ctypes.c_uint64, _I64, _P]),

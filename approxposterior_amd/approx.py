@@ -667,7 +667,7 @@ class ApproxPosterior(object):
 
     def runMCMC(self, samplerKwargs=None, mcmcKwargs=None, runName="apRun",
                 cache=True, estBurnin=True, thinChains=True, verbose=False,
-                args=None, batched=True, onDevice=False, deviceAutocorr=False, tempering=None, **kwargs):
+                args=None, batched=True, onDevice=False, deviceAutocorr=False, tempering=None, hmc=None, **kwargs):
         """Sample the GP-surrogate posterior with the stretch-move ensemble sampler and
         estimate burn-in / thinning (approx.py:757-859): ``(sampler, iburn, ithin)``.
         ``samplerKwargs["moves"]`` (``mcmc.moves.DEMove()``, ``DESnookerMove()``, weighted lists, as emcee's ``moves``)
@@ -691,7 +691,28 @@ class ApproxPosterior(object):
         the cold rungs behind the usual accessors (burn-in, blobs, caching and ``evidence(proposal="gmm")`` work on
         them as they do on a ``DeviceChain``), plus the ladder's diagnostics and ``log_evidence()``.
         ``NotImplementedError`` under a process group.
+        ``hmc`` (opt-in, needs ``onDevice=True``): Hamiltonian Monte Carlo with the surrogate's exact gradient
+        (``GP.sample_hmc``) in place of the ensemble moves, for posteriors of more than ten or so dimensions -- ``True``
+        or a dict with any of ``eps`` (step in the kernel's scaled coordinates, default 0.1), ``nLeap`` (16), ``jitter``
+        (0.1), ``nWarmup`` (200), ``adaptEvery`` (20), ``targetAccept`` (0.8), ``adaptMass`` (False), ``mass``; another
+        key is a ``ValueError``.  The ``nwalkers`` rows of ``initial_state`` start one chain each, ``mcmc.hmc_warmup``
+        adapts the step over ``nWarmup`` iterations that are not kept, and ``iterations`` counts the iterations after it.
+        ``self.sampler`` is then a :class:`mcmc.HMCChain`.  ``ValueError`` together with ``tempering`` or
+        ``samplerKwargs["moves"]``; ``NotImplementedError`` under a process group.
         """
+        if hmc is not None and hmc is not False:
+            if not onDevice:
+                raise ValueError("runMCMC(hmc=...) runs on the device: it needs onDevice=True")
+            if tempering is not None:
+                raise ValueError("runMCMC(hmc=...) and tempering=... are two samplers: choose one")
+            if samplerKwargs is not None and samplerKwargs.get("moves") is not None:
+                raise ValueError("runMCMC(hmc=...) makes no ensemble move: samplerKwargs['moves'] does not apply")
+            hmcSpec = self._hmcSpec(hmc)
+            if self._ranks() is not None:
+                raise NotImplementedError("hmc under a process group: the chains would have to be sharded over the ranks "
+                                          "and the warm-up's acceptance averaged across them")
+        else:
+            hmc = None
         if deviceAutocorr and not onDevice:
             raise ValueError("runMCMC(deviceAutocorr=True) diagnoses the chain of the device sampler: it needs onDevice=True")
         if tempering is not None and not onDevice:
@@ -714,7 +735,9 @@ class ApproxPosterior(object):
                 p0 = p0.reshape(samplerKwargs["nwalkers"], self.ndim)
             if p0.shape != (samplerKwargs["nwalkers"], self.ndim):
                 raise ValueError("incompatible input dimensions")
-        if tempering is not None:
+        if hmc is not None:
+            self.sampler = self._sampleHMC(np.random.randint(0, 2 ** 31 - 1), mcmcKwargs, hmcSpec, deviceAutocorr)
+        elif tempering is not None:
             self.sampler = self._sampleTempered(np.random.randint(0, 2 ** 31 - 1), samplerKwargs, mcmcKwargs, tempering,
                                                 deviceAutocorr)
         elif onDevice or ranks is not None:
@@ -753,6 +776,35 @@ class ApproxPosterior(object):
                                                 thinChains=thinChains, verbose=verbose)
         self._chainCut = (iburn, ithin)     # (evidence(proposal="gmm") fits its proposal to the chain cut this way)
         return self.sampler, iburn, ithin
+
+    _HMC_DEFAULTS = {"eps": 0.1, "nLeap": 16, "jitter": 0.1, "nWarmup": 200, "adaptEvery": 20, "targetAccept": 0.8,
+                     "adaptMass": False, "mass": None}
+
+    def _hmcSpec(self, hmc):
+        """``runMCMC``'s ``hmc`` argument as the full dict of settings; ``ValueError`` for anything else than True or a
+        dict of known keys."""
+        spec = dict(self._HMC_DEFAULTS)
+        if hmc is True:
+            return spec
+        if not isinstance(hmc, dict) or any(k not in spec for k in hmc):
+            raise ValueError("hmc must be True or a dict with keys from %s" % (tuple(spec),))
+        spec.update(hmc)
+        return spec
+
+    def _sampleHMC(self, seed, mcmcKwargs, spec, keepDevice):
+        """The :class:`mcmc.HMCChain` of ``runMCMC(hmc=...)``: the warm-up (``mcmc.hmc_warmup``), then the sampling run
+        at the adapted step, its global iteration numbers following the warm-up's."""
+        joint = self._jointPrior()
+        extra = {} if joint is None else {"prior": joint}
+        coords, eps, mass, history, it = emcee.hmc_warmup(
+            self.gp, self.y, mcmcKwargs["initial_state"], self.bounds, spec["eps"], spec["nLeap"], nWarmup=spec["nWarmup"],
+            adaptEvery=spec["adaptEvery"], targetAccept=spec["targetAccept"], jitter=spec["jitter"], mass=spec["mass"],
+            adaptMass=bool(spec["adaptMass"]), seed=seed, **extra)
+        res = self.gp.sample_hmc(self.y, coords, mcmcKwargs["iterations"], self.bounds, eps, spec["nLeap"],
+                                 jitter=spec["jitter"], mass=mass, seed=seed, iteration0=it, keep_device=bool(keepDevice),
+                                 **extra)
+        res["mass"] = mass
+        return emcee.HMCChain(res, warmup=history)
 
     def _sampleTempered(self, seed, samplerKwargs, mcmcKwargs, tempering, keepDevice):
         """The :class:`mcmc.TemperedChain` of ``runMCMC(tempering=...)``: ``tempering`` is the number of rungs of the
@@ -911,7 +963,7 @@ class ApproxPosterior(object):
             gpHyperPrior=gpUtils.defaultHyperPrior, eps=1.0, convergenceCheck=False,
             minObjMethod="nelder-mead", minObjOptions=None, args=None,
             nCandidates=None, onDevice=False, batched=True, deviceCandidates=None, batchSize=None, pool=None,
-            deviceSearch=None, deviceAutocorr=False, searchJac=False, batchMethod="believer", tempering=None,
+            deviceSearch=None, deviceAutocorr=False, searchJac=False, batchMethod="believer", tempering=None, hmc=None,
             integrated=None, **kwargs):
         """BAPE / AGP outer loop (approx.py:229-524): ``nmax`` times, find ``m`` design
         points (re-fitting the GP every ``optGPEveryN``), sample the surrogate posterior,
@@ -927,12 +979,15 @@ class ApproxPosterior(object):
         (the Nelder-Mead point search on the device) and ``searchJac`` (exact gradients for a gradient
         ``minObjMethod``).  ``deviceAutocorr`` is passed to :meth:`runMCMC` too (burn-in and
         thinning from the device's autocorrelation estimate; needs ``onDevice=True``), and so is ``tempering``
-        (parallel tempering of the device sampler; needs ``onDevice=True``).  ``integrated`` is passed to
+        (parallel tempering of the device sampler; needs ``onDevice=True``) and ``hmc`` (Hamiltonian Monte Carlo on the
+        device in place of the ensemble moves; needs ``onDevice=True``).  ``integrated`` is passed to
         :meth:`findNextPoint` (the integrated acquisition; needs ``nCandidates``)."""
         if deviceAutocorr and not onDevice:
             raise ValueError("run(deviceAutocorr=True) needs onDevice=True")
         if tempering is not None and not onDevice:
             raise ValueError("run(tempering=...) tempers the device sampler: it needs onDevice=True")
+        if hmc is not None and hmc is not False and not onDevice:
+            raise ValueError("run(hmc=...) runs on the device: it needs onDevice=True")
         if batchMethod not in ("believer", "thompson"):
             raise ValueError('batchMethod must be "believer" or "thompson"')
         if batchMethod == "thompson" and batchSize is None:
@@ -980,7 +1035,7 @@ class ApproxPosterior(object):
                                            runName="%s%d" % (runName, iteration), cache=cache,
                                            estBurnin=estBurnin, thinChains=thinChains,
                                            verbose=verbose, args=args, onDevice=onDevice,
-                                           batched=batched, deviceAutocorr=deviceAutocorr, tempering=tempering,
+                                           batched=batched, deviceAutocorr=deviceAutocorr, tempering=tempering, hmc=hmc,
                                            **kwargs)
             self.iburns.append(iburn)
             self.ithins.append(ithin)

@@ -18,6 +18,13 @@
 //   tag 6: snooker -- j, k as tag 3, l = word 2 % (H - 2), l += (l >= min(j, k)), l += (l >= max(j, k));
 //   tag 7: parallel tempering (tempering.hip) -- counter (round low, round high, walker, 7) under the keys of the pair's
 //          lower rung: u01(words 0, 1) is the exchange uniform.
+// Hamiltonian Monte Carlo (hmc.hip) draws under the keys (seed, seed >> 32 ^ chain * 0x9E3779B9) with the GLOBAL iteration
+// number in words 0 and 1:
+//   tag 8: momentum -- counter (it low, it high, d, 8): ens_normal(u01(words 0, 1), u01(words 2, 3)) sqrt(m_d) is p_d
+//          (one counter per dimension: ens_normal turns four words into one normal);
+//   tag 9: step jitter -- counter (it low, it high, 0xffffffff, 9) under chain 0's keys, so every chain of the call
+//          has the iteration's eps (1 + jitter (2 u01(words 0, 1) - 1));
+//   tag 10: the acceptance uniform -- counter (it low, it high, 0xfffffffe, 10): u01(words 0, 1).
 // Moves:
 //   stretch(a):           z = (a - 1) u + 1, zz = z z / a, q = c_j - (c_j - s) zz, factor (D - 1) log zz;
 //   DE(sigma, g0):        gamma = g0 (1 + sigma n), q = s + gamma (c_j - c_k), factor 0;

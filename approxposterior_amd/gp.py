@@ -2240,6 +2240,120 @@ class GP(GeorgeExtras):
                 out["blobs"] = np.where(np.isneginf(blobs), np.nan, blobs)
         return out
 
+    def hmc_scale(self):
+        """``sc`` (D,): the factor between the user's coordinates and the scaled coordinates ``q = theta * sc`` in which
+        :meth:`sample_hmc` takes ``eps`` and integrates (``sc_d = sqrt(inv_metric_d / 2)``: the squared-exponential
+        term is ``amp * exp(-|q - q'|^2)`` there)."""
+        ks = self._kernel_struct()
+        return np.sqrt(0.5 * np.array(ks.inv_metric[:ks.ndim], dtype=np.float64))
+
+    def sample_hmc(self, y, initial_state, iterations, bounds, eps, nLeap, jitter=0.1, mass=None, seed=0, iteration0=0,
+                   prior=None, keep_device=False, store=True, debug=False, gRows=0):
+        """Hamiltonian Monte Carlo over the surrogate, whole chains on the device (``apgp_hmc_sample``): the target of
+        :meth:`sample_ensemble` -- density ``exp(mu)`` on the box ``bounds`` (edges may be infinite), or on
+        ``prior.support()`` under a :class:`~approxposterior_amd.priors.JointPrior` -- sampled by ``C`` independent
+        chains started at ``initial_state`` (C, D), with the exact gradient of the predictive mean.
+
+        One iteration draws a Gaussian momentum, takes ``nLeap`` leapfrog steps of size ``eps * (1 + jitter * (2u - 1))``
+        (one ``u`` per iteration, the same for every chain), reflecting at the finite faces of the box, and accepts
+        with probability ``min(1, exp(-dH))``.  ``eps`` is a step in the kernel's SCALED coordinates ``theta * sc``
+        (:meth:`hmc_scale`), in which the GP's length scales are all 1 / sqrt(2); ``mass`` (D,) is a diagonal mass in
+        the USER's coordinates (converted with ``sc``) and defaults to the identity in scaled coordinates, which makes
+        the GP's own length scales the preconditioner.  The random numbers of chain c at global iteration
+        ``iteration0 + it`` depend on ``(seed, c, iteration0 + it)`` only: a run cut into calls with consecutive
+        ``iteration0``, each fed the previous ``coords``, is the uncut run, bit for bit.
+
+        Returns the dict of :meth:`sample_ensemble` (``chain`` (iterations, C, D), ``log_prob``, ``coords``,
+        ``final_log_prob``, ``naccept``; ``blobs`` with ``prior``; ``chain_device`` with ``keep_device``) and
+        ``accept_prob`` (C,: the mean of ``min(1, exp(-dH))``), ``ndiverge`` (C,: trajectories rejected for a
+        non-finite energy error, one above 1000 or a reflection that did not end), ``eps``, ``g_rows``.  ``debug``
+        adds ``proposals`` (iterations, C, D), ``dH`` (iterations, C) and ``trace`` (iterations, C, nLeap, 2, D): q and
+        p after every leapfrog step in scaled coordinates.  ``gRows``: wavefronts per chain, 0 = the library's rule."""
+        D = self.kernel.ndim
+        p0 = np.ascontiguousarray(np.asarray(initial_state, dtype=np.float64))
+        if p0.ndim == 1:
+            p0 = p0.reshape(-1, D)
+        if p0.ndim != 2 or p0.shape[1] != D or p0.shape[0] < 1:
+            raise ValueError("initial_state must be (C, D)")
+        if not np.all(np.isfinite(p0)):
+            raise ValueError("At least one parameter value was NaN or infinite")
+        C = p0.shape[0]
+        iterations, nLeap, gRows, iteration0 = int(iterations), int(nLeap), int(gRows), int(iteration0)
+        eps, jitter = float(eps), float(jitter)
+        if iterations < 0:
+            raise ValueError("iterations must be >= 0")
+        if not (np.isfinite(eps) and eps > 0.0):
+            raise ValueError("eps must be finite and > 0")
+        if not 0.0 <= jitter < 1.0:
+            raise ValueError("jitter must lie in [0, 1)")
+        if not 1 <= nLeap <= _lib.HMC_MAX_LEAP:
+            raise ValueError("nLeap must lie between 1 and %d" % _lib.HMC_MAX_LEAP)
+        if gRows != 0 and gRows not in _lib.HMC_G_ROWS:
+            raise ValueError("gRows must be 0 (the library's rule) or one of %s" % (_lib.HMC_G_ROWS,))
+        if iteration0 < 0:
+            raise ValueError("iteration0 must be >= 0")
+        if mass is not None:
+            mass = np.asarray(mass, dtype=np.float64).ravel()
+            if mass.shape != (D,) or not np.all(np.isfinite(mass)) or not np.all(mass > 0.0):
+                raise ValueError("mass must be D finite positive numbers (a diagonal mass in the user's coordinates)")
+        if prior is not None:
+            records = self._prior_records(prior, D)
+            bounds = prior.support()
+        lo, hi = _box(bounds, D, optional=False)
+        if any(not lo[d] <= hi[d] for d in range(D)):
+            raise ValueError("bounds: every low edge must be <= its high edge")
+        self.recompute()
+        torch, dev, lib = self._rt()
+        y = self._check_dimensions(y)
+        n = len(self._x)
+        ks = self._kernel_struct()
+        opt = _lib.HmcOptions()
+        opt.eps, opt.jitter, opt.nleap, opt.g_rows, opt.iteration0 = eps, jitter, nLeap, gRows, iteration0
+        sc = self.hmc_scale()
+        ms = np.ones(D) if mass is None else mass / (sc * sc)
+        if not (np.all(np.isfinite(ms)) and np.all(ms > 0.0)):
+            raise ValueError("mass is not finite and positive in the kernel's scaled coordinates")
+        opt.mass[:D] = ms.tolist()
+        with self._on(torch, dev):
+            st = self._stream(torch)
+            self._ensure_xs(y)
+            f64, i64 = dict(dtype=torch.float64, device=dev), dict(dtype=torch.int64, device=dev)
+            coords = torch.from_numpy(p0).to(dev)
+            logp, accp = torch.empty(C, **f64), torch.empty(C, **f64)
+            nacc, ndiv = torch.empty(C, **i64), torch.empty(C, **i64)
+            chain = torch.empty((iterations, C, D), **f64) if store else None
+            lchain = torch.empty((iterations, C), **f64) if store else None
+            prop = torch.empty((iterations, C, D), **f64) if debug else None
+            dH = torch.empty((iterations, C), **f64) if debug else None
+            trace = torch.empty((iterations, C, nLeap, 2, D), **f64) if debug else None
+            _lib.check(lib.apgp_hmc_sample(self._xs.data_ptr(), n, ctypes.byref(ks), float(self.mean.value), lo, hi, C,
+                                           iterations, ctypes.byref(opt), _seed64(seed), coords.data_ptr(), logp.data_ptr(),
+                                           _ptr(chain), _ptr(lchain), nacc.data_ptr(), accp.data_ptr(), ndiv.data_ptr(),
+                                           _ptr(prop), _ptr(dH), _ptr(trace), st), "apgp_hmc_sample")
+            final = logp.cpu().numpy()
+            if np.any(np.isnan(final)):
+                raise FloatingPointError("the HMC sampler returned NaN log-probabilities: the GP mean is not finite at the "
+                                         "chains' positions")
+            out = {"coords": coords.cpu().numpy(), "final_log_prob": final, "naccept": nacc.cpu().numpy(),
+                   "chain": chain.cpu().numpy() if store else None,
+                   "log_prob": lchain.cpu().numpy() if store else None,
+                   "accept_prob": accp.cpu().numpy() / max(iterations, 1), "ndiverge": ndiv.cpu().numpy(),
+                   "eps": eps, "g_rows": gRows if gRows else int(lib.apgp_hmc_rule(C, n, D))}
+            if debug:
+                out["proposals"], out["dH"], out["trace"] = prop.cpu().numpy(), dH.cpu().numpy(), trace.cpu().numpy()
+            if keep_device and store:
+                out["chain_device"] = chain
+            if prior is not None and store:
+                lp = torch.empty(iterations * C, **f64)
+                if iterations:
+                    kind, q0, q1 = records
+                    _lib.check(lib.apgp_prior_lnprior(chain.data_ptr(), iterations * C, D, kind.ctypes.data,
+                                                      q0.ctypes.data, q1.ctypes.data, lp.data_ptr(), st),
+                               "apgp_prior_lnprior")
+                blobs = lp.cpu().numpy().reshape(iterations, C)
+                out["blobs"] = np.where(np.isneginf(blobs), np.nan, blobs)
+        return out
+
     # -- K4: gradient of the log-likelihood ------------------------------------------
     def grad_log_likelihood(self, y, quiet=False):
         """george GP.grad_log_likelihood (gpUtils.py:110): zeros on failure when quiet."""

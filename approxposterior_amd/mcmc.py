@@ -681,3 +681,54 @@ class TemperedChain(DeviceChain):
             se = np.asarray(batchMeansMCSE(self._rung_mean[int(discard):, 0, :]), dtype=np.float64)
             mc = float(np.sqrt(np.sum((w * se) ** 2)))
         return float(logVolume) + integral, abs(integral - coarse), mc
+
+
+class HMCChain(DeviceChain):
+    """Result of a Hamiltonian Monte Carlo run on the device (``GP.sample_hmc``): the chains behind the accessors of
+    :class:`DeviceChain` (a chain stands where a walker does, so ``estimateBurnin``, ``get_autocorr_time``, caching and
+    ``evidence(proposal="gmm")`` work unchanged), and the sampler's own diagnostics."""
+
+    def __init__(self, result, warmup=None):
+        super(HMCChain, self).__init__(result)
+        self.moves = None                  # no ensemble move made this chain
+        self.accept_prob = np.asarray(result["accept_prob"], dtype=np.float64)   # (C,) mean of min(1, exp(-dH))
+        self.ndiverge = np.asarray(result["ndiverge"], dtype=np.int64)           # (C,) divergent trajectories
+        self.step_size = float(result["eps"])                                    # eps of the sampling run
+        self.mass = result.get("mass")                                           # the diagonal mass (user's coordinates) or None
+        self.warmup = [] if warmup is None else list(warmup)                     # eps of every warm-up segment, in order
+
+
+def hmc_warmup(gp, y, initial_state, bounds, eps, nLeap, nWarmup=200, adaptEvery=20, targetAccept=0.8, kappa=1.0,
+               jitter=0.1, mass=None, adaptMass=False, seed=0, iteration0=0, prior=None, gRows=0):
+    """Warm up :meth:`GP.sample_hmc`: ``nWarmup`` iterations in segments of ``adaptEvery`` with consecutive
+    ``iteration0``, each started where the previous one ended.  After a segment ``eps <- eps * exp(kappa * (a -
+    targetAccept))``, ``a`` the segment's mean of ``accept_prob`` over the chains: C numbers cross per segment, no chain.
+    ``adaptMass``: at the end the diagonal mass becomes the inverse of the per-dimension variance pooled over the chains
+    and the second half of the warm-up segments (their pooled first and second moments; in the user's coordinates).
+    Returns ``(coords, eps, mass, history, iteration)``: the chains' final state, the adapted step, the mass (None: the
+    default), the step of every segment in order, and the global iteration number the sampling run starts at."""
+    nWarmup, adaptEvery = int(nWarmup), int(adaptEvery)
+    if nWarmup < 0 or adaptEvery < 1:
+        raise ValueError("nWarmup must be >= 0 and adaptEvery >= 1")
+    if not 0.0 < float(targetAccept) < 1.0:
+        raise ValueError("targetAccept must lie strictly between 0 and 1")
+    coords = np.asarray(initial_state, dtype=np.float64)
+    eps, it, history = float(eps), int(iteration0), []
+    nseg = -(-nWarmup // adaptEvery) if nWarmup else 0
+    cnt, s1, s2 = 0, 0.0, 0.0
+    for k in range(nseg):
+        m = min(adaptEvery, nWarmup - k * adaptEvery)
+        pool = adaptMass and k >= nseg // 2
+        res = gp.sample_hmc(y, coords, m, bounds, eps, nLeap, jitter=jitter, mass=mass, seed=seed, iteration0=it,
+                            prior=prior, store=pool, gRows=gRows)
+        history.append(eps)
+        coords, it = res["coords"], it + m
+        if pool:
+            x = res["chain"].reshape(-1, coords.shape[1])
+            cnt, s1, s2 = cnt + len(x), s1 + x.sum(axis=0), s2 + (x * x).sum(axis=0)
+        eps = eps * float(np.exp(kappa * (float(np.mean(res["accept_prob"])) - float(targetAccept))))
+    if adaptMass and cnt > 1:
+        var = (s2 - s1 * s1 / cnt) / (cnt - 1)
+        if np.all(np.isfinite(var)) and np.all(var > 0.0):
+            mass = 1.0 / var
+    return coords, eps, mass, history, it

@@ -735,6 +735,57 @@ int apgp_tempered_sample(const double* xs, int64_t n, const apgp_kernel_t* kern 
                          int64_t* swap_acc, uint8_t* swap_log, const apgp_ens_move_t* moves /*host*/, int32_t nmoves,
                          double* work, void* stream);
 
+/* ---- Hamiltonian Monte Carlo over the GP-mean surrogate, whole chains on the device (csrc/hmc.hip) ----------------
+ * nchains independent chains sample the target of apgp_ensemble_sample -- density exp(mu) on the box [lo, hi], edges may
+ * be infinite, the box only gates -- with the exact gradient of the predictive mean, which reuses the mean's N kernel
+ * values.  All positions below are in the kernel's scaled coordinates q = theta sc, sc_d = sqrt(inv_metric_d / 2).
+ *   One iteration of chain c, global number i = iteration0 + it, Philox4x32-10 under the keys
+ *   (seed, seed >> 32 ^ c 0x9E3779B9):
+ *     momentum  p_d = sqrt(-2 log u) cospi(2 u') sqrt(mass_d), (u, u') = u01 of words (0, 1), (2, 3) of counter
+ *               (i, i >> 32, d, 8);
+ *     step      eps_i = eps (1 + jitter (2 u - 1)), u = u01 of words 0, 1 of counter (i, i >> 32, 0xffffffff, 9) under
+ *               the keys of chain 0: one draw per iteration, the same for all chains;
+ *     nleap leapfrog steps, each  p += (eps_i / 2) g(q);  q += eps_i p / mass;  reflect;  p += (eps_i / 2) g(q),
+ *               g = d mu / d q (the kick between two steps is two half kicks: a step is a function of (q, p) alone);
+ *     reflect   while q_d lies outside a finite face: q_d = 2 face - q_d, p_d = -p_d, at most 8 times; still outside
+ *               then, or q or p not finite: the trajectory is a divergence.  Infinite faces never reflect;
+ *     accept    dH = (K(p_L) - mu(q_L)) - (K(p_0) - mu(q_0)), K = sum_d p_d^2 (0.5 / mass_d); accepted iff log u < -dH,
+ *               u = u01 of words 0, 1 of counter (i, i >> 32, 0xfffffffe, 10).  dH not finite or > 1000: rejected and
+ *               counted in ndiverge.  A start outside the box has mu = -inf: the chain never moves, naccept = 0.
+ *   A chain's draws depend on (seed, c, i) only: not on nchains, and not on where a run was cut into calls (feed the
+ *   next call the previous coords and iteration0 + iterations).
+ *   mass is diagonal, in scaled coordinates; all ones makes the GP's own length scales the preconditioner.
+ *   Outputs (device): coords (C x D, in = start, out = final state; a chain that accepted nothing keeps its bits), logp
+ *     (C: final mu, -inf outside the box), naccept, ndiverge (C), accprob (C: sum over the iterations of
+ *     min(1, exp(-dH)), 0 for a divergence); may be NULL: chain (iterations x C x D), logp_chain (iterations x C), prop
+ *     (iterations x C x D: the end of every trajectory, accepted or not; NaN where the trajectory left the box for good
+ *     or stopped being finite), dH (iterations x C), trace (iterations x C x
+ *     nleap x 2 D: q then p after every step, in SCALED coordinates, the kernel's own bits).
+ *   iterations == 0 leaves coords and writes logp.
+ *   Schedule: g_rows wavefronts share a chain (their lanes stride the training rows; fixed-order sums, no atomics: the
+ *     same inputs and g_rows give the same bits); offered: 1 and 4 (a workgroup is 4 wavefronts); 0 = the library's rule
+ *     (apgp_hmc_rule reports it).  One launch, nothing waits, the call does not synchronise.
+ * -1 before anything reaches the device: a NULL among xs, kern, lo, hi, opt, coords, logp, naccept, accprob, ndiverge;
+ * n outside 1 .. 2^24; nchains outside 1 .. 2^24; iterations outside 0 .. 2^40; bad kernel parameters; eps not finite or
+ * <= 0; jitter outside [0, 1); nleap outside 1 .. APGP_HMC_MAX_LEAP; g_rows not offered; iteration0 < 0; a mass not
+ * finite or <= 0; lo > hi (or NaN); a trace of more than 2^63 bytes.
+ * Added in ABI 8 without changing anything before it: APGP_ABI_VERSION stays 8.                                   */
+#define APGP_HMC_MAX_LEAP 1024
+typedef struct apgp_hmc_options {
+    double eps, jitter;        /* step in scaled coordinates, > 0; 0 <= jitter < 1 */
+    int32_t nleap;             /* 1 .. APGP_HMC_MAX_LEAP */
+    int32_t g_rows;            /* 0 = the rule, else wavefronts per chain */
+    int64_t iteration0;        /* global number of the call's first iteration */
+    double mass[APGP_MAX_DIM]; /* diagonal mass, scaled coordinates, finite > 0 */
+} apgp_hmc_options_t;
+int apgp_hmc_sample(const double* xs, int64_t n, const apgp_kernel_t* kern /*host*/, double mean,
+                    const double* lo /*host, MAX_DIM*/, const double* hi /*host, MAX_DIM*/, int32_t nchains,
+                    int64_t iterations, const apgp_hmc_options_t* opt /*host*/, uint64_t seed,
+                    double* coords, double* logp, double* chain, double* logp_chain, int64_t* naccept, double* accprob,
+                    int64_t* ndiverge, double* prop, double* dH, double* trace, void* stream);
+/* g_rows the rule picks for these sizes on the current device; -1 for sizes the call refuses, -2 without a device */
+int apgp_hmc_rule(int32_t nchains, int64_t n, int32_t ndim);
+
 /* ---- candidate matrix of the sweep drawn on the device (round 5, opt-in) ------
  * The batched counterpart of the ``sampleFn`` draws utility.minimizeObjective starts from
  * (utility.py:334-338) when the prior is the box: T (m x ndim, device) row i =
