@@ -17,6 +17,7 @@ from .approx import ApproxPosterior  # noqa: F401
 from .gpUtils import defaultHyperPrior, defaultGP, optimizeGP  # noqa: F401
 from .gmmUtils import fitGMM  # noqa: F401
 evidence = ApproxPosterior.evidence  # noqa: E305  (evidence(ap, nSamples=..., proposal=...): the method as a function)
+runNested = ApproxPosterior.runNested  # noqa: E305  (runNested(ap, nlive=..., nruns=...): the method as a function)
 from .mcmcUtils import validateMCMCKwargs, batchMeansMCSE, estimateBurnin  # noqa: F401
 from .utility import (logsubexp, AGPUtility, BAPEUtility, JonesUtility,  # noqa: F401
                       minimizeObjective, sweepObjective, klNumerical, mergeImportance, importanceSummary)

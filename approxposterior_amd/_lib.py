@@ -65,6 +65,8 @@ ENS_MAX_MOVES = 8     # APGP_ENS_MAX_MOVES
 PT_MAX_TEMPS = 64     # APGP_PT_MAX_TEMPS: rungs of a tempering ladder
 HMC_MAX_LEAP = 1024   # APGP_HMC_MAX_LEAP: leapfrog steps per iteration of apgp_hmc_sample
 HMC_G_ROWS = (1, 4)   # wavefronts per chain apgp_hmc_sample offers (g_rows; 0 = the library's rule)
+NESTED_MAX_LIVE = 4096   # live points per run of apgp_nested_sample
+NESTED_MAX_BATCH = 16    # points replaced per batch: a wavefront per walker
 
 
 class HmcOptions(ctypes.Structure):
@@ -173,6 +175,10 @@ SIGNATURES = {
     "apgp_hmc_sample": (ctypes.c_int, [_P, _I64, _KP, _F64, ctypes.POINTER(_F64), ctypes.POINTER(_F64), _I32, _I64,
                                        ctypes.POINTER(HmcOptions), ctypes.c_uint64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "apgp_hmc_rule": (ctypes.c_int, [_I32, _I64, _I32]),
+    "apgp_nested_work_len": (_I64, [_I32, _I32, _I32]),
+    "apgp_nested_xlds": (ctypes.c_int, [_I64, _I32]),
+    "apgp_nested_sample": (ctypes.c_int, [_P, _I64, _KP, _F64, ctypes.POINTER(_F64), ctypes.POINTER(_F64), _I32, _I32, _I32,
+                                          _I32, _F64, _F64, _F64, _I32, ctypes.c_uint64, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "apgp_box_candidates": (ctypes.c_int, [_P, _I64, _I32, ctypes.POINTER(_F64), ctypes.POINTER(_F64), ctypes.c_uint64,
                                            _I64, _P]),
     "apgp_prior_candidates": (ctypes.c_int, [_P, _I64, _I32, _P, _P, _P, ctypes.c_uint64, _I64, _P]),

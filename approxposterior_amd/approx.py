@@ -954,6 +954,39 @@ class ApproxPosterior(object):
             record = part if record is None else ut.mergeImportance(record, part)
         return ut.importanceSummary(record, nSamples, logVolume=logVolume)
 
+    def runNested(self, nlive=512, batch=16, nsteps=None, nruns=None, dlogz=0.01, maxBatches=None, seed=None,
+                  sigma=1.0e-5, gamma0=None):
+        """The model evidence, its error, the information and weighted posterior samples of the surrogate by nested
+        sampling on the device (:meth:`gp.GP.sample_nested`): what :meth:`evidence` gives, without a proposal to choose --
+        the runs start from the prior's box and compress towards the modes wherever they are.  The prior measure is
+        the uniform one on the box, as for ``evidence(proposal="box")``: the GP models the unnormalised log-posterior,
+        so the prior's density is already inside ``mu``.
+
+        The box is ``self.bounds``, intersected with ``lnprior.support()`` under a
+        :class:`~approxposterior_amd.priors.JointPrior` (the gate of :meth:`evidence`); a box that is not finite raises
+        ``ValueError``.  ``seed=None`` takes one from NumPy's global stream; under a process group every rank computes
+        the same numbers from the same seed.  The :class:`mcmc.NestedResult` is returned and kept as ``self.nested``;
+        ``self.sampler`` and everything :meth:`run`, :meth:`runMCMC` and :meth:`evidence` keep are left alone."""
+        b = np.asarray(self.bounds, dtype=np.float64).reshape(-1, 2)
+        joint = self._jointPrior()
+        if joint is not None:
+            s = np.asarray([tuple(r) for r in joint.support()], dtype=np.float64).reshape(-1, 2)
+            if s.shape != b.shape:
+                raise ValueError("runNested: lnprior.support() and bounds disagree on the dimension")
+            b = np.stack([np.maximum(b[:, 0], s[:, 0]), np.minimum(b[:, 1], s[:, 1])], axis=1)
+        if not (np.all(np.isfinite(b)) and np.all(b[:, 0] < b[:, 1])):
+            raise ValueError("runNested needs a finite, non-empty box: the uniform measure on it is the prior measure")
+        args = george.GP._nested_arguments(len(b), b, nlive, batch, nsteps, nruns, dlogz, maxBatches, sigma, gamma0)
+        if seed is None:
+            if self._ranks() is not None:       # one NumPy stream on every rank, as evidence() arranges: the same seed
+                apdist.sync_random_state(0, self.group, enabled=self.distributed)
+            seed = int(np.random.randint(0, 2 ** 31 - 1))
+        _, nlive, batch, nsteps, nruns, dlogz, maxBatches, sigma, gamma0 = args
+        self.nested = self.gp.sample_nested(self.y, b, nlive=nlive, batch=batch, nsteps=nsteps, nruns=nruns, dlogz=dlogz,
+                                            maxBatches=maxBatches, seed=seed, sigma=sigma,
+                                            gamma0=gamma0 if gamma0 > 0.0 else None)
+        return self.nested
+
     # ---------------------------------------------------------------------- outer loop
     def run(self, m=10, nmax=2, seed=None, timing=False, verbose=True,
             mcmcKwargs=None, samplerKwargs=None, estBurnin=False,

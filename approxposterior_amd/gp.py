@@ -2354,6 +2354,115 @@ class GP(GeorgeExtras):
                 out["blobs"] = np.where(np.isneginf(blobs), np.nan, blobs)
         return out
 
+    @staticmethod
+    def _nested_arguments(D, bounds, nlive, batch, nsteps, nruns, dlogz, maxBatches, sigma, gamma0):
+        """The checked arguments of :meth:`sample_nested` (host arithmetic only; ``nruns`` may stay None)."""
+        nlive, batch = int(nlive), int(batch)
+        if not 1 <= batch <= _lib.NESTED_MAX_BATCH:
+            raise ValueError("batch must lie between 1 and %d (a wavefront per walker)" % _lib.NESTED_MAX_BATCH)
+        if not 4 <= nlive <= _lib.NESTED_MAX_LIVE:
+            raise ValueError("nlive must lie between 4 and %d" % _lib.NESTED_MAX_LIVE)
+        if nlive < 2 * batch:
+            raise ValueError("nlive must be at least 2 * batch")
+        nsteps = max(20, 5 * D) if nsteps is None else int(nsteps)
+        if nsteps < 1:
+            raise ValueError("nsteps must be >= 1")
+        if nruns is not None:
+            nruns = int(nruns)
+            if nruns < 1:
+                raise ValueError("nruns must be >= 1")
+        dlogz, sigma = float(dlogz), float(sigma)
+        if not (np.isfinite(dlogz) and dlogz >= 0.0):
+            raise ValueError("dlogz must be finite and >= 0 (0: stop at maxBatches only)")
+        if not (np.isfinite(sigma) and sigma >= 0.0):
+            raise ValueError("sigma must be finite and >= 0")
+        gamma0 = 0.0 if gamma0 is None else float(gamma0)
+        if not (np.isfinite(gamma0) and gamma0 > 0.0) and gamma0 != 0.0:
+            raise ValueError("gamma0 must be finite and > 0 (None: 2.38 / sqrt(2 D))")
+        maxBatches = -(-50 * nlive // batch) if maxBatches is None else int(maxBatches)
+        if maxBatches < 1:
+            raise ValueError("maxBatches must be >= 1")
+        b = np.asarray(bounds, dtype=np.float64).reshape(-1, 2)
+        if len(b) != D:
+            raise ValueError("bounds must have one (lo, hi) pair per dimension")
+        if not (np.all(np.isfinite(b)) and np.all(b[:, 0] < b[:, 1])):
+            raise ValueError("nested sampling needs a finite, non-empty box: its uniform measure is the prior measure")
+        return b, nlive, batch, nsteps, nruns, dlogz, maxBatches, sigma, gamma0
+
+    def sample_nested(self, y, bounds, nlive=512, batch=16, nsteps=None, nruns=None, dlogz=0.01, maxBatches=None, seed=0,
+                      sigma=1.0e-5, gamma0=None, debug=False, timeDevice=False):
+        """Nested sampling over the surrogate, whole runs on the device (``apgp_nested_sample``): the evidence
+        ``Z = V int exp(mu) dU`` under the uniform measure on the finite box ``bounds`` (the measure of
+        ``evidence(proposal="box")``), its error, the information ``H`` and weighted posterior samples, from ``nruns``
+        independent runs merged by :func:`mcmc.nested_weights`.  Nothing is tuned from outside: the runs start from
+        the box and compress towards the modes wherever they are.
+
+        A run keeps ``nlive`` live points.  Per batch the ``batch`` lowest die and each is replaced by a walker that
+        starts at a random survivor and takes ``nsteps`` (default ``max(20, 5 D)``) constrained differential-evolution
+        steps ``q' = q + gamma0 (1 + sigma n)(c_a - c_b)`` in the kernel's scaled coordinates, accepted iff inside the
+        box and ``mu(q') >`` the batch's threshold.  A run stops after the first batch for which the live points could
+        add less than ``dlogz`` to ``logZ``, or after ``maxBatches`` (default ``50 nlive / batch``; ``dlogz=0``: then
+        only).  ``nruns=None`` takes one run per compute unit of the device.  Run r's numbers depend on ``(seed, r)``
+        only.  Returns a :class:`mcmc.NestedResult`.  Too few ``nsteps`` bias a step sampler (``nstuck`` and
+        ``efficiency`` are the symptoms to watch).  ``debug`` adds ``info["trace"]`` (nruns, maxBatches, batch, nsteps,
+        D + 2): every step's proposal, its mean (NaN: outside the box, not evaluated) and 1 / 0 for accepted / not; rows
+        of batches that were not run are NaN.  ``timeDevice`` adds ``info["deviceSeconds"]``, the launch between two
+        events on its stream (the copies and the host's accounting are not in it)."""
+        from .mcmc import NestedResult
+        D = self.kernel.ndim
+        b, nlive, batch, nsteps, nruns, dlogz, maxBatches, sigma, gamma0 = self._nested_arguments(
+            D, bounds, nlive, batch, nsteps, nruns, dlogz, maxBatches, sigma, gamma0)
+        lo, hi = _box(b, D, optional=False)
+        self.recompute()
+        torch, dev, lib = self._rt()
+        y = self._check_dimensions(y)
+        n = len(self._x)
+        ks = self._kernel_struct()
+        with self._on(torch, dev):
+            st = self._stream(torch)
+            self._ensure_xs(y)
+            if nruns is None:
+                nruns = int(torch.cuda.get_device_properties(dev).multi_processor_count)
+            wlen = int(lib.apgp_nested_work_len(D, nlive, nruns))
+            if wlen < 0:
+                raise ValueError("sample_nested: nlive or nruns beyond the library's limits")
+            cap = nlive + batch * maxBatches
+            f64 = dict(dtype=torch.float64, device=dev)
+            work = torch.empty(wlen, **f64)
+            pts = torch.empty((nruns, cap, D), **f64)
+            logl, birth = torch.empty((nruns, cap), **f64), torch.empty((nruns, cap), **f64)
+            rec = torch.empty((nruns, cap), dtype=torch.int32, device=dev)
+            counts = torch.empty((nruns, 4), dtype=torch.int64, device=dev)
+            logz = torch.empty((nruns, 2), **f64)
+            trace = torch.full((nruns, maxBatches, batch, nsteps, D + 2), float("nan"), **f64) if debug else None
+            if timeDevice:
+                ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                ev0.record()
+            _lib.check(lib.apgp_nested_sample(self._xs.data_ptr(), n, ctypes.byref(ks), float(self.mean.value), lo, hi, nlive,
+                                              batch, nsteps, maxBatches, dlogz, sigma, gamma0, nruns, _seed64(seed),
+                                              work.data_ptr(), pts.data_ptr(), logl.data_ptr(), birth.data_ptr(),
+                                              rec.data_ptr(), counts.data_ptr(), logz.data_ptr(), _ptr(trace), st),
+                       "apgp_nested_sample")
+            if timeDevice:
+                ev1.record()
+            cn = counts.cpu().numpy()
+            used = cn[:, 0] * batch + nlive
+            top = int(used.max())
+            P, Ll, Lb, R = (v[:, :top].cpu().numpy() for v in (pts, logl, birth, rec))
+            lz = logz.cpu().numpy()
+        keep = np.arange(top)[None, :] < used[:, None]
+        if np.any(np.isnan(Ll[keep])):
+            raise FloatingPointError("the nested sampler returned NaN log-likelihoods: the GP mean is not finite in the box")
+        run = np.broadcast_to(np.arange(nruns)[:, None], keep.shape)
+        info = {"record": R[keep], "deviceLogZ": lz[:, 0], "deviceLogX": lz[:, 1], "nsteps": nsteps, "batch": batch,
+                "dlogz": dlogz, "maxBatches": maxBatches, "seed": seed}
+        if debug:
+            info["trace"] = trace.cpu().numpy()
+        if timeDevice:
+            info["deviceSeconds"] = 1.0e-3 * ev0.elapsed_time(ev1)
+        return NestedResult(P[keep], Ll[keep], Lb[keep], run[keep], logVolume=float(np.sum(np.log(b[:, 1] - b[:, 0]))),
+                            counts=cn, nlive=nlive, info=info)
+
     # -- K4: gradient of the log-likelihood ------------------------------------------
     def grad_log_likelihood(self, y, quiet=False):
         """george GP.grad_log_likelihood (gpUtils.py:110): zeros on failure when quiet."""

@@ -30,7 +30,8 @@ whole replicas.
 
 import numpy as np
 
-__all__ = ["EnsembleSampler", "integrated_time", "AutocorrError", "StretchMove", "DEMove", "DESnookerMove", "moves"]
+__all__ = ["EnsembleSampler", "integrated_time", "AutocorrError", "StretchMove", "DEMove", "DESnookerMove", "moves",
+           "nested_weights", "NestedResult"]
 
 
 class AutocorrError(Exception):
@@ -732,3 +733,123 @@ def hmc_warmup(gp, y, initial_state, bounds, eps, nLeap, nWarmup=200, adaptEvery
         if np.all(np.isfinite(var)) and np.all(var > 0.0):
             mass = 1.0 / var
     return coords, eps, mass, history, it
+
+
+def _logsumexp(v):
+    v = np.asarray(v, dtype=np.float64)
+    m = np.max(v) if len(v) else -np.inf
+    if not np.isfinite(m):
+        return float(m)
+    return float(m + np.log(np.sum(np.exp(v - m))))
+
+
+def nested_weights(logL, logLBirth, run=None):
+    """The accounting of nested sampling for ANY set of points, each with its log-likelihood ``logL`` and the threshold
+    it was born under ``logLBirth`` (-inf for a point drawn from the whole prior): one rule for the batched removal of a
+    run (live counts n, n - 1, ... inside a batch), its final flush (n, n - 1, ..., 1) and the merge of several runs
+    (the counts add), which is then nothing more than concatenation -- the live-count rule dynesty uses for merged and
+    dynamic runs.
+
+    The points are ordered stably by ``(logL, run, serial)``, serial the input position.  Point j is live at point k iff
+    ``logLBirth[j] < logL[k]`` and j is not before k in the order; ``n_k`` counts them (k included).  Then
+    ``logX_k = -sum_{i <= k} 1 / n_i`` (``E[log t] = -1 / n``) and the rectangle weights are
+    ``logWt_k = logL_k + logX_{k-1} + log(1 - exp(-1 / n_k))``, with ``logX_{-1} = 0``: the prior measure is normalised,
+    a box's log-volume is the caller's to add.
+
+    Returns a dict, every array in the INPUT order: ``order`` (the sorting permutation), ``nlive``, ``logX``, ``logWt``,
+    and the scalars ``logZ``; ``H``, the information; ``logZErr = sqrt(sum_k dH_k / n_k)``, which is ``sqrt(H / n)``
+    for a constant live count; ``ess``, Kish's effective sample size of the posterior weights."""
+    logL = np.asarray(logL, dtype=np.float64).ravel()
+    birth = np.asarray(logLBirth, dtype=np.float64).ravel()
+    M = len(logL)
+    if len(birth) != M or M < 1:
+        raise ValueError("nested_weights: logL and logLBirth must be non-empty and of one length")
+    if np.any(np.isnan(logL)) or np.any(np.isnan(birth)):
+        raise ValueError("nested_weights: NaN in logL or logLBirth")
+    run = np.zeros(M, dtype=np.int64) if run is None else np.asarray(run, dtype=np.int64).ravel()
+    if len(run) != M:
+        raise ValueError("nested_weights: run must have one entry per point")
+    order = np.lexsort((np.arange(M), run, logL))
+    ls = logL[order]
+    # every point before k in the order was born below its own logL <= logL_k: it counts among the births below logL_k
+    n = np.searchsorted(np.sort(birth), ls, side="left") - np.arange(M)
+    n = np.maximum(n, 1).astype(np.float64)
+    inv = 1.0 / n
+    lx = -np.cumsum(inv)
+    lw = ls + np.concatenate([[0.0], lx[:-1]]) + np.log(-np.expm1(-inv))
+    logZ = _logsumexp(lw)
+    if np.isfinite(logZ):
+        w = np.exp(lw - logZ)
+        cz = np.cumsum(w)
+        cl = np.cumsum(np.where(w > 0.0, w * np.where(w > 0.0, ls, 0.0), 0.0))
+        with np.errstate(divide="ignore", invalid="ignore"):
+            Hk = np.where(cz > 0.0, cl / cz - (logZ + np.log(cz)), 0.0)
+        H = float(Hk[-1])
+        var = float(np.sum(np.diff(np.concatenate([[0.0], Hk])) * inv))
+        ess = float(np.sum(w) ** 2 / np.sum(w * w))
+    else:
+        H, var, ess = np.nan, np.nan, 0.0
+    out = {"order": order, "logZ": logZ, "H": H, "logZErr": float(np.sqrt(max(var, 0.0))) if var == var else np.nan,
+           "ess": ess}
+    for key, v in (("nlive", n), ("logX", lx), ("logWt", lw)):
+        a = np.empty(M)
+        a[order] = v
+        out[key] = a
+    return out
+
+
+class NestedResult(object):
+    """Result of nested-sampling runs over the surrogate (``GP.sample_nested``): every point the runs wrote -- the dead
+    points and the final live points of all runs, concatenated -- with the evidence, its error, the information and the
+    weighted posterior.  ``logWt`` and ``logZ`` include ``logVolume``, the log-volume of the prior's box, as
+    ``evidence(proposal="box")`` reports it.
+
+    ``points`` (M, D), ``logL``, ``logLBirth``, ``run`` (M,), ``logX``, ``logWt``, ``logZ``, ``logZErr``, ``H``, ``ess``,
+    ``mean`` (D,), ``cov`` (D, D), ``logZRuns`` (nruns,: every run's own evidence, whose scatter is a second error
+    estimate: ``logZRunsErr`` is its standard error of the mean in log space, NaN for one run), ``nbatch``, ``ncall``,
+    ``naccept``, ``nstuck`` (per run), ``efficiency`` (accepted steps per likelihood call of the walkers)."""
+
+    def __init__(self, points, logL, logLBirth, run, logVolume=0.0, counts=None, nlive=None, info=None):
+        self.points = np.asarray(points, dtype=np.float64)
+        self.logL = np.asarray(logL, dtype=np.float64)
+        self.logLBirth = np.asarray(logLBirth, dtype=np.float64)
+        self.run = np.asarray(run, dtype=np.int64)
+        self.logVolume = float(logVolume)
+        w = nested_weights(self.logL, self.logLBirth, self.run)
+        self.logX, self.nliveAt, self.H, self.logZErr, self.ess = w["logX"], w["nlive"], w["H"], w["logZErr"], w["ess"]
+        self.logWt = w["logWt"] + self.logVolume
+        self.logZ = w["logZ"] + self.logVolume
+        p = self.weights()
+        self.mean = p @ self.points
+        r = self.points - self.mean
+        self.cov = (r * p[:, None]).T @ r
+        runs = np.unique(self.run)
+        self.nruns = len(runs)
+        by = np.argsort(self.run, kind="stable")                    # (the runs' rows, each in its input order)
+        cut = np.searchsorted(self.run[by], runs)
+        self.logZRuns = np.array([nested_weights(self.logL[rows], self.logLBirth[rows])["logZ"]
+                                  for rows in np.split(by, cut[1:])]) + self.logVolume
+        self.logZRunsErr = float(np.std(self.logZRuns, ddof=1) / np.sqrt(self.nruns)) if self.nruns > 1 else np.nan
+        counts = np.zeros((self.nruns, 4), dtype=np.int64) if counts is None else np.asarray(counts, dtype=np.int64)
+        self.nbatch, self.ncall, self.naccept, self.nstuck = counts[:, 0], counts[:, 1], counts[:, 2], counts[:, 3]
+        self.nlive = nlive
+        walk = float(np.sum(self.ncall)) - (0 if nlive is None else float(nlive) * self.nruns)
+        self.efficiency = float(np.sum(self.naccept)) / walk if walk > 0 else np.nan
+        self.info = {} if info is None else dict(info)
+
+    def weights(self):
+        """The normalised posterior weights ``exp(logWt - logZ)`` (M,)."""
+        return np.exp(self.logWt - self.logZ)
+
+    def samples_equal(self, size=None, seed=None):
+        """``size`` equally weighted posterior samples (default: ``ess`` rounded down, at least 1) by systematic
+        resampling: one uniform ``u`` (from ``seed``; None: NumPy's global stream) places the comb ``(u + i) / size``
+        on the cumulative weights."""
+        size = max(1, int(self.ess)) if size is None else int(size)
+        if size < 1:
+            raise ValueError("samples_equal: size must be positive")
+        rs = np.random if seed is None else np.random.RandomState(int(seed) & 0xFFFFFFFF)
+        c = np.cumsum(self.weights())
+        c = c / c[-1]
+        pos = (rs.uniform() + np.arange(size)) / size
+        return self.points[np.minimum(np.searchsorted(c, pos, side="left"), len(c) - 1)]

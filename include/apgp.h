@@ -786,6 +786,64 @@ int apgp_hmc_sample(const double* xs, int64_t n, const apgp_kernel_t* kern /*hos
 /* g_rows the rule picks for these sizes on the current device; -1 for sizes the call refuses, -2 without a device */
 int apgp_hmc_rule(int32_t nchains, int64_t n, int32_t ndim);
 
+/* ---- nested sampling over the GP-mean surrogate, whole runs on the device (csrc/nested.hip) ------------------------
+ * The evidence Z = V int L dU of the likelihood L = exp(mu) under the uniform measure U on the FINITE box [lo, hi] (V its
+ * volume: the measure of the box proposal of apgp_importance_pass's callers), by nruns independent runs of nested
+ * sampling with a constrained differential-evolution step sampler.  Nothing is tuned from outside: no proposal, no
+ * ladder, no step size.  Positions are kept in the caller's coordinates th; the kernel evaluates at q = th sc,
+ * sc_d = sqrt(inv_metric_d / 2).  Run r draws from Philox4x32-10 under the keys (seed, seed >> 32 ^ r 0x9E3779B9): its
+ * output does not depend on nruns.  u01 is the 53-bit uniform of two words.
+ *   start    live point w, dimension d: th = min(fma(hi_d - lo_d, u, lo_d), hi_d), u = u01 of words (0, 1) for even d,
+ *            (2, 3) for odd d, of counter (w, d / 2, 0, 11).  logL = mu(th sc) summed in the order of the
+ *            single-workgroup ensemble kernel: the bits apgp_ensemble_sample(iterations = 0, mode = 1) writes into logp
+ *            for the same coordinates (a NaN would be stored as -inf).  Birth threshold -inf.
+ *   batch b = 0, 1, ...: the live points are ordered ascending by (logL, slot).  The first `batch` die; L* is the logL
+ *            of the last of them.  Dead point i (i = 0 .. batch - 1 in that order) is written to row b batch + i with
+ *            its logL, its birth threshold and rec = b.  The survivors, j = 0 .. S - 1 in the same order (S = nlive -
+ *            batch), are frozen for the batch.  Walker i refills the slot of dead point i:
+ *              start  survivor word 0 % S of counter (b, 0xffffffff, i, 12);
+ *              step s = 0 .. nsteps - 1: a = word 0 % S, k = word 1 % (S - 1), k += (k >= a) of counter (b, s, i, 13);
+ *                     n = sqrt(-2 log u) cospi(2 u'), (u, u') = u01 of words (0, 1), (2, 3) of counter (b, s, i, 14);
+ *                     gamma = gamma0 (1 + sigma n);  q' = fma(gamma, th_a sc - th_k sc, q);  th' = q' / sc;
+ *                     q'' = th' sc (every operation rounded once).  Accepted iff every th'_d is finite and inside
+ *                     [lo_d, hi_d] and mu(q'') > L*; then (th, q, logL) = (th', q'', mu(q'')).  mu is evaluated, and
+ *                     counted in ncall, only for a proposal inside the box.  The proposal is symmetric: the walk
+ *                     leaves the uniform law on {L > L*} invariant.
+ *              The walker's end point takes the dead slot with birth threshold L*.  A walker that accepted nothing is
+ *              a copy of its start point: it is kept and counted in nstuck.
+ *            One lane keeps logX_b and logZ_b over the dead points: per dead point i of a batch, n = nlive - i,
+ *            logZ = logaddexp(logZ, logL + logX + log(1 - exp(-1 / n))), logX -= 1 / n.
+ *   stop     before batch b >= 1 if dlogz > 0 and logaddexp(logZ, Lmax + logX) - logZ < dlogz, Lmax the largest live
+ *            logL; and at b = max_batches.  dlogz = 0: at max_batches only.  The nlive live points are then written
+ *            ascending to rows nb batch ..., rec = -1 (nb = batches done).
+ *   gamma0 = 0 is the default 2.38 / sqrt(2 ndim), the one of APGP_ENS_MOVE_DE.  Tags 11 - 14 are this entry's; 1 - 10
+ *   and the candidate tag belong to the entries above.
+ *   Outputs (device), cap = nlive + batch max_batches rows per run, rows past nb batch + nlive are not written: points
+ *     (nruns x cap x ndim), logl, birth (nruns x cap), rec (int32, nruns x cap), counts (int64, nruns x 4: nb, likelihood
+ *     calls with the nlive start values, accepted steps, stuck walkers), logz (nruns x 2: logZ and logX over the dead
+ *     points when the run stopped; the live points' share is the host's to add); may be NULL: trace (nruns x
+ *     max_batches x batch x nsteps x (ndim + 2): per step th', then mu(q'') -- NaN where th' left the box and mu was not
+ *     evaluated -- then 1 for accepted, 0 for not; rows of batches not run are not written).  work (device,
+ *     apgp_nested_work_len doubles, -1 for sizes the call refuses) holds the live sets; not to be shared by two calls
+ *     at once.
+ *   Schedule: one launch, one workgroup of 16 wavefronts per run, a wavefront per walker (so batch <= 16).  Nothing is
+ *     exchanged between workgroups, nothing spins or waits; every loop is bounded by max_batches, batch, nsteps, nlive
+ *     or the training rows.  The order is a fixed-sequence bitonic sort: the same inputs give the same bits.  The
+ *     training stream is staged in LDS when it fits 96 KiB (apgp_nested_xlds: 1, else 0 and it is read from L2; -1 for
+ *     sizes the call refuses).  The call does not synchronise.
+ * -1 before anything reaches the device: a NULL pointer; n outside 1 .. 2^24; bad kernel parameters; nlive outside
+ * 4 .. 4096; nlive < 2 batch; batch outside 1 .. 16; nsteps outside 1 .. 2^20; max_batches outside 1 .. 2^24; nruns
+ * outside 1 .. 2^20; dlogz, sigma or gamma0 negative or not finite; a box edge not finite or lo >= hi; outputs of more
+ * than 2^63 bytes.
+ * Added in ABI 8 without changing anything before it: APGP_ABI_VERSION stays 8.                                   */
+int64_t apgp_nested_work_len(int32_t ndim, int32_t nlive, int32_t nruns);
+int apgp_nested_xlds(int64_t n, int32_t ndim);
+int apgp_nested_sample(const double* xs, int64_t n, const apgp_kernel_t* kern /*host*/, double mean,
+                       const double* lo /*host, MAX_DIM*/, const double* hi /*host, MAX_DIM*/, int32_t nlive,
+                       int32_t batch, int32_t nsteps, int32_t max_batches, double dlogz, double sigma, double gamma0,
+                       int32_t nruns, uint64_t seed, double* work, double* points, double* logl, double* birth,
+                       int32_t* rec, int64_t* counts, double* logz, double* trace, void* stream);
+
 /* ---- candidate matrix of the sweep drawn on the device (round 5, opt-in) ------
  * The batched counterpart of the ``sampleFn`` draws utility.minimizeObjective starts from
  * (utility.py:334-338) when the prior is the box: T (m x ndim, device) row i =
