@@ -20,6 +20,7 @@ evidence = ApproxPosterior.evidence  # noqa: E305  (evidence(ap, nSamples=..., p
 runNested = ApproxPosterior.runNested  # noqa: E305  (runNested(ap, nlive=..., nruns=...): the method as a function)
 from .mcmcUtils import validateMCMCKwargs, batchMeansMCSE, estimateBurnin  # noqa: F401
 from .utility import (logsubexp, AGPUtility, BAPEUtility, JonesUtility,  # noqa: F401
-                      minimizeObjective, sweepObjective, klNumerical, mergeImportance, importanceSummary)
+                      minimizeObjective, sweepObjective, klNumerical, mergeImportance, importanceSummary,
+                      importanceDrawsSummary)
 from .likelihood import *  # noqa: F401,F403
 from .priors import *  # noqa: F401,F403

@@ -196,6 +196,9 @@ SIGNATURES = {
     "apgp_importance_work_len": (_I64, [_I64]),
     "apgp_importance_pass": (ctypes.c_int, [_P, _I64, _P, _P, _I64, _KP, _F64, ctypes.POINTER(_F64), ctypes.POINTER(_F64),
                                             _P, _P, _P, _P, _P]),
+    "apgp_path_importance_work_len": (_I64, [_I64, _I32]),
+    "apgp_path_importance": (ctypes.c_int, [_P, _I64, _P, _P, _I64, _KP, _F64, _P, _P, _P, _P, _P, _I32, _I32,
+                                            ctypes.POINTER(_F64), ctypes.POINTER(_F64), _P, _P, _P, _P, _P]),
     "apgp_autocorr_work_len": (_I64, [_I64, _I64, _I32]),
     "apgp_autocorr_block": (ctypes.c_int, [_P, _I64, _I64, _I32, _I64, _I64, _I64, _I64, _I32, _P, _P, _P]),
 }

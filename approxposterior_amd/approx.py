@@ -885,7 +885,7 @@ class ApproxPosterior(object):
                          "fitted full-covariance mixture, not %r" % (proposal,))
 
     def evidence(self, nSamples=2 ** 20, proposal="prior", seed=None, chunk=2 ** 20, samples=None, maxComp=3,
-                 covScale=1.0):
+                 covScale=1.0, surrogateDraws=0, nFeatures=2048):
         """The model evidence and chain-free posterior moments of the surrogate by importance sampling on the device.
         The GP models the unnormalised log-posterior (``y = lnlike + lnprior``), so ``Z = int exp(mu(t)) dt`` over the
         prior's support is the evidence; with ``nSamples`` draws from a proposal ``q`` the weights ``exp(mu - ln q)``
@@ -910,10 +910,25 @@ class ApproxPosterior(object):
 
         ``logZErr`` measures the scatter of the weights that were drawn.  A proposal with lighter tails than
         ``exp(mu)`` rarely draws the rows that carry the weight, and ``logZErr`` comes out misleadingly small: watch
-        ``ess`` (a small fraction of ``nSamples`` is the warning) and widen a mixture proposal with ``covScale``."""
+        ``ess`` (a small fraction of ``nSamples`` is the warning) and widen a mixture proposal with ``covScale``.
+
+        All of the above is the plug-in estimate: the GP's mean taken for the log-posterior.  ``surrogateDraws = S > 0``
+        adds the surrogate's own error bar: S functions are drawn from the GP posterior (:meth:`gp.GP.sample_paths` with
+        ``nFeatures`` random features, in groups of at most 32) and every draw is integrated over the SAME proposal rows
+        (:meth:`gp.GP.importance_paths`), so the result gains :func:`utility.importanceDrawsSummary`'s keys --
+        ``logZDraws``, ``essDraws``, ``meanDraws``, ``covDraws``, ``logZSurrogateErr``, ``meanSurrogateErr``,
+        ``logZExpected``, ``nEmptyDraws`` -- while the keys above keep the bits of the ``surrogateDraws=0`` call with
+        the same seed.  ``logZSurrogateErr`` is the scatter of ``logZ`` over the draws: large where the GP has few
+        training points under the posterior's mass, whatever ``logZErr`` says.  NumPy's global stream is used in this
+        order: the seed (if ``seed`` is None), then every group's ``sample_paths`` in turn, all before the first chunk;
+        under a process group the stream is synchronised first, so every rank draws the same functions.  The
+        hyper-parameters are held fixed, and the random-feature error is O(nFeatures^-1/2) in the draws' covariance."""
         nSamples, chunk = int(nSamples), int(chunk)
         if nSamples < 1 or chunk < 1:
             raise ValueError("evidence: nSamples and chunk must be positive")
+        surrogateDraws = int(surrogateDraws)
+        if surrogateDraws < 0:
+            raise ValueError("evidence: surrogateDraws must not be negative")
         joint = self._jointPrior()
         gate = self.bounds if joint is None else [tuple(r) for r in joint.support()]
         logVolume, mixture = 0.0, None
@@ -934,10 +949,14 @@ class ApproxPosterior(object):
             mixture = self._mixtureProposal(gmmUtils.fitGMM(samples, maxComp=maxComp))
         else:
             mixture = self._mixtureProposal(proposal)
-        if seed is None:
+        if seed is None or surrogateDraws > 0:
             if self._ranks() is not None:       # one NumPy stream on every rank, as runMCMC arranges: the same seed
-                apdist.sync_random_state(0, self.group, enabled=self.distributed)
+                apdist.sync_random_state(0, self.group, enabled=self.distributed)     # (and the same function draws)
+        if seed is None:
             seed = int(np.random.randint(0, 2 ** 31 - 1))
+        groups = [self.gp.sample_paths(self.y, min(_lib.MAX_DRAWS, surrogateDraws - g), nFeatures)
+                  for g in range(0, surrogateDraws, _lib.MAX_DRAWS)]
+        drawRecords = [None] * surrogateDraws
         centre = np.array(self.theta[int(np.argmax(self.y))], dtype=np.float64).ravel()
         record = None
         for off in range(0, nSamples, chunk):
@@ -952,7 +971,15 @@ class ApproxPosterior(object):
                 T, lnq = self.gp.box_candidates(mc, self.bounds, seed, idx_offset=off), None      # ln q: logVolume
             part = self.gp.importance_pass(self.y, T, lnq=lnq, bounds=gate, centre=centre)
             record = part if record is None else ut.mergeImportance(record, part)
-        return ut.importanceSummary(record, nSamples, logVolume=logVolume)
+            for g, paths in enumerate(groups):
+                parts = self.gp.importance_paths(self.y, T, paths, lnq=lnq, bounds=gate, centre=centre)
+                for j, p in enumerate(parts):
+                    s = g * _lib.MAX_DRAWS + j
+                    drawRecords[s] = p if drawRecords[s] is None else ut.mergeImportance(drawRecords[s], p)
+        out = ut.importanceSummary(record, nSamples, logVolume=logVolume)
+        if surrogateDraws > 0:
+            out.update(ut.importanceDrawsSummary(drawRecords, nSamples, logVolume=logVolume))
+        return out
 
     def runNested(self, nlive=512, batch=16, nsteps=None, nruns=None, dlogz=0.01, maxBatches=None, seed=None,
                   sigma=1.0e-5, gamma0=None):

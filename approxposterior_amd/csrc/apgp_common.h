@@ -12,6 +12,14 @@ typedef double f64x2 __attribute__((ext_vector_type(2)));
 
 void apgp_set_error(const char* fmt, ...);
 
+// evidence.hip, for pathdraw.hip's apgp_path_importance: the importance records of ndraws vectors of log-weights over
+// the same m rows (logw [draw][m]; pmax [draw][npmax]: maxima whose largest is the draw's maximum; stats_out [draw]
+// [apgp_importance_stats_len]) by the moments kernels of apgp_importance_pass with the draw as a grid dimension.
+// work: apgp_imp_draw_records_work_len(m, ndraws) doubles.  Returns 0 or -2 (launch failure, error set).
+int64_t apgp_imp_draw_records_work_len(int64_t m, int32_t ndraws);
+int apgp_imp_draw_records(const double* T, int64_t m, int ndim, const double* centre, int ndraws, const double* logw,
+                          const double* pmax, int64_t npmax, double* work, double* stats_out, hipStream_t s);
+
 #define APGP_CHECK_ARG(cond, msg)                                   \
     do {                                                            \
         if (!(cond)) {                                              \

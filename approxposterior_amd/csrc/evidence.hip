@@ -203,9 +203,9 @@ __global__ __launch_bounds__(IMP_THREADS) void imp_logw_kernel(ImpArgs a) {
 }
 
 // the largest of the nb per-workgroup maxima, in every thread of the workgroup (a maximum does not depend on the order)
-__device__ __forceinline__ double imp_global_max(const double* pmax, int nb, double* sred) {
+__device__ __forceinline__ double imp_global_max(const double* pmax, long long nb, double* sred) {
     double v = -INFINITY;
-    for (int b = threadIdx.x; b < nb; b += IMP_THREADS) v = fmax(v, pmax[b]);
+    for (long long b = threadIdx.x; b < nb; b += IMP_THREADS) v = fmax(v, pmax[b]);
     for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
     if ((threadIdx.x & 63) == 0) sred[threadIdx.x >> 6] = v;
     __syncthreads();
@@ -221,13 +221,15 @@ __device__ __forceinline__ double imp_global_max(const double* pmax, int nb, dou
 // sum_rows (w a) b for one weight and two slots; a thread owns outputs tid, tid + 256, .. and sums the tile's rows in
 // order, then its tiles in order.  Outputs: 0 = S0, 1 = S2, 2 = cnt, 3 .. 2 + D = s1, then S packed as apgp_gmm_pass
 // packs it (S[i][j], i <= j, at j (j + 1) / 2 + i).
+// blockIdx.y is the draw (apgp_path_importance: one vector of log-weights, one set of maxima and one set of partials per
+// draw over the same rows; apgp_importance_pass launches one): a draw's sums see nothing of the others.
 // ---------------------------------------------------------------------------------------------------------------------
 struct MomArgs {
     const double* T;
     const double* logw;
     const double* pmax;
-    double* partial;               // [nout][nb]
-    long long m;
+    double* partial;               // [draw][nout][nb]
+    long long m, npmax;            // npmax maxima per draw, whose largest is the draw's lmax
     int D, nb, nout;
     double c[APGP_MAX_DIM];
 };
@@ -245,7 +247,9 @@ __global__ __launch_bounds__(IMP_THREADS) void imp_moments_kernel(MomArgs a) {
     __shared__ double wt[3][MT];
     apgp_exp_tab_load(etab);
     const int tid = threadIdx.x, D = a.D;
-    const double lmax = imp_global_max(a.pmax, a.nb, sred);
+    const double* logw = a.logw + (long long)blockIdx.y * a.m;
+    double* partial = a.partial + (long long)blockIdx.y * a.nout * a.nb;
+    const double lmax = imp_global_max(a.pmax + (long long)blockIdx.y * a.npmax, a.npmax, sred);
     // this thread's outputs: weight and the two slots
     int ow[NO], oa[NO], ob[NO];
     double acc[NO];
@@ -270,7 +274,7 @@ __global__ __launch_bounds__(IMP_THREADS) void imp_moments_kernel(MomArgs a) {
         const int rows = (int)(a.m - r0 < MT ? a.m - r0 : MT);
         __syncthreads();                         // the previous tile's sums are done (and etab, lmax are in place)
         if (tid < rows) {
-            const double lw = a.logw[r0 + tid];
+            const double lw = logw[r0 + tid];
             const bool fin = lw > -INFINITY;
             double e = 0.0;
             if (fin) {
@@ -298,18 +302,23 @@ __global__ __launch_bounds__(IMP_THREADS) void imp_moments_kernel(MomArgs a) {
 #pragma unroll
     for (int q = 0; q < NO; ++q) {
         const int o = q * IMP_THREADS + tid;
-        if (o < a.nout) a.partial[(long long)o * a.nb + blockIdx.x] = acc[q];
+        if (o < a.nout) partial[(long long)o * a.nb + blockIdx.x] = acc[q];
     }
 }
 
-// record[0] = lmax (workgroup 0); record[1 + o] = sum_b partial[o][b] (workgroup 1 + o), a fixed tree over the nb partials
-__global__ __launch_bounds__(IMP_THREADS) void imp_final_kernel(const double* __restrict__ pmax,
+// record[0] = lmax (workgroup 0); record[1 + o] = sum_b partial[o][b] (workgroup 1 + o), a fixed tree over the nb partials;
+// blockIdx.y is the draw: its npmax maxima, its nout x nb partials, its record of 1 + nout doubles
+__global__ __launch_bounds__(IMP_THREADS) void imp_final_kernel(const double* __restrict__ pmax, long long npmax,
                                                                 const double* __restrict__ partial, int nb,
                                                                 double* __restrict__ record) {
     __shared__ double red[IMP_THREADS];
     const int tid = threadIdx.x;
+    const int nout = gridDim.x - 1;
+    pmax += (long long)blockIdx.y * npmax;
+    partial += (long long)blockIdx.y * nout * nb;
+    record += (long long)blockIdx.y * (1 + nout);
     if (blockIdx.x == 0) {
-        const double v = imp_global_max(pmax, nb, red);
+        const double v = imp_global_max(pmax, npmax, red);
         if (tid == 0) record[0] = v;
         return;
     }
@@ -324,6 +333,14 @@ __global__ __launch_bounds__(IMP_THREADS) void imp_final_kernel(const double* __
         __syncthreads();
     }
     if (tid == 0) record[1 + o] = red[0];
+}
+
+// dmax[draw] = the largest of the draw's npmax maxima (workgroup = draw)
+__global__ __launch_bounds__(IMP_THREADS) void imp_draw_max_kernel(const double* __restrict__ pmax, long long npmax,
+                                                                   double* __restrict__ dmax) {
+    __shared__ double sred[IMP_THREADS / 64];
+    const double v = imp_global_max(pmax + (long long)blockIdx.x * npmax, npmax, sred);
+    if (threadIdx.x == 0) dmax[blockIdx.x] = v;
 }
 
 inline int imp_nb(long long m) {
@@ -428,7 +445,7 @@ extern "C" int apgp_importance_pass(const double* T, int64_t m, const double* ln
     apgp_fill_kernel(a, kc);
     apgp_fill_box(a, D, lo, hi);
     MomArgs b;
-    b.T = T; b.logw = logw; b.pmax = pmax; b.partial = partial; b.m = m; b.D = D; b.nb = nb; b.nout = nout;
+    b.T = T; b.logw = logw; b.pmax = pmax; b.partial = partial; b.m = m; b.npmax = nb; b.D = D; b.nb = nb; b.nout = nout;
     for (int d = 0; d < APGP_MAX_DIM; ++d) b.c[d] = d < D ? centre[d] : 0.0;
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid((unsigned)nb), block(IMP_THREADS);
@@ -436,8 +453,36 @@ extern "C" int apgp_importance_pass(const double* T, int64_t m, const double* ln
     APGP_CHECK_LAUNCH();
     apgp_by_dpad(kc.dpad, [&](auto dp) { hipLaunchKernelGGL(imp_moments_kernel<decltype(dp)::value>, grid, block, 0, s, b); });
     APGP_CHECK_LAUNCH();
-    hipLaunchKernelGGL(imp_final_kernel, dim3((unsigned)(1 + nout)), block, 0, s, (const double*)pmax,
+    hipLaunchKernelGGL(imp_final_kernel, dim3((unsigned)(1 + nout)), block, 0, s, (const double*)pmax, (long long)nb,
                        (const double*)partial, nb, stats_out);
+    APGP_CHECK_LAUNCH();
+    return 0;
+}
+
+// The records of ndraws vectors of log-weights over the same rows (apgp_common.h; pathdraw.hip's apgp_path_importance):
+// each draw's npmax maxima reduced to one, then the two kernels above with the draw as the grid's second dimension.
+// Scratch: the draws' maxima, then their partial sums.
+int64_t apgp_imp_draw_records_work_len(int64_t m, int32_t ndraws) {
+    return (int64_t)ndraws * (1 + (int64_t)imp_nb(m) * (3 + APGP_MAX_DIM + ev_tri(APGP_MAX_DIM)));
+}
+
+int apgp_imp_draw_records(const double* T, int64_t m, int ndim, const double* centre, int ndraws, const double* logw,
+                          const double* pmax, int64_t npmax, double* work, double* stats_out, hipStream_t s) {
+    const int nb = imp_nb(m), D = ndim;
+    const int nout = 3 + D + ev_tri(D);
+    double* dmax = work;
+    MomArgs b;
+    b.T = T; b.logw = logw; b.pmax = dmax; b.partial = work + ndraws; b.m = m; b.npmax = 1; b.D = D; b.nb = nb; b.nout = nout;
+    for (int d = 0; d < APGP_MAX_DIM; ++d) b.c[d] = d < D ? centre[d] : 0.0;
+    const dim3 block(IMP_THREADS);
+    hipLaunchKernelGGL(imp_draw_max_kernel, dim3((unsigned)ndraws), block, 0, s, pmax, (long long)npmax, dmax);
+    APGP_CHECK_LAUNCH();
+    apgp_by_dpad(apgp_dpad(D), [&](auto dp) {
+        hipLaunchKernelGGL(imp_moments_kernel<decltype(dp)::value>, dim3((unsigned)nb, (unsigned)ndraws), block, 0, s, b);
+    });
+    APGP_CHECK_LAUNCH();
+    hipLaunchKernelGGL(imp_final_kernel, dim3((unsigned)(1 + nout), (unsigned)ndraws), block, 0, s, (const double*)dmax,
+                       1ll, (const double*)b.partial, nb, stats_out);
     APGP_CHECK_LAUNCH();
     return 0;
 }

@@ -13,7 +13,11 @@
 // the S arg-min partials of the workgroup; argmin_draws_kernel merges the partials, one workgroup per draw.
 // Above APGP_PD_MMA_MIN_DRAWS draws (and D padded to at most 8) the contraction runs on the matrix cores instead:
 // path_draws_mma_kernel below, same tiles, same epilogue.
+// apgp_path_importance runs the same two kernels with a second epilogue chosen at compile time (WEIGHTS): log w = f - ln q
+// under the importance gate and the workgroups' maxima instead of F and the arg-min partials; evidence.hip's moments
+// kernels then turn each draw's log-weights into a record.
 #include "apgp_common.h"
+#include <cmath>
 
 #define PD_THREADS 256
 #define PD_ROWS 64         // rows per LDS tile (divides the packed stream's 512-row padding)
@@ -30,6 +34,7 @@ struct PathArgs {
     const double* Wl;
     double* F;
     const unsigned char* mask;
+    const double* lnq;             // the weights epilogue only: ln q per row (NULL: zeros); F then receives log w
     double* part_u;
     long long* part_i;
     long long m, idx_offset, n, nblk;
@@ -83,16 +88,19 @@ __device__ __forceinline__ void pd_cos_turns4(const double (&ph)[4], double (&ou
 // The epilogue of one candidate (this thread's `row`; loads from the clamped `lrow`) for the NS draws s0 .. s0 + NS - 1
 // whose sums are in f: the linear features and the mean, the gate (box, mask, NaN coordinate: u = +inf, F = NaN), the F
 // store, and the wavefront's arg-min of u = -f per draw into su / si (SPAD x wavefronts).
-template <int NS>
+// WEIGHTS (apgp_path_importance): the same f + mean, then log w = (f + mean) - ln q into F where the row passes the
+// importance gate (every coordinate finite and inside the box, f and ln q finite) and -inf elsewhere, and the
+// wavefront's maximum of log w per draw into su.
+template <int NS, bool WEIGHTS>
 __device__ __forceinline__ void pd_epilogue(const PathArgs& a, double (&f)[NS], int s0, long long row, long long lrow,
                                             bool live, double* su, long long* si) {
     constexpr int NW = PD_THREADS / 64;
     const int tid = threadIdx.x;
-    bool adm = !(a.mask && a.mask[lrow] == 0);
+    bool adm = WEIGHTS || !(a.mask && a.mask[lrow] == 0);
     for (int d = 0; d < a.ndim; ++d) {
         const double x = a.T[lrow * a.ndim + d];
         if (a.has_box && !(x >= a.lo[d] && x <= a.hi[d])) adm = false;
-        if (x != x) adm = false;                 // a row with a NaN coordinate is inadmissible, as in the sweep
+        if (WEIGHTS ? !isfinite(x) : x != x) adm = false;        // a row with a NaN coordinate is inadmissible, as in the sweep
         if (a.lin_coef != 0.0) {
             double tp = 1.0;
             for (int e = 0; e < a.lin_order; ++e) tp *= x;
@@ -105,6 +113,20 @@ __device__ __forceinline__ void pd_epilogue(const PathArgs& a, double (&f)[NS], 
         }
     }
     const int wave = tid >> 6;
+    if constexpr (WEIGHTS) {
+        const double lq = a.lnq ? a.lnq[lrow] : 0.0;
+        if (!isfinite(lq)) adm = false;
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+            const double fs = f[s] + a.mean;
+            const double lw = adm && isfinite(fs) ? fs - lq : -INFINITY;
+            if (live && s0 + s < a.ndraws) a.F[(long long)(s0 + s) * a.m + row] = lw;
+            double wm = live ? lw : -INFINITY;
+            for (int o = 32; o > 0; o >>= 1) wm = fmax(wm, __shfl_xor(wm, o));
+            if ((tid & 63) == 0) su[(s0 + s) * NW + wave] = wm;
+        }
+        return;
+    }
 #pragma unroll
     for (int s = 0; s < NS; ++s) {
         const double fs = adm ? f[s] + a.mean : NAN;
@@ -122,10 +144,19 @@ __device__ __forceinline__ void pd_epilogue(const PathArgs& a, double (&f)[NS], 
 }
 
 // the workgroup's partial of every draw from its wavefronts' (call from every thread)
+template <bool WEIGHTS>
 __device__ __forceinline__ void pd_write_partials(const PathArgs& a, const double* su, const long long* si) {
     constexpr int NW = PD_THREADS / 64;
     const int tid = threadIdx.x;
     __syncthreads();
+    if constexpr (WEIGHTS) {                     // the maxima alone, [draw][workgroup]
+        if (tid < a.ndraws) {
+            double wm = su[tid * NW];
+            for (int w = 1; w < NW; ++w) wm = fmax(wm, su[tid * NW + w]);
+            a.part_u[(long long)tid * a.nblk + blockIdx.x] = wm;
+        }
+        return;
+    }
     if (tid < a.ndraws) {
         double bu = su[tid * NW];
         long long bi = si[tid * NW];
@@ -176,7 +207,9 @@ __device__ __forceinline__ void pd_stage_train(const PathArgs& a, long long r0, 
 
 // SPAD: the draws padded to 1 / 8 / 16 / 32 columns (zero weights past ndraws), so that the running sums are indexed
 // statically.  One draw alone would be one dependent FMA chain: it gets four partial sums, as the fantasy pass has.
-template <int DPAD, int SPAD>
+// WEIGHTS selects the epilogue: false -- F and the arg-min partials (apgp_path_draws); true -- the log-weights and the
+// per-workgroup maxima (apgp_path_importance).  The sums above it are the same code, hence the same bits.
+template <int DPAD, int SPAD, bool WEIGHTS = false>
 __global__ __launch_bounds__(PD_THREADS) void path_draws_kernel(PathArgs a) {
     constexpr int NACC = SPAD == 1 ? 4 : 1;
     constexpr int NW = PD_THREADS / 64;
@@ -273,8 +306,8 @@ __global__ __launch_bounds__(PD_THREADS) void path_draws_kernel(PathArgs a) {
     double f[SPAD];
 #pragma unroll
     for (int s = 0; s < SPAD; ++s) f[s] = NACC == 4 ? (acc[0][s] + acc[1 % NACC][s]) + (acc[2 % NACC][s] + acc[3 % NACC][s]) : acc[0][s];
-    pd_epilogue<SPAD>(a, f, 0, row, lrow, live, su, si);
-    pd_write_partials(a, su, si);
+    pd_epilogue<SPAD, WEIGHTS>(a, f, 0, row, lrow, live, su, si);
+    pd_write_partials<WEIGHTS>(a, su, si);
 }
 
 // The same sums with the contraction on the matrix cores (apgp_mma16's fragments: v_mfma_f64_4x4x4_4b, A lane = row +
@@ -285,7 +318,7 @@ __global__ __launch_bounds__(PD_THREADS) void path_draws_kernel(PathArgs a) {
 // of generated values per lane and step; 16 NCB matrix instructions per step in one cluster.  The sums come back to
 // one-thread-per-candidate through a 64 x 16 tile per wavefront in LDS, a column block at a time, and take the shared
 // epilogue.  For D padded to at most 8 (four candidates' coordinates per lane) and S padded to 16 NCB, NCB = 1, 2.
-template <int DPAD, int NCB>
+template <int DPAD, int NCB, bool WEIGHTS = false>
 __global__ __launch_bounds__(PD_THREADS) void path_draws_mma_kernel(PathArgs a) {
     constexpr int SPAD = 16 * NCB;
     constexpr int NW = PD_THREADS / 64;
@@ -413,9 +446,9 @@ __global__ __launch_bounds__(PD_THREADS) void path_draws_mma_kernel(PathArgs a) 
         double f[16];
 #pragma unroll
         for (int s = 0; s < 16; ++s) f[s] = fw[lane * FT + s];
-        pd_epilogue<16>(a, f, 16 * c, row, lrow, live, su, si);
+        pd_epilogue<16, WEIGHTS>(a, f, 16 * c, row, lrow, live, su, si);
     }
-    pd_write_partials(a, su, si);
+    pd_write_partials<WEIGHTS>(a, su, si);
 }
 
 // final arg-min over the per-workgroup partials: workgroup s merges the nblk partials of draw s
@@ -458,21 +491,35 @@ extern "C" int apgp_path_draws_mode(int mode) {
     return was;
 }
 
-template <int DPAD>
+template <int DPAD, bool WEIGHTS>
 static void path_draws_launch(int ndraws, dim3 grid, hipStream_t s, const PathArgs& a) {
     const dim3 block(PD_THREADS);
     if constexpr (DPAD <= 8) {
         const bool mma = g_pd_mode == 2 ? ndraws > 1 : g_pd_mode == 0 && ndraws > APGP_PD_MMA_MIN_DRAWS;
         if (mma) {
-            if (ndraws <= 16) hipLaunchKernelGGL((path_draws_mma_kernel<DPAD, 1>), grid, block, 0, s, a);
-            else hipLaunchKernelGGL((path_draws_mma_kernel<DPAD, 2>), grid, block, 0, s, a);
+            if (ndraws <= 16) hipLaunchKernelGGL((path_draws_mma_kernel<DPAD, 1, WEIGHTS>), grid, block, 0, s, a);
+            else hipLaunchKernelGGL((path_draws_mma_kernel<DPAD, 2, WEIGHTS>), grid, block, 0, s, a);
             return;
         }
     }
-    if (ndraws == 1) hipLaunchKernelGGL((path_draws_kernel<DPAD, 1>), grid, block, 0, s, a);
-    else if (ndraws <= 8) hipLaunchKernelGGL((path_draws_kernel<DPAD, 8>), grid, block, 0, s, a);
-    else if (ndraws <= 16) hipLaunchKernelGGL((path_draws_kernel<DPAD, 16>), grid, block, 0, s, a);
-    else hipLaunchKernelGGL((path_draws_kernel<DPAD, 32>), grid, block, 0, s, a);
+    if (ndraws == 1) hipLaunchKernelGGL((path_draws_kernel<DPAD, 1, WEIGHTS>), grid, block, 0, s, a);
+    else if (ndraws <= 8) hipLaunchKernelGGL((path_draws_kernel<DPAD, 8, WEIGHTS>), grid, block, 0, s, a);
+    else if (ndraws <= 16) hipLaunchKernelGGL((path_draws_kernel<DPAD, 16, WEIGHTS>), grid, block, 0, s, a);
+    else hipLaunchKernelGGL((path_draws_kernel<DPAD, 32, WEIGHTS>), grid, block, 0, s, a);
+}
+
+// what both entry points put into the argument struct once their arguments are checked (the outputs are theirs)
+static void pd_fill_args(PathArgs& a, const KernConst& kc, const double* T, int64_t m, const double* xs, int64_t n,
+                         double mean, const double* V, const double* Z, const double* b, const double* W,
+                         const double* Wl, int32_t nfeat, int32_t ndraws, const double* lo, const double* hi) {
+    a.T = T; a.xs = xs; a.V = V; a.Z = Z; a.b = b; a.W = W; a.Wl = Wl;
+    a.nblk = (m + PD_THREADS - 1) / PD_THREADS;
+    a.m = m; a.n = V ? n : 0; a.nfeat = nfeat; a.ndraws = ndraws; a.mean = mean;
+    a.feat_amp = sqrt(2.0 * kc.amp / (double)nfeat);
+    a.lin_amp = sqrt(kc.lin_coef);
+    a.zscale = sqrt(2.0) * APGP_PD_INV_2PI;      // sqrt2 / (2 pi): the frequencies in turns per scaled unit
+    apgp_fill_kernel(a, kc);
+    apgp_fill_box(a, kc.ndim, lo, hi);
 }
 
 extern "C" int apgp_path_draws(const double* T, int64_t m, int64_t idx_offset, const double* xs, int64_t n,
@@ -492,20 +539,56 @@ extern "C" int apgp_path_draws(const double* T, int64_t m, int64_t idx_offset, c
     APGP_CHECK_ARG(apgp_make_kernconst(kern, &kc) == 0, "kernel parameters");
     APGP_CHECK_ARG(Wl != NULL || kc.lin_coef == 0.0, "null pointer (Wl is required with a linear term)");
     PathArgs a;
-    a.T = T; a.xs = xs; a.V = V; a.Z = Z; a.b = b; a.W = W; a.Wl = Wl; a.F = F; a.mask = mask;
-    a.nblk = (m + PD_THREADS - 1) / PD_THREADS;
+    pd_fill_args(a, kc, T, m, xs, n, mean, V, Z, b, W, Wl, nfeat, ndraws, lo, hi);
+    a.F = F; a.mask = mask; a.lnq = NULL; a.idx_offset = idx_offset;
     a.part_u = (double*)part;
     a.part_i = (long long*)((double*)part + (long long)ndraws * a.nblk);
-    a.m = m; a.idx_offset = idx_offset; a.n = V ? n : 0; a.nfeat = nfeat; a.ndraws = ndraws; a.mean = mean;
-    a.feat_amp = sqrt(2.0 * kc.amp / (double)nfeat);
-    a.lin_amp = sqrt(kc.lin_coef);
-    a.zscale = sqrt(2.0) * APGP_PD_INV_2PI;      // sqrt2 / (2 pi): the frequencies in turns per scaled unit
-    apgp_fill_kernel(a, kc);
-    apgp_fill_box(a, kc.ndim, lo, hi);
     hipStream_t s = (hipStream_t)stream;
     const dim3 grid((unsigned)a.nblk);
-    apgp_by_dpad(kc.dpad, [&](auto dp) { path_draws_launch<decltype(dp)::value>(ndraws, grid, s, a); });
+    apgp_by_dpad(kc.dpad, [&](auto dp) { path_draws_launch<decltype(dp)::value, false>(ndraws, grid, s, a); });
     hipLaunchKernelGGL(argmin_draws_kernel, dim3((unsigned)ndraws), dim3(256), 0, s, a.part_u, a.part_i, a.nblk, best);
     APGP_CHECK_LAUNCH();
     return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// apgp_path_importance (DESIGN.md "Evidence over path draws"): the contraction above with the weights epilogue, then
+// evidence.hip's moments once per draw.  Scratch, per draw: the workgroups' maxima of stage one, what stage two needs
+// (apgp_imp_draw_records_work_len), and m doubles of log w (unused when the caller takes logw_out).
+// ---------------------------------------------------------------------------------------------------------------------
+extern "C" int64_t apgp_path_importance_work_len(int64_t m, int32_t ndraws) {
+    if (m < 1 || ndraws < 1) return 0;
+    if (m > APGP_MAX_M || ndraws > APGP_MAX_DRAWS) return -1;
+    return (int64_t)ndraws * ((m + PD_THREADS - 1) / PD_THREADS + m) + apgp_imp_draw_records_work_len(m, ndraws);
+}
+
+extern "C" int apgp_path_importance(const double* T, int64_t m, const double* lnq, const double* xs, int64_t n,
+                                    const apgp_kernel_t* kern, double mean, const double* V, const double* Z,
+                                    const double* b, const double* W, const double* Wl, int32_t nfeat, int32_t ndraws,
+                                    const double* lo, const double* hi, const double* centre, double* logw_out,
+                                    double* stats_out, double* work, void* stream) {
+    APGP_CHECK_ARG(T && kern && Z && b && W && centre && stats_out && work, "null pointer");
+    APGP_CHECK_ARG(V == NULL || xs != NULL, "null pointer (xs is required with V)");
+    APGP_CHECK_ARG(m >= 1 && m <= APGP_MAX_M, "1 <= m <= APGP_MAX_M required");
+    APGP_CHECK_ARG(n >= 1 && n <= APGP_MAX_N, "1 <= n <= APGP_MAX_N required");
+    APGP_CHECK_ARG((m + PD_THREADS - 1) / PD_THREADS < (1ll << 31), "m too large for one grid");
+    APGP_CHECK_ARG(ndraws >= 1 && ndraws <= APGP_MAX_DRAWS, "1 <= ndraws <= APGP_MAX_DRAWS required");
+    APGP_CHECK_ARG(nfeat >= 1 && nfeat <= APGP_MAX_FEATURES, "1 <= nfeat <= APGP_MAX_FEATURES required");
+    APGP_CHECK_ARG((lo == NULL) == (hi == NULL), "lo and hi must be given together");
+    KernConst kc;
+    APGP_CHECK_ARG(apgp_make_kernconst(kern, &kc) == 0, "kernel parameters");
+    APGP_CHECK_ARG(Wl != NULL || kc.lin_coef == 0.0, "null pointer (Wl is required with a linear term)");
+    for (int d = 0; d < kc.ndim; ++d) APGP_CHECK_ARG(std::isfinite(centre[d]),"the centre must be finite");
+    PathArgs a;
+    pd_fill_args(a, kc, T, m, xs, n, mean, V, Z, b, W, Wl, nfeat, ndraws, lo, hi);
+    double* pmax = work;                                                  // [draw][workgroup of stage one]
+    double* rwork = pmax + (long long)ndraws * a.nblk;
+    double* logw = logw_out ? logw_out : rwork + apgp_imp_draw_records_work_len(m, ndraws);
+    a.F = logw; a.mask = NULL; a.lnq = lnq; a.idx_offset = 0;
+    a.part_u = pmax; a.part_i = NULL;
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 grid((unsigned)a.nblk);
+    apgp_by_dpad(kc.dpad, [&](auto dp) { path_draws_launch<decltype(dp)::value, true>(ndraws, grid, s, a); });
+    APGP_CHECK_LAUNCH();
+    return apgp_imp_draw_records(T, m, kc.ndim, centre, ndraws, logw, pmax, a.nblk, rwork, stats_out, s);
 }

@@ -439,10 +439,14 @@ class PathDraws(object):
         self.mean = float(gp.mean.value)
         self._key, self._x = (gp._factor_key(), self.mean), gp._x
 
-    def _call(self, t, bounds, mask, idx_offset, with_f):
+    def _check_current(self):
         gp = self.gp
         if not gp.computed or gp._x is not self._x or (gp._factor_key(), float(gp.mean.value)) != self._key:
             raise RuntimeError("these draws belong to a factor the GP no longer holds: call sample_paths again")
+
+    def _call(self, t, bounds, mask, idx_offset, with_f):
+        gp = self.gp
+        self._check_current()
         lo, hi = _box(bounds, gp.kernel.ndim)
         T = gp._candidates(t)
         mask_d = mask if hasattr(mask, "data_ptr") else gp._mask(mask, T.shape[0])
@@ -506,6 +510,7 @@ class GP(GeorgeExtras):
         self._mean_work = None        # scratch of the small predictions and of the evaluations: survives refits
         self._p1_work = None
         self._imp_work = None         # scratch of importance_pass
+        self._pimp_work = None        # scratch of importance_paths
         self._pg_work = None
         self._nll_scratch = None
         self._nll_stream = None       # the stream the private buffers of the last _nll evaluation were made on
@@ -1986,28 +1991,14 @@ class GP(GeorgeExtras):
         ``utility.mergeImportance`` joins two.  ``return_logw`` adds the device tensor of ``logw``.  One device pass:
         the means, the weights and the moments never visit the host."""
         torch, dev, lib = self._rt()
-        if not self.computed:
-            raise RuntimeError("ERROR: Need to compute GP before using it!")
-        y = self._check_dimensions(y)
+        y, T, m, c, lo, hi = self._importance_args(y, T, centre, bounds, "importance_pass")
         D = self.kernel.ndim
-        T = self._candidates(T)
-        m = int(T.shape[0])
-        if m < 1:
-            raise ValueError("importance_pass needs at least one row")
-        c = np.array(self._x[int(np.argmax(y))] if centre is None else centre, dtype=np.float64).ravel()
-        if c.shape != (D,) or not np.all(np.isfinite(c)):
-            raise ValueError("centre must be D finite numbers")
-        lo, hi = _box(bounds, D)
         ks = self._kernel_struct()
         with self._on(torch, dev):
             st = self._stream(torch)
             self._ensure_xs(y)
             f64 = dict(dtype=torch.float64, device=dev)
-            if lnq is not None and not hasattr(lnq, "data_ptr"):
-                lnq = torch.from_numpy(np.ascontiguousarray(lnq, dtype=np.float64)).to(dev)
-            if lnq is not None and (tuple(lnq.shape) != (m,) or str(lnq.dtype) != "torch.float64" or not lnq.is_cuda
-                                    or not lnq.is_contiguous()):
-                raise ValueError("lnq must be a contiguous (M,) float64 tensor on the device")
+            lnq = self._importance_lnq(torch, dev, lnq, m)
             logw = torch.empty(m, **f64) if return_logw else None
             nstat = int(lib.apgp_importance_stats_len(D))
             stats = torch.empty(nstat, **f64)
@@ -2020,13 +2011,85 @@ class GP(GeorgeExtras):
                                                 ctypes.addressof(cc), _ptr(logw), stats.data_ptr(),
                                                 self._imp_work.data_ptr(), st), "apgp_importance_pass")
             r = stats.cpu().numpy()
+        rec = self._importance_record(r, c)
+        return (rec, logw) if return_logw else rec
+
+    def _importance_args(self, y, T, centre, bounds, who):
+        """The checked arguments the importance passes share: (y, T on the device, M, centre (D,), lo, hi)."""
+        if not self.computed:
+            raise RuntimeError("ERROR: Need to compute GP before using it!")
+        y = self._check_dimensions(y)
+        D = self.kernel.ndim
+        T = self._candidates(T)
+        m = int(T.shape[0])
+        if m < 1:
+            raise ValueError("%s needs at least one row" % who)
+        c = np.array(self._x[int(np.argmax(y))] if centre is None else centre, dtype=np.float64).ravel()
+        if c.shape != (D,) or not np.all(np.isfinite(c)):
+            raise ValueError("centre must be D finite numbers")
+        lo, hi = _box(bounds, D)
+        return y, T, m, c, lo, hi
+
+    @staticmethod
+    def _importance_lnq(torch, dev, lnq, m):
+        """``lnq`` as the importance passes take it: None, or a contiguous (M,) float64 tensor on the device."""
+        if lnq is not None and not hasattr(lnq, "data_ptr"):
+            lnq = torch.from_numpy(np.ascontiguousarray(lnq, dtype=np.float64)).to(dev)
+        if lnq is not None and (tuple(lnq.shape) != (m,) or str(lnq.dtype) != "torch.float64" or not lnq.is_cuda
+                                or not lnq.is_contiguous()):
+            raise ValueError("lnq must be a contiguous (M,) float64 tensor on the device")
+        return lnq
+
+    @staticmethod
+    def _importance_record(r, c):
+        """The record dict of one ``[lmax, S0, S2, cnt, s1 (D), S packed]`` row of the device's statistics."""
+        D = len(c)
         iu, ju = _triu_colmajor(D)
         S = np.zeros((D, D))
         S[iu, ju] = r[4 + D:]
         S[ju, iu] = r[4 + D:]
-        rec = {"lmax": float(r[0]), "S0": float(r[1]), "S2": float(r[2]), "cnt": float(r[3]), "s1": r[4:4 + D].copy(),
-               "S": S, "centre": c}
-        return (rec, logw) if return_logw else rec
+        return {"lmax": float(r[0]), "S0": float(r[1]), "S2": float(r[2]), "cnt": float(r[3]), "s1": r[4:4 + D].copy(),
+                "S": S, "centre": c}
+
+    def importance_paths(self, y, T, paths, lnq=None, bounds=None, centre=None, return_logw=False):
+        """One importance-sampling record PER POSTERIOR FUNCTION DRAW of ``paths`` (:meth:`sample_paths`) over the rows
+        of ``T``: :meth:`importance_pass` with the draw ``f_s`` in place of the mean, ``logw_s = f_s(t) - lnq`` where
+        every coordinate is finite and inside ``bounds`` and ``f_s`` and ``lnq`` are finite, else -inf.  Returns a list
+        of ``paths.size`` record dicts with :meth:`importance_pass`'s keys, taken about the same ``centre``; their
+        scatter over the draws is the surrogate's own uncertainty about the evidence and the posterior moments
+        (``utility.importanceDrawsSummary``).  ``return_logw`` adds the (S, M) device tensor of the log-weights.
+        One fused device pass (``apgp_path_importance``): the S x M matrix of draw values is never stored unless
+        ``return_logw`` asks for the weights, and nothing visits the host but the S records.  The arguments are
+        checked as :meth:`importance_pass` checks them; draws that belong to a factor the GP no longer holds are
+        refused as :meth:`PathDraws.evaluate` refuses them."""
+        torch, dev, lib = self._rt()
+        if not isinstance(paths, PathDraws) or paths.gp is not self:
+            raise ValueError("importance_paths needs the PathDraws of this GP's sample_paths")
+        paths._check_current()
+        y, T, m, c, lo, hi = self._importance_args(y, T, centre, bounds, "importance_paths")
+        S = paths.size
+        with self._on(torch, dev):
+            st = self._stream(torch)
+            self._ensure_xs(y)
+            f64 = dict(dtype=torch.float64, device=dev)
+            lnq = self._importance_lnq(torch, dev, lnq, m)
+            logw = torch.empty((S, m), **f64) if return_logw else None
+            nstat = int(lib.apgp_importance_stats_len(self.kernel.ndim))
+            stats = torch.empty((S, nstat), **f64)
+            need = int(lib.apgp_path_importance_work_len(m, S)) - (S * m if return_logw else 0)
+            if self._pimp_work is None or self._pimp_work.numel() < need:
+                self._pimp_work = torch.empty(need, **f64)
+            cc = (ctypes.c_double * _lib.MAX_DIM)(*c)
+            V = paths.V
+            _lib.check(lib.apgp_path_importance(T.data_ptr(), m, _ptr(lnq), _ptr(self._xs if V is not None else None),
+                                                len(self._x), ctypes.byref(paths.ks), float(paths.mean), _ptr(V),
+                                                paths.Z.data_ptr(), paths.b.data_ptr(), paths.W.data_ptr(),
+                                                paths.Wl.data_ptr(), paths.nFeatures, S, lo, hi, ctypes.addressof(cc),
+                                                _ptr(logw), stats.data_ptr(), self._pimp_work.data_ptr(), st),
+                       "apgp_path_importance")
+            r = stats.cpu().numpy()
+        recs = [self._importance_record(r[s], c) for s in range(S)]
+        return (recs, logw) if return_logw else recs
 
     # -- on-device ensemble MCMC over the GP mean ------------------------------------
     def sample_ensemble(self, y, initial_state, iterations, bounds, a=2.0, seed=0, store=True, prior=None,

@@ -23,7 +23,7 @@ from scipy.stats import norm
 
 __all__ = ["logsubexp", "AGPUtility", "BAPEUtility", "JonesUtility", "EIVUtility",
            "minimizeObjective", "sweepObjective", "utilityKind", "searchKind", "klNumerical",
-           "mergeImportance", "importanceSummary"]
+           "mergeImportance", "importanceSummary", "importanceDrawsSummary"]
 
 
 def klNumerical(x, p, q):
@@ -349,3 +349,40 @@ def importanceSummary(record, m, logVolume=0.0):
             "mean": c + d,
             "cov": np.asarray(record["S"], dtype=float) / S0 - np.outer(d, d),
             "nInside": int(record["cnt"])}
+
+
+def importanceDrawsSummary(records, m, logVolume=0.0):
+    """What the importance records of S posterior function draws (``GP.importance_paths``; one record per draw, all over
+    the same ``m`` proposal rows) say about the surrogate's own uncertainty, as a dict:
+
+    ``logZDraws``, ``essDraws``, ``meanDraws``, ``covDraws``  :func:`importanceSummary` of every draw: (S,), (S,), (S, D),
+                          (S, D, D)
+    ``logZSurrogateErr``  the standard deviation (ddof = 1) of ``logZDraws``: how far the evidence moves when the GP is
+                          redrawn from its posterior; NaN for fewer than two draws
+    ``meanSurrogateErr``  the same per dimension for ``meanDraws``, (D,)
+    ``logZExpected``      ``logsumexp(logZDraws) - log S``: the log of the mean of the draws' evidences, i.e. the
+                          evidence of the expected posterior ``exp(mu + sigma^2 / 2)``
+    ``nEmptyDraws``       draws with ``S0 = 0`` (no admissible row): left out of the three aggregates
+
+    The draws share the proposal rows, so the scatter is the surrogate's alone: the sampling error of the proposal is
+    ``logZErr`` of the plug-in record.  A draw's ``ess`` collapses where the predictive variance is large under a
+    narrow proposal; watch ``essDraws``."""
+    records = list(records)
+    if not records:
+        raise ValueError("importanceDrawsSummary needs at least one record")
+    per = [importanceSummary(r, m, logVolume=logVolume) for r in records]
+    logZ = np.array([p["logZ"] for p in per], dtype=float)
+    mean = np.array([p["mean"] for p in per], dtype=float)
+    keep = np.array([float(r["S0"]) > 0.0 for r in records])
+    lz, mk = logZ[keep], mean[keep]
+    nan_d = np.full(mean.shape[1:], np.nan)
+    if len(lz):
+        top = lz.max()
+        expected = float(top + np.log(np.sum(np.exp(lz - top))) - np.log(len(lz)))
+    else:
+        expected = -np.inf
+    return {"logZDraws": logZ, "essDraws": np.array([p["ess"] for p in per], dtype=float), "meanDraws": mean,
+            "covDraws": np.array([p["cov"] for p in per], dtype=float),
+            "logZSurrogateErr": float(np.std(lz, ddof=1)) if len(lz) > 1 else np.nan,
+            "meanSurrogateErr": np.std(mk, axis=0, ddof=1) if len(lz) > 1 else nan_d,
+            "logZExpected": expected, "nEmptyDraws": int(np.sum(~keep))}

@@ -946,6 +946,43 @@ int apgp_importance_pass(const double* T, int64_t m, const double* lnq, const do
                          const double* hi /*host*/, const double* centre /*host*/, double* logw_out,
                          double* stats_out, double* work, void* stream);
 
+/* ---- Evidence over posterior function draws (GP.importance_paths, ApproxPosterior.evidence(surrogateDraws=)) ----
+ * apgp_importance_pass integrates exp(mu): the surrogate's mean taken for the log-posterior.  apgp_path_importance takes
+ * S = ndraws posterior function draws f_s instead -- exactly apgp_path_draws' functions: the same arguments (xs, n, kern,
+ * mean, V, Z, b, W, Wl, nfeat, ndraws; V == NULL allowed), the same limits, the same switch apgp_path_draws_mode -- and
+ * leaves one importance record per draw, so that the scatter of the records over s is the surrogate's own error bar on
+ * the evidence and the moments.  For the m rows t of T (m x ndim, device) and lnq (m, device; NULL: zeros):
+ *   logw_s(row) = f_s(t_row) - lnq[row]   if every coordinate is finite and inside [lo, hi] (host, NULL: no box) and
+ *                                         f_s and lnq are finite, else -inf
+ * (a gated row still counts in m).  Where the row is admissible logw_s is F[s, row] - lnq[row] in one rounded subtraction,
+ * F being what apgp_path_draws stores for the same inputs in the same mode, bit for bit: the two share the contraction.
+ * stats_out (device, S x apgp_importance_stats_len(ndim)): record s has apgp_importance_pass's layout and definitions,
+ *   [lmax, S0, S2, cnt, s1 (D), S packed],
+ * about centre (host, ndim finite doubles) over draw s's log-weights: lmax their exact maximum, e = exp(logw - lmax) (0
+ * below -700 and for -inf); no admissible row gives (-inf, 0, 0, 0, zeros).  logw_out (S x m row-major, device, may be
+ * NULL) receives the log-weights.
+ * work (device): apgp_path_importance_work_len(m, ndraws) doubles =
+ *   ndraws (ceil(m / 256) + m + 1 + min(ceil(m / APGP_IMP_BLOCK), APGP_IMP_MAX_BLOCKS) (3 + 32 + 528))
+ * -- per draw the maxima of the first stage's workgroups, the log-weights (not used with logw_out), the draw's maximum
+ * and the partial sums of the moments; -1 beyond the limits, 0 for m < 1 or ndraws < 1.
+ * Two stages: the path-draw contraction with a weights epilogue (a candidate per thread, 256 per workgroup), then the
+ * moments kernels of apgp_importance_pass with the draw as a grid dimension.  No atomics; every sum runs in a fixed
+ * order that depends on (m, ndraws) only: the same input gives the same bits, and a draw's record does not depend on
+ * the other draws' weights.
+ * Refused (-1) before anything reaches the device: a null T, kern, Z, b, W, centre, stats_out or work; xs null with V
+ * not null; lo without hi; Wl null with a linear term; ndraws outside 1 .. APGP_MAX_DRAWS; nfeat outside 1 ..
+ * APGP_MAX_FEATURES; m or n below 1 or beyond 2^40 / 2^24; a non-finite centre.
+ * Added in ABI 8 without changing anything before it: APGP_ABI_VERSION stays 8.                                      */
+int64_t apgp_path_importance_work_len(int64_t m, int32_t ndraws);
+int apgp_path_importance(const double* T, int64_t m, const double* lnq,
+                         const double* xs, int64_t n, const apgp_kernel_t* kern /*host*/, double mean,
+                         const double* V, const double* Z, const double* b, const double* W, const double* Wl,
+                         int32_t nfeat, int32_t ndraws,
+                         const double* lo /*host*/, const double* hi /*host*/, const double* centre /*host*/,
+                         double* logw_out /* S x m row-major, may be NULL */,
+                         double* stats_out /* S x apgp_importance_stats_len(ndim) */,
+                         double* work, void* stream);
+
 /* ---- Chain diagnostics: a block of the walker-averaged autocorrelation function ------------
  * (mcmc.integrated_time(onDevice=True).)  x (device, fp64) is an ensemble chain laid out (steps, n_w, n_d) row-major as
  * GP.sample_ensemble stores it; step t of the series is row row0 + t * row_stride of it (a get_chain(discard=, thin=)
