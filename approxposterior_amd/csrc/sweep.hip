@@ -186,6 +186,17 @@ __host__ __device__ inline double* s2_fold_item(double* sp_q, int nrb, long long
 // feeders' k* and the tile's barrier do not halve with the rows), that is delta = 0.4 (docs/experiments.md, Round 22)
 #define S2_HALF_COST 7
 #define S2_WHOLE_COST 10
+// the parked route of the seed launch (seed_park_kernel): a tile re-read from the parked stream and a generating
+// (diagonal) one, per kind of item, in hundredths of a microsecond.  Measured where the launch is one item per CU and
+// so lasts its heaviest item (docs/experiments.md, Round 26): whole items, N = 2048 and 1152 at J0 = nrb, 112 + 16 and
+// 48 + 16 tiles in 291.4 and 142.9 us: 2.32 re-read, 1.97 generating (a diagonal tile is half empty); half items,
+// N = 2048 at J0 = 0 and N = 1152 at J0 = 2, the same tile counts in 184.4 and 110.1 us: 1.16 re-read, 3.40 generating
+// (the item's fixed part -- prologue, the upper half's idle last diagonal tiles -- falls to this term).  With them the
+// model gives 588 / 457 / 387 us for J0 = 16 / 8 / 0 at N = 4096 (measured 592-602 / 468 / 397).
+#define S2P_HALF_GEN 340
+#define S2P_HALF_PARK 116
+#define S2P_WHOLE_GEN 197
+#define S2P_WHOLE_PARK 232
 __host__ __device__ inline int s2_nkc_of(int jb, int n) {
     const int v = S2_CPB * (jb + 1), lim = (n + SW_KC - 1) / SW_KC;
     return v < lim ? v : lim;
@@ -245,6 +256,9 @@ template <int DPAD, bool LIN, int MODE, bool LIST = false, bool RHALF = false>
 __global__ __launch_bounds__(S2_THREADS, 1) void sweep2_kernel(SweepArgs a) {
     static_assert(!RHALF || (MODE == 0 && LIST), "row-half items: inverse form, list launches");
     constexpr bool SOLVE = MODE != 0;
+    // the seed launch of a pure squared-exponential kernel may read its blocks' parked stream (seed_park_kernel):
+    // a.ncache > 0 there means "read slot blk0, never store"; with a LinearKernel term the instantiation is what it was
+    constexpr bool SPARK = RHALF && !LIN;
     constexpr bool STATIC_DIAG = MODE == 2;
     constexpr int XS = DPAD + 2;
     constexpr int NKK = SW_KC / 4;
@@ -749,8 +763,10 @@ __global__ __launch_bounds__(S2_THREADS, 1) void sweep2_kernel(SweepArgs a) {
     const unsigned hoff = (unsigned)ht * 16u;
     const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc((void*)a.linv, 0, (int)a.linv_bytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t rs_x = __builtin_amdgcn_make_buffer_rsrc((void*)a.xs, 0, (int)a.xs_bytes, 0x00020000);
+    // (SPARK, the seed launch: the slot seed_park_kernel filled for this item's block, its position in the list; every
+    // item of the block reads it and none writes it)
     const __amdgpu_buffer_rsrc_t rs_k = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(a.kcache + (long long)blockIdx.x * a.ncache * SW_BCH), 0, (int)a.kslot_bytes, 0x00020000);
+        (void*)(a.kcache + (SPARK ? blk0 : (long long)blockIdx.x) * a.ncache * SW_BCH), 0, (int)a.kslot_bytes, 0x00020000);
     // an x chunk is XCHUNK16 16-byte pieces, one per feeder thread -- two for the first threads when Dpad = 32 (272 pieces,
     // 256 threads): XQ carries the second piece, dead code for the other instantiations
     constexpr bool X2 = XCHUNK16 > 256;
@@ -861,7 +877,7 @@ __global__ __launch_bounds__(S2_THREADS, 1) void sweep2_kernel(SweepArgs a) {
                     mu_tot += m;
                     mu_cur = 0.0;
                 }
-                if (!SOLVE && park && jb + 1 < nrb2) {
+                if (!SOLVE && !SPARK && park && jb + 1 < nrb2) {      // (SPARK: the slot is read-only, see rs_k)
                     const unsigned soff = (unsigned)kc * (unsigned)(SW_BCH * 8);
                     f64x2 q0, q1;
                     q0.x = bfv[0]; q0.y = bfv[1]; q1.x = bfv[2]; q1.y = bfv[3];
@@ -974,7 +990,13 @@ __global__ __launch_bounds__(S2_THREADS, 1) void sweep2_kernel(SweepArgs a) {
         };
         auto nd0_of = [&](int jb) { const int v = S2_CPB * jb, n = nkc_of(jb); return park ? (v < n ? v : n) : 0; };
         auto next_gen = [&](int& jb, int& kc) {
-            if (kc + 1 < nkc_of(jb)) { ++kc; return; }
+            if (kc + 1 < nkc_of(jb)) {
+                ++kc;
+                // (SPARK with the parked stream: the prologue generates chunk 0 of any row block, and the next
+                // generating tile is the row block's first diagonal one)
+                if constexpr (SPARK) { if (kc < nd0_of(jb)) kc = nd0_of(jb); }
+                return;
+            }
             jb = jb + 1 < jb_hi ? jb + 1 : jb_lo;
             kc = nd0_of(jb);
         };
@@ -1001,6 +1023,9 @@ __global__ __launch_bounds__(S2_THREADS, 1) void sweep2_kernel(SweepArgs a) {
                 const int nkc = nkc_of(jb), nd0 = nd0_of(jb);
                 // ---- run of parked tiles: image + parked operands by LDS-DMA, nothing else ----
                 for (int kc = 0; kc < nd0; ++kc) {
+                    if constexpr (SPARK) {            // (an item of a row block > 0: T_0, the prologue's, is of this run)
+                        if (first_tile) { first_tile = false; continue; }
+                    }
                     dma_tile(slot, jb, kc);
                     dma_parked(par, kc);
                     slot = slot == 2 ? 0 : slot + 1;
@@ -1020,7 +1045,7 @@ __global__ __launch_bounds__(S2_THREADS, 1) void sweep2_kernel(SweepArgs a) {
                         next_gen(gj, xk);
                         next_gen(gj, xk);
                     }
-                    const bool stores = !SOLVE && park && kc >= S2_CPB * jb && jb + 1 < nrb2;
+                    const bool stores = !SOLVE && !SPARK && park && kc >= S2_CPB * jb && jb + 1 < nrb2;
                     produce_b(jb, kc, par, gpar);
                     x_dma(gpar == 0 ? 2 : gpar - 1, xk);
                     slot = slot == 2 ? 0 : slot + 1;
@@ -1115,7 +1140,7 @@ __global__ __launch_bounds__(S2_THREADS, 1) void sweep2_kernel(SweepArgs a) {
             // register load hipcc tracks itself).  They are the LAST requests issued, and gfx9 VMEM
             // completes in issue order, so "at most n outstanding" still means the images and parked
             // operands of tile i+1 have landed -- without the ~1-2 k cycles of store acknowledgement.
-            int n_pend = (!SOLVE && is_gen(p1) && park && p1.kc >= S2_CPB * p1.jb && p1.jb + 1 < nrb2) ? 2 : 0;
+            int n_pend = (!SOLVE && !SPARK && is_gen(p1) && park && p1.kc >= S2_CPB * p1.jb && p1.jb + 1 < nrb2) ? 2 : 0;
             if (is_gen(p3)) { xq = x_fetch(p3.kc); n_pend += X2 ? 2 : 1; }
             last_m2 = last_m1;
             last_m1 = (p1.jb == jb_hi - 1 && p1.kc == nkc_of(p1.jb) - 1);
@@ -1221,6 +1246,70 @@ __global__ __launch_bounds__(256) void sweep_fold_kernel(SweepArgs a) {
     if ((lane >> 4) == 0) a.sp_q[((long long)pos * SW_CAND + w * 16 + (lane & 15)) * a.nrb + jb] = qtot;
 }
 
+// The parked stream of the seed blocks (before the seed launch): one workgroup per (list position, SP_NCH chunks
+// kc < ncache), its 256 threads the feeder threads of the block.  It writes the 1024 operands a feeder of the persistent
+// sweep would have parked for each chunk kc, into slot `position` of the k* scratch, so that the seed launch's 2 nrb
+// items per block read the chunks left of their diagonal instead of generating them once each.  The bits are those of
+// produce_b, said explicitly with contraction off (tests/kvalue_ref.py, site "sweep"): chunk 0 is the tile an item
+// generates in its prologue, where hipcc contracts the scaling into the subtraction, df = fma(t, sc, -xs); every other
+// chunk takes the rounded tt = t sc.  Rows past m enter as t = 0, as in load_candidates.  Pure squared-exponential
+// kernels only.  Sized for the cap; a workgroup whose position is at or past the device count leaves at once.
+#define SP_NCH 4                         // chunks per workgroup
+template <int DPAD>
+__global__ __launch_bounds__(256) void seed_park_kernel(SweepArgs a) {
+#pragma clang fp contract(off)
+    constexpr int XS = DPAD + 2;
+    constexpr int NKK = SW_KC / 4;
+    __shared__ double Etab[APGP_EXP_TAB_N];
+    const int ngrp = a.ncache / SP_NCH;           // (ncache is a multiple of S2_CPB)
+    const int pos = (int)blockIdx.x / ngrp, kc0 = (int)blockIdx.x % ngrp * SP_NCH;
+    const long long cnt = *a.blk_count;
+    if (cnt <= a.list_lo || cnt > a.list_hi || pos >= cnt) return;
+    apgp_exp_tab_load(Etab);
+    __syncthreads();
+    const int ht = threadIdx.x, lane = ht & 63, hw = ht >> 6;
+    const int cl = lane & 15, kq = lane >> 4;
+    const long long blk = a.blk_list[pos];
+    const long long crow = blk * SW_CAND + hw * 16 + cl;
+    const bool inb = blk < a.blk_end && crow < a.m;
+    double tv[DPAD], tt[DPAD];
+#pragma unroll
+    for (int d = 0; d < DPAD; ++d) {
+        double v = 0.0;
+        if (inb && d < a.ndim) v = a.T[crow * a.ndim + d];
+        tv[d] = v;
+        tt[d] = v * a.sc[d];
+    }
+    for (int kc = kc0; kc < kc0 + SP_NCH; ++kc) {
+        const double* Xb = a.xs + (long long)kc * (SW_KC * XS);
+        double s2[NKK], s3[NKK];
+#pragma unroll
+        for (int kk = 0; kk < NKK; ++kk) { s2[kk] = 0.0; s3[kk] = 0.0; }
+#pragma unroll
+        for (int d = 0; d < DPAD; d += 2)
+#pragma unroll
+            for (int kk = 0; kk < NKK; ++kk) {
+                const f64x2 xa = *(const f64x2*)(Xb + (kk * 4 + kq) * XS + d);
+                double df0, df1;
+                if (kc == 0) { df0 = fma(tv[d], a.sc[d], -xa.x); df1 = fma(tv[d + 1], a.sc[d + 1], -xa.y); }
+                else { df0 = tt[d] - xa.x; df1 = tt[d + 1] - xa.y; }
+                s2[kk] = fma(df0, df0, s2[kk]);
+                s3[kk] = fma(df1, df1, s3[kk]);
+            }
+        double ex[NKK], bfv[NKK];
+#pragma unroll
+        for (int kk = 0; kk < NKK; ++kk) ex[kk] = -(s2[kk] + s3[kk]);
+        apgp_exp4(ex, bfv, Etab);
+#pragma unroll
+        for (int kk = 0; kk < NKK; ++kk) bfv[kk] = bfv[kk] * a.amp;
+        // the layout produce_b stores: thread ht's q0 at byte 16 ht, q1 at 16 ht + 4096, chunk stride SW_BCH * 8
+        f64x2* dst = (f64x2*)(a.kcache + ((long long)pos * a.ncache + kc) * SW_BCH) + ht;
+        f64x2 q0, q1;
+        q0.x = bfv[0]; q0.y = bfv[1]; q1.x = bfv[2]; q1.y = bfv[3];
+        dst[0] = q0; dst[256] = q1;
+    }
+}
+
 // blocks of the last round that are split by row block (measured break-even at N = 4096:
 // ~190 of 256 -- the split launch regenerates every k* and its largest item is 1/nrb of a block): S2_SPLIT_MAX, above
 
@@ -1317,10 +1406,20 @@ extern "C" int apgp_set_seed_rowsplit(int v) {
 
 extern "C" int apgp_get_seed_rowsplit(void) { return __atomic_load_n(&g_seed_rowsplit, __ATOMIC_RELAXED); }
 
+// ---- whether the seed launch reads its blocks' k* from the parked stream (seed_park_kernel) ----
+// 1 (default): yes, for pure squared-exponential kernels; 0: every item generates every tile, the launch as it was
+static int g_seed_park = 1;
+
+extern "C" int apgp_set_seed_park(int v) { return __atomic_exchange_n(&g_seed_park, v != 0 ? 1 : 0, __ATOMIC_RELAXED); }
+
+extern "C" int apgp_get_seed_park(void) { return __atomic_load_n(&g_seed_park, __ATOMIC_RELAXED); }
+
 // Time of a launch of cap x (row items for J0) workgroups on SW_GRID CUs, one at a time per CU, in the order the
 // kernel numbers them (s2_row_item: heaviest first), each to the CU that falls free first; in units of the cost model
 // (S2_WHOLE_COST per tile of a whole item, S2_HALF_COST per tile of a half item or of a last block of <= 128 rows).
-static long long seed_launch_cost(int nrb, int cap, int n, int j0) {
+// `parked`: the launch reads the chunks left of an item's diagonal from the parked stream; a re-read tile and a
+// generating (diagonal) tile then have prices of their own (S2P_*), in units that only compare with each other.
+static long long seed_launch_cost(int nrb, int cap, int n, int j0, bool parked) {
     long long load[SW_GRID] = {0};
     const int nitem = nrb + s2_nhalved(nrb, j0, n);
     long long last = 0;
@@ -1328,7 +1427,10 @@ static long long seed_launch_cost(int nrb, int cap, int n, int j0) {
         int jb = 0, h = -1;
         s2_row_item(i, nrb, j0, n, jb, h);
         const bool light = h >= 0 || n - S2_ROWS * jb <= S2_ROWS / 2;
-        const long long c = (long long)(light ? S2_HALF_COST : S2_WHOLE_COST) * s2_nkc_of(jb, n);
+        const int nkc = s2_nkc_of(jb, n), nre = S2_CPB * jb < nkc ? S2_CPB * jb : nkc;
+        const long long c = parked ? (long long)(light ? S2P_HALF_GEN : S2P_WHOLE_GEN) * (nkc - nre) +
+                                         (long long)(light ? S2P_HALF_PARK : S2P_WHOLE_PARK) * nre
+                                   : (long long)(light ? S2_HALF_COST : S2_WHOLE_COST) * nkc;
         for (int k = 0; k < cap; ++k) {
             int best = 0;
             for (int q = 1; q < SW_GRID; ++q)
@@ -1342,20 +1444,20 @@ static long long seed_launch_cost(int nrb, int cap, int n, int j0) {
 
 // The rule: J0 of {0, nrb / 2, nrb} with the shortest modelled launch (ties: the fewest items).  Remembered for the last
 // (nrb, cap, n): a fit's calls repeat them.
-static int seed_j0(int nrb, int cap, int n) {
+static int seed_j0(int nrb, int cap, int n, bool parked) {
     const int v = apgp_get_seed_rowsplit();
     if (v >= 0) return v < nrb ? v : nrb;
     static std::mutex mu;
-    static int k_nrb = -1, k_cap = -1, k_n = -1, k_j0 = 0;
+    static int k_nrb = -1, k_cap = -1, k_n = -1, k_parked = -1, k_j0 = 0;
     std::lock_guard<std::mutex> g(mu);
-    if (k_nrb != nrb || k_cap != cap || k_n != n) {
+    if (k_nrb != nrb || k_cap != cap || k_n != n || k_parked != (int)parked) {
         int best = nrb;
-        long long best_c = seed_launch_cost(nrb, cap, n, nrb);
+        long long best_c = seed_launch_cost(nrb, cap, n, nrb, parked);
         for (int j0 : {nrb / 2, 0}) {
-            const long long c = seed_launch_cost(nrb, cap, n, j0);
+            const long long c = seed_launch_cost(nrb, cap, n, j0, parked);
             if (c < best_c) { best = j0; best_c = c; }
         }
-        k_nrb = nrb; k_cap = cap; k_n = n; k_j0 = best;
+        k_nrb = nrb; k_cap = cap; k_n = n; k_parked = (int)parked; k_j0 = best;
     }
     return k_j0;
 }
@@ -1375,9 +1477,19 @@ static void launch_sweep_list(const SweepArgs& a0, hipStream_t s, bool solve, co
         SweepArgs b = a;
         b.split = 1; b.ncache = 0; b.kslot_bytes = SW_BCH * 8;
         b.list_lo = 0; b.list_hi = cap;
-        const int j0 = rowsplit ? seed_j0(nrb2, (int)cap, b.n) : nrb2;
+        // the seed launch of a pure squared-exponential kernel reads the chunks left of an item's diagonal from the
+        // parked stream: seed_park_kernel fills slot `position` of the k* scratch, idle until the survivors' persistent
+        // launch later on this stream (slots >= the seed count), and the launch goes through the RHALF instantiation
+        // whether a row block is halved or not (it runs whole items with rh = -1)
+        const bool parked = rowsplit && b.lin_coef == 0.0 && apgp_get_seed_park() != 0;
+        const int j0 = rowsplit ? seed_j0(nrb2, (int)cap, b.n, parked) : nrb2;
         const int nhalf = s2_nhalved(nrb2, j0, b.n);
-        if (nhalf > 0) {
+        if (parked) {
+            b.ncache = (int)s2_ncache(b.n);
+            b.kslot_bytes = (unsigned)(b.ncache * (SW_BCH * 8));
+            hipLaunchKernelGGL(seed_park_kernel<DPAD>, dim3((unsigned)(cap * (b.ncache / SP_NCH))), dim3(256), 0, s, b);
+        }
+        if (nhalf > 0 || parked) {
             const size_t lds = s2_lds_bytes<DPAD>();
             const unsigned grid = (unsigned)(cap * (nrb2 + nhalf));
             b.split = 2 + j0;
@@ -1385,7 +1497,7 @@ static void launch_sweep_list(const SweepArgs& a0, hipStream_t s, bool solve, co
                 hipLaunchKernelGGL((sweep2_kernel<DPAD, true, 0, true, true>), dim3(grid), dim3(S2_THREADS), lds, s, b);
             else
                 hipLaunchKernelGGL((sweep2_kernel<DPAD, false, 0, true, true>), dim3(grid), dim3(S2_THREADS), lds, s, b);
-            hipLaunchKernelGGL(sweep_fold_kernel, dim3((unsigned)(cap * nrb2)), dim3(256), 0, s, b);
+            if (nhalf > 0) hipLaunchKernelGGL(sweep_fold_kernel, dim3((unsigned)(cap * nrb2)), dim3(256), 0, s, b);
         } else {
             s2_launch<DPAD, true>(b, s, solve, (unsigned)(cap * nrb2));
         }

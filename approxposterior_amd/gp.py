@@ -498,6 +498,10 @@ class GP(GeorgeExtras):
         # (apgp_set_seed_rowsplit; same bits whatever the value): None: the library's process-wide setting (default:
         # its rule); -1: the rule; 0: every row block; >= ceil(n / 256): none
         self.seed_rowsplit = None
+        # the same launch reads its blocks' k* from a stream generated once per call instead of generating it in every
+        # workgroup (apgp_set_seed_park; same bits either way): None: the library's process-wide setting (default: on);
+        # True / 1: on; False / 0: off
+        self.seed_park = None
         self.sweep_prune_stats = False   # True: keep (seed blocks, surviving blocks, bits of tau, blocks the coarse
         self.last_prune_counts = None     # bound left) of the last pruned sweep here, as a device int64[4] tensor
         self._computed = False
@@ -1427,6 +1431,7 @@ class GP(GeorgeExtras):
                     _ptr(self._prune_rows), st)
             prune_was = None if self.sweep_prune is None else lib.apgp_set_sweep_prune(int(self.sweep_prune))
             rowsplit_was = None if self.seed_rowsplit is None else lib.apgp_set_seed_rowsplit(int(self.seed_rowsplit))
+            park_was = None if self.seed_park is None else lib.apgp_set_seed_park(int(self.seed_park))
             try:
                 if use_solve:
                     _lib.check(lib.apgp_acquire_solve_rows(T.data_ptr(), m, int(idx_offset),
@@ -1439,6 +1444,8 @@ class GP(GeorgeExtras):
                     lib.apgp_set_sweep_prune(prune_was)
                 if rowsplit_was is not None:
                     lib.apgp_set_seed_rowsplit(rowsplit_was)
+                if park_was is not None:
+                    lib.apgp_set_seed_park(park_was)
             if self.sweep_prune_stats and kind_id != _lib.UTIL_NONE and mu is None and var is None and u is None:
                 off = int(lib.apgp_sweep_prune_counts_offset(m, n))
                 self.last_prune_counts = part[off:off + 4].view(torch.int64).clone()

@@ -373,11 +373,19 @@ int apgp_acquire_solve(const double* T, int64_t m, int64_t idx_offset,
  * lower half goes as TWO workgroups of 128 rows each, and a fold step puts their sums together in the whole row
  * block's order -- the bits do not depend on J0.  -1 (default): J0 by the library's rule (a model of the launch on
  * the chip's 256 CUs); v >= 0: J0 = v (0: every such row block, v >= ceil(n / 256): none).  Inverse form only;
- * apgp_acquire_solve ignores it.  Added in ABI 8 without changing anything before it: APGP_ABI_VERSION stays 8.  */
+ * apgp_acquire_solve ignores it.  Added in ABI 8 without changing anything before it: APGP_ABI_VERSION stays 8.
+ * apgp_set_seed_park(v): process-wide switch of the same launch, returns the previous value.  1 (default): the
+ * k*(t, x) operands of the seed blocks are generated once, by a launch of their own, into the parked-operand
+ * region of `part`, and the seed launch's workgroups read the chunks left of their diagonal from there; 0: every
+ * workgroup generates every operand it needs, the launch as it was.  The bits do not depend on it.  Pure
+ * squared-exponential kernels, inverse form, n > 256; everything else ignores it.  apgp_acquire_work_len is
+ * unchanged; APGP_ABI_VERSION stays 8.  */
 int apgp_set_sweep_prune(int v);
 int apgp_get_sweep_prune(void);
 int apgp_set_seed_rowsplit(int v);
 int apgp_get_seed_rowsplit(void);
+int apgp_set_seed_park(int v);
+int apgp_get_seed_park(void);
 int64_t apgp_sweep_prune_counts_offset(int64_t m, int64_t n);
 int apgp_sweep_prune_select(const double* bmin, int64_t ncb, const int64_t* seeds, int64_t* counts,
                             double tau, int64_t* list, void* stream);
