@@ -16,11 +16,12 @@ from . import gp, gpUtils, utility, likelihood, mcmc, mcmcUtils, approx, dist, g
 from .approx import ApproxPosterior  # noqa: F401
 from .gpUtils import defaultHyperPrior, defaultGP, optimizeGP  # noqa: F401
 from .gmmUtils import fitGMM  # noqa: F401
+from .gp import sobolSample  # noqa: F401
 evidence = ApproxPosterior.evidence  # noqa: E305  (evidence(ap, nSamples=..., proposal=...): the method as a function)
 runNested = ApproxPosterior.runNested  # noqa: E305  (runNested(ap, nlive=..., nruns=...): the method as a function)
 from .mcmcUtils import validateMCMCKwargs, batchMeansMCSE, estimateBurnin  # noqa: F401
 from .utility import (logsubexp, AGPUtility, BAPEUtility, JonesUtility,  # noqa: F401
                       minimizeObjective, sweepObjective, klNumerical, mergeImportance, importanceSummary,
-                      importanceDrawsSummary)
+                      importanceDrawsSummary, importanceReplicatesSummary)
 from .likelihood import *  # noqa: F401,F403
 from .priors import *  # noqa: F401,F403

@@ -194,6 +194,11 @@ SIGNATURES = {
     "apgp_gmm_pass": (ctypes.c_int, [_P, _I64, _I32, _I32, _P, _I32, _P, _P, _P, _P]),
     "apgp_mix_params_len": (_I64, [_I32, _I32]),
     "apgp_mix_candidates": (ctypes.c_int, [_P, _P, _I64, _I32, _I32, _P, ctypes.c_uint64, _I64, _P]),
+    "apgp_sobol_direction": (_I32, [_I32, _I32]),
+    "apgp_sobol_box_candidates": (ctypes.c_int, [_P, _I64, _I32, ctypes.POINTER(_F64), ctypes.POINTER(_F64), ctypes.c_uint64,
+                                                 _I32, _I32, _I64, _P]),
+    "apgp_sobol_prior_candidates": (ctypes.c_int, [_P, _I64, _I32, _P, _P, _P, ctypes.c_uint64, _I32, _I32, _I64, _P]),
+    "apgp_sobol_mix_candidates": (ctypes.c_int, [_P, _P, _I64, _I32, _I32, _P, ctypes.c_uint64, _I32, _I32, _I64, _P]),
     "apgp_importance_stats_len": (_I64, [_I32]),
     "apgp_importance_work_len": (_I64, [_I64]),
     "apgp_importance_pass": (ctypes.c_int, [_P, _I64, _P, _P, _I64, _KP, _F64, ctypes.POINTER(_F64), ctypes.POINTER(_F64),

@@ -292,22 +292,7 @@ class ApproxPosterior(object):
         total = int(nCandidates)
         kind = ut.utilityKind(utility) if (ranks is not None or self.deviceCandidates) else None
         lo, hi = apdist.shard_bounds(total, ranks[1], ranks[0]) if ranks is not None else (0, total)
-        if self.deviceCandidates and joint is not None:
-            # drawn from the prior itself on the device (same stream as box_candidates); the winning row alone is
-            # regenerated below
-            seed = int(np.random.randint(0, 2 ** 31 - 1))
-            mine = self.gp.prior_candidates(hi - lo, joint, seed, idx_offset=lo)
-            row = lambda g: self.gp.prior_candidates(1, joint, seed, idx_offset=g).cpu().numpy()[0]       # noqa: E731
-        elif self.deviceCandidates:
-            # the global matrix is a function of (seed, row) alone: this rank generates its rows in HBM, no host draw,
-            # no H2D copy; the box ``bounds`` IS the prior here (priorSample is not consulted)
-            seed = int(np.random.randint(0, 2 ** 31 - 1))
-            mine = self.gp.box_candidates(hi - lo, self.bounds, seed, idx_offset=lo)
-            row = lambda g: self.gp.box_candidates(1, self.bounds, seed, idx_offset=g).cpu().numpy()[0]   # noqa: E731
-        else:
-            draws = np.asarray(self.priorSample(total), dtype=float).reshape(total, -1)
-            mine = draws if ranks is None else np.ascontiguousarray(draws[lo:hi])
-            row = lambda g: np.array(draws[g])                                                              # noqa: E731
+        mine, row = self._candidateDraw(total, joint, lo, hi)
         if ranks is None and not self.deviceCandidates:
             point, value = ut.sweepObjective(utility, self.y, self.gp, mine, bounds=gate)
         else:
@@ -329,6 +314,41 @@ class ApproxPosterior(object):
                 point, value = self._agree(point, value)
         return point, value
 
+    def _candidateDraw(self, total, joint, lo=0, hi=None):
+        """``(cands, row)``: rows ``lo .. hi - 1`` (default: all) of ONE global candidate draw of ``total`` rows, and
+        ``row(g)``, global row ``g`` alone as a host array -- the draw every ``nCandidates`` selection starts from.
+        Without ``deviceCandidates`` the rows are ``priorSample`` draws on the host.  With it they are generated on the
+        device from one integer of NumPy's global stream, from the prior itself when ``lnprior`` is a JointPrior
+        (``joint``), else uniformly in the box ``bounds`` (which then IS the prior: priorSample is not consulted): no host
+        draw, no H2D copy, and the global matrix is a function of (seed, row) alone, so a rank generates its own rows and
+        the winning row is regenerated alone.  ``True``: the Philox streams (``GP.prior_candidates``,
+        ``GP.box_candidates``); ``"sobol"``: one scrambled Sobol replicate (``GP.sobol_candidates``)."""
+        hi = total if hi is None else hi
+        mode = self.deviceCandidates
+        if not mode:
+            draws = np.asarray(self.priorSample(total), dtype=float).reshape(total, -1)
+            return (draws if (lo, hi) == (0, total) else np.ascontiguousarray(draws[lo:hi])), lambda g: np.array(draws[g])
+        if mode == "sobol" and total > george.SOBOL_MAX_ROWS:
+            raise ValueError('deviceCandidates="sobol": the sequence has 2^30 rows, nCandidates = %d is beyond it' % total)
+        seed = int(np.random.randint(0, 2 ** 31 - 1))
+        if mode == "sobol":
+            source = {"bounds": self.bounds} if joint is None else {"prior": joint}
+            gen = lambda m, off: self.gp.sobol_candidates(m, seed=seed, idx_offset=off, **source)         # noqa: E731
+        elif joint is not None:
+            gen = lambda m, off: self.gp.prior_candidates(m, joint, seed, idx_offset=off)                 # noqa: E731
+        else:
+            gen = lambda m, off: self.gp.box_candidates(m, self.bounds, seed, idx_offset=off)             # noqa: E731
+        return gen(hi - lo, lo), lambda g: gen(1, g).cpu().numpy()[0]
+
+    @staticmethod
+    def _candidatesMode(deviceCandidates):
+        """``deviceCandidates`` as kept on the object: False, True (the Philox streams) or "sobol"."""
+        if isinstance(deviceCandidates, str):
+            if deviceCandidates != "sobol":
+                raise ValueError('deviceCandidates must be False, True or "sobol"')
+            return "sobol"
+        return bool(deviceCandidates)
+
     def _selectBatch(self, utilities, nCandidates, batchMethod="believer"):
         """``len(utilities)`` design points chosen jointly (:meth:`GP.acquire_batch`, the kriging believer) from
         ONE candidate draw -- the draw :meth:`_selectPoint` makes for one point; pick j minimises
@@ -340,18 +360,9 @@ class ApproxPosterior(object):
         kinds = [ut.utilityKind(fn) for fn in utilities]
         joint = self._jointPrior()
         gate = self.bounds if joint is None else [tuple(r) for r in joint.support()]
-        if self.deviceCandidates and joint is not None:
-            seed = int(np.random.randint(0, 2 ** 31 - 1))
-            cands = self.gp.prior_candidates(total, joint, seed)
-            row = lambda g: self.gp.prior_candidates(1, joint, seed, idx_offset=g).cpu().numpy()[0]       # noqa: E731
-        elif self.deviceCandidates:
-            seed = int(np.random.randint(0, 2 ** 31 - 1))
-            cands = self.gp.box_candidates(total, self.bounds, seed)
-            row = lambda g: self.gp.box_candidates(1, self.bounds, seed, idx_offset=g).cpu().numpy()[0]   # noqa: E731
-        else:
-            draws = np.asarray(self.priorSample(total), dtype=float).reshape(total, -1)
-            cands = self.gp.parse_samples(draws)
-            row = lambda g: np.array(draws[g])                                                              # noqa: E731
+        cands, row = self._candidateDraw(total, joint)
+        if not self.deviceCandidates:
+            cands = self.gp.parse_samples(cands)
         if batchMethod == "thompson":
             idx = self.gp.thompson_batch(self.y, cands, len(kinds), bounds=gate)
             picked = [int(g) for g in idx if g >= 0]
@@ -392,18 +403,9 @@ class ApproxPosterior(object):
         total = int(nCandidates)
         joint = self._jointPrior()
         gate = self.bounds if joint is None else [tuple(r) for r in joint.support()]
-        if self.deviceCandidates and joint is not None:
-            seed = int(np.random.randint(0, 2 ** 31 - 1))
-            cands = self.gp.prior_candidates(total, joint, seed)
-            row = lambda g: self.gp.prior_candidates(1, joint, seed, idx_offset=g).cpu().numpy()[0]       # noqa: E731
-        elif self.deviceCandidates:
-            seed = int(np.random.randint(0, 2 ** 31 - 1))
-            cands = self.gp.box_candidates(total, self.bounds, seed)
-            row = lambda g: self.gp.box_candidates(1, self.bounds, seed, idx_offset=g).cpu().numpy()[0]   # noqa: E731
-        else:
-            draws = np.asarray(self.priorSample(total), dtype=float).reshape(total, -1)
-            cands = self.gp.parse_samples(draws)
-            row = lambda g: np.array(draws[g])                                                              # noqa: E731
+        cands, row = self._candidateDraw(total, joint)
+        if not self.deviceCandidates:
+            cands = self.gp.parse_samples(cands)
         refs, density = self._integrationRefs(integrated)
         weights = self.gp.integration_weights(self.y, refs, density)
         best, value = self.gp.acquire_integrated(self.y, cands, refs, logWeights=weights, bounds=gate)
@@ -451,6 +453,10 @@ class ApproxPosterior(object):
         ``priorSample`` -- valid when the prior IS that box; when ``lnprior`` is a
         :class:`~approxposterior_amd.priors.JointPrior` they are drawn from that prior instead
         (``GP.prior_candidates``), and every ``nCandidates`` sweep is gated by ``lnprior.support()``.
+        ``deviceCandidates="sobol"`` draws them quasi-randomly instead: one scrambled Sobol replicate
+        (``GP.sobol_candidates``) keyed by the same integer, from the same prior or box, sharded and regenerated
+        row by row in the same way -- a sweep that covers the prior without clumps or holes.  At most 2^30
+        candidates (``ValueError`` beyond).
 
         ``batchSize=q`` (with ``nCandidates``): the points are chosen ``q`` at a time from one candidate draw
         per batch by :meth:`GP.acquire_batch` (each pick conditions the GP on the previous picks at their
@@ -511,7 +517,7 @@ class ApproxPosterior(object):
                 raise NotImplementedError("batchSize under a process group: a sharded batch would need the winning "
                                           "row's fantasy columns broadcast from the rank that owns it")
         if deviceCandidates is not None:
-            self.deviceCandidates = bool(deviceCandidates)
+            self.deviceCandidates = self._candidatesMode(deviceCandidates)
         if deviceSearch is not None:
             self.deviceSearch = bool(deviceSearch)
         assert isinstance(numNewPoints, int) and numNewPoints >= 1
@@ -885,7 +891,7 @@ class ApproxPosterior(object):
                          "fitted full-covariance mixture, not %r" % (proposal,))
 
     def evidence(self, nSamples=2 ** 20, proposal="prior", seed=None, chunk=2 ** 20, samples=None, maxComp=3,
-                 covScale=1.0, surrogateDraws=0, nFeatures=2048):
+                 covScale=1.0, surrogateDraws=0, nFeatures=2048, qmc=None):
         """The model evidence and chain-free posterior moments of the surrogate by importance sampling on the device.
         The GP models the unnormalised log-posterior (``y = lnlike + lnprior``), so ``Z = int exp(mu(t)) dt`` over the
         prior's support is the evidence; with ``nSamples`` draws from a proposal ``q`` the weights ``exp(mu - ln q)``
@@ -922,10 +928,30 @@ class ApproxPosterior(object):
         training points under the posterior's mass, whatever ``logZErr`` says.  NumPy's global stream is used in this
         order: the seed (if ``seed`` is None), then every group's ``sample_paths`` in turn, all before the first chunk;
         under a process group the stream is synchronised first, so every rank draws the same functions.  The
-        hyper-parameters are held fixed, and the random-feature error is O(nFeatures^-1/2) in the draws' covariance."""
+        hyper-parameters are held fixed, and the random-feature error is O(nFeatures^-1/2) in the draws' covariance.
+
+        ``qmc = R >= 2`` (randomised quasi-Monte Carlo; ``ValueError`` for 1 and for R > nSamples) replaces the
+        pseudo-random rows by R independently scrambled replicates of a Sobol sequence (``GP.sobol_candidates``):
+        replicate r is rows ``0 .. n - 1`` of the sequence with ``replicate=r`` under the same ``seed``,
+        ``n = nSamples // R`` -- take ``n`` a power of two, the sizes at which the sequence is balanced.  Every proposal
+        kind works, ``chunk`` and ``surrogateDraws`` work as before (draw records merged across replicates), and the
+        result is :func:`utility.importanceReplicatesSummary`'s: ``logZ``, ``mean``, ``cov``, ``ess``, ``nInside`` pooled
+        over the ``R n`` rows, ``logZErr`` the scatter of the replicates' evidences, plus ``logZReplicates``,
+        ``meanReplicates``, ``meanErr``, ``logZErrIID`` (the delta-method figure above, which over-states a
+        quasi-random error) and ``qmc``.  The integrand is smooth -- a GP mean -- so at low dimension the error falls
+        far faster than ``nSamples^-1/2``; the gain shrinks with the dimension and where the proposal covers the mass
+        badly, and a proposal that misses the mass still gives a small error bar next to a small ``ess``.  The default
+        ``qmc=None`` is the pseudo-random estimate, bit for bit."""
         nSamples, chunk = int(nSamples), int(chunk)
         if nSamples < 1 or chunk < 1:
             raise ValueError("evidence: nSamples and chunk must be positive")
+        if qmc is not None:
+            qmc = int(qmc)
+            if qmc < 2 or qmc > nSamples:
+                raise ValueError("evidence: qmc is the number of scrambled replicates: 2 <= qmc <= nSamples (the error "
+                                 "bar is their scatter)")
+            if nSamples // qmc > george.SOBOL_MAX_ROWS:
+                raise ValueError("evidence: a Sobol replicate has at most 2^30 rows")
         surrogateDraws = int(surrogateDraws)
         if surrogateDraws < 0:
             raise ValueError("evidence: surrogateDraws must not be negative")
@@ -958,27 +984,43 @@ class ApproxPosterior(object):
                   for g in range(0, surrogateDraws, _lib.MAX_DRAWS)]
         drawRecords = [None] * surrogateDraws
         centre = np.array(self.theta[int(np.argmax(self.y))], dtype=np.float64).ravel()
-        record = None
-        for off in range(0, nSamples, chunk):
-            mc = min(chunk, nSamples - off)
+        # the rows: one Philox stream of nSamples rows, or qmc Sobol replicates of nSamples // qmc rows each
+        nRows = nSamples if qmc is None else nSamples // qmc
+
+        def draw(mc, off, rep):
+            """(T, lnq) of rows off .. off + mc - 1 (lnq None: the constant -logVolume of the box)."""
+            sobol = None if qmc is None else dict(seed=seed, replicate=rep, idx_offset=off)
             if mixture is not None:
-                T, lnq = self.gp.mixture_candidates(mc, mixture[0], mixture[1], mixture[2], seed, idx_offset=off,
-                                                    covScale=covScale)
-            elif proposal == "prior":
-                T = self.gp.prior_candidates(mc, joint, seed, idx_offset=off)
-                lnq = self.gp.prior_lnprior(T, joint)
-            else:
-                T, lnq = self.gp.box_candidates(mc, self.bounds, seed, idx_offset=off), None      # ln q: logVolume
-            part = self.gp.importance_pass(self.y, T, lnq=lnq, bounds=gate, centre=centre)
-            record = part if record is None else ut.mergeImportance(record, part)
-            for g, paths in enumerate(groups):
-                parts = self.gp.importance_paths(self.y, T, paths, lnq=lnq, bounds=gate, centre=centre)
-                for j, p in enumerate(parts):
-                    s = g * _lib.MAX_DRAWS + j
-                    drawRecords[s] = p if drawRecords[s] is None else ut.mergeImportance(drawRecords[s], p)
-        out = ut.importanceSummary(record, nSamples, logVolume=logVolume)
+                if sobol is not None:
+                    return self.gp.sobol_candidates(mc, mixture=mixture, covScale=covScale, **sobol)
+                return self.gp.mixture_candidates(mc, mixture[0], mixture[1], mixture[2], seed, idx_offset=off,
+                                                  covScale=covScale)
+            if proposal == "prior":
+                T = (self.gp.prior_candidates(mc, joint, seed, idx_offset=off) if sobol is None
+                     else self.gp.sobol_candidates(mc, prior=joint, **sobol))
+                return T, self.gp.prior_lnprior(T, joint)
+            return (self.gp.box_candidates(mc, self.bounds, seed, idx_offset=off) if sobol is None
+                    else self.gp.sobol_candidates(mc, bounds=self.bounds, **sobol)), None
+
+        records = []
+        for rep in range(1 if qmc is None else qmc):
+            record = None
+            for off in range(0, nRows, chunk):
+                T, lnq = draw(min(chunk, nRows - off), off, rep)
+                part = self.gp.importance_pass(self.y, T, lnq=lnq, bounds=gate, centre=centre)
+                record = part if record is None else ut.mergeImportance(record, part)
+                for g, paths in enumerate(groups):
+                    parts = self.gp.importance_paths(self.y, T, paths, lnq=lnq, bounds=gate, centre=centre)
+                    for j, p in enumerate(parts):
+                        s = g * _lib.MAX_DRAWS + j
+                        drawRecords[s] = p if drawRecords[s] is None else ut.mergeImportance(drawRecords[s], p)
+            records.append(record)
+        if qmc is None:
+            out = ut.importanceSummary(records[0], nSamples, logVolume=logVolume)
+        else:
+            out = ut.importanceReplicatesSummary(records, nRows, logVolume=logVolume)
         if surrogateDraws > 0:
-            out.update(ut.importanceDrawsSummary(drawRecords, nSamples, logVolume=logVolume))
+            out.update(ut.importanceDrawsSummary(drawRecords, len(records) * nRows, logVolume=logVolume))
         return out
 
     def runNested(self, nlive=512, batch=16, nsteps=None, nruns=None, dlogz=0.01, maxBatches=None, seed=None,

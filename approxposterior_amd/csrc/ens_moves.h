@@ -37,7 +37,8 @@
 
 #define ENS_MAXW 256
 
-__device__ __forceinline__ void philox4x32(unsigned int (&c)[4], unsigned int k0, unsigned int k1) {
+// (host too: sobol.hip hashes its per-dimension scramble seeds on the host)
+__host__ __device__ __forceinline__ void philox4x32(unsigned int (&c)[4], unsigned int k0, unsigned int k1) {
 #pragma unroll
     for (int r = 0; r < 10; ++r) {
         const unsigned long long p0 = (unsigned long long)0xD2511F53u * c[0];

@@ -21,7 +21,8 @@
 #include "apgp_common.h"
 #include "scratch.h"
 #include "ens_moves.h"
-#include "ens_body.h"      // EnsArgs and the sampler body the kernels below share with tempering.hip
+#include "draws.h"         // the box's and the prior's argument records and transforms, shared with sobol.hip
+#include "ens_body.h"     // EnsArgs and the sampler body the kernels below share with tempering.hip
 #include <atomic>
 #include <mutex>
 
@@ -373,15 +374,8 @@ extern "C" int apgp_ensemble_sample_moves(const double* xs, int64_t n, const apg
 // Philox4x32-10, counter = (i low, i high, d / 2, 0x43414e44 "CAND"), key = seed -- so rank r of a sharded sweep
 // generates exactly its rows [lo, hi) with idx_offset = lo, and anybody can regenerate the winning row alone.
 //   T[i][d] = lo[d] + (hi[d] - lo[d]) * u,  u = 53-bit uniform in (0, 1) (u01 above).
+// (BoxArgs and the bounds' checks: draws.h, shared with the Sobol generator of sobol.hip)
 // ---------------------------------------------------------------------------
-struct BoxArgs {
-    double* T;
-    long long m, idx_offset;
-    int ndim;
-    unsigned long long seed;
-    double lo[APGP_MAX_DIM], span[APGP_MAX_DIM];
-};
-
 __global__ __launch_bounds__(256) void box_candidates_kernel(BoxArgs a) {
     const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
     if (i >= a.m) return;
@@ -402,12 +396,9 @@ extern "C" int apgp_box_candidates(double* T, int64_t m, int32_t ndim, const dou
     APGP_CHECK_ARG(ndim >= 1 && ndim <= APGP_MAX_DIM, "1 <= ndim <= APGP_MAX_DIM required");
     if (m == 0) return 0;
     BoxArgs a;
-    a.T = T; a.m = m; a.idx_offset = idx_offset; a.ndim = ndim; a.seed = seed;
-    for (int d = 0; d < APGP_MAX_DIM; ++d) {
-        a.lo[d] = d < ndim ? lo[d] : 0.0;
-        a.span[d] = d < ndim ? hi[d] - lo[d] : 0.0;
-        APGP_CHECK_ARG(d >= ndim || (a.span[d] >= 0.0 && a.span[d] < INFINITY), "bounds must be finite with lo <= hi");
-    }
+    const char* bad = box_args(a, ndim, lo, hi);
+    APGP_CHECK_ARG(bad == nullptr, bad);
+    a.T = T; a.m = m; a.idx_offset = idx_offset; a.seed = seed;
     hipLaunchKernelGGL(box_candidates_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, (hipStream_t)stream, a);
     APGP_CHECK_LAUNCH();
     return 0;
@@ -424,27 +415,7 @@ extern "C" int apgp_box_candidates(double* T, int64_t m, int32_t ndim, const dou
 // -log(sigma) - log(2 pi) / 2) minus z^2 / 2 for Gaussian dimensions, z = (x - mu) / sigma; -inf for a non-finite
 // coordinate or one outside a Uniform factor's [low, high].
 // ---------------------------------------------------------------------------
-#define APGP_PRIOR_UNIFORM 0
-#define APGP_PRIOR_GAUSSIAN 1
-
-struct PriorArgs {
-    double* T;                 // candidates out (m x ndim) | rows in for the log-density
-    double* out;               // log-density out (m), NULL for candidates
-    long long m, idx_offset;
-    int ndim;
-    unsigned long long seed;
-    int kind[APGP_MAX_DIM];
-    double p0[APGP_MAX_DIM];   // low | mu
-    double p1[APGP_MAX_DIM];   // candidates: span | sigma;  log-density: high | sigma
-    double lc[APGP_MAX_DIM];   // log-density constant of the factor
-};
-
-// (prior_gauss: csrc/ens_moves.h, shared with the mixture proposal of evidence.hip)
-__device__ __forceinline__ double prior_draw(const PriorArgs& a, int d, double u) {
-    if (a.kind[d] == APGP_PRIOR_UNIFORM) return fma(a.p1[d], u, a.p0[d]);
-    return prior_gauss(a.p0[d], a.p1[d], u);
-}
-
+// (PriorArgs, prior_draw and the factors' checks prior_args: draws.h, shared with the Sobol generator of sobol.hip)
 __global__ __launch_bounds__(256) void prior_candidates_kernel(PriorArgs a) {
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < a.m; i += (long long)gridDim.x * 256) {
         const unsigned long long g = (unsigned long long)(a.idx_offset + i);
@@ -476,35 +447,6 @@ __global__ __launch_bounds__(256) void prior_lnprior_kernel(PriorArgs a) {
         }
         a.out[i] = in ? s : -INFINITY;
     }
-}
-
-// the checks both entries share; fills a (kinds and parameters) or returns the failed check's message
-static const char* prior_args(PriorArgs& a, int32_t ndim, const int32_t* kind, const double* p0, const double* p1,
-                              bool span) {
-    if (!(ndim >= 1 && ndim <= APGP_MAX_DIM)) return "1 <= ndim <= APGP_MAX_DIM required";
-    a.ndim = ndim;
-    for (int d = 0; d < APGP_MAX_DIM; ++d) {
-        a.kind[d] = APGP_PRIOR_UNIFORM;
-        a.p0[d] = a.p1[d] = a.lc[d] = 0.0;
-        if (d >= ndim) continue;
-        const double u = p0[d], v = p1[d];
-        if (kind[d] == APGP_PRIOR_UNIFORM) {
-            if (!(std::isfinite(u) && std::isfinite(v) && u < v && std::isfinite(v - u)))
-                return "a Uniform factor needs finite low < high";
-            a.p0[d] = u;
-            a.p1[d] = span ? v - u : v;
-            a.lc[d] = -std::log(v - u);
-        } else if (kind[d] == APGP_PRIOR_GAUSSIAN) {
-            if (!(std::isfinite(u) && std::isfinite(v) && v > 0.0)) return "a Gaussian factor needs finite mu and sigma > 0";
-            a.kind[d] = APGP_PRIOR_GAUSSIAN;
-            a.p0[d] = u;
-            a.p1[d] = v;
-            a.lc[d] = -std::log(v) - 0.5 * std::log(2.0 * M_PI);
-        } else {
-            return "kind must be 0 (Uniform) or 1 (Gaussian)";
-        }
-    }
-    return nullptr;
 }
 
 static inline unsigned prior_grid(long long m) {

@@ -12,6 +12,7 @@
 //                         the global maximum; a fixed-tree reduction of the partials.  No atomics: every sum runs in an
 //                         order that depends on m alone.
 #include "apgp_common.h"
+#include "draws.h"
 #include "ens_moves.h"
 #include "gmm_logpdf.h"
 #include "scratch.h"
@@ -19,53 +20,30 @@
 #include <mutex>
 #include <vector>
 
-#define MIX_MAX_K 16
 #define MIX_TAG 0x4d495854u            // "MIXT": the mixture proposal's Philox counter tag
-#define MIX_SCRATCH_SLOT 6             // the device image of the mixture parameters
 #define IMP_THREADS APGP_IMP_BLOCK     // candidates per workgroup pass, one per thread
 #define IMP_NB_MAX APGP_IMP_MAX_BLOCKS // workgroups of a pass: beyond it a workgroup takes further tiles of candidates
 #define IMP_ROWS 128                   // training rows per LDS tile
 
 namespace {
 
-constexpr int ev_tri(int d) { return d * (d + 1) / 2; }
-
 // ---------------------------------------------------------------------------------------------------------------------
-// Mixture proposal.  Device image of the parameters (DP = the padded dimension):
-//   [cumw (MIX_MAX_K)] [per component: log w, log det U, c (DP), U packed in DP columns (gmm_logpdf's layout)]
-//   [per component: A packed lower triangle row by row, A[i][j] at i (i + 1) / 2 + j, D (D + 1) / 2 entries]
+// Mixture proposal (the parameters' device image, MixArgs and the row's arithmetic: draws.h, shared with sobol.hip).
 // Row g: Philox4x32-10, key = seed, counter (g low, g high, j, "MIXT"); j = 0: u01(words 0, 1) picks the component (the
 // first k with u < cumw[k]); j = 1 + d / 2: words 0, 1 give dimension d's uniform, words 2, 3 dimension d + 1's;
 // z_d = prior_gauss(0, 1, u); t_i = c_i + sum_{j <= i} A_ij z_j (an fma chain in ascending j, then one addition).
 // ln q is evaluated at the stored t: logsumexp_k(gmm_logpdf(t | k)), the arithmetic of gmm_pass_kernel's score.
 // ---------------------------------------------------------------------------------------------------------------------
-struct MixArgs {
-    double* T;
-    double* lnq;
-    const double* P;
-    long long m, idx_offset;
-    int D, K;
-    unsigned long long seed;
-};
-
 template <int DP>
 __global__ __launch_bounds__(256) void mix_candidates_kernel(MixArgs a) {
-    constexpr int QP = 2 + DP + ev_tri(DP);
     __shared__ double slp[MIX_MAX_K][256];
-    const double* cumw = a.P;
-    const double* G = a.P + MIX_MAX_K;
-    const int triD = ev_tri(a.D);
-    const double* A = G + a.K * QP;
     const int tid = threadIdx.x;
     const unsigned int k0 = (unsigned int)a.seed, k1 = (unsigned int)(a.seed >> 32);
     for (long long i = (long long)blockIdx.x * 256 + tid; i < a.m; i += (long long)gridDim.x * 256) {
         const unsigned long long g = (unsigned long long)(a.idx_offset + i);
         unsigned int c[4] = {(unsigned int)g, (unsigned int)(g >> 32), 0u, MIX_TAG};
         philox4x32(c, k0, k1);
-        const double uc = u01(c[0], c[1]);
-        int k = a.K - 1;
-        for (int j = a.K - 2; j >= 0; --j)
-            if (uc < cumw[j]) k = j;
+        const int k = mix_pick(a, u01(c[0], c[1]));
         double z[DP];
 #pragma unroll
         for (int d = 0; d < DP; d += 2) {
@@ -78,34 +56,7 @@ __global__ __launch_bounds__(256) void mix_candidates_kernel(MixArgs a) {
                 if (d + 1 < a.D) z[d + 1] = prior_gauss(0.0, 1.0, u01(cd[2], cd[3]));
             }
         }
-        const double* ck = G + k * QP + 2;
-        const double* Ak = A + (long long)k * triD;
-        double t[DP];
-#pragma unroll
-        for (int r = 0; r < DP; ++r) {
-            t[r] = 0.0;
-            if (r < a.D) {
-                double acc = 0.0;
-#pragma unroll
-                for (int j = 0; j <= r; ++j) acc = fma(Ak[r * (r + 1) / 2 + j], z[j], acc);
-                t[r] = __dadd_rn(ck[r], acc);
-            }
-        }
-        double* row = a.T + i * a.D;
-#pragma unroll
-        for (int d = 0; d < DP; ++d)
-            if (d < a.D) row[d] = t[d];
-        if (a.lnq) {
-            double mx = -INFINITY;
-            for (int kk = 0; kk < a.K; ++kk) {
-                const double lp = gmm_logpdf<DP>(t, G + kk * QP, a.D);
-                slp[kk][tid] = lp;
-                if (lp > mx) mx = lp;
-            }
-            double s = 0.0;
-            for (int kk = 0; kk < a.K; ++kk) s += exp(slp[kk][tid] - mx);
-            a.lnq[i] = mx + log(s);
-        }
+        mix_row<DP>(a, i, tid, k, z, slp);
     }
 }
 
@@ -348,8 +299,6 @@ inline int imp_nb(long long m) {
     return (int)(t < IMP_NB_MAX ? t : IMP_NB_MAX);
 }
 
-inline long long mix_user_len(int D) { return 3 + D + 2 * ev_tri(D); }
-
 }  // namespace
 
 extern "C" int64_t apgp_mix_params_len(int32_t ndim, int32_t ncomp) {
@@ -359,58 +308,13 @@ extern "C" int64_t apgp_mix_params_len(int32_t ndim, int32_t ncomp) {
 
 extern "C" int apgp_mix_candidates(double* T, double* lnq, int64_t m, int32_t ndim, int32_t ncomp, const double* params,
                                    uint64_t seed, int64_t idx_offset, void* stream) {
-    APGP_CHECK_ARG(T && params, "null pointer");
-    APGP_CHECK_ARG(m >= 0 && m <= APGP_MAX_M && idx_offset >= 0, "0 <= m <= APGP_MAX_M and idx_offset >= 0 required");
-    APGP_CHECK_ARG(ndim >= 1 && ndim <= APGP_MAX_DIM, "1 <= ndim <= APGP_MAX_DIM required");
-    APGP_CHECK_ARG(ncomp >= 1 && ncomp <= MIX_MAX_K, "1 <= ncomp <= 16 required");
-    const int D = ndim, K = ncomp, DP = apgp_dpad(ndim), tri = ev_tri(D);
-    const int QP = 2 + DP + ev_tri(DP);
-    const long long R = mix_user_len(D);
-    std::vector<double> img((size_t)MIX_MAX_K + (size_t)K * QP + (size_t)K * tri, 0.0);
-    double prev = 0.0;
-    for (int k = 0; k < K; ++k) {
-        const double* p = params + k * R;
-        const double cw = p[0], lw = p[1], ld = p[2];
-        APGP_CHECK_ARG(cw >= 0.0 && cw <= 1.0 && cw >= prev, "cumulative weights must not fall and lie in [0, 1]");
-        APGP_CHECK_ARG(lw <= 0.0 && std::isfinite(ld), "log weights must be <= 0 and log-determinants finite");
-        prev = cw;
-        img[k] = cw;
-        double* g = img.data() + MIX_MAX_K + (size_t)k * QP;
-        g[0] = lw; g[1] = ld;
-        for (int d = 0; d < D; ++d) {
-            APGP_CHECK_ARG(std::isfinite(p[3 + d]), "centres must be finite");
-            g[2 + d] = p[3 + d];
-        }
-        for (int e = 0; e < tri; ++e) {
-            APGP_CHECK_ARG(std::isfinite(p[3 + D + e]) && std::isfinite(p[3 + D + tri + e]), "factors must be finite");
-            g[2 + DP + e] = p[3 + D + e];           // (the first D columns of the DP-column packing sit at the same offsets)
-            img[(size_t)MIX_MAX_K + (size_t)K * QP + (size_t)k * tri + e] = p[3 + D + tri + e];
-        }
-        for (int d = 0; d < D; ++d)
-            APGP_CHECK_ARG(p[3 + D + tri + ev_tri(d) + d] > 0.0, "the diagonal of a Cholesky factor must be positive");
-    }
-    APGP_CHECK_ARG(prev == 1.0, "the last cumulative weight must be 1.0");
-    for (int k = K; k < MIX_MAX_K; ++k) img[k] = 1.0;
-    if (m == 0) return 0;
-    hipStream_t s = (hipStream_t)stream;
-    std::lock_guard<std::mutex> lock(apgp_stream_lock(s));
-    double* dev = apgp_stream_scratch(MIX_SCRATCH_SLOT, s, img.size());
-    if (!dev) {
-        apgp_set_error("apgp_mix_candidates: scratch allocation failed");
-        return -2;
-    }
-    // (ordered on the stream and complete on return: img is a temporary)
-    if (hipMemcpyWithStream(dev, img.data(), img.size() * sizeof(double), hipMemcpyHostToDevice, s) != hipSuccess) {
-        apgp_set_error("apgp_mix_candidates: parameter upload failed");
-        return -2;
-    }
-    MixArgs a;
-    a.T = T; a.lnq = lnq; a.P = dev; a.m = m; a.idx_offset = idx_offset; a.D = D; a.K = K; a.seed = seed;
-    const long long b = (m + 255) / 256;
-    const dim3 grid((unsigned)(b < 65536 ? b : 65536)), block(256);
-    apgp_by_dpad(DP, [&](auto dp) { hipLaunchKernelGGL(mix_candidates_kernel<decltype(dp)::value>, grid, block, 0, s, a); });
-    APGP_CHECK_LAUNCH();
-    return 0;
+    return mix_draw_call(__func__, T, lnq, m, ndim, ncomp, params, seed, idx_offset, stream,
+                         [](const MixArgs& a, int DP, long long blocks, hipStream_t s) {
+                             const dim3 grid((unsigned)(blocks < 65536 ? blocks : 65536)), block(256);
+                             apgp_by_dpad(DP, [&](auto dp) {
+                                 hipLaunchKernelGGL(mix_candidates_kernel<decltype(dp)::value>, grid, block, 0, s, a);
+                             });
+                         });
 }
 
 extern "C" int64_t apgp_importance_stats_len(int32_t ndim) {

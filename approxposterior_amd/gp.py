@@ -42,7 +42,7 @@ from . import _lib
 from .george_extras import GeorgeExtras
 
 __all__ = ["GP", "ExpSquaredKernel", "ConstantKernel", "Product", "ConstantModel",
-           "kernels", "UTILITY_KINDS"]
+           "kernels", "UTILITY_KINDS", "sobolSample"]
 
 UTILITY_KINDS = {"agp": _lib.UTIL_AGP, "bape": _lib.UTIL_BAPE, "jones": _lib.UTIL_JONES}
 # objectives of the device point search (GP.nelder_mead_search): the utilities and -mu (ApproxPosterior.findMAP)
@@ -1974,6 +1974,24 @@ class GP(GeorgeExtras):
                                                int(idx_offset), self._stream(torch)), "apgp_mix_candidates")
         return T, lnq
 
+    # -- quasi-random draws (DESIGN.md "Quasi-random draws") ---------------------------------
+    def sobol_candidates(self, m, bounds=None, prior=None, mixture=None, seed=0, replicate=0, scramble=True,
+                         idx_offset=0, covScale=1.0):
+        """Rows ``idx_offset .. idx_offset + m - 1`` of replicate ``replicate`` of the scrambled Sobol sequence keyed by
+        ``seed``, pushed through the transform of exactly one source: ``bounds`` (the box of :meth:`box_candidates`),
+        ``prior`` (a :class:`~approxposterior_amd.priors.JointPrior`, as :meth:`prior_candidates`) or ``mixture``
+        (``(weights, means, covariances)``, covariances scaled by ``covScale``, as :meth:`mixture_candidates`: Sobol
+        dimensions 0 .. D - 1 give the normals, dimension D the component).  Returns the device tensor ``T (m, D)``, or
+        ``(T, lnq (m,))`` for a mixture.  A row depends on (seed, replicate, row number) only, so sharding by
+        ``idx_offset``, chunking and regenerating one row work as for the Philox draws.  ``scramble=False`` is the plain
+        sequence (torch's ``SobolEngine``, whose row 0 is the origin).  The sequence has 2^30 rows."""
+        if (bounds is not None) + (prior is not None) + (mixture is not None) != 1:
+            raise ValueError("sobol_candidates draws from exactly one of bounds, prior and mixture")
+        torch, dev, lib = self._rt()
+        with self._on(torch, dev):
+            return _sobol_draw(torch, dev, lib, self._stream(torch), int(m), self.kernel.ndim, bounds, prior, mixture,
+                               seed, replicate, scramble, idx_offset, covScale)
+
     def prior_lnprior(self, T, prior):
         """``prior``'s log-density (a :class:`~approxposterior_amd.priors.JointPrior`) at the rows of the device
         tensor ``T`` (M, D), as a device tensor (M,)."""
@@ -2596,3 +2614,60 @@ class GP(GeorgeExtras):
                 grad.extend(o[2:2 + ndim])
         walk(self.kernel, False)
         return np.array(grad, dtype=np.float64)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# quasi-random draws (DESIGN.md "Quasi-random draws")
+# ---------------------------------------------------------------------------------------------------------------------
+SOBOL_MAX_ROWS = 1 << 30        # the sequence's length: idx_offset + m may not exceed it
+
+
+def _sobol_draw(torch, dev, lib, stream, m, D, bounds, prior, mixture, seed, replicate, scramble, idx_offset, covScale):
+    """Rows of the Sobol sequence through one of the three transforms (exactly one of ``bounds``, ``prior``, ``mixture``
+    is given; ``dev`` is current): the device tensor ``T (m, D)``, with ``lnq (m,)`` for a mixture."""
+    key = (_seed64(seed), int(replicate), 1 if scramble else 0, int(idx_offset), stream)
+    T = torch.empty((m, D), dtype=torch.float64, device=dev)
+    if mixture is not None:
+        K, Dm, rec = GP._mixture_params(mixture[0], mixture[1], mixture[2], covScale)
+        if Dm != D:
+            raise ValueError("the mixture must have %d dimensions" % D)
+        lnq = torch.empty(m, dtype=torch.float64, device=dev)
+        rec = np.ascontiguousarray(rec.ravel())
+        if m:
+            _lib.check(lib.apgp_sobol_mix_candidates(T.data_ptr(), lnq.data_ptr(), m, D, K, rec.ctypes.data, *key),
+                       "apgp_sobol_mix_candidates")
+        return T, lnq
+    if m == 0:
+        return T
+    if prior is not None:
+        kind, p0, p1 = GP._prior_records(prior, D)
+        _lib.check(lib.apgp_sobol_prior_candidates(T.data_ptr(), m, D, kind.ctypes.data, p0.ctypes.data, p1.ctypes.data,
+                                                   *key), "apgp_sobol_prior_candidates")
+    else:
+        lo, hi = _box(bounds, D, optional=False)
+        _lib.check(lib.apgp_sobol_box_candidates(T.data_ptr(), m, D, lo, hi, *key), "apgp_sobol_box_candidates")
+    return T
+
+
+def sobolSample(n, bounds=None, prior=None, seed=None):
+    """A space-filling initial design: ``n`` rows of one scrambled Sobol replicate in the box ``bounds`` (a (lo, hi) pair
+    per dimension) or under ``prior`` (a :class:`~approxposterior_amd.priors.JointPrior`) -- exactly one of the two -- as
+    a NumPy array (n, D), from the kernels behind :meth:`GP.sobol_candidates`; no GP is needed.  ``seed=None`` takes one
+    integer from NumPy's global stream.  For the best balance take ``n`` a power of two."""
+    if (bounds is None) == (prior is None):
+        raise ValueError("sobolSample draws from exactly one of bounds and prior")
+    n = int(n)
+    if not 0 <= n <= SOBOL_MAX_ROWS:
+        raise ValueError("sobolSample: 0 <= n <= 2^30 required")
+    D = len(np.asarray(bounds, dtype=np.float64).reshape(-1, 2)) if prior is None else len(prior.records()[0])
+    if not 1 <= D <= _lib.MAX_DIM:
+        raise ValueError("sobolSample: between 1 and %d dimensions" % _lib.MAX_DIM)
+    if seed is None:
+        seed = int(np.random.randint(0, 2 ** 31 - 1))
+    import torch
+    lib = _lib.load()
+    if not torch.cuda.is_available():
+        raise _lib.ApgpError("no MI355X visible: approxposterior_amd has no CPU fallback")
+    dev = torch.device("cuda", torch.cuda.current_device())
+    T = _sobol_draw(torch, dev, lib, GP._stream(torch), n, D, bounds, prior, None, seed, 0, True, 0, 1.0)
+    return T.cpu().numpy()

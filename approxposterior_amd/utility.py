@@ -23,7 +23,8 @@ from scipy.stats import norm
 
 __all__ = ["logsubexp", "AGPUtility", "BAPEUtility", "JonesUtility", "EIVUtility",
            "minimizeObjective", "sweepObjective", "utilityKind", "searchKind", "klNumerical",
-           "mergeImportance", "importanceSummary", "importanceDrawsSummary"]
+           "mergeImportance", "importanceSummary", "importanceDrawsSummary",
+           "importanceReplicatesSummary"]
 
 
 def klNumerical(x, p, q):
@@ -349,6 +350,48 @@ def importanceSummary(record, m, logVolume=0.0):
             "mean": c + d,
             "cov": np.asarray(record["S"], dtype=float) / S0 - np.outer(d, d),
             "nInside": int(record["cnt"])}
+
+
+def importanceReplicatesSummary(records, n, logVolume=0.0):
+    """What R >= 2 importance records say together when each is taken over the ``n`` rows of another independently
+    scrambled replicate of a quasi-random sequence (``ApproxPosterior.evidence(qmc=R)``).  The pooled estimates are
+    :func:`importanceSummary` of the records merged in order (:func:`mergeImportance`) over ``R n`` rows: ``logZ``,
+    ``ess``, ``mean``, ``cov``, ``nInside``.  The rows of a replicate are not independent, so the error comes from the
+    scatter of the replicates, which are:
+
+    ``logZErr``         ``std(Z_r, ddof=1) / sqrt(R) / mean(Z_r)`` with ``Z_r = exp(logZ_r - max_r logZ_r)``: the relative
+                        standard error of the mean of the replicates' evidences, i.e. the standard error of ``logZ``
+    ``meanErr``         ``std(mean_r, ddof=1) / sqrt(R)`` per dimension, (D,)
+    ``logZReplicates``  (R,), ``meanReplicates`` (R, D): :func:`importanceSummary` of every replicate
+    ``logZErrIID``      the pooled record's delta-method figure, which takes the rows for independent draws and
+                        over-states the error of a quasi-random estimate
+    ``qmc``             R
+
+    A replicate with no admissible row has ``logZ_r = -inf`` (``Z_r = 0``) and a NaN mean: it counts in ``logZErr`` and
+    makes ``meanErr`` NaN.  With no admissible row at all ``logZErr`` is NaN.  The error bar is the scatter of R numbers:
+    itself uncertain by about ``1 / sqrt(2 (R - 1))`` of its value, and blind -- like every importance estimate -- to
+    mass the proposal never reaches."""
+    records = list(records)
+    R = len(records)
+    if R < 2:
+        raise ValueError("importanceReplicatesSummary needs at least two replicates: the error is their scatter")
+    pooled = records[0]
+    for r in records[1:]:
+        pooled = mergeImportance(pooled, r)
+    out = importanceSummary(pooled, R * float(n), logVolume=logVolume)
+    per = [importanceSummary(r, n, logVolume=logVolume) for r in records]
+    logZ = np.array([p["logZ"] for p in per], dtype=float)
+    mean = np.array([p["mean"] for p in per], dtype=float)
+    out["logZErrIID"] = out["logZErr"]
+    top = logZ.max()
+    if top > -np.inf:
+        Z = np.exp(logZ - top)
+        out["logZErr"] = float(np.std(Z, ddof=1) / np.sqrt(R) / np.mean(Z))
+    else:
+        out["logZErr"] = np.nan
+    out["meanErr"] = np.std(mean, axis=0, ddof=1) / np.sqrt(R)
+    out["logZReplicates"], out["meanReplicates"], out["qmc"] = logZ, mean, R
+    return out
 
 
 def importanceDrawsSummary(records, m, logVolume=0.0):

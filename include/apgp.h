@@ -954,6 +954,32 @@ int apgp_importance_pass(const double* T, int64_t m, const double* lnq, const do
                          const double* hi /*host*/, const double* centre /*host*/, double* logw_out,
                          double* stats_out, double* work, void* stream);
 
+/* ---- Quasi-random siblings of the three candidate generators (DESIGN.md "Quasi-random draws") ----------------
+ * Rows idx_offset .. idx_offset + m - 1 of replicate `replicate` of a scrambled Sobol sequence keyed by `seed`, pushed
+ * through the sibling's transform of a uniform: fma(hi - lo, u, lo) for the box and a Uniform factor, mu + (sigma sqrt 2)
+ * erfcinv(2 (1 - u)) for a Gaussian factor; for the mixture the Sobol dimensions 0 .. D - 1 give the standard normals,
+ * dimension D picks the component (the first k with u < cumw[k]), t = c_k + A_k z and ln q at the stored row follow by
+ * apgp_mix_candidates' arithmetic.  Every other argument is the sibling's, checked as the sibling checks it.
+ * Point g (0 <= g < 2^30), dimension d: x = XOR over the set bits b of g ^ (g >> 1) of V32[d][b] = V[d][b] << 2, V the
+ * Joe-Kuo direction numbers as torch.quasirandom.SobolEngine holds them: x / 2^32 is row g of SobolEngine's draw (row 0 is
+ * the origin).  scramble = 1 (nested uniform, hash-based: Laine-Karras as in Burley 2020), per dimension:
+ *   x <- rev32(lk(rev32(x), h_d)),  lk(v, h): v += h; v ^= v * 0x6c50b47c; v ^= v * 0xb82f1e52; v ^= v * 0xc7afe638;
+ *   v ^= v * 0x8d22f6e6 (uint32),  h_d = word 0 of Philox4x32-10 with counter (d, replicate, 0, 0x534f424c "SOBL"), key = seed.
+ * scramble = 0 leaves x alone (seed and replicate then change nothing).  u = (x + 0.5) 2^-32: exact, never 0 or 1.
+ * A row depends on (seed, replicate, scramble, global row) only.  Refused (-1) before any launch, besides the sibling's
+ * refusals: idx_offset + m > 2^30, replicate < 0, scramble outside {0, 1}.  m = 0: nothing is done.
+ * apgp_sobol_direction: V[d][b] (30 bits) of the compiled table, 0 <= d <= 32, 0 <= b <= 29; -1 out of range.  Host only.
+ * Added in ABI 8 without changing anything before it: APGP_ABI_VERSION stays 8.                                      */
+int32_t apgp_sobol_direction(int32_t d, int32_t b);
+int apgp_sobol_box_candidates(double* T, int64_t m, int32_t ndim, const double* lo /*host*/, const double* hi /*host*/,
+                              uint64_t seed, int32_t replicate, int32_t scramble, int64_t idx_offset, void* stream);
+int apgp_sobol_prior_candidates(double* T, int64_t m, int32_t ndim, const int32_t* kind /*host*/,
+                                const double* p0 /*host*/, const double* p1 /*host*/, uint64_t seed, int32_t replicate,
+                                int32_t scramble, int64_t idx_offset, void* stream);
+int apgp_sobol_mix_candidates(double* T, double* lnq, int64_t m, int32_t ndim, int32_t ncomp,
+                              const double* params /*host*/, uint64_t seed, int32_t replicate, int32_t scramble,
+                              int64_t idx_offset, void* stream);
+
 /* ---- Evidence over posterior function draws (GP.importance_paths, ApproxPosterior.evidence(surrogateDraws=)) ----
  * apgp_importance_pass integrates exp(mu): the surrogate's mean taken for the log-posterior.  apgp_path_importance takes
  * S = ndraws posterior function draws f_s instead -- exactly apgp_path_draws' functions: the same arguments (xs, n, kern,
