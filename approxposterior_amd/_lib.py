@@ -123,6 +123,10 @@ SIGNATURES = {
     "apgp_get_seed_rowsplit": (ctypes.c_int, []),
     "apgp_set_seed_park": (ctypes.c_int, [ctypes.c_int]),
     "apgp_get_seed_park": (ctypes.c_int, []),
+    "apgp_set_seed_first": (ctypes.c_int, [ctypes.c_int]),
+    "apgp_get_seed_first": (ctypes.c_int, []),
+    "apgp_set_seed_parts": (ctypes.c_int, [ctypes.c_int]),
+    "apgp_get_seed_parts": (ctypes.c_int, []),
     "apgp_sweep_prune_counts_offset": (_I64, [_I64, _I64]),
     "apgp_sweep_prune_select": (ctypes.c_int, [_P, _I64, _P, _P, _F64, _P, _P]),
     "apgp_prune_bounds": (ctypes.c_int, [_P, _I64, _P, _I64, _KP, _F64, _I32, ctypes.POINTER(_F64), ctypes.POINTER(_F64),

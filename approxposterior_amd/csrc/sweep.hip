@@ -168,8 +168,12 @@ __global__ __launch_bounds__(1024) void argmin_final_kernel(const double* part_u
 // chain over s = 0 .. 7 (S2_HQ_PRE doubles), the h = 1 item its 32 accumulators per lane (S2_HQ_ACC doubles), and
 // sweep_fold_kernel runs the chain on from the prefix through the stored values, then the same gather and
 // reductions (s2_q_gather), and writes the share sweep_finish_kernel reads.  No workgroup waits for another.
+// Finer row parts (the seed waves, below): a row block >= J0 goes as 2 / 4 / 8 items of 4 / 2 / 1 sub-block pairs, pairs
+// [pp p, pp p + pp) for part p.  The chain is continued through all parts in s order: part 0 stores its prefix over
+// s = 0 .. 2 pp - 1, every other part its 2 pp x 4 accumulators per lane at their place s of the whole item (the fold
+// region holds sub-blocks 2 .. 15: part 0 covers 0 and 1 at least), and the fold runs the chain on from s = 2 pp.
 #define S2_HQ_PRE (4 * 256)              // doubles per (position, row block): 4 per matrix lane
-#define S2_HQ_ACC (32 * 256)             // doubles per (position, row block): 8 sub-blocks x 4 rotations per matrix lane
+#define S2_HQ_ACC (56 * 256)             // doubles per (position, row block): sub-blocks 2 .. 15 x 4 rotations per matrix lane
 // The fold inputs lie s2_fold_off doubles behind sp_q, at the end of the caller's scratch (apgp_acquire_work_len): behind
 // the split shares and the pruned sweep's 3 ncb + S2_PRUNE_WORDS words, at an even offset (16-byte accesses).  A function
 // of the launch's own arguments (ncb = SweepArgs::blk_end in a list launch; split = 2 + J0 there), not a pointer in
@@ -197,27 +201,59 @@ __host__ __device__ inline double* s2_fold_item(double* sp_q, int nrb, long long
 #define S2P_HALF_PARK 116
 #define S2P_WHOLE_GEN 197
 #define S2P_WHOLE_PARK 232
+// the two-pair and one-pair items of the parked route, measured the same way (docs/experiments.md, Round 27): a wave
+// of fewer items than CUs lasts its heaviest item.  Two pairs: N = 4096 and 2048, 240 + 16 and 112 + 16 tiles in 265.0
+// and 139.6 us: 0.98 re-read, 1.87 generating (N = 1024, 48 + 16 tiles: 77.0 modelled, 77.2 measured).  One pair (the
+// predicated two-pair body with its second pair off): 221.1 and 116.9 us: 0.81 and 1.61 (N = 1024: 64.8, 65.4 measured).
+// Halving an item's rows takes only a sixth off its re-read tile (half: 1.16): the tile waits for its barrier and the
+// feeders' fetch, not for its MFMAs (0.22 us per pair).
+#define S2P_PAIR2_GEN 187
+#define S2P_PAIR2_PARK 98
+#define S2P_PAIR1_GEN 161
+#define S2P_PAIR1_PARK 81
+// what a second wave costs when none of its seeds is swept: four launches that leave at once (4.7 - 5.4 us each)
+#define S2P_WAVE2 2000
+// ---- the seed waves' launch word (SweepArgs::split of the seed route's launches) -----------------------------------------
+// The PR_SEED seeds are swept in two waves, list positions [0, K) and [K, PR_SEED) (launch_sweep_list).  A wave's launches
+// carry J0, lg = log2(parts of a split row block) and the wave's positions [P0, P1) in SweepArgs::split: the argument block
+// stays what it was.  P0 > 0 marks the second wave, whose K is P0.  (A plain split launch has split = 1: J0 < 0 is never
+// read there, lg = P0 = P1 = 0.)  S2W_SEED: the seed route's sweep_finish_kernel, which resets the wave counter.
+#define S2W_WORD(j0, lg, p0, p1) ((2 + (j0)) | ((lg) << 8) | ((p0) << 12) | ((p1) << 20))
+#define S2W_J0(sp) (((sp) & 0xff) - 2)
+#define S2W_LG(sp) (((sp) >> 8) & 3)
+#define S2W_P0(sp) (((sp) >> 12) & 31)
+#define S2W_P1(sp) (((sp) >> 20) & 31)
+#define S2W_SEED (1 << 28)
 __host__ __device__ inline int s2_nkc_of(int jb, int n) {
     const int v = S2_CPB * (jb + 1), lim = (n + SW_KC - 1) / SW_KC;
     return v < lim ? v : lim;
 }
-// row block jb goes as two half items: at or above J0, and with rows in its lower half
-__host__ __device__ inline bool s2_halved(int jb, int j0, int n) { return jb >= j0 && n - S2_ROWS * jb > S2_ROWS / 2; }
-__host__ __device__ inline int s2_nhalved(int nrb, int j0, int n) {
+// items of row block jb: 2^lg at or above J0, fewer where its rows end sooner (lg = 1: two halves if it has rows in its
+// lower half), one (a whole item) otherwise
+__host__ __device__ inline int s2_nparts(int jb, int j0, int n, int lg) {
+    if (jb < j0 || lg == 0) return 1;
+    const int per = S2_ROWS >> lg, c = (n - S2_ROWS * jb + per - 1) / per;
+    return c > (1 << lg) ? (1 << lg) : (c < 1 ? 1 : c);
+}
+// items of one candidate block
+__host__ __device__ inline int s2_nitems(int nrb, int j0, int n, int lg) {
     int c = 0;
-    for (int jb = j0 < 0 ? 0 : j0; jb < nrb; ++jb) c += s2_halved(jb, j0, n) ? 1 : 0;
+    for (int jb = 0; jb < nrb; ++jb) c += s2_nparts(jb, j0, n, lg);
     return c;
 }
-// Row item idx of nrb + s2_nhalved(..), heaviest first by the cost model: the merge of two descending runs -- the row
-// blocks >= J0 from the last down (their halves, h = 1 first: its diagonal tiles are the fuller ones; a last block
-// without a lower half as one item of four-pair tiles) and the whole row blocks below J0.  h = -1: a whole item.
-__host__ __device__ inline void s2_row_item(int idx, int nrb, int j0, int n, int& jb, int& h) {
-    int hj = nrb - 1, hh = 1, wj = (j0 < nrb ? j0 : nrb) - 1;
+// cost of a tile of an item of 8 >> lg pairs, for the order of the items (lg 0, 1: S2_WHOLE_COST, S2_HALF_COST)
+__host__ __device__ inline int s2_part_cost(int lg) { return lg == 0 ? S2_WHOLE_COST : lg == 1 ? S2_HALF_COST : lg == 2 ? 5 : 4; }
+// Row item idx of s2_nitems(..), heaviest first by the cost model: the merge of two descending runs -- the row
+// blocks >= J0 from the last down (their parts, the last first: its diagonal tiles are the fuller ones; a last block
+// with the rows of one part only as one whole item) and the whole row blocks below J0.  h = -1: a whole item.
+__host__ __device__ inline void s2_row_item(int idx, int nrb, int j0, int n, int lg, int& jb, int& h) {
+    int hj = nrb - 1, hh = hj >= 0 ? s2_nparts(hj, j0, n, lg) - 1 : 0, wj = (j0 < nrb ? j0 : nrb) - 1;
+    const int pc = s2_part_cost(lg);
     for (int i = 0;; ++i) {
-        if (hj >= j0 && (wj < 0 || S2_HALF_COST * s2_nkc_of(hj, n) >= S2_WHOLE_COST * s2_nkc_of(wj, n))) {
-            const bool two = s2_halved(hj, j0, n);
-            if (i == idx) { jb = hj; h = two ? hh : -1; return; }
-            if (two && hh == 1) hh = 0; else { --hj; hh = 1; }
+        if (hj >= j0 && (wj < 0 || pc * s2_nkc_of(hj, n) >= S2_WHOLE_COST * s2_nkc_of(wj, n))) {
+            const int np = s2_nparts(hj, j0, n, lg);
+            if (i == idx) { jb = hj; h = np > 1 ? hh : -1; return; }
+            if (hh > 0) --hh; else { --hj; hh = hj >= 0 ? s2_nparts(hj, j0, n, lg) - 1 : 0; }
         } else {
             if (i == idx || wj < 0) { jb = wj < 0 ? 0 : wj; h = -1; return; }    // (wj < 0: idx past the last item)
             --wj;
@@ -235,6 +271,16 @@ __device__ __forceinline__ double s2_q_gather(const double (&qr)[4], int lane) {
     qs += __shfl_xor(qs, 16);
     qs += __shfl_xor(qs, 32);
     return qs;
+}
+// Second wave (p0 = K > 0): tau_1 = the smallest utility the first wave's seeds found; the seed at `pos` is left alone
+// if its bound says it can neither win nor tie.  bmin lies behind the two row-block share tables that start at sp_q.
+// Uniform over the workgroup, before its first barrier.
+__device__ __forceinline__ bool s2_wave_skip(const SweepArgs& a, int nrb, int p0, long long pos) {
+    if (p0 == 0) return false;
+    const double* bmin = a.sp_q + 2ll * S2_SPLIT_MAX * SW_CAND * nrb;
+    double tau = INFINITY;
+    for (int i = 0; i < p0; ++i) tau = fmin(tau, a.part_u[a.blk_list[i]]);       // (fmin: as prune_select_kernel)
+    return !(bmin[a.blk_list[pos]] <= tau);
 }
 
 // which form of the feeder loop an instantiation gets (see the feeder role)
@@ -283,12 +329,22 @@ __global__ __launch_bounds__(S2_THREADS, 1) void sweep2_kernel(SweepArgs a) {
     // variables: the full sweep's instantiation reads a.blk_begin / a.blk_end where it always did -- loaded once at
     // the top instead, hipcc allocated the feeders' scalars differently.)
     long long lst_end = 0;
+    [[maybe_unused]] int wv_n = 0;                // RHALF: positions of this seed wave
     if constexpr (LIST) {
         lst_end = *a.blk_count;
         if (lst_end <= a.list_lo || lst_end > a.list_hi) return;    // (the whole grid: another launch has this count)
         long long nwg = a.split ? lst_end * ((a.n + S2_ROWS - 1) / S2_ROWS) : lst_end;
-        if constexpr (RHALF) nwg += lst_end * s2_nhalved((a.n + S2_ROWS - 1) / S2_ROWS, a.split - 2, a.n);
+        if constexpr (RHALF) {
+            // a seed wave: the positions [P0, P1) below the count, each with its row items
+            const int p0 = S2W_P0(a.split), p1 = S2W_P1(a.split);
+            wv_n = (int)((lst_end < p1 ? lst_end : p1) - p0);
+            if (wv_n <= 0) return;
+            nwg = (long long)wv_n * s2_nitems((a.n + S2_ROWS - 1) / S2_ROWS, S2W_J0(a.split), a.n, S2W_LG(a.split));
+        }
         if ((long long)blockIdx.x >= nwg) return;                   // (before the first barrier, the whole workgroup)
+        if constexpr (RHALF) {
+            if (s2_wave_skip(a, (a.n + S2_ROWS - 1) / S2_ROWS, S2W_P0(a.split), S2W_P0(a.split) + (int)blockIdx.x % wv_n)) return;
+        }
     }
 #define S2_BLK_BEGIN (LIST ? 0ll : a.blk_begin)
 #define S2_BLK_END (LIST ? lst_end : a.blk_end)
@@ -318,17 +374,20 @@ __global__ __launch_bounds__(S2_THREADS, 1) void sweep2_kernel(SweepArgs a) {
     // Split mode (short last round / small launches): ONE (candidate block, row block) item,
     // heaviest row blocks first; the shares go to sp_q / sp_mu and sweep_finish_kernel.
     int jb_lo = 0, jb_hi = nrb2;
-    int rh = -1;                                  // RHALF: half h of row block jb_lo (pairs [4 h, 4 h + 4)); -1: a whole item
+    int rh = -1;                                  // RHALF: part h of row block jb_lo (pairs [pp h, pp h + pp)); -1: a whole item
     long long blk0 = S2_BLK_BEGIN + blockIdx.x, blk_step = gridDim.x;
     if (a.split) {
-        const int nsplit = (int)(S2_BLK_END - S2_BLK_BEGIN);
+        const int nsplit = RHALF ? wv_n : (int)(S2_BLK_END - S2_BLK_BEGIN);
         blk0 = S2_BLK_BEGIN + (int)blockIdx.x % nsplit;
-        if constexpr (RHALF) s2_row_item((int)blockIdx.x / nsplit, nrb2, a.split - 2, a.n, jb_lo, rh);
-        else jb_lo = nrb2 - 1 - (int)blockIdx.x / nsplit;
+        if constexpr (RHALF) {
+            blk0 += S2W_P0(a.split);
+            s2_row_item((int)blockIdx.x / nsplit, nrb2, S2W_J0(a.split), a.n, S2W_LG(a.split), jb_lo, rh);
+        } else jb_lo = nrb2 - 1 - (int)blockIdx.x / nsplit;
         jb_hi = jb_lo + 1;
         blk_step = S2_BLK_END;
     }
-    const int rsh = rh > 0 ? S2_NP / 2 : 0;       // RHALF: first sub-block pair of this item
+    const int rpp = RHALF ? S2_NP >> S2W_LG(a.split) : S2_NP;     // RHALF: sub-block pairs of a part item (4, 2 or 1)
+    const int rsh = rh > 0 ? rh * rpp : 0;        // RHALF: first sub-block pair of this item
     auto successor = [&](int& jb, int& kc, long long& blk) {
         ++kc;
         if (kc >= nkc_of(jb)) { ++jb; kc = 0; }
@@ -402,7 +461,10 @@ __global__ __launch_bounds__(S2_THREADS, 1) void sweep2_kernel(SweepArgs a) {
                     if constexpr (RHALF) p0 -= rsh;     // (a half item's pairs sit in pieces 0 .. 3 and acc[0 .. 7])
                     if (p0 < 0) p0 = 0;
                     int p1 = (a.n - S2_ROWS * jb + 31) >> 5;
-                    if constexpr (RHALF) p1 -= rsh;
+                    if constexpr (RHALF) {
+                        p1 -= rsh;
+                        if (rh >= 0 && p1 > rpp) p1 = rpp;      // (a one-pair item runs the two-pair body: its second pair is off)
+                    }
                     if (p1 > NP) p1 = NP;
 #pragma unroll
                     for (int pr = 0; pr < NPA; ++pr) {
@@ -467,10 +529,16 @@ __global__ __launch_bounds__(S2_THREADS, 1) void sweep2_kernel(SweepArgs a) {
                     // a half item: its straight tiles with the four-pair body (rows past the end are zero in the
                     // packed factor), its diagonal tiles with the predicated four-pair body; kc == nkc after them, and
                     // none of the loops below runs.  (Plain loops in sequence, as there.)
-                    const int nhalf4 = rh >= 0 ? ndiag0 : 0;
+                    const int nhalf4 = (rh >= 0 && rpp == 4) ? ndiag0 : 0;
                     for (; kc < nhalf4; ++kc) do_tile_n(std::false_type{}, std::integral_constant<int, 4>{});
-                    const int nhalfp = rh >= 0 ? nkc : 0;
+                    const int nhalfp = (rh >= 0 && rpp == 4) ? nkc : 0;
                     for (; kc < nhalfp; ++kc) do_tile_n(std::true_type{}, std::integral_constant<int, 4>{});
+                    // a two-pair item: the same with the two-pair bodies on acc[0 .. 3]; a one-pair item: every tile
+                    // with the predicated two-pair body, whose second pair p1 = 1 switches off
+                    const int npair2 = (rh >= 0 && rpp == 2) ? ndiag0 : 0;
+                    for (; kc < npair2; ++kc) do_tile_n(std::false_type{}, std::integral_constant<int, 2>{});
+                    const int npair2p = (rh >= 0 && rpp <= 2) ? nkc : 0;
+                    for (; kc < npair2p; ++kc) do_tile_n(std::true_type{}, std::integral_constant<int, 2>{});
                 }
                 const int nstraight = (a.n - S2_ROWS * jb >= S2_ROWS) ? ndiag0 : 0;
                 for (; kc < nstraight; ++kc) do_tile(std::false_type{});
@@ -724,7 +792,7 @@ __global__ __launch_bounds__(S2_THREADS, 1) void sweep2_kernel(SweepArgs a) {
                 }
                 if constexpr (RHALF) {
                     if (rh >= 0) {
-                        // the fold's inputs instead of a share (acc[8 .. 15] are zero: qr is the chain over s = 0 .. 7);
+                        // the fold's inputs instead of a share (acc[2 pp ..] are zero: qr is the chain over s = 0 .. 2 pp - 1);
                         // [16-byte piece][matrix thread]: a wavefront's store is 1 KiB in one piece
                         double* item = s2_fold_item(a.sp_q, nrb2, a.blk_end, blk0, jb);
                         if (rh == 0) {
@@ -733,12 +801,15 @@ __global__ __launch_bounds__(S2_THREADS, 1) void sweep2_kernel(SweepArgs a) {
                             v0.x = qr[0]; v0.y = qr[1]; v1.x = qr[2]; v1.y = qr[3];
                             P[0] = v0; P[256] = v1;
                         } else {
-                            f64x2* A = (f64x2*)(item + S2_HQ_PRE) + t;
+                            // (sub-block s of the whole item at piece pair s - 2: S2_HQ_ACC)
+                            f64x2* A = (f64x2*)(item + S2_HQ_PRE) + (2 * (2 * rsh - 2)) * 256 + t;
 #pragma unroll
                             for (int s_ = 0; s_ < NP; ++s_) {
-                                f64x2 v0, v1;
-                                v0.x = acc[s_][0]; v0.y = acc[s_][1]; v1.x = acc[s_][2]; v1.y = acc[s_][3];
-                                A[(2 * s_) * 256] = v0; A[(2 * s_ + 1) * 256] = v1;
+                                if (s_ < 2 * rpp) {
+                                    f64x2 v0, v1;
+                                    v0.x = acc[s_][0]; v0.y = acc[s_][1]; v1.x = acc[s_][2]; v1.y = acc[s_][3];
+                                    A[(2 * s_) * 256] = v0; A[(2 * s_ + 1) * 256] = v1;
+                                }
                             }
                         }
                     }
@@ -957,12 +1028,13 @@ __global__ __launch_bounds__(S2_THREADS, 1) void sweep2_kernel(SweepArgs a) {
             double* dst = Aring + slot * S2_TILE + hw_s * 128;
             const unsigned toffs = tile_off(jb, kc);
             if constexpr (RHALF) {
-                // a half item: pieces 4 h .. 4 h + 3 of the image into pieces 0 .. 3 of the slot
+                // a part item: pieces pp h .. pp h + pp - 1 of the image into pieces 0 .. pp - 1 of the slot
                 if (rh >= 0) {
 #pragma unroll
                     for (int q = 0; q < 4; ++q)
-                        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_w, (lds_void*)(dst + q * 512), 16, (unsigned)lane * 16u,
-                                                                 toffs + (unsigned)((q + rsh) * 4096) + (unsigned)hw_s * 1024u, 0, 0);
+                        if (q < rpp)
+                            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_w, (lds_void*)(dst + q * 512), 16, (unsigned)lane * 16u,
+                                                                     toffs + (unsigned)((q + rsh) * 4096) + (unsigned)hw_s * 1024u, 0, 0);
                     return;
                 }
             }
@@ -1078,12 +1150,13 @@ __global__ __launch_bounds__(S2_THREADS, 1) void sweep2_kernel(SweepArgs a) {
             double* dst = Aring + slot * S2_TILE + hw_s * 128;
             const unsigned toffs = tile_off(jb, kc);
             if constexpr (RHALF) {
-                // a half item: pieces 4 h .. 4 h + 3 of the image into pieces 0 .. 3 of the slot
+                // a part item: pieces pp h .. pp h + pp - 1 of the image into pieces 0 .. pp - 1 of the slot
                 if (rh >= 0) {
 #pragma unroll
                     for (int q = 0; q < 4; ++q)
-                        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_w, (lds_void*)(dst + q * 512), 16, (unsigned)lane * 16u,
-                                                                 toffs + (unsigned)((q + rsh) * 4096) + (unsigned)hw_s * 1024u, 0, 0);
+                        if (q < rpp)
+                            __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_w, (lds_void*)(dst + q * 512), 16, (unsigned)lane * 16u,
+                                                                     toffs + (unsigned)((q + rsh) * 4096) + (unsigned)hw_s * 1024u, 0, 0);
                     return;
                 }
             }
@@ -1170,10 +1243,15 @@ __global__ __launch_bounds__(S2_THREADS, 1) void sweep2_kernel(SweepArgs a) {
 __global__ __launch_bounds__(64) void sweep_finish_kernel(SweepArgs a) {
     const int c = threadIdx.x;
     long long blk = a.blk_begin + blockIdx.x;
+    const int pos = S2W_P0(a.split) + (int)blockIdx.x;        // (a seed wave starts at list position P0; 0 otherwise)
     if (a.blk_list) {                             // pruned sweep: the split launch's blocks come from the device list
         const long long cnt = *a.blk_count;
-        if (cnt <= a.list_lo || cnt > a.list_hi || (long long)blockIdx.x >= cnt) return;
-        blk = a.blk_list[blockIdx.x];
+        // (the seed route's first wave: no second-wave seed swept yet -- the word behind the counters the select steps write)
+        if ((a.split & S2W_SEED) && pos == 0 && c == 0) ((long long*)a.blk_count)[4] = 0;
+        if (cnt <= a.list_lo || cnt > a.list_hi || pos >= cnt) return;
+        if (s2_wave_skip(a, a.nrb, S2W_P0(a.split), pos)) return;
+        if (S2W_P0(a.split) > 0 && c == 0) atomicAdd((unsigned long long*)a.blk_count + 4, 1ull);
+        blk = a.blk_list[pos];
     }
     const long long crow = blk * SW_CAND + c;
     double bu = INFINITY;
@@ -1193,7 +1271,7 @@ __global__ __launch_bounds__(64) void sweep_finish_kernel(SweepArgs a) {
             }
         }
         if (a.mask && a.mask[crow] == 0) adm = false;
-        const long long e0 = ((long long)blockIdx.x * SW_CAND + c) * a.nrb;
+        const long long e0 = ((long long)pos * SW_CAND + c) * a.nrb;
         double q = 0.0, mup = 0.0;
         for (int ib = 0; ib < a.nrb; ++ib) { q += a.sp_q[e0 + ib]; mup += a.sp_mu[e0 + ib]; }
         double mu = mup + a.mean;
@@ -1222,8 +1300,10 @@ __global__ __launch_bounds__(64) void sweep_finish_kernel(SweepArgs a) {
 // item's order, and writes the share the whole item would have written.  Sized for the cap; leaves on the device count.
 __global__ __launch_bounds__(256) void sweep_fold_kernel(SweepArgs a) {
     const long long cnt = *a.blk_count;
-    const int pos = (int)blockIdx.x / a.nrb, jb = (int)blockIdx.x % a.nrb;
-    if (cnt <= a.list_lo || cnt > a.list_hi || pos >= cnt || !s2_halved(jb, a.split - 2, a.n)) return;
+    const int pos = S2W_P0(a.split) + (int)blockIdx.x / a.nrb, jb = (int)blockIdx.x % a.nrb;
+    const int lg = S2W_LG(a.split), np = s2_nparts(jb, S2W_J0(a.split), a.n, lg);
+    if (cnt <= a.list_lo || cnt > a.list_hi || pos >= cnt || np < 2) return;
+    if (s2_wave_skip(a, a.nrb, S2W_P0(a.split), pos)) return;
     const int t = threadIdx.x, lane = t & 63, w = t >> 6;
     const double* base = s2_fold_item(a.sp_q, a.nrb, a.blk_end, pos, jb);
     const f64x2* P = (const f64x2*)base + t;
@@ -1233,8 +1313,9 @@ __global__ __launch_bounds__(256) void sweep_fold_kernel(SweepArgs a) {
         const f64x2 v0 = P[0], v1 = P[256];
         qr[0] = v0.x; qr[1] = v0.y; qr[2] = v1.x; qr[3] = v1.y;
     }
-#pragma unroll
-    for (int s_ = 0; s_ < S2_NP; ++s_) {
+    // sub-blocks 2 pp .. 2 pp np - 1 of the whole item, the parts after the first (sub-block s at piece pair s - 2)
+    const int s_lo = 2 * (S2_NP >> lg) - 2, s_hi = 2 * (S2_NP >> lg) * np - 2;
+    for (int s_ = s_lo; s_ < s_hi; ++s_) {
         const f64x2 v0 = A[(2 * s_) * 256], v1 = A[(2 * s_ + 1) * 256];
         qr[0] = fma(v0.x, v0.x, qr[0]);
         qr[1] = fma(v0.y, v0.y, qr[1]);
@@ -1262,9 +1343,10 @@ __global__ __launch_bounds__(256) void seed_park_kernel(SweepArgs a) {
     constexpr int NKK = SW_KC / 4;
     __shared__ double Etab[APGP_EXP_TAB_N];
     const int ngrp = a.ncache / SP_NCH;           // (ncache is a multiple of S2_CPB)
-    const int pos = (int)blockIdx.x / ngrp, kc0 = (int)blockIdx.x % ngrp * SP_NCH;
+    const int pos = S2W_P0(a.split) + (int)blockIdx.x / ngrp, kc0 = (int)blockIdx.x % ngrp * SP_NCH;
     const long long cnt = *a.blk_count;
     if (cnt <= a.list_lo || cnt > a.list_hi || pos >= cnt) return;
+    if (s2_wave_skip(a, a.nrb, S2W_P0(a.split), pos)) return;
     apgp_exp_tab_load(Etab);
     __syncthreads();
     const int ht = threadIdx.x, lane = ht & 63, hw = ht >> 6;
@@ -1414,23 +1496,46 @@ extern "C" int apgp_set_seed_park(int v) { return __atomic_exchange_n(&g_seed_pa
 
 extern "C" int apgp_get_seed_park(void) { return __atomic_load_n(&g_seed_park, __ATOMIC_RELAXED); }
 
+// ---- how many of the PR_SEED seeds the first seed wave sweeps ----
+// -1: the rule (S2_SEED_FIRST where the split seed route applies, all of them elsewhere); 1 .. 16: that many (16: one wave)
+#define S2_SEED_FIRST 4
+static int g_seed_first = -1;
+
+extern "C" int apgp_set_seed_first(int v) {
+    return __atomic_exchange_n(&g_seed_first, v < 1 ? -1 : (v > 16 ? 16 : v), __ATOMIC_RELAXED);
+}
+
+extern "C" int apgp_get_seed_first(void) { return __atomic_load_n(&g_seed_first, __ATOMIC_RELAXED); }
+
+// ---- sub-block pairs per item of a split row block of the seed launches ----
+// -1: the rule (seed_plan); 8 / 4 / 2 / 1: whole items, halves, two-pair, one-pair items
+static int g_seed_parts = -1;
+
+extern "C" int apgp_set_seed_parts(int v) {
+    return __atomic_exchange_n(&g_seed_parts, (v == 8 || v == 4 || v == 2 || v == 1) ? v : -1, __ATOMIC_RELAXED);
+}
+
+extern "C" int apgp_get_seed_parts(void) { return __atomic_load_n(&g_seed_parts, __ATOMIC_RELAXED); }
+
 // Time of a launch of cap x (row items for J0) workgroups on SW_GRID CUs, one at a time per CU, in the order the
 // kernel numbers them (s2_row_item: heaviest first), each to the CU that falls free first; in units of the cost model
 // (S2_WHOLE_COST per tile of a whole item, S2_HALF_COST per tile of a half item or of a last block of <= 128 rows).
 // `parked`: the launch reads the chunks left of an item's diagonal from the parked stream; a re-read tile and a
 // generating (diagonal) tile then have prices of their own (S2P_*), in units that only compare with each other.
-static long long seed_launch_cost(int nrb, int cap, int n, int j0, bool parked) {
+// `lg`: a split row block goes as 2^lg parts; a part of two pairs or of one has its own prices on the parked route.
+static long long seed_launch_cost(int nrb, int cap, int n, int j0, int lg, bool parked) {
+    static const int gen[4] = {S2P_WHOLE_GEN, S2P_HALF_GEN, S2P_PAIR2_GEN, S2P_PAIR1_GEN};
+    static const int park[4] = {S2P_WHOLE_PARK, S2P_HALF_PARK, S2P_PAIR2_PARK, S2P_PAIR1_PARK};
     long long load[SW_GRID] = {0};
-    const int nitem = nrb + s2_nhalved(nrb, j0, n);
+    const int nitem = s2_nitems(nrb, j0, n, lg);
     long long last = 0;
     for (int i = 0; i < nitem; ++i) {
         int jb = 0, h = -1;
-        s2_row_item(i, nrb, j0, n, jb, h);
-        const bool light = h >= 0 || n - S2_ROWS * jb <= S2_ROWS / 2;
+        s2_row_item(i, nrb, j0, n, lg, jb, h);
+        const int kind = h >= 0 ? lg : (n - S2_ROWS * jb <= S2_ROWS / 2 ? 1 : 0);     // (a last block of <= 128 rows: a half's prices)
         const int nkc = s2_nkc_of(jb, n), nre = S2_CPB * jb < nkc ? S2_CPB * jb : nkc;
-        const long long c = parked ? (long long)(light ? S2P_HALF_GEN : S2P_WHOLE_GEN) * (nkc - nre) +
-                                         (long long)(light ? S2P_HALF_PARK : S2P_WHOLE_PARK) * nre
-                                   : (long long)(light ? S2_HALF_COST : S2_WHOLE_COST) * nkc;
+        const long long c = parked ? (long long)gen[kind] * (nkc - nre) + (long long)park[kind] * nre
+                                   : (long long)s2_part_cost(kind) * nkc;
         for (int k = 0; k < cap; ++k) {
             int best = 0;
             for (int q = 1; q < SW_GRID; ++q)
@@ -1444,25 +1549,43 @@ static long long seed_launch_cost(int nrb, int cap, int n, int j0, bool parked) 
 
 // The rule: J0 of {0, nrb / 2, nrb} with the shortest modelled launch (ties: the fewest items).  Remembered for the last
 // (nrb, cap, n): a fit's calls repeat them.
-static int seed_j0(int nrb, int cap, int n, bool parked) {
-    const int v = apgp_get_seed_rowsplit();
-    if (v >= 0) return v < nrb ? v : nrb;
+// The parts of a split row block follow the same rule: halves, or (parked route) two-pair items where the model says
+// they shorten the launch; one-pair items only when forced.  Remembered for the last few (nrb, blocks, n, parked, forced
+// values): a call's two waves and a fit's calls repeat them.
+struct SeedPlan { int j0, lg; long long cost; };
+static SeedPlan seed_plan(int nrb, int cap, int n, bool parked) {
+    const int v = apgp_get_seed_rowsplit(), fp = apgp_get_seed_parts();
+    const int flg = fp == 8 ? 0 : fp == 4 ? 1 : fp == 2 ? 2 : fp == 1 ? 3 : -1;
+    struct Memo { int nrb, cap, n, parked, v, flg; SeedPlan plan; };
     static std::mutex mu;
-    static int k_nrb = -1, k_cap = -1, k_n = -1, k_parked = -1, k_j0 = 0;
+    static Memo memo[8];
+    static int nmemo = 0, next = 0;
     std::lock_guard<std::mutex> g(mu);
-    if (k_nrb != nrb || k_cap != cap || k_n != n || k_parked != (int)parked) {
-        int best = nrb;
-        long long best_c = seed_launch_cost(nrb, cap, n, nrb, parked);
-        for (int j0 : {nrb / 2, 0}) {
-            const long long c = seed_launch_cost(nrb, cap, n, j0, parked);
-            if (c < best_c) { best = j0; best_c = c; }
-        }
-        k_nrb = nrb; k_cap = cap; k_n = n; k_parked = (int)parked; k_j0 = best;
+    for (int i = 0; i < nmemo; ++i) {
+        const Memo& e = memo[i];
+        if (e.nrb == nrb && e.cap == cap && e.n == n && e.parked == (int)parked && e.v == v && e.flg == flg) return e.plan;
     }
-    return k_j0;
+    SeedPlan best = {nrb, 1, 0};
+    long long best_c = -1;
+    for (int lg = 1; lg <= (parked ? 2 : 1); ++lg) {
+        if (flg >= 0 && lg != 1) continue;         // (forced parts: one pass, with them)
+        const int l = flg >= 0 ? flg : lg;
+        for (int j0 : {nrb, nrb / 2, 0}) {
+            if (v >= 0 && j0 != nrb) continue;     // (forced J0: one pass, with it)
+            const int j = v >= 0 ? (v < nrb ? v : nrb) : j0;
+            if (lg > 1 && j == nrb) continue;
+            const long long c = seed_launch_cost(nrb, cap, n, j, l, parked);
+            if (best_c < 0 || c < best_c) { best = {j, l, c}; best_c = c; }
+        }
+    }
+    memo[next] = {nrb, cap, n, (int)parked, v, flg, best};
+    next = (next + 1) % 8;
+    if (nmemo < 8) ++nmemo;
+    return best;
 }
 
-// `rowsplit` (the seed launch): row blocks from seed_j0 on go as two row-half items each, folded by sweep_fold_kernel.
+// `rowsplit` (the seed launches): row blocks from seed_plan's J0 on go as 2, 4 or 8 row-part items each, folded by
+// sweep_fold_kernel, and the seeds go in two waves.
 template <int DPAD>
 static void launch_sweep_list(const SweepArgs& a0, hipStream_t s, bool solve, const long long* list,
                               const long long* count, long long max_count, long long cap, bool rowsplit = false) {
@@ -1482,26 +1605,48 @@ static void launch_sweep_list(const SweepArgs& a0, hipStream_t s, bool solve, co
         // launch later on this stream (slots >= the seed count), and the launch goes through the RHALF instantiation
         // whether a row block is halved or not (it runs whole items with rh = -1)
         const bool parked = rowsplit && b.lin_coef == 0.0 && apgp_get_seed_park() != 0;
-        const int j0 = rowsplit ? seed_j0(nrb2, (int)cap, b.n, parked) : nrb2;
-        const int nhalf = s2_nhalved(nrb2, j0, b.n);
-        if (parked) {
-            b.ncache = (int)s2_ncache(b.n);
-            b.kslot_bytes = (unsigned)(b.ncache * (SW_BCH * 8));
-            hipLaunchKernelGGL(seed_park_kernel<DPAD>, dim3((unsigned)(cap * (b.ncache / SP_NCH))), dim3(256), 0, s, b);
+        // Two seed waves (pure squared-exponential kernels): the first K seeds, then -- each workgroup on its own, from
+        // tau_1 of the first wave and the seed's bound (s2_wave_skip) -- those of the other seeds that could still win or
+        // tie.  At the benchmark's sizes none can: the seeds' bounds lie further apart than the bound's slack, and the
+        // first wave is all the exact work tau needs.  Both waves are the same four launches over their positions.
+        int first = (int)cap;
+        if (rowsplit && b.lin_coef == 0.0) {
+            const int v = apgp_get_seed_first();
+            // the rule: S2_SEED_FIRST where the model says the shorter first wave pays for the second one's launches
+            // (from N ~ 2048 on; below, 16 blocks' items are about one per CU and a wave lasts its heaviest item either
+            // way).  By the parked route's prices with the stream on or off: the same seeds are swept.
+            first = v > 0 ? v : S2_SEED_FIRST;
+            if (first > (int)cap) first = (int)cap;
+            if (v <= 0 && first < (int)cap &&
+                seed_plan(nrb2, (int)cap, b.n, true).cost - seed_plan(nrb2, first, b.n, true).cost <= S2P_WAVE2)
+                first = (int)cap;
         }
-        if (nhalf > 0 || parked) {
-            const size_t lds = s2_lds_bytes<DPAD>();
-            const unsigned grid = (unsigned)(cap * (nrb2 + nhalf));
-            b.split = 2 + j0;
-            if (b.lin_coef != 0.0)
-                hipLaunchKernelGGL((sweep2_kernel<DPAD, true, 0, true, true>), dim3(grid), dim3(S2_THREADS), lds, s, b);
-            else
-                hipLaunchKernelGGL((sweep2_kernel<DPAD, false, 0, true, true>), dim3(grid), dim3(S2_THREADS), lds, s, b);
-            if (nhalf > 0) hipLaunchKernelGGL(sweep_fold_kernel, dim3((unsigned)(cap * nrb2)), dim3(256), 0, s, b);
-        } else {
-            s2_launch<DPAD, true>(b, s, solve, (unsigned)(cap * nrb2));
+        for (int wave = 0; wave < (first < (int)cap ? 2 : 1); ++wave) {
+            const int p0 = wave ? first : 0, p1 = wave ? (int)cap : first, nw = p1 - p0;
+            const SeedPlan plan = rowsplit ? seed_plan(nrb2, nw, b.n, parked) : SeedPlan{nrb2, 0, 0};
+            const int nitem = s2_nitems(nrb2, plan.j0, b.n, plan.lg);
+            b.split = S2W_WORD(plan.j0, plan.lg, p0, p1);
+            if (parked) {
+                b.ncache = (int)s2_ncache(b.n);
+                b.kslot_bytes = (unsigned)(b.ncache * (SW_BCH * 8));
+                hipLaunchKernelGGL(seed_park_kernel<DPAD>, dim3((unsigned)(nw * (b.ncache / SP_NCH))), dim3(256), 0, s, b);
+            }
+            if (nitem > nrb2 || parked || first < (int)cap) {
+                const size_t lds = s2_lds_bytes<DPAD>();
+                const unsigned grid = (unsigned)(nw * nitem);
+                if (b.lin_coef != 0.0)
+                    hipLaunchKernelGGL((sweep2_kernel<DPAD, true, 0, true, true>), dim3(grid), dim3(S2_THREADS), lds, s, b);
+                else
+                    hipLaunchKernelGGL((sweep2_kernel<DPAD, false, 0, true, true>), dim3(grid), dim3(S2_THREADS), lds, s, b);
+                if (nitem > nrb2) hipLaunchKernelGGL(sweep_fold_kernel, dim3((unsigned)(nw * nrb2)), dim3(256), 0, s, b);
+            } else {
+                b.split = 1;
+                s2_launch<DPAD, true>(b, s, solve, (unsigned)(cap * nrb2));
+            }
+            SweepArgs f = b;
+            f.split = rowsplit ? (S2W_WORD(plan.j0, plan.lg, p0, p1) | S2W_SEED) : 1;
+            hipLaunchKernelGGL(sweep_finish_kernel, dim3((unsigned)nw), dim3(64), 0, s, f);
         }
-        hipLaunchKernelGGL(sweep_finish_kernel, dim3((unsigned)cap), dim3(64), 0, s, b);
     }
     if (!can_split || max_count > cap) {
         a.split = 0;
@@ -1531,7 +1676,9 @@ static void launch_sweep_list(const SweepArgs& a0, hipStream_t s, bool solve, co
 #define PR_THREADS 256
 #define PR_CPT 2            // candidates per thread: two blocks per wavefront, half the LDS reads per kernel value
 #define PR_ROWS 128         // training rows per LDS tile (divides the packed stream's 512-row padding)
-#define PR_SEED 16          // seed blocks: one split launch of 16 x nrb workgroups covers the chip from N = 4096 on
+#define PR_SEED 16          // seed blocks: the SELECTION -- tau is the minimum over all 16, and all 16 stay out of the lists;
+                            // the first wave sweeps K of them (apgp_set_seed_first), the second those of the rest
+                            // whose bound does not lie above the first wave's tau_1 (launch_sweep_list)
 // candidates below which the full sweep is taken (apgp_set_sweep_prune(1)).  The pruned call costs about one block's
 // time whatever m is (the seeds), the full sweep m N^2.  Re-measured with the fp32 bound pass (docs/experiments.md,
 // round 9): pruned / full = 0.95 at m = 4096 and 0.29 at 16384 for N = 4096; 0.94 at 16384 and 0.27 at 65536 for
@@ -2210,6 +2357,8 @@ static int launch_pruned(const SweepArgs& a, hipStream_t s, bool solve, void* pa
     launch_bound<DPAD>(p, s, coarse);
     hipLaunchKernelGGL(prune_seed_kernel, dim3(1), dim3(1024), 0, s, coarse ? (const double*)p.est : (const double*)bmin, ncb,
                        seeds, counts);
+    // (counts[4], the second-wave seeds swept: the split seed route's first finish resets it; no waves elsewhere)
+    if (solve || s2_nrb(a.n) < 2 || a.sp_q == NULL) (void)hipMemsetAsync(counts + 4, 0, sizeof(long long), s);
     launch_sweep_list<DPAD>(a, s, solve, seeds, counts, ncb < PR_SEED ? ncb : PR_SEED, PR_SEED, true);
     hipLaunchKernelGGL(prune_select_kernel, dim3(1), dim3(1024), 0, s, bmin, ncb, seeds, counts, a.part_u, 0.0, list,
                        counts + 3);
@@ -2226,9 +2375,10 @@ static int launch_pruned(const SweepArgs& a, hipStream_t s, bool solve, void* pa
 // Layout of the caller's scratch (doubles): [2 ncb arg-min partials | slots x ncache x SW_BCH
 // parked operands | 2 x S2_SPLIT_MAX x SW_CAND x nrb row-block shares of the split last round (s2_work_len up to
 // here) | pruned sweep: ncb block bounds bmin | ncb surviving block numbers | PR_SEED seed block numbers | 8 words:
-// seed count, survivor count, bit pattern of tau, blocks the coarse bound kept (list A; list B is written over it) |
-// ncb block minima of the coarse stage's b without slack | PR_SEED x nrb x (S2_HQ_PRE + S2_HQ_ACC) fold inputs of the seed
-// launch's row-half items (from pr_work_len, an even offset: 16-byte accesses; n > S2_ROWS only)]
+// seed count, survivor count, bit pattern of tau, blocks the coarse bound kept (list A; list B is written over it),
+// second-wave seeds swept | ncb block minima of the coarse stage's b without slack | PR_SEED x nrb x (S2_HQ_PRE +
+// S2_HQ_ACC) fold inputs of the seed launches' row-part items (from pr_work_len, an even offset: 16-byte accesses;
+// n > S2_ROWS only)]
 static_assert(S2_PRUNE_WORDS == PR_SEED + 8, "the fold inputs start behind the seed numbers and the counters");
 static inline long long pr_work_len(int64_t m, int64_t n) {       // (sp_q lies 2 S2_SPLIT_MAX SW_CAND nrb before s2_work_len)
     return s2_work_len(m, n) - 2ll * S2_SPLIT_MAX * SW_CAND * s2_nrb(n) + s2_fold_off(s2_nrb(n), pr_ncb(m));

@@ -502,8 +502,16 @@ class GP(GeorgeExtras):
         # workgroup (apgp_set_seed_park; same bits either way): None: the library's process-wide setting (default: on);
         # True / 1: on; False / 0: off
         self.seed_park = None
+        # the 16 seed blocks go in two waves, the first seed_first of them and then those of the rest that could still
+        # win (apgp_set_seed_first; same winner whatever the value): None: the library's process-wide setting (default:
+        # its rule, 4 where the parked seed route applies); -1: the rule; 1 .. 16: that many (16: one wave)
+        self.seed_first = None
+        # sub-block pairs (32 rows) per workgroup of a split row block of the seed launches (apgp_set_seed_parts; same
+        # bits whatever the value): None: the library's process-wide setting (default: its rule); -1: the rule; 8 / 4 / 2 / 1
+        self.seed_parts = None
         self.sweep_prune_stats = False   # True: keep (seed blocks, surviving blocks, bits of tau, blocks the coarse
-        self.last_prune_counts = None     # bound left) of the last pruned sweep here, as a device int64[4] tensor
+        self.last_prune_counts = None     # bound left, second-wave seeds swept) of the last pruned sweep here, as a
+                                          # device int64[5] tensor
         self._computed = False
         self._x = None
         self._yerr2 = 0.0
@@ -1432,6 +1440,8 @@ class GP(GeorgeExtras):
             prune_was = None if self.sweep_prune is None else lib.apgp_set_sweep_prune(int(self.sweep_prune))
             rowsplit_was = None if self.seed_rowsplit is None else lib.apgp_set_seed_rowsplit(int(self.seed_rowsplit))
             park_was = None if self.seed_park is None else lib.apgp_set_seed_park(int(self.seed_park))
+            first_was = None if self.seed_first is None else lib.apgp_set_seed_first(int(self.seed_first))
+            parts_was = None if self.seed_parts is None else lib.apgp_set_seed_parts(int(self.seed_parts))
             try:
                 if use_solve:
                     _lib.check(lib.apgp_acquire_solve_rows(T.data_ptr(), m, int(idx_offset),
@@ -1446,9 +1456,13 @@ class GP(GeorgeExtras):
                     lib.apgp_set_seed_rowsplit(rowsplit_was)
                 if park_was is not None:
                     lib.apgp_set_seed_park(park_was)
+                if first_was is not None:
+                    lib.apgp_set_seed_first(first_was)
+                if parts_was is not None:
+                    lib.apgp_set_seed_parts(parts_was)
             if self.sweep_prune_stats and kind_id != _lib.UTIL_NONE and mu is None and var is None and u is None:
                 off = int(lib.apgp_sweep_prune_counts_offset(m, n))
-                self.last_prune_counts = part[off:off + 4].view(torch.int64).clone()
+                self.last_prune_counts = part[off:off + 5].view(torch.int64).clone()
             if ev is not None:
                 e1 = torch.cuda.Event(enable_timing=True)
                 e1.record()

@@ -379,13 +379,28 @@ int apgp_acquire_solve(const double* T, int64_t m, int64_t idx_offset,
  * region of `part`, and the seed launch's workgroups read the chunks left of their diagonal from there; 0: every
  * workgroup generates every operand it needs, the launch as it was.  The bits do not depend on it.  Pure
  * squared-exponential kernels, inverse form, n > 256; everything else ignores it.  apgp_acquire_work_len is
- * unchanged; APGP_ABI_VERSION stays 8.  */
+ * unchanged; APGP_ABI_VERSION stays 8.
+ * apgp_set_seed_first(v): process-wide switch of the seed step, returns the previous value.  The 16 seed blocks are
+ * swept in two waves: the first K of them, then those of the others whose bound does not lie above the smallest
+ * utility the first wave found (a seed that can neither win nor tie keeps the +inf partial the bound pass wrote).  tau
+ * and the winner do not depend on K.  -1 (default): K = 4 for pure squared-exponential kernels, inverse form, n > 256,
+ * where the library's launch model says two waves are the shorter (from n ~ 2048 on), 16 (one wave, the launches as
+ * they were) elsewhere; 1 .. 16: K = v for those kernels, that form and n > 256.  A fifth int64 behind the four of
+ * apgp_sweep_prune_counts_offset counts the second-wave seeds that were swept.
+ * apgp_set_seed_parts(v): process-wide switch of the seed launches, returns the previous value.  A row block that
+ * apgp_set_seed_rowsplit splits goes as 8 / v workgroups of v sub-block pairs (32 v rows) each: 8: whole, 4: the two
+ * halves, 2 and 1: finer; -1 (default): the library's rule.  The bits do not depend on it.  apgp_acquire_work_len
+ * grew with the fold inputs of the finer parts; APGP_ABI_VERSION stays 8.  */
 int apgp_set_sweep_prune(int v);
 int apgp_get_sweep_prune(void);
 int apgp_set_seed_rowsplit(int v);
 int apgp_get_seed_rowsplit(void);
 int apgp_set_seed_park(int v);
 int apgp_get_seed_park(void);
+int apgp_set_seed_first(int v);
+int apgp_get_seed_first(void);
+int apgp_set_seed_parts(int v);
+int apgp_get_seed_parts(void);
 int64_t apgp_sweep_prune_counts_offset(int64_t m, int64_t n);
 int apgp_sweep_prune_select(const double* bmin, int64_t ncb, const int64_t* seeds, int64_t* counts,
                             double tau, int64_t* list, void* stream);

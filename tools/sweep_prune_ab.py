@@ -56,6 +56,7 @@ def ab(gp, y, T, kind, box, pairs, warmup, on_value):
     return {"off": off, "on": on, "on_over_off": on["median_ms"] / off["median_ms"],
             "blocks": (T.shape[0] + 63) // 64, "seed_blocks": int(c[0]), "surviving_blocks": int(c[1]),
             "coarse_blocks": int(c[3]) if len(c) > 3 else None,
+            "second_wave_seeds_swept": int(c[4]) if len(c) > 4 else None,
             "tau": float(c[2:3].view(np.float64)[0]), "best": [int(res[0][0]), float(res[0][1])]}
 
 
