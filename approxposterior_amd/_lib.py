@@ -25,6 +25,7 @@ NM_MAX_FEV = 1 << 20
 # APGP_NM_STEP_*: the step of one Nelder-Mead iteration in apgp_nm_search's trace
 NM_STEPS = {1: "reflect", 2: "expand", 3: "reflect_exp", 4: "contract_out", 5: "contract_in",
             6: "shrink_out", 7: "shrink_in", 8: "maxfev"}
+PRUNE_ROWS_SPLIT, PRUNE_ROWS_SIGNED = 0, 1   # APGP_PRUNE_ROWS_*: the kind of a coarse-bound row stream
 GMM_EM, GMM_SCORE, GMM_KMEANS = 0, 1, 2
 GMM_MAX_COMP = 16
 IMP_BLOCK = 256        # APGP_IMP_BLOCK: candidates per workgroup pass of apgp_importance_pass
@@ -142,6 +143,16 @@ SIGNATURES = {
                                                _F64, _F64, _P, _P, _P, _P, _P, _P, _P]),
     "apgp_prune_bounds_rows": (ctypes.c_int, [_P, _I64, _P, _I64, _KP, _F64, _I32, ctypes.POINTER(_F64),
                                               ctypes.POINTER(_F64), _P, _F64, _F64, ctypes.c_int, _P, _P, _P]),
+    "apgp_prune_srows_len": (_I64, [_I64, _I32]),
+    "apgp_pack_prune_srows": (ctypes.c_int, [_P, _I64, _KP, _P, _P]),
+    "apgp_acquire_rows2": (ctypes.c_int, [_P, _I64, _I64, _P, _P, _I64, _KP, _F64, _I32,
+                                          ctypes.POINTER(_F64), ctypes.POINTER(_F64), _P,
+                                          _F64, _F64, _P, _P, _P, _P, _P, _P, _I32, _P]),
+    "apgp_acquire_solve_rows2": (ctypes.c_int, [_P, _I64, _I64, _P, _P, _I64, _KP, _F64, _I32,
+                                                ctypes.POINTER(_F64), ctypes.POINTER(_F64), _P,
+                                                _F64, _F64, _P, _P, _P, _P, _P, _P, _I32, _P]),
+    "apgp_prune_bounds_rows2": (ctypes.c_int, [_P, _I64, _P, _I64, _KP, _F64, _I32, ctypes.POINTER(_F64),
+                                               ctypes.POINTER(_F64), _P, _F64, _F64, ctypes.c_int, _P, _P, _I32, _P, _P]),
     "apgp_acquire_fantasy_work_len": (_I64, [_I64]),
     "apgp_acquire_fantasy": (ctypes.c_int, [_P, _I64, _I64, _P, _I64, _KP, _P, _I64, _I32, _P, _I64,
                                             _P, _P, _P, _I32, ctypes.POINTER(_F64), ctypes.POINTER(_F64), _P,

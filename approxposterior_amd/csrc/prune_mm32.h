@@ -74,7 +74,8 @@
 //     partial sum (16 u of sum |alpha| k^, the terms of S32 below) are relative too: with
 //         eta = eta0 + 24 u       (4.1 + 1.01 + 16.1 and room)
 //     |sum alpha_i (k^_i - k_i)| <= (e^eta - 1) sum |alpha_i| k^_i.  The kernel accumulates S32 = sum |alpha_i| k^_i
-//     beside mu32, one v_fmac more per value; summed like mu32 it is below the exact sum by <= 17 u of it and is taken
+//     beside mu32, one v_fmac more per value (none over the sign-sorted stream, SGN below: there S32 is the sum of
+//     |partial sum of mu32|, the same bits); summed like mu32 it is below the exact sum by <= 17 u of it and is taken
 //     times 1 + 2^-16, expm1 times 1 + 2^-20.
 //   * gate: eta <= 2^-8 keeps e^eta - 1 a small multiple of eta (and k^ <= e^eta where a candidate sits on a training
 //     point).  It needs B, which the staging threads carry with the tiles (max over the rows < n; the pre-split stream
@@ -95,7 +96,7 @@
 // A block whose bound came out -inf (gate failed: data far wider than the length scale; or a NaN bound) is left to
 // prune_bound32_kernel<DPAD, true>, launched behind this kernel: the -inf in bmin is the mark, no other scratch.
 // Variants measured: docs/experiments.md, round 13 (the fp32 form), round 17 (what the fp32 MFMA leaves to the vector
-// ALU), round 18 (this form), round 19 (the rows split once per fit).
+// ALU), round 18 (this form), round 19 (the rows split once per fit), round 29 (the rows sorted by alpha's sign).
 #pragma once
 #include <utility>
 
@@ -234,10 +235,146 @@ __global__ __launch_bounds__(PR_THREADS) void pmm_pack_rows_kernel(const double*
     }
 }
 
+// The sign-sorted stream of a fit (apgp_pack_prune_srows): the same tile images and fp32 alphas as the pre-split stream,
+// behind a header of PMM_SHDR bytes (bm2, sal, nrt, 0), with the rows in another order, so that the 16 rows a lane of
+// the bound kernel accumulates -- one half h of one 32-row matrix tile -- carry alphas of ONE sign:
+//   * class P: the rows < n whose alpha is not below 0 (+0 and -0 among them), in their original order; class N: the
+//     rows with alpha < 0, in their original order.  gP = ceil(|P| / 16), gN = ceil(|N| / 16).
+//   * group q < gP holds P's rows 16 q .. 16 q + 15, group gP + q holds N's; group q is half q & 1 of matrix tile q >> 1,
+//     its slot s the tile's row (s & 3) + 8 (s >> 2) + 4 (q & 1): pmm_srow.  nrt = ceil((gP + gN) / 2) matrix tiles hold a
+//     row; the stream has room for pmm_stiles(n) staged tiles, enough for any split of n rows into the two classes.
+//   * every slot without a row is a padding row of the pre-split stream: coordinates and norm 0, the "1" entry 1, alpha 0.
+//   * bm2 is a maximum and has no order.  sal: thread t of the PR_THREADS adds |alpha| of the rows t, t + PR_THREADS, ..
+//     in fp64 in that order, then the wavefront's shuffle tree (xor 32, 16, .. 1), then the wavefronts' sums in order.
+// One workgroup.  A round places PR_THREADS consecutive rows: a row's rank in its class is the class's count before the
+// round, plus the counts of the wavefronts before its own, plus the set bits below its lane in the class's ballot.
+__host__ __device__ inline long long pmm_srow(long long q, int s) {
+    return 32 * (q >> 1) + (s & 3) + 8 * (s >> 2) + 4 * (int)(q & 1);
+}
+__host__ __device__ inline long long pmm_stiles(long long n) {        // ceil(n / 16) + 1 groups at most, two per matrix tile
+    const long long nrt_max = ((n + 15) / 16 + 2) / 2;
+    return (nrt_max + PMM_ROWS / 32 - 1) / (PMM_ROWS / 32);
+}
+#define PMM_SHDR 32
+
+// one row's LDS image and fp32 alpha into their place in a tile of a stream (the statements of pmm_pack_rows_kernel)
+template <int DPAD>
+__device__ __forceinline__ void pmm_put_row(unsigned char* tile, int srow, const float (&pe)[DPAD + 2], float alpha) {
+    using SH = PmmShape<DPAD>;
+    __bf16* xrow = (__bf16*)tile + srow * SH::PITCH;
+    pmm_store_row<DPAD>(xrow, pe, std::make_integer_sequence<int, 2 * SH::NI>{});
+    ((float*)(tile + 16 * SH::XPIECES))[srow] = alpha;
+    *(bf16x8*)(xrow + 16 * SH::NI) = bf16x8{(__bf16)0.0f, (__bf16)0.0f, (__bf16)0.0f, (__bf16)0.0f,
+                                            (__bf16)0.0f, (__bf16)0.0f, (__bf16)0.0f, (__bf16)0.0f};              // the pad
+}
+
+template <int DPAD>
+__global__ __launch_bounds__(PR_THREADS) void pmm_pack_srows_kernel(const double* xs, long long n, unsigned char* rows) {
+    using SH = PmmShape<DPAD>;
+    constexpr int XS = DPAD + 2, NW = PR_THREADS / 64;
+    const double kappa = PR32_KAPPA;
+    __shared__ int wp[2][NW], wn[2][NW];
+    __shared__ double wmax[NW], wsal[NW];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    double cen[DPAD];
+#pragma unroll
+    for (int d = 0; d < DPAD; ++d) cen[d] = xs[d];
+    // |P|
+    int cnt = 0;
+    for (long long i = tid; i < n; i += PR_THREADS) cnt += xs[i * XS + DPAD] < 0.0 ? 0 : 1;
+    for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o);
+    if (lane == 0) wp[0][w] = cnt;
+    __syncthreads();
+    long long np = 0;
+#pragma unroll
+    for (int i = 0; i < NW; ++i) np += wp[0][i];
+    __syncthreads();                                     // (wp[0] is written again in round 0)
+    const long long nn = n - np, gp = (np + 15) / 16, gn = (nn + 15) / 16;
+    unsigned char* img = rows + PMM_SHDR;
+    double sal = 0.0, bm2 = 0.0;
+    long long base_p = 0, base_n = 0;                    // rows of either class before this round
+    const long long nround = (n + PR_THREADS - 1) / PR_THREADS;
+    for (long long rd = 0; rd < nround; ++rd) {
+        const long long i = rd * PR_THREADS + tid;
+        const bool in = i < n;
+        const f64x2* src = (const f64x2*)(xs + (in ? i : 0) * XS);
+        f64x2 pre[XS / 2];
+#pragma unroll
+        for (int j = 0; j < XS / 2; ++j) pre[j] = src[j];
+        const double alpha = pre[DPAD / 2].x;
+        const bool neg = in && alpha < 0.0, pos = in && !neg;
+        const unsigned long long mp = __ballot(pos), mn = __ballot(neg), below = (1ull << lane) - 1ull;
+        const int b = (int)(rd & 1);                     // two sets of counts: one barrier per round
+        if (lane == 0) { wp[b][w] = __popcll(mp); wn[b][w] = __popcll(mn); }
+        __syncthreads();
+        long long k = pos ? base_p : base_n;
+#pragma unroll
+        for (int j = 0; j < NW; ++j) {
+            if (j < w) k += pos ? wp[b][j] : wn[b][j];
+            base_p += wp[b][j];
+            base_n += wn[b][j];
+        }
+        k += __popcll((pos ? mp : mn) & below);
+        if (in) {
+            float pe[DPAD + 2];                          // P's entries, as pmm_pack_rows_kernel forms them
+            double n2 = 0.0, b2 = 0.0;
+#pragma unroll
+            for (int d = 0; d < DPAD; ++d) {
+                const double x = (d & 1) ? pre[d >> 1].y : pre[d >> 1].x;
+                const double df = x - cen[d];
+                b2 = fma(df, df, b2);
+                const float bf = (float)(df * kappa);
+                n2 = fma((double)bf, (double)bf, n2);
+                pe[d + 2] = 2.0f * bf;
+            }
+            bm2 = fmax(bm2, b2);
+            sal += fabs(alpha);
+            pe[0] = -(float)n2;
+            pe[1] = 1.0f;
+            const long long r = pmm_srow((pos ? 0 : gp) + (k >> 4), (int)(k & 15));
+            pmm_put_row<DPAD>(img + r / PMM_ROWS * (16ll * SH::PIECES), (int)(r % PMM_ROWS), pe, (float)alpha);
+        }
+    }
+    // the slots without a row
+    for (long long r = tid; r < pmm_stiles(n) * PMM_ROWS; r += PR_THREADS) {
+        const int rr = (int)(r & 31), s = (rr & 3) + 4 * (rr >> 3);
+        const long long q = 2 * (r >> 5) + ((rr >> 2) & 1);
+        const bool empty = q < gp ? 16 * q + s >= np : q < gp + gn ? 16 * (q - gp) + s >= nn : true;
+        if (empty) {
+            float pe[DPAD + 2];
+#pragma unroll
+            for (int d = 0; d < DPAD; ++d) pe[d + 2] = 0.0f;
+            pe[0] = -0.0f;                               // (the pre-split stream's padding row: its norm is negated)
+            pe[1] = 1.0f;
+            pmm_put_row<DPAD>(img + r / PMM_ROWS * (16ll * SH::PIECES), (int)(r % PMM_ROWS), pe, 0.0f);
+        }
+    }
+    for (int o = 32; o > 0; o >>= 1) { bm2 = fmax(bm2, __shfl_xor(bm2, o)); sal += __shfl_xor(sal, o); }
+    if (lane == 0) { wmax[w] = bm2; wsal[w] = sal; }
+    __syncthreads();
+    if (tid == 0) {
+        sal = 0.0;
+#pragma unroll
+        for (int i = 0; i < NW; ++i) { bm2 = fmax(bm2, wmax[i]); sal += wsal[i]; }
+        ((double*)rows)[0] = bm2;
+        ((double*)rows)[1] = sal;
+        ((long long*)rows)[2] = (gp + gn + 1) / 2;
+        ((long long*)rows)[3] = 0;
+    }
+}
+
 // PRE: the training rows come pre-split (PruneArgs::prune_rows, pmm_pack_rows_kernel): staging is a copy of the next
 // tile's image into the other of two LDS buffers, one barrier per tile, and bm2 and sal come from the stream's header.
-template <int DPAD, bool PRE = false>
+// SGN (with PRE): the stream is the sign-sorted one (pmm_pack_srows_kernel).  The 16 rows of a lane's fp32 partial sum
+// then carry alphas of one sign, every term k alpha of the chain ps = fma(k, alpha, ps) has that sign (or is zero), and
+// the chain on |alpha| is its mirror image: negating every product and the accumulator negates every rounded result
+// (round to nearest is symmetric), so pS == |ps| bit for bit and the second chain is not run.  The error analysis
+// above carries over term by term: each partial sum is still an fp32 chain of 16 fma, S32 is still below the exact sum
+// by <= 17 u of it; only the order of the rows, which it never used, is another.  The matrix tiles are taken up to the
+// header's nrt: the last staged tile may hold one to four.
+template <int DPAD, bool PRE = false, bool SGN = false>
 __global__ __launch_bounds__(PR_THREADS, PMM_G <= 4 ? 2 : 1) void prune_bound_mm32_kernel(PruneArgs a) {
+    static_assert(PRE || !SGN, "the sign-sorted rows come as a stream only");
     using SH = PmmShape<DPAD>;
     constexpr int XS = DPAD + 2;                         // packed stream row: scaled x | alpha | 0
     constexpr int K = SH::K, NI = SH::NI, PITCH = SH::PITCH, G = PMM_G;
@@ -294,11 +431,13 @@ __global__ __launch_bounds__(PR_THREADS, PMM_G <= 4 ? 2 : 1) void prune_bound_mm
     double accm[G], accs[G], sal = 0.0, bm2 = 0.0;
 #pragma unroll
     for (int g = 0; g < G; ++g) { accm[g] = 0.0; accs[g] = 0.0; }
-    const long long ntile = (a.n + PMM_ROWS - 1) / PMM_ROWS;
-    // one staged tile: its PMM_ROWS / 32 matrix tiles against the G candidate groups
-    auto consume = [&](int xo, int ao) {          // (element offsets of the LDS buffer in xt and at)
+    long long nrt = 0;                                   // SGN: the matrix tiles that hold a row (wave-uniform)
+    if constexpr (SGN) nrt = ((const long long*)a.prune_rows)[2];
+    const long long ntile = SGN ? (nrt + PMM_ROWS / 32 - 1) / (PMM_ROWS / 32) : (a.n + PMM_ROWS - 1) / PMM_ROWS;
+    // one staged tile: its first nr (SGN; else all PMM_ROWS / 32) matrix tiles against the G candidate groups
+    auto consume = [&](int xo, int ao, int nr) {  // (element offsets of the LDS buffer in xt and at)
 #pragma unroll 1
-        for (int rt = 0; rt < PMM_ROWS / 32; ++rt) {
+        for (int rt = 0; rt < (SGN ? nr : PMM_ROWS / 32); ++rt) {
             const __bf16* xr = xt + xo + (rt * 32 + l32) * PITCH + 8 * h;
             bf16x8 pop[NI];                              // the training rows' side, this lane half's k slots
 #pragma unroll
@@ -326,10 +465,10 @@ __global__ __launch_bounds__(PR_THREADS, PMM_G <= 4 ? 2 : 1) void prune_bound_mm
                 for (int r = 0; r < 16; ++r) {
                     const float k = __builtin_amdgcn_exp2f(cur[r]);
                     ps = fmaf(k, al[r], ps);
-                    pS = fmaf(k, fabsf(al[r]), pS);
+                    if constexpr (!SGN) pS = fmaf(k, fabsf(al[r]), pS);
                 }
                 accm[g] += (double)ps;
-                accs[g] += (double)pS;
+                accs[g] += (double)(SGN ? fabsf(ps) : pS);       // (SGN: one sign per 16 rows, |ps| IS the chain on |alpha|)
                 cur = nxt;
             }
         }
@@ -340,7 +479,7 @@ __global__ __launch_bounds__(PR_THREADS, PMM_G <= 4 ? 2 : 1) void prune_bound_mm
         // again, into the buffer nobody reads any more: no branch around the loads.
         typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
         constexpr int NPC = SH::PIECES, NL = (NPC + PR_THREADS - 1) / PR_THREADS;
-        const u32x4* img = (const u32x4*)((const unsigned char*)a.prune_rows + 16);
+        const u32x4* img = (const u32x4*)((const unsigned char*)a.prune_rows + (SGN ? PMM_SHDR : 16));
         u32x4 pre[NL];
         auto fetch = [&](long long ti) {
             const u32x4* src = img + ti * NPC;
@@ -366,7 +505,8 @@ __global__ __launch_bounds__(PR_THREADS, PMM_G <= 4 ? 2 : 1) void prune_bound_mm
         for (long long ti = 0; ti < ntile; ++ti) {
             const int b = (int)(ti & 1);
             fetch(ti + 1 < ntile ? ti + 1 : ntile - 1);
-            consume(b * PMM_ROWS * PITCH, b * PMM_ROWS);
+            const long long left = nrt - ti * (PMM_ROWS / 32);           // (SGN alone)
+            consume(b * PMM_ROWS * PITCH, b * PMM_ROWS, left < PMM_ROWS / 32 ? (int)left : PMM_ROWS / 32);
             put(b ^ 1);
             __syncthreads();                             // the next tile is in; this one has been consumed
         }
@@ -405,7 +545,7 @@ __global__ __launch_bounds__(PR_THREADS, PMM_G <= 4 ? 2 : 1) void prune_bound_mm
             }
             __syncthreads();
             if (ti + 1 < ntile) fetch(ti + 1);
-            consume(0, 0);
+            consume(0, 0, PMM_ROWS / 32);
             __syncthreads();                             // the tile has been consumed
         }
         // B = max |x - c| and sum |alpha| over the training rows: the stagers' maxima and sums, over the workgroup (every

@@ -1705,6 +1705,9 @@ struct PruneArgs {
     // coarse stage up to Dpad = 8: the training rows split into bf16 parts once per fit (apgp_pack_prune_rows), or NULL:
     // every workgroup splits them itself
     const void* prune_rows;
+    // which stream prune_rows is (host side only: launch_bound picks the kernel by it): APGP_PRUNE_ROWS_SPLIT, or
+    // APGP_PRUNE_ROWS_SIGNED: the rows sorted by alpha's sign (apgp_pack_prune_srows), the one-chain route
+    int rows_kind;
 };
 
 // Slack of a coarse bound: prune_bound_kernel's (derived there) with S <= amp sum|alpha| for its S, added in that
@@ -2292,26 +2295,32 @@ extern "C" int apgp_sweep_prune_select(const double* bmin, int64_t ncb, const in
     return 0;
 }
 
+// the kinds of stream the entry points take: the sign-sorted one cannot be left out (no kernel sorts rows per call)
+static inline bool pr_rows_kind_ok(const void* prune_rows, int rows_kind) {
+    return rows_kind == APGP_PRUNE_ROWS_SPLIT || (rows_kind == APGP_PRUNE_ROWS_SIGNED && prune_rows != NULL);
+}
+
 // the one place that fills a PruneArgs.  Kern: a KernConst, or an argument struct that apgp_fill_kernel has filled;
 // lo, hi: the box in the caller's coordinates, or NULL both
 template <class Kern>
 static PruneArgs pr_args(const double* T, int64_t m, const double* xs, int64_t n, const uint8_t* mask, const Kern& kern,
                          double mean, int32_t kind, const double* lo, const double* hi, double zeta, double ybest,
-                         double* bmin, double* part_u, long long* part_i, const void* prune_rows) {
+                         double* bmin, double* part_u, long long* part_i, const void* prune_rows, int rows_kind) {
     PruneArgs p;
     p.T = T; p.xs = xs; p.mask = mask; p.bmin = bmin; p.part_u = part_u; p.part_i = part_i;
     p.m = m; p.ncb = pr_ncb(m); p.n = n;
     p.kind = kind; p.mean = mean; p.zeta = zeta; p.ybest = ybest;
     apgp_fill_kernel(p, kern);
     apgp_fill_box(p, p.ndim, lo, hi);
-    p.blk_list = NULL; p.blk_count = NULL; p.est = NULL; p.prune_rows = prune_rows;
+    p.blk_list = NULL; p.blk_count = NULL; p.est = NULL; p.prune_rows = prune_rows; p.rows_kind = rows_kind;
     return p;
 }
 
 // the bound pass over all blocks: coarse (fp32 kernel values; pure squared-exponential kernels only) or fp64.  Coarse up to
 // Dpad = 8: the exponents on the matrix cores (prune_mm32.h), and the vector-ALU kernel behind it for the blocks whose
 // gate failed there -- as a rule none, and its workgroups leave at once.  Dpad 16 and 32 keep the vector-ALU kernel.
-// With PruneArgs::prune_rows the matrix-core kernel copies the pre-split rows instead of splitting them (same bits).
+// With PruneArgs::prune_rows the matrix-core kernel copies the pre-split rows instead of splitting them (same bits), or,
+// with rows_kind = APGP_PRUNE_ROWS_SIGNED, the sign-sorted rows, and runs one chain per kernel value (other last bits).
 // With PruneArgs::blk_list (fp64 only): the refine stage, over the blocks of that list; the launch is sized for all blocks.
 template <int DPAD>
 static void launch_bound(const PruneArgs& p, hipStream_t s, bool coarse) {
@@ -2321,7 +2330,9 @@ static void launch_bound(const PruneArgs& p, hipStream_t s, bool coarse) {
     if (coarse) {
         if constexpr (DPAD <= 8) {
             const dim3 mm_grid = grid_of(PMM_G / 2);
-            if (p.prune_rows)
+            if (p.prune_rows && p.rows_kind == APGP_PRUNE_ROWS_SIGNED)
+                hipLaunchKernelGGL((prune_bound_mm32_kernel<DPAD, true, true>), mm_grid, dim3(PR_THREADS), 0, s, p);
+            else if (p.prune_rows)
                 hipLaunchKernelGGL((prune_bound_mm32_kernel<DPAD, true>), mm_grid, dim3(PR_THREADS), 0, s, p);
             else
                 hipLaunchKernelGGL((prune_bound_mm32_kernel<DPAD, false>), mm_grid, dim3(PR_THREADS), 0, s, p);
@@ -2342,7 +2353,8 @@ static void launch_bound(const PruneArgs& p, hipStream_t s, bool coarse) {
 // exceeds the spread of the bounds (an ill-conditioned fit: sum |alpha| is huge against the spread of mu) the bounds
 // themselves order the blocks by little more than |t - c|, the seeds would be arbitrary and tau prune nothing.
 template <int DPAD>
-static int launch_pruned(const SweepArgs& a, hipStream_t s, bool solve, void* part, const void* prune_rows) {
+static int launch_pruned(const SweepArgs& a, hipStream_t s, bool solve, void* part, const void* prune_rows,
+                         int rows_kind) {
     const int rc = s2_prepare_device<DPAD>();
     if (rc != 0) return rc;
     const long long ncb = pr_ncb(a.m);
@@ -2352,7 +2364,7 @@ static int launch_pruned(const SweepArgs& a, hipStream_t s, bool solve, void* pa
     long long* counts = seeds + PR_SEED;
     const bool coarse = a.lin_coef == 0.0;
     PruneArgs p = pr_args(a.T, a.m, a.xs, a.n, a.mask, a, a.mean, a.kind, a.has_box ? a.lo : NULL, a.has_box ? a.hi : NULL,
-                          a.zeta, a.ybest, bmin, a.part_u, a.part_i, prune_rows);
+                          a.zeta, a.ybest, bmin, a.part_u, a.part_i, prune_rows, rows_kind);
     if (coarse) p.est = (double*)(counts + 8);
     launch_bound<DPAD>(p, s, coarse);
     hipLaunchKernelGGL(prune_seed_kernel, dim3(1), dim3(1024), 0, s, coarse ? (const double*)p.est : (const double*)bmin, ncb,
@@ -2394,8 +2406,9 @@ static int acquire_impl(bool solve, const double* T, int64_t m, int64_t idx_offs
                         const double* xs, int64_t n, const apgp_kernel_t* kern, double mean,
                         int32_t kind, const double* lo, const double* hi, const uint8_t* mask,
                         double zeta, double ybest, double* mu, double* var, double* u, void* part,
-                        apgp_best_t* best, const void* prune_rows, void* stream) {
+                        apgp_best_t* best, const void* prune_rows, int rows_kind, void* stream) {
     APGP_CHECK_ARG(T && packed_linv && xs && kern, "null pointer");
+    APGP_CHECK_ARG(pr_rows_kind_ok(prune_rows, rows_kind), "rows_kind: SPLIT, or SIGNED with its stream");
     APGP_CHECK_ARG(m >= 1 && m <= APGP_MAX_M && n >= 1 && n <= APGP_MAX_N, "m >= 1 and n >= 1 required");
     APGP_CHECK_ARG(kind >= APGP_UTIL_AGP && kind <= APGP_UTIL_NONE, "unknown utility kind");
     APGP_CHECK_ARG(kind == APGP_UTIL_NONE || best, "best required for an acquisition");
@@ -2437,7 +2450,7 @@ static int acquire_impl(bool solve, const double* T, int64_t m, int64_t idx_offs
     const bool prune = pr_mode > 0 && kind != APGP_UTIL_NONE && !mu && !var && !u && part &&
                        m >= (pr_mode == 1 ? pr_min_m(n) : (int64_t)pr_mode);
     const int rc = apgp_by_dpad(kc.dpad, [&](auto dp) {
-        return prune ? launch_pruned<decltype(dp)::value>(a, s, solve, part, prune_rows)
+        return prune ? launch_pruned<decltype(dp)::value>(a, s, solve, part, prune_rows, rows_kind)
                      : launch_sweep<decltype(dp)::value>(a, s, solve);
     });
     if (rc != 0) return rc;
@@ -2453,7 +2466,7 @@ extern "C" int apgp_acquire(const double* T, int64_t m, int64_t idx_offset, cons
                             double zeta, double ybest, double* mu, double* var, double* u, void* part,
                             apgp_best_t* best, void* stream) {
     return acquire_impl(false, T, m, idx_offset, packed_linv, xs, n, kern, mean, kind, lo, hi, mask, zeta, ybest,
-                        mu, var, u, part, best, NULL, stream);
+                        mu, var, u, part, best, NULL, APGP_PRUNE_ROWS_SPLIT, stream);
 }
 
 // apgp_acquire with the fit's pre-split rows of the coarse bound (apgp_pack_prune_rows; NULL: apgp_acquire itself)
@@ -2463,7 +2476,17 @@ extern "C" int apgp_acquire_rows(const double* T, int64_t m, int64_t idx_offset,
                                  double zeta, double ybest, double* mu, double* var, double* u, void* part,
                                  apgp_best_t* best, const void* prune_rows, void* stream) {
     return acquire_impl(false, T, m, idx_offset, packed_linv, xs, n, kern, mean, kind, lo, hi, mask, zeta, ybest,
-                        mu, var, u, part, best, prune_rows, stream);
+                        mu, var, u, part, best, prune_rows, APGP_PRUNE_ROWS_SPLIT, stream);
+}
+
+// apgp_acquire_rows with the kind of its stream (APGP_PRUNE_ROWS_*)
+extern "C" int apgp_acquire_rows2(const double* T, int64_t m, int64_t idx_offset, const double* packed_linv,
+                                  const double* xs, int64_t n, const apgp_kernel_t* kern, double mean,
+                                  int32_t kind, const double* lo, const double* hi, const uint8_t* mask,
+                                  double zeta, double ybest, double* mu, double* var, double* u, void* part,
+                                  apgp_best_t* best, const void* prune_rows, int32_t rows_kind, void* stream) {
+    return acquire_impl(false, T, m, idx_offset, packed_linv, xs, n, kern, mean, kind, lo, hi, mask, zeta, ybest,
+                        mu, var, u, part, best, prune_rows, rows_kind, stream);
 }
 
 // Test hooks of the pruned arg-min (include/apgp.h): one bound pass over all blocks into the caller's buffer, and the
@@ -2496,11 +2519,39 @@ extern "C" int apgp_pack_prune_rows(const double* xs, int64_t n, const apgp_kern
     return 0;
 }
 
+// The same rows sorted by alpha's sign (prune_mm32.h: pmm_pack_srows_kernel).  Doubles: the 32-byte header and
+// pmm_stiles(n) tiles, room for any split of the n rows into the two classes.
+extern "C" int64_t apgp_prune_srows_len(int64_t n, int32_t ndim) {
+    if (n < 0 || n > APGP_MAX_N || ndim < 1 || ndim > APGP_MAX_DIM) return -1;
+    const int dpad = apgp_dpad(ndim);
+    if (n == 0 || dpad > 8) return 0;
+    return apgp_by_dpad(dpad, [&](auto dp) -> int64_t {
+        if constexpr (decltype(dp)::value <= 8)
+            return PMM_SHDR / 8 + pmm_stiles(n) * 2 * PmmShape<decltype(dp)::value>::PIECES;
+        else return 0;
+    });
+}
+
+extern "C" int apgp_pack_prune_srows(const double* xs, int64_t n, const apgp_kernel_t* kern, void* rows, void* stream) {
+    APGP_CHECK_ARG(xs && kern && rows, "null pointer");
+    APGP_CHECK_ARG(n >= 1 && n <= APGP_MAX_N, "n >= 1 required");
+    KernConst kc;
+    APGP_CHECK_ARG(apgp_make_kernconst(kern, &kc) == 0, "kernel parameters");
+    APGP_CHECK_ARG(kc.dpad <= 8, "no sign-sorted rows beyond 8 dimensions (apgp_prune_srows_len is 0)");
+    apgp_by_dpad(kc.dpad, [&](auto dp) {
+        if constexpr (decltype(dp)::value <= 8)
+            hipLaunchKernelGGL(pmm_pack_srows_kernel<decltype(dp)::value>, dim3(1), dim3(PR_THREADS), 0, (hipStream_t)stream,
+                               xs, (long long)n, (unsigned char*)rows);
+    });
+    APGP_CHECK_LAUNCH();
+    return 0;
+}
+
 // (who: the entry point's name, which the refusals of apgp_prune_bounds have always carried)
 static int prune_bounds_impl(const char* who, const double* T, int64_t m, const double* xs, int64_t n,
                              const apgp_kernel_t* kern, double mean, int32_t kind, const double* lo, const double* hi,
                              const uint8_t* mask, double zeta, double ybest, int coarse, double* bmin_out,
-                             const void* prune_rows, void* stream) {
+                             const void* prune_rows, int rows_kind, double* est_out, void* stream) {
 #define PB_CHECK_ARG(cond, msg)                                     \
     do {                                                            \
         if (!(cond)) {                                              \
@@ -2512,11 +2563,13 @@ static int prune_bounds_impl(const char* who, const double* T, int64_t m, const 
     PB_CHECK_ARG(m >= 1 && m <= APGP_MAX_M && n >= 1 && n <= APGP_MAX_N, "m >= 1 and n >= 1 required");
     PB_CHECK_ARG(kind >= APGP_UTIL_AGP && kind < APGP_UTIL_NONE, "unknown utility kind");
     PB_CHECK_ARG((lo == NULL) == (hi == NULL), "lo and hi must be given together");
+    PB_CHECK_ARG(pr_rows_kind_ok(prune_rows, rows_kind), "rows_kind: SPLIT, or SIGNED with its stream");
     KernConst kc;
     PB_CHECK_ARG(apgp_make_kernconst(kern, &kc) == 0, "kernel parameters");
     PB_CHECK_ARG(!coarse || kc.lin_coef == 0.0, "the coarse bound takes pure squared-exponential kernels only");
 #undef PB_CHECK_ARG
-    const PruneArgs p = pr_args(T, m, xs, n, mask, kc, mean, kind, lo, hi, zeta, ybest, bmin_out, NULL, NULL, prune_rows);
+    PruneArgs p = pr_args(T, m, xs, n, mask, kc, mean, kind, lo, hi, zeta, ybest, bmin_out, NULL, NULL, prune_rows, rows_kind);
+    if (coarse) p.est = est_out;                         // (the fp64 bound has no use for it)
     hipStream_t s = (hipStream_t)stream;
     apgp_by_dpad(kc.dpad, [&](auto dp) { launch_bound<decltype(dp)::value>(p, s, coarse != 0); });
     APGP_CHECK_LAUNCH();
@@ -2527,7 +2580,7 @@ extern "C" int apgp_prune_bounds(const double* T, int64_t m, const double* xs, i
                                  double mean, int32_t kind, const double* lo, const double* hi, const uint8_t* mask,
                                  double zeta, double ybest, int coarse, double* bmin_out, void* stream) {
     return prune_bounds_impl(__func__, T, m, xs, n, kern, mean, kind, lo, hi, mask, zeta, ybest, coarse, bmin_out, NULL,
-                             stream);
+                             APGP_PRUNE_ROWS_SPLIT, NULL, stream);
 }
 
 extern "C" int apgp_prune_bounds_rows(const double* T, int64_t m, const double* xs, int64_t n, const apgp_kernel_t* kern,
@@ -2535,7 +2588,15 @@ extern "C" int apgp_prune_bounds_rows(const double* T, int64_t m, const double* 
                                       double zeta, double ybest, int coarse, double* bmin_out, const void* prune_rows,
                                       void* stream) {
     return prune_bounds_impl(__func__, T, m, xs, n, kern, mean, kind, lo, hi, mask, zeta, ybest, coarse, bmin_out,
-                             prune_rows, stream);
+                             prune_rows, APGP_PRUNE_ROWS_SPLIT, NULL, stream);
+}
+
+extern "C" int apgp_prune_bounds_rows2(const double* T, int64_t m, const double* xs, int64_t n, const apgp_kernel_t* kern,
+                                       double mean, int32_t kind, const double* lo, const double* hi, const uint8_t* mask,
+                                       double zeta, double ybest, int coarse, double* bmin_out, const void* prune_rows,
+                                       int32_t rows_kind, double* est_out, void* stream) {
+    return prune_bounds_impl(__func__, T, m, xs, n, kern, mean, kind, lo, hi, mask, zeta, ybest, coarse, bmin_out,
+                             prune_rows, rows_kind, est_out, stream);
 }
 
 extern "C" int apgp_sweep_prune_seeds(const double* bmin, int64_t ncb, int64_t* seeds, int64_t* counts, void* stream) {
@@ -2563,7 +2624,7 @@ extern "C" int apgp_acquire_solve(const double* T, int64_t m, int64_t idx_offset
                                   double zeta, double ybest, double* mu, double* var, double* u, void* part,
                                   apgp_best_t* best, void* stream) {
     return acquire_impl(true, T, m, idx_offset, packed_lsolve, xs, n, kern, mean, kind, lo, hi, mask, zeta, ybest,
-                        mu, var, u, part, best, NULL, stream);
+                        mu, var, u, part, best, NULL, APGP_PRUNE_ROWS_SPLIT, stream);
 }
 
 extern "C" int apgp_acquire_solve_rows(const double* T, int64_t m, int64_t idx_offset, const double* packed_lsolve,
@@ -2572,7 +2633,16 @@ extern "C" int apgp_acquire_solve_rows(const double* T, int64_t m, int64_t idx_o
                                        double zeta, double ybest, double* mu, double* var, double* u, void* part,
                                        apgp_best_t* best, const void* prune_rows, void* stream) {
     return acquire_impl(true, T, m, idx_offset, packed_lsolve, xs, n, kern, mean, kind, lo, hi, mask, zeta, ybest,
-                        mu, var, u, part, best, prune_rows, stream);
+                        mu, var, u, part, best, prune_rows, APGP_PRUNE_ROWS_SPLIT, stream);
+}
+
+extern "C" int apgp_acquire_solve_rows2(const double* T, int64_t m, int64_t idx_offset, const double* packed_lsolve,
+                                        const double* xs, int64_t n, const apgp_kernel_t* kern, double mean,
+                                        int32_t kind, const double* lo, const double* hi, const uint8_t* mask,
+                                        double zeta, double ybest, double* mu, double* var, double* u, void* part,
+                                        apgp_best_t* best, const void* prune_rows, int32_t rows_kind, void* stream) {
+    return acquire_impl(true, T, m, idx_offset, packed_lsolve, xs, n, kern, mean, kind, lo, hi, mask, zeta, ybest,
+                        mu, var, u, part, best, prune_rows, rows_kind, stream);
 }
 
 // ---------------------------------------------------------------------------

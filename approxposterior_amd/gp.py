@@ -509,6 +509,10 @@ class GP(GeorgeExtras):
         # sub-block pairs (32 rows) per workgroup of a split row block of the seed launches (apgp_set_seed_parts; same
         # bits whatever the value): None: the library's process-wide setting (default: its rule); -1: the rule; 8 / 4 / 2 / 1
         self.seed_parts = None
+        # the coarse bound of the pruned sweep reads the fit's rows sorted by alpha's sign and runs one sum chain per
+        # kernel value (apgp_pack_prune_srows; same winner either way, the bounds differ in their last bits):
+        # True (default): that route; False: the rows in their own order, two chains (the route of _prune_rows)
+        self.prune_signed = True
         self.sweep_prune_stats = False   # True: keep (seed blocks, surviving blocks, bits of tau, blocks the coarse
         self.last_prune_counts = None     # bound left, second-wave seeds swept) of the last pruned sweep here, as a
                                           # device int64[5] tensor
@@ -550,6 +554,7 @@ class GP(GeorgeExtras):
         self._work = None         # trtri work (dense L^-1 in first panel)
         self._xs = None           # packed training stream (depends on alpha)
         self._prune_rows = None   # its rows split for the coarse prune bound (apgp_pack_prune_rows); lives and dies with _xs
+        self._prune_srows = None  # the same rows sorted by alpha's sign (apgp_pack_prune_srows); lives and dies with _xs
         self._xs_key = None
         for key in ("nll", "one", "mean", "pgrad"):
             self._replays.pop(key, None)
@@ -806,7 +811,7 @@ class GP(GeorgeExtras):
             self._kernel_struct(ks)
             # (as _reset_device_state: whatever was derived from the previous factor is stale)
             self._alpha = self._packed = self._packed_solve = self._work = self._xs = self._xs_key = None
-            self._prune_rows = None
+            self._prune_rows = self._prune_srows = None
             self._computed = False
             r.args[4] = float(self.mean.value)
             try:
@@ -981,7 +986,7 @@ class GP(GeorgeExtras):
                     self._ztz_host = self._trsv(st, self._y_d, float(self.mean.value), 0, self._z, ztz, "forward",
                                                 retry_ss=ztz)
                 self._alpha = None
-                self._xs = self._prune_rows = None
+                self._xs = self._prune_rows = self._prune_srows = None
                 self._alpha_y = np.array(y, copy=True)
                 self._alpha_mean = self.mean.value
             if need_alpha and self._alpha is None:
@@ -993,7 +998,7 @@ class GP(GeorgeExtras):
                                "apgp_winv_apply(backward)")
                 else:
                     self._trsv(st, self._z, 0.0, 1, self._alpha, torch.empty(1, dtype=torch.float64, device=dev), "backward")
-                self._xs = self._prune_rows = None
+                self._xs = self._prune_rows = self._prune_srows = None
         return self._ztz_host
 
     def log_likelihood(self, y, quiet=False):
@@ -1205,6 +1210,19 @@ class GP(GeorgeExtras):
                 self._prune_rows = torch.empty(rows_len, dtype=torch.float64, device=dev)
                 _lib.check(lib.apgp_pack_prune_rows(self._xs.data_ptr(), n, ctypes.byref(ks),
                                                     self._prune_rows.data_ptr(), st), "apgp_pack_prune_rows")
+            # and sorted by alpha's sign, for the bound's one-chain route (prune_signed)
+            srows_len = int(lib.apgp_prune_srows_len(n, ks.ndim))
+            self._prune_srows = None
+            if srows_len > 0:
+                self._prune_srows = torch.empty(srows_len, dtype=torch.float64, device=dev)
+                _lib.check(lib.apgp_pack_prune_srows(self._xs.data_ptr(), n, ctypes.byref(ks),
+                                                     self._prune_srows.data_ptr(), st), "apgp_pack_prune_srows")
+
+    def _prune_stream(self):
+        """(pointer or None, APGP_PRUNE_ROWS_* kind) of the row stream the coarse bound reads: ``prune_signed``."""
+        if self.prune_signed and self._prune_srows is not None:
+            return self._prune_srows.data_ptr(), _lib.PRUNE_ROWS_SIGNED
+        return _ptr(self._prune_rows), _lib.PRUNE_ROWS_SPLIT
 
     # -- predict (george GP.predict; SURVEY.md Appendix A.7) ----------------------------
     def predict(self, y, t, return_cov=True, return_var=False, cache=True, **kwargs):
@@ -1436,7 +1454,7 @@ class GP(GeorgeExtras):
                 e0.record()
             args = (self._xs.data_ptr(), n, ctypes.byref(ks), float(self.mean.value), kind_id, lo, hi, _ptr(mask_d),
                     float(zeta), float(np.max(y)), _ptr(mu), _ptr(var), _ptr(u), part.data_ptr(), best.data_ptr(),
-                    _ptr(self._prune_rows), st)
+                    *self._prune_stream(), st)
             prune_was = None if self.sweep_prune is None else lib.apgp_set_sweep_prune(int(self.sweep_prune))
             rowsplit_was = None if self.seed_rowsplit is None else lib.apgp_set_seed_rowsplit(int(self.seed_rowsplit))
             park_was = None if self.seed_park is None else lib.apgp_set_seed_park(int(self.seed_park))
@@ -1444,11 +1462,11 @@ class GP(GeorgeExtras):
             parts_was = None if self.seed_parts is None else lib.apgp_set_seed_parts(int(self.seed_parts))
             try:
                 if use_solve:
-                    _lib.check(lib.apgp_acquire_solve_rows(T.data_ptr(), m, int(idx_offset),
-                                                           self._packed_solve.data_ptr(), *args), "apgp_acquire_solve_rows")
+                    _lib.check(lib.apgp_acquire_solve_rows2(T.data_ptr(), m, int(idx_offset),
+                                                            self._packed_solve.data_ptr(), *args), "apgp_acquire_solve_rows2")
                 else:
-                    _lib.check(lib.apgp_acquire_rows(T.data_ptr(), m, int(idx_offset), self._packed.data_ptr(), *args),
-                               "apgp_acquire_rows")
+                    _lib.check(lib.apgp_acquire_rows2(T.data_ptr(), m, int(idx_offset), self._packed.data_ptr(), *args),
+                               "apgp_acquire_rows2")
             finally:
                 if prune_was is not None:
                     lib.apgp_set_sweep_prune(prune_was)
@@ -1525,11 +1543,11 @@ class GP(GeorgeExtras):
         with self._on(torch, dev):
             self._ensure_xs(y)
             bmin = torch.empty((m + 63) // 64, dtype=torch.float64, device=dev)
-            _lib.check(lib.apgp_prune_bounds_rows(T.data_ptr(), m, self._xs.data_ptr(), len(self._x), ctypes.byref(ks),
-                                                  float(self.mean.value), kind_id, lo, hi, _ptr(mask_d), float(zeta),
-                                                  float(np.max(y)), int(bool(coarse)), bmin.data_ptr(),
-                                                  _ptr(self._prune_rows), self._stream(torch)),
-                       "apgp_prune_bounds_rows")
+            _lib.check(lib.apgp_prune_bounds_rows2(T.data_ptr(), m, self._xs.data_ptr(), len(self._x), ctypes.byref(ks),
+                                                   float(self.mean.value), kind_id, lo, hi, _ptr(mask_d), float(zeta),
+                                                   float(np.max(y)), int(bool(coarse)), bmin.data_ptr(),
+                                                   *self._prune_stream(), None, self._stream(torch)),
+                       "apgp_prune_bounds_rows2")
         return bmin.cpu().numpy()
 
     def nelder_mead_search(self, y, starts, kind, bounds=None, zeta=0.01, options=None, trace=False):

@@ -450,6 +450,49 @@ int apgp_prune_bounds_rows(const double* T, int64_t m, const double* xs, int64_t
                            double zeta, double ybest, int coarse, double* bmin_out, const void* prune_rows,
                            void* stream);
 
+/* ---- the same rows sorted by the sign of alpha (the coarse bound's one-chain route) --
+ * The coarse bound adds sum alpha k and sum |alpha| k per candidate in fp32 partial sums over 16 training rows.  In
+ * the stream below the rows stand in an order in which every such 16 rows carry alphas of one sign; the second sum is
+ * then the absolute value of the first, bit for bit, and the bound kernel runs one chain of fused multiply-adds per
+ * kernel value where the route above runs two.  The bounds differ from the other routes' in their last bits (another
+ * order of the rows); they are valid bounds under the same slack, and the winner does not depend on the route.
+ * apgp_prune_srows_len: doubles in the stream (16-byte aligned device memory); 0 beyond 8 dimensions.  Layout: a 32-byte
+ * header -- max |x - c|^2 and sum |alpha| (fp64), the number of 32-row matrix tiles that hold a row (int64), 8 bytes of
+ * zero -- and per 128-row tile the image and the 128 fp32 alphas of apgp_pack_prune_rows.  Rows with alpha >= 0 come
+ * first, 16 to a group, in their original order, then the rows with alpha < 0 in theirs; group q is the rows
+ * (s & 3) + 8 (s >> 2) + 4 (q & 1), s = 0 .. 15, of 32-row tile q >> 1; a slot without a row has alpha 0.
+ * apgp_pack_prune_srows: one launch; rows receives the stream.  It depends on xs alone: once per fit.
+ * apgp_acquire_rows2, apgp_acquire_solve_rows2, apgp_prune_bounds_rows2: the entry points above with the kind of the
+ * stream as one more argument: APGP_PRUNE_ROWS_SPLIT (the stream of apgp_pack_prune_rows: the entry points above
+ * themselves) or APGP_PRUNE_ROWS_SIGNED (this one); any other kind, or SIGNED with a NULL stream, is refused (-1).
+ * apgp_prune_bounds_rows2 also takes est_out (device, ceil(m / 64) doubles, or NULL): with coarse = 1 it receives per
+ * block the smallest b WITHOUT its slack -- what the pruned arg-min chooses its seeds by; a block's bmin and est come
+ * from the same row where one row of the block is admissible.  Not written with coarse = 0.
+ * Added in ABI 8 without changing anything before it: APGP_ABI_VERSION stays 8.             */
+#define APGP_PRUNE_ROWS_SPLIT 0
+#define APGP_PRUNE_ROWS_SIGNED 1
+int64_t apgp_prune_srows_len(int64_t n, int32_t ndim);
+int apgp_pack_prune_srows(const double* xs, int64_t n, const apgp_kernel_t* kern /*host*/, void* rows, void* stream);
+int apgp_acquire_rows2(const double* T, int64_t m, int64_t idx_offset,
+                       const double* packed_linv, const double* xs, int64_t n,
+                       const apgp_kernel_t* kern /*host*/, double mean, int32_t kind,
+                       const double* lo /*host*/, const double* hi /*host*/,
+                       const uint8_t* mask, double zeta, double ybest,
+                       double* mu, double* var, double* u,
+                       void* part, apgp_best_t* best, const void* prune_rows, int32_t rows_kind, void* stream);
+int apgp_acquire_solve_rows2(const double* T, int64_t m, int64_t idx_offset,
+                             const double* packed_lsolve, const double* xs, int64_t n,
+                             const apgp_kernel_t* kern /*host*/, double mean, int32_t kind,
+                             const double* lo /*host*/, const double* hi /*host*/,
+                             const uint8_t* mask, double zeta, double ybest,
+                             double* mu, double* var, double* u,
+                             void* part, apgp_best_t* best, const void* prune_rows, int32_t rows_kind, void* stream);
+int apgp_prune_bounds_rows2(const double* T, int64_t m, const double* xs, int64_t n,
+                            const apgp_kernel_t* kern /*host*/, double mean, int32_t kind,
+                            const double* lo /*host*/, const double* hi /*host*/, const uint8_t* mask,
+                            double zeta, double ybest, int coarse, double* bmin_out, const void* prune_rows,
+                            int32_t rows_kind, double* est_out, void* stream);
+
 /* ---- fantasy update of a sweep (batch design points, kriging believer) -----------
  * After a sweep over T (mu, var = v_0 written) and picks x_1 .. x_j, conditioning the GP on
  * x_j = T[pick_row] observed at y = mu(x_j) (hyper-parameters unchanged) leaves mu as it is
