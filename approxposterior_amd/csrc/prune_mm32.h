@@ -96,7 +96,8 @@
 // A block whose bound came out -inf (gate failed: data far wider than the length scale; or a NaN bound) is left to
 // prune_bound32_kernel<DPAD, true>, launched behind this kernel: the -inf in bmin is the mark, no other scratch.
 // Variants measured: docs/experiments.md, round 13 (the fp32 form), round 17 (what the fp32 MFMA leaves to the vector
-// ALU), round 18 (this form), round 19 (the rows split once per fit), round 29 (the rows sorted by alpha's sign).
+// ALU), round 18 (this form), round 19 (the rows split once per fit), round 29 (the rows sorted by alpha's sign),
+// round 30 (the row loop pipelined).
 #pragma once
 #include <utility>
 
@@ -372,9 +373,12 @@ __global__ __launch_bounds__(PR_THREADS) void pmm_pack_srows_kernel(const double
 // above carries over term by term: each partial sum is still an fp32 chain of 16 fma, S32 is still below the exact sum
 // by <= 17 u of it; only the order of the rows, which it never used, is another.  The matrix tiles are taken up to the
 // header's nrt: the last staged tile may hold one to four.
-template <int DPAD, bool PRE = false, bool SGN = false>
+// PIPE (with PRE and SGN): the same statements in a pinned order of issue, consume_pipe below; no value is formed otherwise.
+template <int DPAD, bool PRE = false, bool SGN = false, bool PIPE = false>
 __global__ __launch_bounds__(PR_THREADS, PMM_G <= 4 ? 2 : 1) void prune_bound_mm32_kernel(PruneArgs a) {
     static_assert(PRE || !SGN, "the sign-sorted rows come as a stream only");
+    static_assert((PRE && SGN) || !PIPE, "the pipelined row loop is written for the sign-sorted stream");
+    static_assert(!PIPE || (PMM_G == 4 && PMM_ROWS == 128), "consume_pipe: four groups alternate two accumulator tiles, four matrix tiles alternate two register sets");
     using SH = PmmShape<DPAD>;
     constexpr int XS = DPAD + 2;                         // packed stream row: scaled x | alpha | 0
     constexpr int K = SH::K, NI = SH::NI, PITCH = SH::PITCH, G = PMM_G;
@@ -452,9 +456,11 @@ __global__ __launch_bounds__(PR_THREADS, PMM_G <= 4 ? 2 : 1) void prune_bound_mm
                 return c;
             };
             // Written as a two-tile pipeline, but hipcc issues all G groups' chains first and the vector work behind them
-            // (64 accumulators fit).  Unlike the fp32 form this one leaves the vector issue free for most of its
-            // cycles, so the exponentials run under the products of the SIMD's other wavefront
-            // (tools/probes/mfma_bf16_shadow.hip; docs/experiments.md, round 18).
+            // (64 accumulators fit), behind the reads of the iteration and their wait: a wavefront waits for LDS, then
+            // feeds only the matrix pipe, then only the vector ALU, and overlaps nothing of its own; what overlap there
+            // is comes from the SIMD's other wavefront, which belongs to another workgroup and waits at its barriers
+            // (tools/probes/mfma_bf16_shadow.hip, mfma_bf16_pipe.hip; docs/experiments.md, rounds 18 and 30).  This loop
+            // is kept for the instantiations without PIPE; with PIPE the order is pinned, consume_pipe below.
             f32x16 cur = product(0);
 #pragma unroll
             for (int g = 0; g < G; ++g) {
@@ -470,6 +476,113 @@ __global__ __launch_bounds__(PR_THREADS, PMM_G <= 4 ? 2 : 1) void prune_bound_mm
                 accm[g] += (double)ps;
                 accs[g] += (double)(SGN ? fabsf(ps) : pS);       // (SGN: one sign per 16 rows, |ps| IS the chain on |alpha|)
                 cur = nxt;
+            }
+        }
+    };
+    // PIPE: the same statements per value, in an order of issue that sched_barrier pins (a wavefront overlaps its own
+    // LDS reads, matrix products and vector work; docs/experiments.md, round 30):
+    //   * a group step runs the 16 exponentials and 16 fma of group g in NI slices, and in front of every slice ONE of
+    //     the NI chained matrix products of the NEXT group: the chain's next link finds its predecessor finished, and
+    //     the vector lanes never stand behind a burst of products.  Two accumulator tiles live, c0 (even groups) and c1.
+    //   * the next group of group G - 1 is group 0 of the next matrix tile, whose fragments and alphas go into the other
+    //     of two register sets (A: even matrix tiles of a staged tile, B: odd): the fragments in front of this tile's
+    //     vector work, the alphas in front of its last group step.
+    //   * across the barrier: the last group of a staged tile stays pending in c1 with its alphas in set B, and runs
+    //     under group 0 of the next staged tile, whose rows are read behind the barrier.  The last matrix tile of the
+    //     call drains: its last group has no product in front.
+    // The four matrix tiles of a full staged tile are written out, so that the register sets alternate without moves;
+    // only the last staged tile can hold fewer, and takes them one at a time, each drained.
+    [[maybe_unused]] f32x16 c0, c1;
+    [[maybe_unused]] bf16x8 pA[NI], pB[NI];
+    [[maybe_unused]] float alA[16], alB[16];
+    // (first, last: the first and the last staged tile of the call; fetch_next: the global loads of the next staged tile)
+    auto consume_pipe = [&](int xo, int ao, int nr, bool first, bool last, auto&& fetch_next)
+                            __attribute__((always_inline)) {
+        auto rdp = [&](int rt, bf16x8 (&p)[NI]) __attribute__((always_inline)) {
+            const __bf16* xr = xt + xo + (rt * 32 + l32) * PITCH + 8 * h;
+#pragma unroll
+            for (int t = 0; t < NI; ++t) p[t] = *(const bf16x8*)(xr + 16 * t);
+        };
+        auto rda = [&](int rt, float (&al)[16]) __attribute__((always_inline)) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) *(f32x4*)(al + 4 * q) = *(const f32x4*)(at + ao + rt * 32 + 8 * q + 4 * h);
+        };
+        // The vector work of group g (exponents cc, alphas al); NEXT: under the product of group gn with the rows pn -> cn
+        // (else pn, gn and cn are not used).  The matrix product, the exponential and the fma have no side effect, and instruction selection orders such
+        // nodes by register pressure before the scheduler ever sees a sched_barrier: written plainly, all products
+        // came out in a burst again.  So every slice ties its values to its place with empty asm statements (no
+        // instruction, no move: each names a register set in place), which ARE ordered against the barriers.
+        auto step = [&](auto next, f32x16& cc, const float (&al)[16], int g, f32x16& cn, const bf16x8 (&pn)[NI],
+                        int gn) __attribute__((always_inline)) {
+            constexpr bool NEXT = decltype(next)::value;
+            f32x16 c = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+            float ps = 0.0f;
+#pragma unroll
+            for (int t = 0; t < NI; ++t) {
+                if constexpr (NEXT) {
+                    if (t) asm volatile("" : "+v"(c));
+                    c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(pn[t], qop[gn][t], c, 0, 0, 0);
+                    asm volatile("" : "+v"(c));
+                    asm volatile("" : "+v"(cc));
+                }
+#pragma unroll
+                for (int r = 16 * t / NI; r < 16 * (t + 1) / NI; ++r) {
+                    const float k = __builtin_amdgcn_exp2f(cc[r]);
+                    ps = fmaf(k, al[r], ps);
+                }
+                if constexpr (NEXT) {
+                    asm volatile("" : "+v"(ps));
+                    __builtin_amdgcn_sched_barrier(0);
+                }
+            }
+            accm[g] += (double)ps;
+            accs[g] += (double)fabsf(ps);                // (one sign per 16 rows, |ps| IS the chain on |alpha|)
+            if constexpr (NEXT) cn = c;
+        };
+        const std::true_type under{};
+        const std::false_type alone{};
+        auto product0 = [&](const bf16x8 (&p)[NI]) __attribute__((always_inline)) {
+            f32x16 c = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
+#pragma unroll
+            for (int t = 0; t < NI; ++t) c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(p[t], qop[0][t], c, 0, 0, 0);
+            c0 = c;
+        };
+        // a matrix tile with its rows in (p, al) and group 0 in c0; MORE: the next one's rows go into (pn, aln) and its
+        // group 0 into c0; else group G - 1 is left pending in c1
+        auto tile = [&](auto more, int rt, const bf16x8 (&p)[NI], const float (&al)[16], bf16x8 (&pn)[NI], float (&aln)[16])
+                        __attribute__((always_inline)) {
+            constexpr bool MORE = decltype(more)::value;
+            if constexpr (MORE) rdp(rt + 1, pn);         // a whole tile ahead of their first use, in the last group step
+            step(under, c0, al, 0, c1, p, 1);
+            step(under, c1, al, 1, c0, p, 2);
+            step(under, c0, al, 2, c1, p, 3);
+            if constexpr (MORE) {
+                rda(rt + 1, aln);                        // a group step ahead: p is dead by now, no register set more
+                step(under, c1, al, G - 1, c0, pn, 0);
+            }
+        };
+        if (nr == PMM_ROWS / 32) {
+            // a full staged tile, straight-line: no value has two places
+            rdp(0, pA);
+            rda(0, alA);
+            if (first) product0(pA);
+            else step(under, c1, alB, G - 1, c0, pA, 0);
+            tile(under, 0, pA, alA, pB, alB);
+            tile(under, 1, pB, alB, pA, alA);
+            tile(under, 2, pA, alA, pB, alB);
+            if (!last) fetch_next();                     // (set A is dead from here on: the copy's registers are its)
+            tile(alone, 3, pB, alB, pA, alA);
+            if (last) step(alone, c1, alB, G - 1, c0, pA, 0);
+        } else {
+            // the last staged tile where it holds fewer than four matrix tiles: one at a time, each drained
+#pragma unroll 1
+            for (int rt = 0; rt < nr; ++rt) {
+                rdp(rt, pA);
+                rda(rt, alA);
+                if (rt == 0 && !first) step(under, c1, alB, G - 1, c0, pA, 0);
+                else product0(pA);
+                tile(alone, rt, pA, alA, pB, alB);
+                step(alone, c1, alA, G - 1, c0, pA, 0);
             }
         }
     };
@@ -504,10 +617,18 @@ __global__ __launch_bounds__(PR_THREADS, PMM_G <= 4 ? 2 : 1) void prune_bound_mm
         __syncthreads();
         for (long long ti = 0; ti < ntile; ++ti) {
             const int b = (int)(ti & 1);
-            fetch(ti + 1 < ntile ? ti + 1 : ntile - 1);
+            if constexpr (!PIPE) fetch(ti + 1 < ntile ? ti + 1 : ntile - 1);
             const long long left = nrt - ti * (PMM_ROWS / 32);           // (SGN alone)
-            consume(b * PMM_ROWS * PITCH, b * PMM_ROWS, left < PMM_ROWS / 32 ? (int)left : PMM_ROWS / 32);
-            put(b ^ 1);
+            if constexpr (PIPE) {
+                // the next tile is loaded in front of this one's last matrix tile, where a register set is free, and
+                // there is no copy behind the last staged tile
+                consume_pipe(b * PMM_ROWS * PITCH, b * PMM_ROWS, left < PMM_ROWS / 32 ? (int)left : PMM_ROWS / 32, ti == 0,
+                             ti + 1 == ntile, [&]() __attribute__((always_inline)) { fetch(ti + 1); });
+                if (ti + 1 < ntile) put(b ^ 1);
+            } else {
+                consume(b * PMM_ROWS * PITCH, b * PMM_ROWS, left < PMM_ROWS / 32 ? (int)left : PMM_ROWS / 32);
+                put(b ^ 1);
+            }
             __syncthreads();                             // the next tile is in; this one has been consumed
         }
         bm2 = ((const double*)a.prune_rows)[0];

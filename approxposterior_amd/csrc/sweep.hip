@@ -1496,6 +1496,14 @@ extern "C" int apgp_set_seed_park(int v) { return __atomic_exchange_n(&g_seed_pa
 
 extern "C" int apgp_get_seed_park(void) { return __atomic_load_n(&g_seed_park, __ATOMIC_RELAXED); }
 
+// ---- whether the coarse bound over the sign-sorted rows runs its pipelined row loop (prune_mm32.h, PIPE) ----
+// 1 (default): yes; 0: the loop as hipcc orders it, the kernel as it was.  The same bits either way.
+static int g_prune_pipe = 1;
+
+extern "C" int apgp_set_prune_pipe(int v) { return __atomic_exchange_n(&g_prune_pipe, v != 0 ? 1 : 0, __ATOMIC_RELAXED); }
+
+extern "C" int apgp_get_prune_pipe(void) { return __atomic_load_n(&g_prune_pipe, __ATOMIC_RELAXED); }
+
 // ---- how many of the PR_SEED seeds the first seed wave sweeps ----
 // -1: the rule (S2_SEED_FIRST where the split seed route applies, all of them elsewhere); 1 .. 16: that many (16: one wave)
 #define S2_SEED_FIRST 4
@@ -2330,7 +2338,9 @@ static void launch_bound(const PruneArgs& p, hipStream_t s, bool coarse) {
     if (coarse) {
         if constexpr (DPAD <= 8) {
             const dim3 mm_grid = grid_of(PMM_G / 2);
-            if (p.prune_rows && p.rows_kind == APGP_PRUNE_ROWS_SIGNED)
+            if (p.prune_rows && p.rows_kind == APGP_PRUNE_ROWS_SIGNED && apgp_get_prune_pipe())
+                hipLaunchKernelGGL((prune_bound_mm32_kernel<DPAD, true, true, true>), mm_grid, dim3(PR_THREADS), 0, s, p);
+            else if (p.prune_rows && p.rows_kind == APGP_PRUNE_ROWS_SIGNED)
                 hipLaunchKernelGGL((prune_bound_mm32_kernel<DPAD, true, true>), mm_grid, dim3(PR_THREADS), 0, s, p);
             else if (p.prune_rows)
                 hipLaunchKernelGGL((prune_bound_mm32_kernel<DPAD, true>), mm_grid, dim3(PR_THREADS), 0, s, p);

@@ -513,6 +513,9 @@ class GP(GeorgeExtras):
         # kernel value (apgp_pack_prune_srows; same winner either way, the bounds differ in their last bits):
         # True (default): that route; False: the rows in their own order, two chains (the route of _prune_rows)
         self.prune_signed = True
+        # that route's bound kernel runs its row loop in a pinned, pipelined order of issue (apgp_set_prune_pipe; same
+        # bits either way): None: the library's process-wide setting (default: on); True / 1: on; False / 0: off
+        self.prune_pipe = None
         self.sweep_prune_stats = False   # True: keep (seed blocks, surviving blocks, bits of tau, blocks the coarse
         self.last_prune_counts = None     # bound left, second-wave seeds swept) of the last pruned sweep here, as a
                                           # device int64[5] tensor
@@ -1460,6 +1463,7 @@ class GP(GeorgeExtras):
             park_was = None if self.seed_park is None else lib.apgp_set_seed_park(int(self.seed_park))
             first_was = None if self.seed_first is None else lib.apgp_set_seed_first(int(self.seed_first))
             parts_was = None if self.seed_parts is None else lib.apgp_set_seed_parts(int(self.seed_parts))
+            pipe_was = None if self.prune_pipe is None else lib.apgp_set_prune_pipe(int(self.prune_pipe))
             try:
                 if use_solve:
                     _lib.check(lib.apgp_acquire_solve_rows2(T.data_ptr(), m, int(idx_offset),
@@ -1478,6 +1482,8 @@ class GP(GeorgeExtras):
                     lib.apgp_set_seed_first(first_was)
                 if parts_was is not None:
                     lib.apgp_set_seed_parts(parts_was)
+                if pipe_was is not None:
+                    lib.apgp_set_prune_pipe(pipe_was)
             if self.sweep_prune_stats and kind_id != _lib.UTIL_NONE and mu is None and var is None and u is None:
                 off = int(lib.apgp_sweep_prune_counts_offset(m, n))
                 self.last_prune_counts = part[off:off + 5].view(torch.int64).clone()
@@ -1543,11 +1549,16 @@ class GP(GeorgeExtras):
         with self._on(torch, dev):
             self._ensure_xs(y)
             bmin = torch.empty((m + 63) // 64, dtype=torch.float64, device=dev)
-            _lib.check(lib.apgp_prune_bounds_rows2(T.data_ptr(), m, self._xs.data_ptr(), len(self._x), ctypes.byref(ks),
-                                                   float(self.mean.value), kind_id, lo, hi, _ptr(mask_d), float(zeta),
-                                                   float(np.max(y)), int(bool(coarse)), bmin.data_ptr(),
-                                                   *self._prune_stream(), None, self._stream(torch)),
-                       "apgp_prune_bounds_rows2")
+            pipe_was = None if self.prune_pipe is None else lib.apgp_set_prune_pipe(int(self.prune_pipe))
+            try:
+                _lib.check(lib.apgp_prune_bounds_rows2(T.data_ptr(), m, self._xs.data_ptr(), len(self._x), ctypes.byref(ks),
+                                                       float(self.mean.value), kind_id, lo, hi, _ptr(mask_d), float(zeta),
+                                                       float(np.max(y)), int(bool(coarse)), bmin.data_ptr(),
+                                                       *self._prune_stream(), None, self._stream(torch)),
+                           "apgp_prune_bounds_rows2")
+            finally:
+                if pipe_was is not None:
+                    lib.apgp_set_prune_pipe(pipe_was)
         return bmin.cpu().numpy()
 
     def nelder_mead_search(self, y, starts, kind, bounds=None, zeta=0.01, options=None, trace=False):

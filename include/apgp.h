@@ -390,13 +390,20 @@ int apgp_acquire_solve(const double* T, int64_t m, int64_t idx_offset,
  * apgp_set_seed_parts(v): process-wide switch of the seed launches, returns the previous value.  A row block that
  * apgp_set_seed_rowsplit splits goes as 8 / v workgroups of v sub-block pairs (32 v rows) each: 8: whole, 4: the two
  * halves, 2 and 1: finer; -1 (default): the library's rule.  The bits do not depend on it.  apgp_acquire_work_len
- * grew with the fold inputs of the finer parts; APGP_ABI_VERSION stays 8.  */
+ * grew with the fold inputs of the finer parts; APGP_ABI_VERSION stays 8.
+ * apgp_set_prune_pipe(v): process-wide switch of the coarse bound pass over the sign-sorted rows
+ * (APGP_PRUNE_ROWS_SIGNED), returns the previous value.  1 (default): the kernel whose row loop issues the next
+ * group's matrix products between slices of this group's exponentials and reads the next matrix tile's rows ahead;
+ * 0: the loop in the order the compiler gives it, the kernel as it was.  The bits do not depend on it.  Every other
+ * kind of rows ignores it.  APGP_ABI_VERSION stays 8.  */
 int apgp_set_sweep_prune(int v);
 int apgp_get_sweep_prune(void);
 int apgp_set_seed_rowsplit(int v);
 int apgp_get_seed_rowsplit(void);
 int apgp_set_seed_park(int v);
 int apgp_get_seed_park(void);
+int apgp_set_prune_pipe(int v);
+int apgp_get_prune_pipe(void);
 int apgp_set_seed_first(int v);
 int apgp_get_seed_first(void);
 int apgp_set_seed_parts(int v);
