@@ -126,6 +126,8 @@ SIGNATURES = {
     "apgp_get_seed_park": (ctypes.c_int, []),
     "apgp_set_prune_pipe": (ctypes.c_int, [ctypes.c_int]),
     "apgp_get_prune_pipe": (ctypes.c_int, []),
+    "apgp_set_seed_prefetch": (ctypes.c_int, [ctypes.c_int]),
+    "apgp_get_seed_prefetch": (ctypes.c_int, []),
     "apgp_set_seed_first": (ctypes.c_int, [ctypes.c_int]),
     "apgp_get_seed_first": (ctypes.c_int, []),
     "apgp_set_seed_parts": (ctypes.c_int, [ctypes.c_int]),

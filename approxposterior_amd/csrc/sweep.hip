@@ -211,6 +211,15 @@ __host__ __device__ inline double* s2_fold_item(double* sp_q, int nrb, long long
 #define S2P_PAIR2_PARK 98
 #define S2P_PAIR1_GEN 161
 #define S2P_PAIR1_PARK 81
+// the same items through the stage-ring loop (sweep2_kernel<.., DEEP>; docs/experiments.md, Round 31), measured the same
+// way (tools/seed_tile_prices.py: first waves of no more items than CUs, every row block split, N = 4096 and 2048,
+// checked at N = 1024; profiles/r31_seed_tile_prices.json).  Whole items of that launch keep S2P_WHOLE_*.
+#define S2Q_HALF_GEN 220
+#define S2Q_HALF_PARK 101
+#define S2Q_PAIR2_GEN 183
+#define S2Q_PAIR2_PARK 54
+#define S2Q_PAIR1_GEN 183
+#define S2Q_PAIR1_PARK 45
 // what a second wave costs when none of its seeds is swept: four launches that leave at once (4.7 - 5.4 us each)
 #define S2P_WAVE2 2000
 // ---- the seed waves' launch word (SweepArgs::split of the seed route's launches) -----------------------------------------
@@ -224,6 +233,24 @@ __host__ __device__ inline double* s2_fold_item(double* sp_q, int nrb, long long
 #define S2W_P0(sp) (((sp) >> 12) & 31)
 #define S2W_P1(sp) (((sp) >> 20) & 31)
 #define S2W_SEED (1 << 28)
+// ---- the stage ring of a part item (sweep2_kernel<.., DEEP>) ---------------------------------------
+// A part item of pp sub-block pairs fills pp of the 8 pieces of a tile slot, and its re-read tiles wait for their fetch,
+// not for their MFMAs.  In the DEEP instantiation such an item keeps its tiles in a ring of stages inside the three tile
+// slots: stage = the tile's pp image pieces (4 KiB each) followed by its B operands (8 KiB); tile i lies in stage
+// i mod R, R = 4 / 6 / 8 for pp = 4 / 2 / 1.  The feeders request the re-read tiles D <= R - 2 tiles ahead (live stages:
+// i - 1, read by the matrix wavefronts until their barrier i, to i + D, being filled); the launch carries D in
+// bits 25 .. 27 of SweepArgs::split.
+#define S2W_PF(sp) (((sp) >> 25) & 7)
+#define S2_STAGE(pp) ((pp) * 512 + 2 * 4 * 128)          // doubles per stage
+#define S2_NRING(pp) (3 * S2_TILE / S2_STAGE(pp))        // stages in the three tile slots
+static_assert(S2_NRING(4) == 4 && S2_NRING(2) == 6 && S2_NRING(1) == 8, "the stage ring fits the three tile slots");
+static_assert(S2_NRING(4) * S2_STAGE(4) <= 3 * S2_TILE && S2_NRING(2) * S2_STAGE(2) <= 3 * S2_TILE &&
+              S2_NRING(1) * S2_STAGE(1) <= 3 * S2_TILE, "the stage ring fits the three tile slots");
+// The counts the loop's wait can ask for are (pp + 2) requests per tile x the tiles requested beyond i+1, at most
+// D - 1 <= S2_NRING(pp) - 3 of them: {6} for pp = 4, {4, 8, 12} for pp = 2, {3, 6, 9, 12, 15} for pp = 1, and 1 or 2 behind
+// the x fetch of a generating iteration.  These are the cases of the loop's switch; a count it does not list waits
+// with vmcnt(0), which is correct but gives the depth away -- a change of the ring must change the switch with it.
+static_assert(S2_NRING(4) - 3 == 1 && S2_NRING(2) - 3 == 3 && S2_NRING(1) - 3 == 5, "the DEEP loop's vmcnt cases follow the ring");
 __host__ __device__ inline int s2_nkc_of(int jb, int n) {
     const int v = S2_CPB * (jb + 1), lim = (n + SW_KC - 1) / SW_KC;
     return v < lim ? v : lim;
@@ -298,9 +325,13 @@ static constexpr bool s2_structured_feeder(int dpad, bool solve) { return dpad =
 // candidates are loaded; the tile loop never sees it.
 // RHALF (MODE 0, LIST, split launches only): row blocks >= J0 = a.split - 2 go as two row-half items (above).  Again an
 // instantiation of its own: every other one keeps its code.
-template <int DPAD, bool LIN, int MODE, bool LIST = false, bool RHALF = false>
+// DEEP (RHALF without a LinearKernel term; the parked seed launch at apgp_set_seed_prefetch > 0): a part item keeps its tiles
+// in a ring of stages and requests its re-read tiles several tiles ahead (S2_STAGE above; the loop at the head of the feeder
+// role).  Once more an instantiation of its own.
+template <int DPAD, bool LIN, int MODE, bool LIST = false, bool RHALF = false, bool DEEP = false>
 __global__ __launch_bounds__(S2_THREADS, 1) void sweep2_kernel(SweepArgs a) {
     static_assert(!RHALF || (MODE == 0 && LIST), "row-half items: inverse form, list launches");
+    static_assert(!DEEP || (RHALF && !LIN), "stage ring: the parked seed route");
     constexpr bool SOLVE = MODE != 0;
     // the seed launch of a pure squared-exponential kernel may read its blocks' parked stream (seed_park_kernel):
     // a.ncache > 0 there means "read slot blk0, never store"; with a LinearKernel term the instantiation is what it was
@@ -388,6 +419,10 @@ __global__ __launch_bounds__(S2_THREADS, 1) void sweep2_kernel(SweepArgs a) {
     }
     const int rpp = RHALF ? S2_NP >> S2W_LG(a.split) : S2_NP;     // RHALF: sub-block pairs of a part item (4, 2 or 1)
     const int rsh = rh > 0 ? rh * rpp : 0;        // RHALF: first sub-block pair of this item
+    // DEEP: a part item that reads the parked stream keeps its tiles in the stage ring (both roles agree on this)
+    [[maybe_unused]] const bool deep = DEEP && rh >= 0 && a.ncache > 0;
+    [[maybe_unused]] const int sstr = deep ? S2_STAGE(rpp) : S2_TILE;      // doubles between two stages / tile slots
+    [[maybe_unused]] const int nring = deep ? (rpp == 4 ? S2_NRING(4) : rpp == 2 ? S2_NRING(2) : S2_NRING(1)) : 3;
     auto successor = [&](int& jb, int& kc, long long& blk) {
         ++kc;
         if (kc >= nkc_of(jb)) { ++jb; kc = 0; }
@@ -403,7 +438,7 @@ __global__ __launch_bounds__(S2_THREADS, 1) void sweep2_kernel(SweepArgs a) {
         for (int r = 0; r < 4; ++r) lr[r] = (lane & 48) | ((lane + 4 * r) & 15);
         f64x2 av[2][2][2];
         auto load_a = [&](f64x2 (&dst)[2][2], int slot, int p) {
-            const f64x2* A2 = (const f64x2*)(Aring + slot * S2_TILE) + lane;
+            const f64x2* A2 = (const f64x2*)(Aring + slot * (DEEP ? sstr : S2_TILE)) + lane;     // (DEEP: slot = stage)
 #pragma unroll
             for (int h = 0; h < 2; ++h)
 #pragma unroll
@@ -415,8 +450,10 @@ __global__ __launch_bounds__(S2_THREADS, 1) void sweep2_kernel(SweepArgs a) {
         int slot = 0, bpar = 0;
         // B operands of the current tile in all four rotations; half 0 = k-steps 0-1, 1 = 2-3
         double brot[4][NKK];
-        auto load_b = [&](int buf, int half) {
+        auto load_b = [&](int buf, int half, [[maybe_unused]] int stg = 0) {
             const f64x2* Bw = (const f64x2*)(Bbuf + buf * 1024 + w * 256) + half * 64;
+            // (a part item of the stage ring: the operands lie behind the image pieces of the tile's stage)
+            if constexpr (DEEP) { if (deep) Bw = (const f64x2*)(Aring + stg * sstr + rpp * 512 + w * 256) + half * 64; }
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const f64x2 bv = Bw[lr[r]];
@@ -447,7 +484,7 @@ __global__ __launch_bounds__(S2_THREADS, 1) void sweep2_kernel(SweepArgs a) {
                     // of a partial last row block, whose remaining rows are zero in the packed factor; even,
                     // so that the last pair's prefetch of the next tile lands in the free fragment buffer)
                     constexpr int NPA = decltype(npa_tag)::value;
-                    const int nslot = slot == 2 ? 0 : slot + 1;
+                    const int nslot = slot == (DEEP ? nring - 1 : 2) ? 0 : slot + 1;
                     auto mfma_pair = [&](int pr, int kk) {
 #pragma unroll
                         for (int r = 0; r < 4; ++r) {
@@ -480,7 +517,7 @@ __global__ __launch_bounds__(S2_THREADS, 1) void sweep2_kernel(SweepArgs a) {
                         if (pr + 1 < NPA) {
                             // (first pair: the k-step 2-3 half of this tile's B operands; its
                             // registers were still in use when the 0-1 half was prefetched)
-                            if (pr == 0) load_b(bpar, 1);
+                            if (pr == 0) load_b(bpar, 1, slot);
                             load_a(av[(pr + 1) & 1], slot, pr + 1);
                             if (act) {
                                 mfma_pair(pr, 1);
@@ -504,7 +541,7 @@ __global__ __launch_bounds__(S2_THREADS, 1) void sweep2_kernel(SweepArgs a) {
                             load_a(av[0], nslot, 0);
                             if (act) mfma_pair(pr, 1);
                             __builtin_amdgcn_sched_barrier(0);
-                            load_b(bpar ^ 1, 0);
+                            load_b(bpar ^ 1, 0, nslot);
                             if (act) {
                                 mfma_pair(pr, 2);
                                 mfma_pair(pr, 3);
@@ -904,7 +941,7 @@ __global__ __launch_bounds__(S2_THREADS, 1) void sweep2_kernel(SweepArgs a) {
     };
     // generate the B operands of tile (jb, kc) of the current block -> LDS buffer bb (and, on
     // the chunk's first visit, the parked stream and this row block's share of mu)
-    auto produce_b = [&](int jb, int kc, int bb, int xb) {
+    auto produce_b = [&](int jb, int kc, int bb, int xb, [[maybe_unused]] int stg = -1) {
         double bfv[NKK];
         {
             const double* Xb = Xbuf + xb * XSTRIDE;
@@ -958,6 +995,9 @@ __global__ __launch_bounds__(S2_THREADS, 1) void sweep2_kernel(SweepArgs a) {
             }
             f64x2 o0, o1;
             o0.x = bfv[0]; o0.y = bfv[1]; o1.x = bfv[2]; o1.y = bfv[3];
+            if constexpr (DEEP) {                 // (stg >= 0: into stage stg of a part item's ring)
+                if (stg >= 0) { f64x2* Bw = (f64x2*)(Aring + stg * sstr + rpp * 512 + hw * 256); Bw[lane] = o0; Bw[64 + lane] = o1; return; }
+            }
             if (bb == 0) { f64x2* Bw = (f64x2*)(Bbuf + hw * 256); Bw[lane] = o0; Bw[64 + lane] = o1; }
             else { f64x2* Bw = (f64x2*)(Bbuf + 1024 + hw * 256); Bw[lane] = o0; Bw[64 + lane] = o1; }
         }
@@ -1017,6 +1057,96 @@ __global__ __launch_bounds__(S2_THREADS, 1) void sweep2_kernel(SweepArgs a) {
     // spilled one read back with v_readlane costs 30-100 cycles), and that differs between the DPAD
     // instantiations.  Structured: +8-13 % at N = 1024-2048 for DPAD 2 / 4 / 16 (inverse form) and for
     // DPAD 2 (substitution form); the single loop is 1.5-2.5 % faster for DPAD 8 (C3, C5).
+    // DEEP, a part item of the stage ring: one item is one run of tiles of one row block -- tile 0 (generated, the
+    // prologue's), the re-read tiles [1, nd0) and the generating tiles [nd0, nt) --, so its loop needs none of the stream
+    // bookkeeping below, and one form serves every Dpad.  After barrier i-1 the feeders request the re-read tiles up to
+    // i + dist into their stages (free since the matrix wavefronts passed barrier i-1: tile i-2 and older are read out)
+    // and wait, in front of barrier i, until at most the requests of the tiles newer than i+1 are outstanding: every
+    // feeder wavefront issues rpp + 2 requests per tile, VMEM completes in issue order, so tile i+1 has landed.  No
+    // __syncthreads() in this loop (hipcc would drain the queue in front of it).  The generating tiles follow at distance
+    // one as in the forms below; by then the run's last request has been waited for.
+    if constexpr (DEEP) {
+        if (deep) {
+            const int hw_s = __builtin_amdgcn_readfirstlane(hw);
+            typedef __attribute__((address_space(3))) void lds_void;
+            const int jb = jb_lo, nt = nkc_of(jb);
+            const int nd0 = S2_CPB * jb < nt ? S2_CPB * jb : nt;
+            int dist = S2W_PF(a.split);
+            dist = dist < 1 ? 1 : (dist > nring - 2 ? nring - 2 : dist);
+            const int nreq = rpp + 2;
+            auto dma_stage = [&](int stg, int kc) {
+                double* dst = Aring + stg * sstr + hw_s * 128;
+                const unsigned toffs = tile_off(jb, kc);
+#pragma unroll
+                for (int q = 0; q < 4; ++q)
+                    if (q < rpp)
+                        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_w, (lds_void*)(dst + q * 512), 16, (unsigned)lane * 16u,
+                                                                 toffs + (unsigned)((q + rsh) * 4096) + (unsigned)hw_s * 1024u, 0, 0);
+            };
+            auto dma_stage_b = [&](int stg, int c) {
+                double* dst = Aring + stg * sstr + rpp * 512 + hw_s * 256;
+                const unsigned soff = (unsigned)c * (unsigned)(SW_BCH * 8) + (unsigned)hw_s * 1024u;
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_k, (lds_void*)dst, 16, (unsigned)lane * 16u, soff, 0, SW_KAUX);
+                __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_k, (lds_void*)(dst + 128), 16, (unsigned)lane * 16u, soff + 4096u, 0, SW_KAUX);
+            };
+            // generating tiles: 0, then g1, g1 + 1, ...; the g-th of them reads x buffer g & 1
+            const int g1 = nd0 > 1 ? nd0 : 1;
+            __syncthreads();                          // C : constants visible
+            load_candidates(blk0);
+            dma_stage(0, 0);
+            x_put(0, x_fetch(0));
+            x_put(1, x_fetch(g1 < nt ? g1 : 0));
+            __syncthreads();                          // P0
+            produce_b(jb, 0, 0, 0, 0);
+            XQ xq = x_fetch(g1 + 1 < nt ? g1 + 1 : 0);
+            __syncthreads();                          // P
+            int nx = 1, stx = 1;                      // next re-read tile to request, its stage
+            int st1 = 1, g = 1;                       // stage of tile i+1; generating tiles so far
+            for (int i = 0; i < nt; ++i) {
+                // the matrix wavefronts have just passed barrier i-1
+                const int t1 = i + 1;
+                int n_pend = 0;
+                if (t1 >= nd0) {
+                    if (t1 < nt) {
+                        __builtin_amdgcn_s_setprio(3);
+                        dma_stage(st1, t1);
+                        produce_b(jb, t1, 0, g & 1, st1);
+                        x_put((g & 1) ^ 1, xq);       // x chunk of the generating tile after this one
+                        if (t1 + 2 < nt) { xq = x_fetch(t1 + 2); n_pend = X2 ? 2 : 1; }
+                        ++g;
+                        __builtin_amdgcn_s_setprio(0);
+                    }
+                } else {
+                    while (nx < nd0 && nx <= i + dist) {
+                        dma_stage(stx, nx);
+                        dma_stage_b(stx, nx);
+                        ++nx;
+                        stx = stx + 1 == nring ? 0 : stx + 1;
+                    }
+                    n_pend = (nx - 1 - t1) * nreq;    // requests of the tiles newer than i+1
+                }
+                st1 = st1 + 1 == nring ? 0 : st1 + 1;
+                // barrier i (the counts: the comment at S2_NRING; one not listed: vmcnt(0), which waits for more than it must)
+#define S2_DEEP_BARRIER(n) asm volatile("s_waitcnt vmcnt(" #n ") lgkmcnt(0)\n\ts_barrier" ::: "memory")
+                switch (n_pend) {
+                    case 1: S2_DEEP_BARRIER(1); break;
+                    case 2: S2_DEEP_BARRIER(2); break;
+                    case 3: S2_DEEP_BARRIER(3); break;
+                    case 4: S2_DEEP_BARRIER(4); break;
+                    case 6: S2_DEEP_BARRIER(6); break;
+                    case 8: S2_DEEP_BARRIER(8); break;
+                    case 9: S2_DEEP_BARRIER(9); break;
+                    case 12: S2_DEEP_BARRIER(12); break;
+                    case 15: S2_DEEP_BARRIER(15); break;
+                    default: S2_DEEP_BARRIER(0); break;
+                }
+#undef S2_DEEP_BARRIER
+            }
+            load_candidates(S2_BLK_END);              // (no next block: only snapshots the finished one)
+            epilogue();
+            return;
+        }
+    }
     if constexpr (SF) {
         const int hw_s = __builtin_amdgcn_readfirstlane(hw);
         typedef __attribute__((address_space(3))) void lds_void;
@@ -1424,7 +1554,8 @@ static int s2_prepare_device() {
                            (const void*)sweep2_kernel<DPAD, false, 0, true>, (const void*)sweep2_kernel<DPAD, true, 0, true>,
                            (const void*)sweep2_kernel<DPAD, false, 1, true>, (const void*)sweep2_kernel<DPAD, true, 1, true>,
                            (const void*)sweep2_kernel<DPAD, false, 2, true>, (const void*)sweep2_kernel<DPAD, true, 2, true>,
-                           (const void*)sweep2_kernel<DPAD, false, 0, true, true>, (const void*)sweep2_kernel<DPAD, true, 0, true, true>});
+                           (const void*)sweep2_kernel<DPAD, false, 0, true, true>, (const void*)sweep2_kernel<DPAD, true, 0, true, true>,
+                           (const void*)sweep2_kernel<DPAD, false, 0, true, true, true>});
 }
 
 // one launch of the kernel that fits (form, N, LinearKernel term); LIST: its blocks come from a.blk_list
@@ -1504,6 +1635,19 @@ extern "C" int apgp_set_prune_pipe(int v) { return __atomic_exchange_n(&g_prune_
 
 extern "C" int apgp_get_prune_pipe(void) { return __atomic_load_n(&g_prune_pipe, __ATOMIC_RELAXED); }
 
+// ---- how far ahead the parked seed launch requests the re-read tiles of its part items (sweep2_kernel, DEEP) ----
+// 0: one tile ahead, the launch as it was; d > 0: the stage-ring instantiation, up to d tiles ahead (at most what the ring
+// of the item's part size holds: 2 / 4 / 6 for four / two / one pair).  The same bits either way.
+#define S2_PREFETCH_MAX 6
+static_assert(S2_PREFETCH_MAX == S2_NRING(1) - 2 && S2_PREFETCH_MAX <= 7, "the deepest ring's distance, in three bits of split");
+static int g_seed_prefetch = S2_PREFETCH_MAX;
+
+extern "C" int apgp_set_seed_prefetch(int v) {
+    return __atomic_exchange_n(&g_seed_prefetch, v < 0 ? 0 : (v > S2_PREFETCH_MAX ? S2_PREFETCH_MAX : v), __ATOMIC_RELAXED);
+}
+
+extern "C" int apgp_get_seed_prefetch(void) { return __atomic_load_n(&g_seed_prefetch, __ATOMIC_RELAXED); }
+
 // ---- how many of the PR_SEED seeds the first seed wave sweeps ----
 // -1: the rule (S2_SEED_FIRST where the split seed route applies, all of them elsewhere); 1 .. 16: that many (16: one wave)
 #define S2_SEED_FIRST 4
@@ -1531,9 +1675,15 @@ extern "C" int apgp_get_seed_parts(void) { return __atomic_load_n(&g_seed_parts,
 // `parked`: the launch reads the chunks left of an item's diagonal from the parked stream; a re-read tile and a
 // generating (diagonal) tile then have prices of their own (S2P_*), in units that only compare with each other.
 // `lg`: a split row block goes as 2^lg parts; a part of two pairs or of one has its own prices on the parked route.
-static long long seed_launch_cost(int nrb, int cap, int n, int j0, int lg, bool parked) {
+// `route`: S2R_PLAIN (nothing parked), S2R_PARKED, or S2R_RING: the parked route whose part items run the stage-ring loop
+// (apgp_set_seed_prefetch > 0) and have the S2Q_* prices; its whole items run the other loop and keep S2P_*.
+enum { S2R_PLAIN = 0, S2R_PARKED = 1, S2R_RING = 2 };
+static long long seed_launch_cost(int nrb, int cap, int n, int j0, int lg, int route) {
     static const int gen[4] = {S2P_WHOLE_GEN, S2P_HALF_GEN, S2P_PAIR2_GEN, S2P_PAIR1_GEN};
     static const int park[4] = {S2P_WHOLE_PARK, S2P_HALF_PARK, S2P_PAIR2_PARK, S2P_PAIR1_PARK};
+    static const int gen_ring[4] = {S2P_WHOLE_GEN, S2Q_HALF_GEN, S2Q_PAIR2_GEN, S2Q_PAIR1_GEN};
+    static const int park_ring[4] = {S2P_WHOLE_PARK, S2Q_HALF_PARK, S2Q_PAIR2_PARK, S2Q_PAIR1_PARK};
+    const bool parked = route != S2R_PLAIN;
     long long load[SW_GRID] = {0};
     const int nitem = s2_nitems(nrb, j0, n, lg);
     long long last = 0;
@@ -1542,7 +1692,8 @@ static long long seed_launch_cost(int nrb, int cap, int n, int j0, int lg, bool 
         s2_row_item(i, nrb, j0, n, lg, jb, h);
         const int kind = h >= 0 ? lg : (n - S2_ROWS * jb <= S2_ROWS / 2 ? 1 : 0);     // (a last block of <= 128 rows: a half's prices)
         const int nkc = s2_nkc_of(jb, n), nre = S2_CPB * jb < nkc ? S2_CPB * jb : nkc;
-        const long long c = parked ? (long long)gen[kind] * (nkc - nre) + (long long)park[kind] * nre
+        const bool ring = route == S2R_RING && h >= 0;
+        const long long c = parked ? (long long)(ring ? gen_ring : gen)[kind] * (nkc - nre) + (long long)(ring ? park_ring : park)[kind] * nre
                                    : (long long)s2_part_cost(kind) * nkc;
         for (int k = 0; k < cap; ++k) {
             int best = 0;
@@ -1558,35 +1709,36 @@ static long long seed_launch_cost(int nrb, int cap, int n, int j0, int lg, bool 
 // The rule: J0 of {0, nrb / 2, nrb} with the shortest modelled launch (ties: the fewest items).  Remembered for the last
 // (nrb, cap, n): a fit's calls repeat them.
 // The parts of a split row block follow the same rule: halves, or (parked route) two-pair items where the model says
-// they shorten the launch; one-pair items only when forced.  Remembered for the last few (nrb, blocks, n, parked, forced
-// values): a call's two waves and a fit's calls repeat them.
+// they shorten the launch; one-pair items only when forced, or (stage-ring route, whose prices make them the shortest
+// around N = 1152) where the model says so.  Remembered for the last few (nrb, blocks, n, route, forced values): a call's
+// two waves and a fit's calls repeat them.
 struct SeedPlan { int j0, lg; long long cost; };
-static SeedPlan seed_plan(int nrb, int cap, int n, bool parked) {
+static SeedPlan seed_plan(int nrb, int cap, int n, int route) {
     const int v = apgp_get_seed_rowsplit(), fp = apgp_get_seed_parts();
     const int flg = fp == 8 ? 0 : fp == 4 ? 1 : fp == 2 ? 2 : fp == 1 ? 3 : -1;
-    struct Memo { int nrb, cap, n, parked, v, flg; SeedPlan plan; };
+    struct Memo { int nrb, cap, n, route, v, flg; SeedPlan plan; };
     static std::mutex mu;
     static Memo memo[8];
     static int nmemo = 0, next = 0;
     std::lock_guard<std::mutex> g(mu);
     for (int i = 0; i < nmemo; ++i) {
         const Memo& e = memo[i];
-        if (e.nrb == nrb && e.cap == cap && e.n == n && e.parked == (int)parked && e.v == v && e.flg == flg) return e.plan;
+        if (e.nrb == nrb && e.cap == cap && e.n == n && e.route == route && e.v == v && e.flg == flg) return e.plan;
     }
     SeedPlan best = {nrb, 1, 0};
     long long best_c = -1;
-    for (int lg = 1; lg <= (parked ? 2 : 1); ++lg) {
+    for (int lg = 1; lg <= (route == S2R_RING ? 3 : route == S2R_PARKED ? 2 : 1); ++lg) {
         if (flg >= 0 && lg != 1) continue;         // (forced parts: one pass, with them)
         const int l = flg >= 0 ? flg : lg;
         for (int j0 : {nrb, nrb / 2, 0}) {
             if (v >= 0 && j0 != nrb) continue;     // (forced J0: one pass, with it)
             const int j = v >= 0 ? (v < nrb ? v : nrb) : j0;
             if (lg > 1 && j == nrb) continue;
-            const long long c = seed_launch_cost(nrb, cap, n, j, l, parked);
+            const long long c = seed_launch_cost(nrb, cap, n, j, l, route);
             if (best_c < 0 || c < best_c) { best = {j, l, c}; best_c = c; }
         }
     }
-    memo[next] = {nrb, cap, n, (int)parked, v, flg, best};
+    memo[next] = {nrb, cap, n, route, v, flg, best};
     next = (next + 1) % 8;
     if (nmemo < 8) ++nmemo;
     return best;
@@ -1617,21 +1769,24 @@ static void launch_sweep_list(const SweepArgs& a0, hipStream_t s, bool solve, co
         // tau_1 of the first wave and the seed's bound (s2_wave_skip) -- those of the other seeds that could still win or
         // tie.  At the benchmark's sizes none can: the seeds' bounds lie further apart than the bound's slack, and the
         // first wave is all the exact work tau needs.  Both waves are the same four launches over their positions.
+        // (the prices of the loop the part items run: the stage ring's at apgp_set_seed_prefetch > 0)
+        const int kroute = apgp_get_seed_prefetch() > 0 ? S2R_RING : S2R_PARKED;
         int first = (int)cap;
         if (rowsplit && b.lin_coef == 0.0) {
             const int v = apgp_get_seed_first();
             // the rule: S2_SEED_FIRST where the model says the shorter first wave pays for the second one's launches
             // (from N ~ 2048 on; below, 16 blocks' items are about one per CU and a wave lasts its heaviest item either
-            // way).  By the parked route's prices with the stream on or off: the same seeds are swept.
+            // way).  By the parked route's prices with the stream on or off: the same seeds are swept.  (K may differ
+            // between the two values of apgp_set_seed_prefetch; tau and the winner depend on neither.)
             first = v > 0 ? v : S2_SEED_FIRST;
             if (first > (int)cap) first = (int)cap;
             if (v <= 0 && first < (int)cap &&
-                seed_plan(nrb2, (int)cap, b.n, true).cost - seed_plan(nrb2, first, b.n, true).cost <= S2P_WAVE2)
+                seed_plan(nrb2, (int)cap, b.n, kroute).cost - seed_plan(nrb2, first, b.n, kroute).cost <= S2P_WAVE2)
                 first = (int)cap;
         }
         for (int wave = 0; wave < (first < (int)cap ? 2 : 1); ++wave) {
             const int p0 = wave ? first : 0, p1 = wave ? (int)cap : first, nw = p1 - p0;
-            const SeedPlan plan = rowsplit ? seed_plan(nrb2, nw, b.n, parked) : SeedPlan{nrb2, 0, 0};
+            const SeedPlan plan = rowsplit ? seed_plan(nrb2, nw, b.n, parked ? kroute : S2R_PLAIN) : SeedPlan{nrb2, 0, 0};
             const int nitem = s2_nitems(nrb2, plan.j0, b.n, plan.lg);
             b.split = S2W_WORD(plan.j0, plan.lg, p0, p1);
             if (parked) {
@@ -1642,9 +1797,14 @@ static void launch_sweep_list(const SweepArgs& a0, hipStream_t s, bool solve, co
             if (nitem > nrb2 || parked || first < (int)cap) {
                 const size_t lds = s2_lds_bytes<DPAD>();
                 const unsigned grid = (unsigned)(nw * nitem);
+                const int pf = parked ? apgp_get_seed_prefetch() : 0;
                 if (b.lin_coef != 0.0)
                     hipLaunchKernelGGL((sweep2_kernel<DPAD, true, 0, true, true>), dim3(grid), dim3(S2_THREADS), lds, s, b);
-                else
+                else if (pf > 0) {                // (the part items' stage ring; whole items run as in the other instantiation)
+                    SweepArgs d = b;
+                    d.split |= pf << 25;
+                    hipLaunchKernelGGL((sweep2_kernel<DPAD, false, 0, true, true, true>), dim3(grid), dim3(S2_THREADS), lds, s, d);
+                } else
                     hipLaunchKernelGGL((sweep2_kernel<DPAD, false, 0, true, true>), dim3(grid), dim3(S2_THREADS), lds, s, b);
                 if (nitem > nrb2) hipLaunchKernelGGL(sweep_fold_kernel, dim3((unsigned)(nw * nrb2)), dim3(256), 0, s, b);
             } else {

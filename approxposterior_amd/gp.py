@@ -502,6 +502,10 @@ class GP(GeorgeExtras):
         # workgroup (apgp_set_seed_park; same bits either way): None: the library's process-wide setting (default: on);
         # True / 1: on; False / 0: off
         self.seed_park = None
+        # that launch's row-part workgroups request their re-read tiles up to this many tiles ahead, through a ring of
+        # stages in LDS (apgp_set_seed_prefetch; same bits whatever the value): None: the library's process-wide setting
+        # (default: 6, as far as the ring of the part size holds); 0: one tile ahead, the launch as it was
+        self.seed_prefetch = None
         # the 16 seed blocks go in two waves, the first seed_first of them and then those of the rest that could still
         # win (apgp_set_seed_first; same winner whatever the value): None: the library's process-wide setting (default:
         # its rule, 4 where the parked seed route applies); -1: the rule; 1 .. 16: that many (16: one wave)
@@ -1461,6 +1465,7 @@ class GP(GeorgeExtras):
             prune_was = None if self.sweep_prune is None else lib.apgp_set_sweep_prune(int(self.sweep_prune))
             rowsplit_was = None if self.seed_rowsplit is None else lib.apgp_set_seed_rowsplit(int(self.seed_rowsplit))
             park_was = None if self.seed_park is None else lib.apgp_set_seed_park(int(self.seed_park))
+            prefetch_was = None if self.seed_prefetch is None else lib.apgp_set_seed_prefetch(int(self.seed_prefetch))
             first_was = None if self.seed_first is None else lib.apgp_set_seed_first(int(self.seed_first))
             parts_was = None if self.seed_parts is None else lib.apgp_set_seed_parts(int(self.seed_parts))
             pipe_was = None if self.prune_pipe is None else lib.apgp_set_prune_pipe(int(self.prune_pipe))
@@ -1478,6 +1483,8 @@ class GP(GeorgeExtras):
                     lib.apgp_set_seed_rowsplit(rowsplit_was)
                 if park_was is not None:
                     lib.apgp_set_seed_park(park_was)
+                if prefetch_was is not None:
+                    lib.apgp_set_seed_prefetch(prefetch_was)
                 if first_was is not None:
                     lib.apgp_set_seed_first(first_was)
                 if parts_was is not None:

@@ -395,7 +395,15 @@ int apgp_acquire_solve(const double* T, int64_t m, int64_t idx_offset,
  * (APGP_PRUNE_ROWS_SIGNED), returns the previous value.  1 (default): the kernel whose row loop issues the next
  * group's matrix products between slices of this group's exponentials and reads the next matrix tile's rows ahead;
  * 0: the loop in the order the compiler gives it, the kernel as it was.  The bits do not depend on it.  Every other
- * kind of rows ignores it.  APGP_ABI_VERSION stays 8.  */
+ * kind of rows ignores it.  APGP_ABI_VERSION stays 8.
+ * apgp_set_seed_prefetch(v): process-wide switch of the parked seed launch (apgp_set_seed_park on), returns the previous
+ * value.  A row-part workgroup of that launch keeps its tiles in a ring of stages in LDS and requests the re-read
+ * tiles up to v tiles ahead of the matrix wavefronts, at most what the ring holds for its part size (2 / 4 / 6 tiles
+ * for parts of four / two / one sub-block pair).  0: one tile ahead, the launch as it was; 6 (default; larger values
+ * count as 6, negative ones as 0).  The bits do not depend on it.  Everything but the parked seed launch ignores it;
+ * APGP_ABI_VERSION stays 8.  */
+int apgp_set_seed_prefetch(int v);
+int apgp_get_seed_prefetch(void);
 int apgp_set_sweep_prune(int v);
 int apgp_get_sweep_prune(void);
 int apgp_set_seed_rowsplit(int v);
